@@ -68,7 +68,13 @@ def parse():
                          "collectives are staged through the host, the timings mean nothing)")
     ap.add_argument("--share-gpu", action="store_true", help="every rank uses cuda:0 (testing, with --dist-backend gloo)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the configs[1] / N1 / N2 secondary timings")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (a fixed, seeded sample of the "
+                         "queries: their signatures, norms, candidate pairs with scores and top-K rows) as DIR/<name>.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def workload_label(nq_total, P, b, D, world, K, mean_set):
@@ -197,6 +203,62 @@ def self_launch(n):
     return subprocess.run(cmd, env=env).returncode
 
 
+# --dump-outputs: a fixed, seeded sample of the step's result, small enough to keep (<= 64 MB in all).  The sample
+# depends on the shape alone, so two builds (or one GPU and N ranks) of the same command write comparable arrays.
+DUMP_SEED = 20240
+DUMP_QUERIES = 16384          # sampled queries: their signature rows, norms, candidate pairs and top-K rows
+DUMP_SIG_BYTES = 24 << 20     # fewer sampled queries when P is so large that their rows would not fit this
+DUMP_MAX_ROWS = 1 << 19       # pair / top-K rows beyond this are thinned by a seeded subsample
+
+
+def dump_query_ids(nq_total, P):
+    """the sorted global query ids --dump-outputs writes"""
+    n = min(nq_total, DUMP_QUERIES, DUMP_SIG_BYTES // (4 * P + 16))
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(nq_total, size=n, replace=False))
+
+
+def dump_part(res, qids, nq_total, q0, nq_local):
+    """this rank's share of the dump, on the host: signature rows, norms and top-K rows of the sampled queries it
+    owns, and the candidate pairs it holds that have an end among the sampled queries"""
+    from qrlsh import ops
+    dev = res.pairs.device
+    mine = qids[(qids >= q0) & (qids < q0 + nq_local)]
+    loc = torch.from_numpy(mine - q0).to(dev)
+    sampled = torch.zeros(nq_total, dtype=torch.bool, device=dev)
+    sampled[torch.from_numpy(qids).to(dev)] = True
+    i, j = res.pairs >> 32, res.pairs & 0xFFFFFFFF
+    on = sampled[i] | sampled[j]
+    kept = sampled[res.src.long()]
+    return {"queries": mine,
+            "sig": ops.sig_to_int32(res.sig.index_select(0, loc)).cpu().numpy(),
+            "norm2": res.norm2.index_select(0, loc).cpu().numpy(),
+            "pairs": torch.stack([i[on], j[on]], 1).cpu().numpy(), "milli": res.milli[on].cpu().numpy(),
+            "src": res.src[kept].cpu().numpy(), "dst": res.dst[kept].cpu().numpy(), "val": res.val[kept].cpu().numpy()}
+
+
+def write_dump(out_dir, parts):
+    """merge the ranks' parts (rank order = query order; pairs re-sorted, as one GPU returns them) and write them as
+    float32 (values that fit 24 bits) / float64 (ids, norms) .npy files -> bytes written"""
+    cat = {k: np.concatenate([p[k] for p in parts]) for k in parts[0]}
+    order = np.lexsort((cat["pairs"][:, 1], cat["pairs"][:, 0]))
+    cat["pairs"], cat["milli"] = cat["pairs"][order], cat["milli"][order]
+    for keys in (("pairs", "milli"), ("src", "dst", "val")):
+        n = len(cat[keys[0]])
+        if n > DUMP_MAX_ROWS:
+            pick = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, size=DUMP_MAX_ROWS, replace=False))
+            for k in keys:
+                cat[k] = cat[k][pick]
+    f64 = ("queries", "norm2", "pairs", "src", "dst")
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for k, v in cat.items():
+        path = os.path.join(out_dir, k + ".npy")
+        np.save(path, v.astype(np.float64 if k in f64 else np.float32))
+        total += os.path.getsize(path)
+    assert total <= 64 << 20, "dump of %d bytes exceeds 64 MB" % total
+    return total
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -292,6 +354,16 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs:            # the last timed step's result, before anything else runs
+        part = dump_part(res, dump_query_ids(nq_total, P), nq_total, q0, nq_local)
+        parts = [part]
+        if dist is not None:
+            parts = [None] * world
+            dist.all_gather_object(parts, part)
+        if rank == 0:
+            nbytes = write_dump(args.dump_outputs, parts)
+            sys.stderr.write("bench.py: wrote the sampled outputs of the last timed step to %s (%d bytes)\n"
+                             % (args.dump_outputs, nbytes))
     if sharded:
         _lib.prof_pause(True)
         for _ in range(PHASE_STEPS):

@@ -2,7 +2,7 @@
 # A/B of compile-time switches on ONE box: tools/ab_flags.sh "<flags A>" "<flags B>" ...  (development tool)
 # rebuilds libqrlsh.so with each set of -D flags and runs tools/kbench.py at 10 M and 1 M queries (or $AB_CMD).
 set -e
-R=/root/repo
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R/query-recommendation-system_amd/csrc
 BASE="-O3 -std=c++17 -fPIC -fvisibility=hidden --offload-arch=gfx950 -Wall -Wno-unused-function"
 i=0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Capture golden input/output vectors from the reference's own Python code.
 
-Runs ONLY in the build container (needs /root/reference; the GPU box never has it).
+Needs a checkout of the reference, named by the QRLSH_REFERENCE environment variable.
 Writes small .npz / .csv fixtures under tests/golden/.  The fixtures are data
 (inputs + the reference's outputs on them); no reference source is copied.
 
@@ -20,6 +20,7 @@ How the reference is run:
 Usage:  python tools/make_golden.py            (rewrites the round-1 base fixtures)
         python tools/make_golden.py NAME...    (only the named later additions: full_p100_r5,
                                                 full_p50_r5_wrap, pieces_p96_b12, cfg1_scores, cfg1b, cfg2)
+        with QRLSH_REFERENCE=<the reference's directory> in the environment.
 """
 import os
 import sys
@@ -35,7 +36,7 @@ sys.dont_write_bytecode = True
 import numpy as np
 import pandas as pd
 
-REF = "/root/reference"
+REF = os.environ.get("QRLSH_REFERENCE", "")
 OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "tests", "golden")
 
 
@@ -437,7 +438,7 @@ def fixture_lsh_edge(lsh_mod):
 
 def main():
     if not os.path.isdir(REF):
-        sys.exit("make_golden.py needs the reference tree at " + REF)
+        sys.exit("make_golden.py needs the reference tree: set QRLSH_REFERENCE to its directory")
     os.makedirs(OUT, exist_ok=True)
     _install_placeholders()
     sys.path.insert(0, REF)

@@ -6,8 +6,8 @@
 set -e
 TAG=${1:-r02}
 NQ=${2:-1000000}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=/root/repo
 O=$R/gpurun_out
 i=0
 for C in "TA_BUSY_avr TA_TA_BUSY_sum" "TCP_PENDING_STALL_CYCLES_sum TCP_TCC_READ_REQ_sum" \

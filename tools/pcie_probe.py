@@ -1,5 +1,6 @@
-import sys, time, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/query-recommendation-system_amd")
+import os, sys, time, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "query-recommendation-system_amd"))
 import qrlsh
 from qrlsh import ops, pipeline
 nq, D = 10_000_000, 32768

@@ -7,8 +7,8 @@
 # tools/summarise_profile.py <tag> ... then condenses them into profiles/ (run in the repo afterwards).
 set -e
 TAG=${1:-r02}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=/root/repo
 O=$R/gpurun_out
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_trace -o run -- python3 $R/bench.py --cpu-sample 0 --no-secondary > $O/${TAG}_trace_bench.json 2> $O/${TAG}_trace.err
 echo "trace done"

@@ -7,8 +7,8 @@ set -e
 TAG=${1:-r02}
 STAGE=${2:-bucket}
 NQ=${3:-10000000}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp
-R=/root/repo
 O=$R/gpurun_out
 i=0
 for C in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY" "SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS SQ_INSTS_LDS" \
