@@ -238,7 +238,10 @@ int qrlsh_region_unique_fill(const uint64_t *tmp, int64_t n, int32_t group_bits,
  * words_per_query: what a query of the populated id range emits on average (0: n / nids) -- sizes the regions (3 x the
  * mean + 4096: i is the smaller id of a pair, so low ids carry up to twice the mean).  *overflow_out != 0: a region
  * outgrew its capacity (group with qrlsh_sort_u64 instead).  qrlsh_pair_regions_words returns 0 when the id space has
- * more than 65536 regions (not served).  qrlsh_region_unique_count_regions is qrlsh_region_unique_count on those
+ * more than 65536 regions, or when a level's regions reach 2^32 words -- the scatter places words with 32-bit offsets,
+ * so it needs na * cap_a < 2^32 (level 1: na = tmp_words / cap_a coarse digits) and 2^rb * cap_b < 2^32 (the final
+ * regions of one coarse digit) -- (not served; the scatter rejects such sizes with QRLSH_EINVAL before any device
+ * work; a large words_per_query hint reaches them first).  qrlsh_region_unique_count_regions is qrlsh_region_unique_count on those
  * regions (tmp: as many words as the region buffer); qrlsh_region_unique_fill follows it as usual. */
 size_t qrlsh_pair_regions_words(int64_t n, int64_t nids, int32_t group_bits, double words_per_query);
 size_t qrlsh_pair_regions_tmp_words(int64_t n, int64_t nids, int32_t group_bits, double words_per_query);

@@ -810,11 +810,18 @@ static PairRegions pair_regions(int64_t n, int64_t nids, int group_bits, double 
   return r;
 }
 
+// pair_group_scatter_kernel places a word at (digit * cap + position) in 32 bits inside one batch: the regions a level
+// deals into (na x cap_a at level 1, 2^rb x cap_b per tmp region at level 2) must stay below 2^32 words
+static bool pair_regions_fit_u32(const PairRegions &r) {
+  return (uint64_t)r.na * r.cap_a < (1ull << 32) && ((uint64_t)r.cap_b << r.rb) < (1ull << 32);
+}
+
 // words of the region buffer (and of the tmp buffer of level 1; 0 when one level is enough), the region capacity and count
 QRLSH_EXPORT size_t qrlsh_pair_regions_words(int64_t n, int64_t nids, int32_t group_bits, double words_per_query) {
   if (n <= 0 || nids <= 0 || group_bits < 0 || group_bits > 8) return 0;
   const PairRegions r = pair_regions(n, nids, group_bits, words_per_query);
   if (r.rbits > 16) return 0;   // more than 65536 regions: not served (two levels of at most 256 digits)
+  if (!pair_regions_fit_u32(r)) return 0;   // a level's regions reach 2^32 words: not served either
   return (size_t)r.nregions * r.cap_b;
 }
 QRLSH_EXPORT size_t qrlsh_pair_regions_tmp_words(int64_t n, int64_t nids, int32_t group_bits, double words_per_query) {
@@ -842,6 +849,9 @@ QRLSH_EXPORT int qrlsh_pair_regions_scatter(const uint64_t *words, int64_t n, in
   hipStream_t st = static_cast<hipStream_t>(stream);
   const PairRegions r = pair_regions(n > 0 ? n : 1, nids, group_bits, words_per_query);
   QR_CHECK_ARG(r.rbits <= 16 && r.na <= RADIX, "qrlsh_pair_regions_scatter: %d region bits", r.rbits);
+  QR_CHECK_ARG(pair_regions_fit_u32(r),
+               "qrlsh_pair_regions_scatter: regions reach 2^32 words (na * cap_a = %llu, 2^rb * cap_b = %llu; need both < 2^32)",
+               (unsigned long long)r.na * r.cap_a, (unsigned long long)r.cap_b << r.rb);
   if (hipMemsetAsync(counts, 0, ((size_t)r.nregions + RADIX) * sizeof(uint32_t), st) != hipSuccess ||
       hipMemsetAsync(overflow_out, 0, sizeof(uint32_t), st) != hipSuccess) {
     qrlsh_set_error("qrlsh_pair_regions_scatter: hipMemsetAsync failed");
@@ -2016,6 +2026,15 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
     const int ngroups = (b + per - 1) / per;
     const uint64_t list_room = (slots - MAX_GROUPS) / (uint64_t)ngroups;
     const uint32_t big_max = (uint32_t)(list_room < FIN_BIG_LIST ? list_room : FIN_BIG_LIST);
+    // With two or more groups, a group's gather (bucket_big_gather_kernel) scans the run descriptors while the next
+    // group's partition, on the other stream, counts new runs in before it writes their descriptors: a slot in
+    // between still holds what an earlier call left there, and one that names a part of this group would be counted
+    // twice (the overflow flag, and the step on the general path).  Cleared, such a slot reads {0, 0 records}: it
+    // matches at most slot 0 and adds nothing.
+    if (ngroups > 1 && hipMemsetAsync(w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
+      return QRLSH_EHIP;
+    }
     hipStream_t aux = nullptr;
     int gi = 0;
     for (int g0 = 0; g0 < b; g0 += per, ++gi) {

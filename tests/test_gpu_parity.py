@@ -489,6 +489,37 @@ def test_pipeline_equals_oracle_on_synthetic(nq, D, P, b):
     assert np.array_equal(res.val.cpu().numpy(), v)
 
 
+@pytest.mark.parametrize("nq,cluster,mean,p_replace", [(1_500_000, 8, 16.0, 0.15),    # T = 9: two-step partition
+                                                       (3_000_000, 8, 16.0, 0.15),    # T = 10
+                                                       (1_000_000, 64, 16.0, 0.05),   # buckets of 64, long rows
+                                                       (1_000_000, 8, 1.5, 0.15)])    # tiny answer sets
+def test_pipeline_equals_oracle_on_synthetic_shapes(nq, cluster, mean, p_replace):
+    """shapes test_pipeline_equals_oracle_on_synthetic does not reach: partition depths 9 and 10, big clusters (hot
+    rows, popular buckets), answer sets of one or two rows -- signatures, pairs, scores and top-K exactly the oracle's"""
+    D, P, b = 32768, 128, 32
+    K = pipeline.max_candidates(nq)
+    O.set_threads(16)
+    off, rows = qrlsh.synth_csr(nq, D, seed=1, cluster=cluster, mean=mean, p_replace=p_replace, device=DEV)
+    perms = ops.legacy_permutations(P, D, seed=7)
+    res = pipeline.query_similarities(off, rows, ops.perm_table(perms, DEV), b, K)
+    torch.cuda.synchronize()
+    ho, hr = off.cpu().numpy(), rows.cpu().numpy()
+    roff, rrows = O.synth_csr(nq, D, seed=1, cluster=cluster, mean=mean, p_replace=p_replace)
+    assert np.array_equal(ho, roff) and np.array_equal(hr, rrows)
+    if mean < 2:
+        assert np.diff(ho).mean() < 3               # (the generator's sets are tiny here, not empty)
+    sig = O.minhash(ho, hr, perms)
+    assert np.array_equal(res.sig_int32().cpu().numpy(), sig)
+    pairs = O.candidates(O.band_keys(sig, b), P // b)
+    assert np.array_equal(u64(res.pairs), pairs)
+    milli = O.score_pairs(sig, pairs, mode=1)
+    assert np.array_equal(res.milli.cpu().numpy(), milli)
+    s, d, v = O.topk(pairs, milli, K)
+    assert np.array_equal(res.src.cpu().numpy(), s)
+    assert np.array_equal(res.dst.cpu().numpy(), d)
+    assert np.array_equal(res.val.cpu().numpy(), v)
+
+
 def test_full_size_config2_properties_and_oracle():
     """BASELINE config 2 (1 M queries, P=128, b=32): exact equality with the oracle for the
     integer stages (it finishes in seconds on the box's host cores) plus size-independent

@@ -110,6 +110,62 @@ def test_host_size_rules():
     assert lib.qrlsh_row_unique_workspace_bytes(10 ** 8) > lib.qrlsh_row_unique_workspace_bytes(10 ** 6)
 
 
+def test_pair_region_offsets_stay_below_2_pow_32():
+    """pair_group_scatter_kernel places a word at digit * cap + position in 32 bits: with two levels of 256 digits
+    (nids = 2^24 at group_bits = 8) a large words-per-query hint grows the region capacities until a level's regions
+    pass 2^32 words.  From the first such hint on, qrlsh_pair_regions_words says "not served" (0, the caller sorts
+    instead) and the scatter refuses the sizes -- before any device work, so host buffers and no GPU do here."""
+    from qrlsh import _lib
+    lib = _lib.load()
+    n, nids, g = 100_000_000, 1 << 24, 8
+    assert lib.qrlsh_pair_regions_count(n, nids, g, 0.0) == 65536
+
+    def breaks(hint):   # level 1: na x cap_a (na = 256 coarse digits); level 2: 2^8 x cap_b per coarse digit
+        tmp = lib.qrlsh_pair_regions_tmp_words(n, nids, g, float(hint))
+        return tmp >= 1 << 32 or 256 * lib.qrlsh_pair_regions_cap(n, nids, g, float(hint)) >= 1 << 32
+
+    lo, hi = 0, 1 << 20
+    assert not breaks(lo) and breaks(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if breaks(mid) else (mid, hi)
+    assert 20 < hi < 1000                               # a hint a caller can pass (~100 words per query)
+    assert lib.qrlsh_pair_regions_words(n, nids, g, float(hi)) == 0
+    assert lib.qrlsh_pair_regions_words(n, nids, g, float(lo)) == 65536 * lib.qrlsh_pair_regions_cap(n, nids, g, float(lo))
+    counts = np.zeros(65536 + 256, dtype=np.uint32)
+    ovf = np.zeros(1, dtype=np.uint32)
+    rc = lib.qrlsh_pair_regions_scatter(None, n, g, nids, float(hi), None, None, counts.ctypes.data, ovf.ctypes.data, None)
+    assert rc == _lib.QRLSH_EINVAL
+    assert b"2^32" in lib.qrlsh_last_error()
+    assert not counts.any() and not ovf.any()          # nothing was touched
+    # the same with one level (nids <= 256 regions): 2^rb x cap_b alone bounds it
+    n1, nids1 = 1_000_000, 1 << 16
+    assert lib.qrlsh_pair_regions_tmp_words(n1, nids1, g, 0.0) == 0
+    h1 = next(h for h in range(1, 1 << 16, 7) if 256 * lib.qrlsh_pair_regions_cap(n1, nids1, g, float(h)) >= 1 << 32)
+    assert lib.qrlsh_pair_regions_words(n1, nids1, g, float(h1)) == 0
+    assert lib.qrlsh_pair_regions_words(n1, nids1, g, float(h1 - 7)) > 0
+    rc = lib.qrlsh_pair_regions_scatter(None, n1, g, nids1, float(h1), None, None, counts.ctypes.data, ovf.ctypes.data,
+                                        None)
+    assert rc == _lib.QRLSH_EINVAL and b"2^32" in lib.qrlsh_last_error()
+
+
+def test_bucket_case_builders_build_what_they_say():
+    """tests/bucket_cases.py (the GPU suite's adversarial bucket structures): its numpy mixer is the library's, and a
+    built case's target part holds the records it reports"""
+    import bucket_cases as B
+    from qrlsh import _lib
+    lib = _lib.load()
+    rng = np.random.default_rng(3)
+    ks = rng.integers(0, 1 << 63, size=1000, dtype=np.int64)
+    assert [int(x) for x in B.np_mix64(ks.view(np.uint64))] == [lib.qrlsh_mix64_host(int(k)) for k in ks]
+    c = B.same_part_keys(rng, 300_000, 8, None, fill_to=2000)
+    assert c.count == 2000 == B.part_count(c.keys, 8, 0, c.part)
+    c = B.same_part_keys(rng, 300_000, 9, [700, 300, 900])
+    assert c.count >= 1900 and all(lib.qrlsh_mix64_host(k) >> 55 == c.part for k in c.hot)
+    c = B.planted_keys(rng, 200_000, 2, [(2, 100), (500, 1)], 8)
+    assert c.count >= 500 and lib.qrlsh_mix64_host(c.hot[0]) >> 56 == c.part
+
+
 def test_legacy_permutations_follow_the_global_stream():
     from qrlsh import ops
     from oracle import oracle as O
