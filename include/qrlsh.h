@@ -428,6 +428,30 @@ int qrlsh_predict(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t 
                   int32_t sum_order, int32_t *out, uint32_t *too_long_out, int32_t kq, void *workspace,
                   size_t workspace_bytes, void *stream);
 
+/* ---- recommendations: top-k unrated queries per user (the consumer of N1's output) ---------------------
+ * Replaces the selection of the interactive prompt, recommender.py:357-375 (just_scored of :361, the argsort of
+ * :370), in batch form over the completed matrix.  ratings / pred int32 [nu][nq] (qrlsh_predict's input and output),
+ * both base pointers 16-byte aligned.  users[m] (int32 row ids), or NULL for all nu rows in order (then m = nu).
+ * For each requested user u: eligible = { j : ratings[u][j] == 0 and pred[u][j] != 0 } (negative values included),
+ * avail_out[i] = |eligible|, idx_out[i][0 .. min(k, avail) - 1] = the eligible columns with the largest pred, ordered
+ * by value descending then column ascending, val_out[i][.] their values; unused slots idx -1 / val 0.  The result
+ * is exact and depends on neither the form nor `slices` nor `lo`.
+ * A user id outside [0, nu) is not read: its row gets avail_out = -1 and a padded output (the host reads it back).
+ * Forms (qrlsh_recommend_workspace_bytes(m, nq, k, slices) bytes of workspace; 0 = none needed):
+ *   rows form (nq <= 2048, slices = 0): one workgroup per row sorts the row's eligible cells in LDS; no workspace;
+ *   slice form: (row, slice) workgroups, slices = 1 .. 256 (0 = auto: about 2048 workgroups, >= 8192 columns per
+ *     slice).  An LDS histogram of the values over the window [lo, lo + 4096) finds the k-th largest value; when it
+ *     falls outside the window (wide-range values) up to three radix rounds (12 / 12 / 8 bits of the biased key)
+ *     find it, decided on the device; then one sweep emits the <= k winners and a per-row sort orders them.
+ * Limits: 1 <= k <= QRLSH_RECOMMEND_MAX_K, nq < 2^31 (QRLSH_EINVAL otherwise); m x max(slices, 1) <= 2^24
+ * workgroups (QRLSH_EUNSUPPORTED above).  m = 0 returns at once; nq = 0 gives avail 0 and padded rows.
+ */
+#define QRLSH_RECOMMEND_MAX_K 1024
+size_t qrlsh_recommend_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices);
+int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pred, int64_t nu, int64_t nq, const int32_t *users,
+                         int64_t m, int32_t k, int32_t lo, int32_t slices, int32_t *idx_out, int32_t *val_out,
+                         int32_t *avail_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- N4: user similarity, the part after the clustering ----------------------------------------
  * Recommender.compute_userSimilarities, recommender.py:263-288: inside a cluster every user's row is centred on
  * the mean of its non-zero ratings IN AN INTEGER ARRAY (the centred values are truncated toward zero), then

@@ -26,6 +26,7 @@ SORT_OWNER = 8
 SORT_HOST = 16
 SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
+RECOMMEND_MAX_K = 1024
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -98,6 +99,9 @@ SIGNATURES = {
     "qrlsh_predict_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "qrlsh_predict": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, _i32, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "qrlsh_recommend_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "qrlsh_recommend_topk": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
+                                            _vp]),
     "qrlsh_center_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "qrlsh_user_gram_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_user_gram": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

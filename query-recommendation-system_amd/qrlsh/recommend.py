@@ -1,0 +1,115 @@
+"""Top-k unrated queries for every requested user, on the device (qrlsh_recommend_topk).
+
+The batch form of the selection inside the reference's interactive prompt (recommender.py:357-375): for user u the
+eligible queries are those it has not rated and that have a non-zero prediction (`just_scored`, :361); the k with the
+largest predicted value come first, ties broken by query index ascending (the project's tie rule; the reference's
+np.argsort order among equal values is arbitrary)."""
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _ptr, _stream
+
+MAX_K = _lib.RECOMMEND_MAX_K
+MAX_SLICES = 256
+WORKSPACE_BUDGET = 1 << 30   # bytes of workspace per library call; larger user sets are served in row blocks
+
+
+def _matrix(x, name):
+    """2-D int32 view of a tensor / array / DataFrame; host data is checked to fit int32 (nothing is uploaded)"""
+    if isinstance(x, torch.Tensor):
+        if x.dim() != 2:
+            raise ValueError("%s must be 2-D, got shape %s" % (name, tuple(x.shape)))
+        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
+            raise ValueError("%s must hold integers, got %s" % (name, x.dtype))
+        return x
+    a = np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x)
+    if a.ndim != 2:
+        raise ValueError("%s must be 2-D, got shape %s" % (name, a.shape))
+    if a.dtype != np.int32:
+        if not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("%s must hold integers, got %s" % (name, a.dtype))
+        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+            raise ValueError("%s holds values outside int32" % name)
+    return a
+
+
+def _on_device(x, device):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32))
+    t = t.to(device=device, dtype=torch.int32).contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()   # the kernels read rows as 16-byte vectors from a 16-byte-aligned base
+    return t
+
+
+def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
+    """ratings: (nu, nq) utility matrix, 0 = unrated; predictions: (nu, nq) completed matrix (fill_predictions'
+    output, or compute_scores' DataFrame); tensors are used where they are, host data is uploaded as int32.
+    users: row ids to serve (any order, repeats allowed), default all rows in order.  lo: start of the value window
+    of the fast path (values outside [lo, lo + 4096) take the radix refinement; same result).  slices: column
+    slices per row (1 .. 256), 0 = chosen by the library.
+    -> (idx int32 (m, k), val int32 (m, k), avail int32 (m,)) device tensors: per requested user the query columns
+    with the largest predictions among its eligible cells (value descending, index ascending), their values, and
+    the number of eligible cells; idx -1 / val 0 past min(k, avail).
+    Raises ValueError for a bad k, slices or shape and for a user id outside [0, nu) (host ids are checked before
+    anything is uploaded; ids given as a device tensor through the library's per-row flag)."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
+        raise ValueError("k must be an integer in 1..%d, got %r" % (MAX_K, k))
+    k = int(k)
+    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= MAX_SLICES:
+        raise ValueError("slices must be an integer in 0..%d, got %r" % (MAX_SLICES, slices))
+    if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
+        raise ValueError("lo must be an int32, got %r" % (lo,))
+    r = _matrix(ratings, "ratings")
+    p = _matrix(predictions, "predictions")
+    if tuple(r.shape) != tuple(p.shape):
+        raise ValueError("ratings %s and predictions %s differ in shape" % (tuple(r.shape), tuple(p.shape)))
+    nu, nq = (int(d) for d in r.shape)
+    if nq >= 2**31:
+        raise ValueError("at most 2^31 - 1 queries per row")
+    check_flag = False
+    if users is None:
+        u = None
+        m = nu
+    elif isinstance(users, torch.Tensor):
+        if users.dim() != 1 or users.dtype.is_floating_point or users.dtype == torch.bool:
+            raise ValueError("users must be a 1-D integer tensor")
+        u = users
+        m = int(u.numel())
+        check_flag = True
+    else:
+        ua = np.asarray(users)
+        if ua.ndim != 1 or not (ua.size == 0 or np.issubdtype(ua.dtype, np.integer)):
+            raise ValueError("users must be a 1-D sequence of integer row ids")
+        if ua.size and (ua.min() < 0 or ua.max() >= nu):
+            raise ValueError("user id outside [0, %d)" % nu)
+        u = ua
+        m = int(ua.size)
+
+    lib = _lib.load()
+    rt, pt = _on_device(r, device), _on_device(p, device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=device)
+    val = torch.empty((m, k), dtype=torch.int32, device=device)
+    avail = torch.empty((m,), dtype=torch.int32, device=device)
+    if m == 0:
+        return idx, val, avail
+    blk = m
+    while blk > 1 and int(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices))) > WORKSPACE_BUDGET:
+        blk = (blk + 1) // 2
+    if u is None and blk < m:
+        u = torch.arange(nu, dtype=torch.int32, device=device)
+    ut = None if u is None else (u if isinstance(u, torch.Tensor) else torch.from_numpy(u.astype(np.int64)))
+    if ut is not None:   # ids past int32 must stay out of range, not wrap into it
+        ut = ut.to(device=device, dtype=torch.int64).clamp(-1, nu).to(torch.int32).contiguous()
+    ws = torch.empty((max(int(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices))), 16),), dtype=torch.uint8,
+                     device=device)
+    st = _stream()
+    for i0 in range(0, m, blk):
+        i1 = min(m, i0 + blk)
+        _lib.check(lib.qrlsh_recommend_topk(_ptr(rt), _ptr(pt), nu, nq, None if ut is None else _ptr(ut[i0:i1]),
+                                            i1 - i0, k, int(lo), int(slices), _ptr(idx[i0:i1]), _ptr(val[i0:i1]),
+                                            _ptr(avail[i0:i1]), _ptr(ws), ws.numel(), st))
+    if check_flag and bool((avail < 0).any().item()):
+        bad = int(torch.nonzero(avail < 0)[0, 0].item())
+        raise ValueError("user id %d (position %d) outside [0, %d)" % (int(u[bad].item()), bad, nu))
+    return idx, val, avail

@@ -232,6 +232,29 @@ class Recommender:
         scores_missed = np.array(np.where(finalPredictions == 0)).T
         return scores_to_predict, finalPredictions, scores_missed
 
+    # ---- recommendations (device): the selection of top_k_queries for many users at once --------------------------
+    def recommend(self, predictions, k, users=None):
+        """Top-k unrated queries of each requested user (default: every user), the batch form of the selection in
+        top_k_queries (recommender.py:357-375) on the device.  predictions: compute_scores' DataFrame, or an array /
+        tensor of the same shape; the unrated cells are those of self.ratings.
+        -> {u: {'indexes': int64[query columns, 0-based], 'values': int64[predicted values], 'available': int}}: the
+        eligible queries (unrated, non-zero prediction: just_scored of :361) with the largest values, value
+        descending then index ascending (the reference's order among equal values is np.argsort's, arbitrary);
+        'available' = len(just_scored), the prompt's [Max: N].  Raises ValueError for a bad k, shape or user id."""
+        from qrlsh import recommend as rec
+        pred = predictions.to_numpy() if hasattr(predictions, "to_numpy") else predictions
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        idx, val, avail = rec.top_k(self.ratings, pred, k, users=users, device=self.device)
+        idx, val, avail = ops.to_host(idx), ops.to_host(val), ops.to_host(avail)
+        ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
+        out = {}
+        for i, u in enumerate(ids):
+            n = min(int(k), int(avail[i]))
+            out[u] = {"indexes": idx[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
+                      "available": int(avail[i])}
+        return out
+
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
         """Interactive top-k prompt of recommender.py:345-381 (`ask` is injectable for tests)."""
         pred = predictions.to_numpy()
