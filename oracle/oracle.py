@@ -432,23 +432,40 @@ def weighted_average(ratings_row, indexes, values, summation=np_sum_order):
     return summation(ur * vals) / wsum
 
 
+def predict_cells(ratings, query_sims, user_sims, cells, summation=np_sum_order, query_weight=QUERY_WEIGHT,
+                  user_weight=USER_WEIGHT, default_mean=DEFAULT_MEAN):
+    """finalPredictions[i][j] of compute_scores (recommender.py:301-331) for each listed cell (i, j): a rated
+    cell keeps its rating; a zero cell gets round(...) of the blend of the query-side and user-side weighted
+    averages (Python round = half to even), in the reference's operand order.  Only the listed cells are
+    computed, so a large matrix can be checked on a sample.  -> int64 [len(cells)]"""
+    ratings = np.asarray(ratings)
+    cells = np.asarray(cells, dtype=np.int64).reshape(-1, 2)
+    out = np.empty(len(cells), dtype=np.int64)
+    for c, (i, j) in enumerate(cells.tolist()):
+        own = ratings[i, j]
+        if own != 0:
+            out[c] = own
+            continue
+        qp = 0.0
+        if j in query_sims:
+            qp = weighted_average(ratings[i], query_sims[j]["indexes"], query_sims[j]["values"], summation)
+        up = weighted_average(ratings[:, j], user_sims[i]["indexes"], user_sims[i]["values"], summation)
+        if up == 0 and qp == 0:
+            out[c] = 0
+        elif up == 0:
+            out[c] = round(qp * (query_weight + (user_weight * 0.5)) + default_mean * (user_weight * 0.5))
+        elif qp == 0:
+            out[c] = round(up * (user_weight + (query_weight * 0.5)) + default_mean * (query_weight * 0.5))
+        else:
+            out[c] = round(qp * query_weight + up * user_weight)
+    return out
+
+
 def predict_scores(ratings, query_sims, user_sims, summation=np_sum_order):
-    """The hybrid loop of compute_scores, recommender.py:301-331: every zero cell (i, j) gets
-    round(...) of the blend of the query-side and user-side weighted averages (Python round =
-    half to even).  -> int64 matrix like `finalPredictions`."""
+    """The hybrid loop of compute_scores, recommender.py:301-331, over the whole matrix: every zero cell (i, j)
+    gets predict_cells' value.  -> int64 matrix like `finalPredictions`."""
     ratings = np.asarray(ratings)
     final = ratings.astype(np.int64).copy()
-    for i, j in np.array(np.where(ratings == 0)).T:
-        qp = 0.0
-        if int(j) in query_sims:
-            qp = weighted_average(ratings[i], query_sims[int(j)]["indexes"], query_sims[int(j)]["values"], summation)
-        up = weighted_average(ratings.T[j], user_sims[int(i)]["indexes"], user_sims[int(i)]["values"], summation)
-        if up == 0 and qp == 0:
-            final[i][j] = 0
-        elif up == 0:
-            final[i][j] = round(qp * (QUERY_WEIGHT + (USER_WEIGHT * 0.5)) + DEFAULT_MEAN * (USER_WEIGHT * 0.5))
-        elif qp == 0:
-            final[i][j] = round(up * (USER_WEIGHT + (QUERY_WEIGHT * 0.5)) + DEFAULT_MEAN * (QUERY_WEIGHT * 0.5))
-        else:
-            final[i][j] = round(qp * QUERY_WEIGHT + up * USER_WEIGHT)
+    zero = np.array(np.where(ratings == 0)).T
+    final[zero[:, 0], zero[:, 1]] = predict_cells(ratings, query_sims, user_sims, zero, summation)
     return final

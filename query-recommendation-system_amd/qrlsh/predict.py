@@ -41,7 +41,11 @@ def fill_predictions(ratings, q_src, q_dst, q_milli, user_sims, query_weight=QUE
     q_off = torch.zeros((nq + 1,), dtype=torch.int64, device=device)
     torch.cumsum(counts, dim=0, out=q_off[1:])
     q_idx = q_dst.to(device).to(torch.int32).contiguous()
-    q_val = (q_milli.to(device).to(torch.float64) / 1000.0).contiguous()
+    # milli / 1000 correctly rounded, as the reference's np.around values are.  The divisor is a device tensor: with
+    # a Python-scalar divisor torch's GPU kernel multiplies by the reciprocal, which is an ulp off for 144 of the
+    # 1001 milli values and moves predictions that lie on the edge of a rounding step.
+    thousand = torch.full((), 1000.0, dtype=torch.float64, device=device)
+    q_val = (q_milli.to(device).to(torch.float64) / thousand).contiguous()
     ku = max((len(user_sims[u]["indexes"]) for u in user_sims), default=0)
     if ku > MAX_NEIGHBOURS:
         raise ValueError("a user has %d neighbours; the prediction kernel handles at most %d" % (ku, MAX_NEIGHBOURS))

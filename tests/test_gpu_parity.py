@@ -1827,7 +1827,10 @@ def test_prediction_row_form_stages_the_row_in_lds_or_reads_it_from_memory():
     """the sweep's row form (one workgroup per user slice, the user's row staged in LDS as bytes) against the
     oracle and against the CSR-form kernel, on rows that span several workgroup strides and slices; ratings beyond
     255 (not the reference's domain, but legal int32 input) make a workgroup read its row from memory instead --
-    in some rows only, in all rows -- with the same results"""
+    in some rows only, in all rows -- with the same results.  The user lists here are at most 6 long, so
+    variant 0 (every rating fits a byte) runs the tile form, not the row form; variants 1 and 2 make the tile
+    form stand down and the row form run.  tests/test_gpu_predict.py reaches the LDS row form with padded user
+    lists."""
     from qrlsh import predict
     rng = np.random.default_rng(77)
     ratings, qs, us, coo = _random_prediction_case(rng, 12, 3000, 20, 6, 0.6)
