@@ -1,7 +1,9 @@
 /*
  * qrlsh.h -- C ABI of libqrlsh.so, the MI355X (gfx950) implementation of the
  * MinHash-LSH candidate-generation + pair-scoring hot path of
- * wamuumu/query-recommendation-system (lsh.py, recommender.py:105-214).
+ * wamuumu/query-recommendation-system (lsh.py, recommender.py:105-214), the steps around it (answer sets, the
+ * prediction loop, user similarity, recommendations), and the serving of queries that were not in the indexed set
+ * (qrlsh_index_*, qrlsh_predict_columns).
  *
  * The reference is pure Python and has no FFI of its own; this header is the
  * boundary its Python call surface (lsh.LSH, Recommender.compute_signatures /
@@ -427,6 +429,65 @@ int qrlsh_predict(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t 
                   int32_t ku, double query_weight, double user_weight, double default_mean,
                   int32_t sum_order, int32_t *out, uint32_t *too_long_out, int32_t kq, void *workspace,
                   size_t workspace_bytes, void *stream);
+
+/* Column prediction for NEW queries (not columns of the matrix): x has no ratings, so the user side of every cell
+ * (u, x) is 0 (recommender.py:320 over an all-zero column) and
+ *     out[x][u] = qp == 0 ? 0 : round(qp * (query_weight + user_weight * 0.5) + default_mean * (user_weight * 0.5)),
+ *     qp = weighted_average(ratings[u], idx[off[x] ..), milli[off[x] ..) / 1000.0)
+ * -- qrlsh_predict's cell of a zero column appended to the matrix, same arithmetic (float64, no FMA, half to even, the
+ * similarity a true division, both sum orders).  ratings int32 [nu][nq]; x's neighbour list in CSR form (off[m+1],
+ * idx in [0, nq), milli) as qrlsh_index_probe_finish writes it; out int32 [m][nu] (query-major: the rows
+ * qrlsh_recommend_topk reads for the users of each new query).  *flags_out (device uint32, required) = 0, or bit 0:
+ * a list is longer than 64 entries, bit 1: an index outside [0, nq); such a list is never walked, its row gets 0
+ * and the result is not to be used -- the caller reads the flags back.  nu <= 65535 * 256. */
+int qrlsh_predict_columns(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *off, const int32_t *idx,
+                          const int32_t *milli, int64_t m, double query_weight, double user_weight, double default_mean,
+                          int32_t sum_order, int32_t *out, uint32_t *flags_out, void *stream);
+
+/* ---- serving new queries: a band-key index of a finished run, probed many times ---------------------------------
+ * The neighbours a query x that was NOT in the indexed set gets (LSH.get_candidates, lsh.py:40-55, and
+ * recommender.py:187-214 for x appended alone, K held fixed): its candidates are the indexed ids that share with x a
+ * band whose r = P / b values are equal after the int16 cast and not all -1 (65535 counts as -1); each once, however
+ * many bands it shares.  Score: milli = rint(1000 * dot / (sqrt(na) * sqrt(nb))), qrlsh_score_pairs bit for bit.
+ * List: the K best candidates by milli descending, then id ascending.  New queries never see each other, so a
+ * query's result does not depend on the batch around it.
+ *   build: keys [b][n] (band keys of the n indexed queries: qrlsh_band_keys / qrlsh_minhash keys_out, or the
+ *     caller's own -- keys only filter, every candidate is checked against the rows) are sorted in place per band with
+ *     their ids (ids [b][n] uint32 output; keys_tmp / ids_tmp scratch of the same size; qrlsh_sort_u64 over the top
+ *     32 bits of mix64(key), workspace qrlsh_index_build_workspace_bytes) and dir_out (qrlsh_index_dir_words uint32)
+ *     receives a per-band directory over the top qrlsh_index_dir_bits(n) bits of mix64(key).  n < 2^32 - 1.
+ *   probe count / fill: probe_keys [b][m] of the new queries' signatures (same key rule as the index).  count
+ *     leaves the number of raw candidate words in *total_out (device uint64) and per-(query, band) offsets in
+ *     `workspace` (qrlsh_index_probe_workspace_bytes(m, b)); fill writes them: raw_out[*] = (q * b + band) << 32 | id,
+ *     duplicates across bands included.  m * b < 2^32.
+ *   finish: dedupe, verify and score the raw words against the rows (sig / norm2 of the index, probe_sig /
+ *     probe_norm2 of the new queries, one sig_dtype for both; a norm may be NULL: summed from the rows), select and
+ *     cut.  probe_workspace: the workspace count / fill used; workspace: qrlsh_index_finish_workspace_bytes(m, K,
+ *     n_raw).  Outputs: off_out int64 [m+1] (CSR), idx_out / milli_out int32 [m * K] capacity (off_out[m] used),
+ *     avail_out int32 [m] = number of distinct candidates before the cut.  1 <= K <= 256 (QRLSH_EINVAL otherwise).
+ *     Lists of up to 4096 raw words are selected in one LDS image; longer ones (a popular key) stream through it,
+ *     decided on the device.  Afterwards the first n_raw uint64 words of `workspace` hold, per raw word, its
+ *     select key (1000 - milli) << 32 | id, or ~0 for a word dropped as a duplicate or a key collision: every
+ *     candidate uncut (LSH.query reads them). */
+int32_t qrlsh_index_dir_bits(int64_t n);
+size_t qrlsh_index_dir_words(int64_t n, int32_t b);
+size_t qrlsh_index_build_workspace_bytes(int64_t n, int32_t b);
+int qrlsh_index_build(uint64_t *keys, uint64_t *keys_tmp, uint32_t *ids, uint32_t *ids_tmp, int64_t n, int32_t b,
+                      uint32_t *dir_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t qrlsh_index_probe_workspace_bytes(int64_t m, int32_t b);
+int qrlsh_index_probe_count(const uint64_t *sorted_keys, const uint32_t *dir, int64_t n, int32_t b, int32_t r,
+                            const uint64_t *probe_keys, int64_t m, void *workspace, size_t workspace_bytes,
+                            uint64_t *total_out, void *stream);
+int qrlsh_index_probe_fill(const uint64_t *sorted_keys, const uint32_t *sorted_ids, const uint32_t *dir, int64_t n,
+                           int32_t b, int32_t r, const uint64_t *probe_keys, int64_t m, const void *workspace,
+                           size_t workspace_bytes, uint64_t *raw_out, void *stream);
+size_t qrlsh_index_finish_workspace_bytes(int64_t m, int32_t K, int64_t n_raw);
+int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                             const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
+                             const void *probe_workspace, const uint64_t *raw, int64_t n_raw, int32_t K,
+                             int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
+                             void *workspace, size_t workspace_bytes, void *stream);
+#define QRLSH_INDEX_MAX_K 256
 
 /* ---- recommendations: top-k unrated queries per user (the consumer of N1's output) ---------------------
  * Replaces the selection of the interactive prompt, recommender.py:357-375 (just_scored of :361, the argsort of

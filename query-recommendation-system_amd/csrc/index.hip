@@ -1,0 +1,469 @@
+// index.hip -- serving new queries: a band-key index built once from a finished hot-path run, probed many times.
+//
+// Reference: LSH.get_candidates (lsh.py:40-55) and the neighbour lists of compute_querySimilarities
+// (recommender.py:187-214) for a query x that was NOT in the indexed set: its candidates are the indexed ids that
+// share with it a band whose r int16 values are equal and not all -1, its list the top K of them by rounded cosine.
+//
+//   build:  per band, (key, id) sorted by the top 32 bits of mix64(key) (qrlsh_sort_u64, QRLSH_SORT_MIX, 4 passes;
+//           equal keys adjacent up to 32-bit mix collisions, ids ascending) and a directory over the top d bits of
+//           mix64(key): dir[t][h] = first position of band t whose mix bits are >= h.
+//   probe:  one lane per (new query, band): two directory words, a binary search for the run of equal top-32 mix
+//           bits, then a full-key compare over that run (a run longer than IX_SERIAL records -- a popular key -- is
+//           scanned by the whole wave).  count -> exclusive scan -> fill writes the raw candidate words
+//           (q * b + band) << 32 | id, duplicates across bands included.
+//   finish: one lane per raw word checks the candidate's row against the probe's row band by band and keeps the
+//           word only if its band is the FIRST band with equal, non-empty int16 values.  That one test drops
+//           duplicates (a candidate is kept once, at its first shared band), verifies hashed keys of wide bands and
+//           drops caller keys that collide, with no sort.  The same pass computes the exact integer dot product
+//           and score.hip's expression milli = rint(dot / (sqrt(na) * sqrt(nb)) * 1000).  A kept word becomes the
+//           key (1000 - milli) << 32 | id.  Then one workgroup per new query streams its keys through an LDS
+//           image of IX_CAP keys.  Keys below the current K-th are appended; a full image is sorted and cut to K.
+//           Short lists take one pass and one sort, long lists (a popular key) several; the route is decided on
+//           the device.  An exclusive scan of min(K, avail) gives the CSR offsets, and a compaction writes the
+//           lists.
+#include "common.h"
+
+constexpr int IX_MAXK = 256;    // longest neighbour list a probe returns
+constexpr int IX_CAP = 4096;    // keys in the LDS image of the per-query select (32 KB)
+constexpr int IX_SERIAL = 32;   // runs of equal mix bits longer than this are scanned by the whole wave
+
+// directory bits for n indexed queries: about 4 - 8 records per directory entry, so the directory is 1/2 - 1/4 of
+// a word per record (<= 1/24 of the 12 bytes of key + id the band holds) and a probe's run is found in ~3 steps
+QRLSH_EXPORT int32_t qrlsh_index_dir_bits(int64_t n) {
+  int lg = 0;
+  while (lg < 62 && (1ll << lg) < n) ++lg;
+  int d = lg - 3;
+  if (d < 1) d = 1;
+  if (d > 26) d = 26;
+  return d;
+}
+
+QRLSH_EXPORT size_t qrlsh_index_dir_words(int64_t n, int32_t b) {
+  if (n < 0 || b <= 0) return 0;
+  return (size_t)b * (((size_t)1 << qrlsh_index_dir_bits(n)) + 1);
+}
+
+QRLSH_EXPORT size_t qrlsh_index_build_workspace_bytes(int64_t n, int32_t b) { return qrlsh_sort_workspace_bytes(n, b); }
+
+// dir[t][h] = first position of sorted band t whose top d mix bits are >= h, h = 0 .. 2^d (dir[t][2^d] = n)
+__global__ __launch_bounds__(256) void index_dir_kernel(const uint64_t *__restrict__ keys, int64_t n, int d,
+                                                        uint32_t *__restrict__ dir) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int64_t t = blockIdx.y;
+  const uint64_t *k = keys + t * n;
+  uint32_t *dr = dir + t * ((1ll << d) + 1);
+  const int64_t h = (int64_t)(qr_mix64(k[i]) >> (64 - d));
+  const int64_t hp = i == 0 ? -1 : (int64_t)(qr_mix64(k[i - 1]) >> (64 - d));
+  for (int64_t x = hp + 1; x <= h; ++x) dr[x] = (uint32_t)i;
+  if (i == n - 1)
+    for (int64_t x = h + 1; x <= (1ll << d); ++x) dr[x] = (uint32_t)n;
+}
+
+QRLSH_EXPORT int qrlsh_index_build(uint64_t *keys, uint64_t *keys_tmp, uint32_t *ids, uint32_t *ids_tmp, int64_t n,
+                                   int32_t b, uint32_t *dir_out, void *workspace, size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && b > 0 && b <= 65535, "qrlsh_index_build: bad sizes n=%lld b=%d",
+               (long long)n, b);
+  QR_CHECK_ARG(dir_out, "qrlsh_index_build: null directory");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    if (hipMemsetAsync(dir_out, 0, qrlsh_index_dir_words(n, b) * sizeof(uint32_t), st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_index_build: hipMemsetAsync failed");
+      return QRLSH_EHIP;
+    }
+    return QRLSH_OK;
+  }
+  QR_CHECK_ARG(keys && keys_tmp && ids && ids_tmp, "qrlsh_index_build: null pointer");
+  const int rc = qrlsh_sort_u64(keys, keys_tmp, ids, ids_tmp, n, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0,
+                                workspace, workspace_bytes, stream);
+  if (rc < 0) return rc;
+  if (rc == 1) {  // the result is always left in keys / ids
+    if (hipMemcpyAsync(keys, keys_tmp, (size_t)b * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(ids, ids_tmp, (size_t)b * n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_index_build: hipMemcpyAsync failed");
+      return QRLSH_EHIP;
+    }
+  }
+  const int d = qrlsh_index_dir_bits(n);
+  QR_LAUNCH("index_dir", index_dir_kernel, dim3((unsigned)ceil_div64(n, 256), (unsigned)b), dim3(256), 0, st,
+            (const uint64_t *)keys, n, d, dir_out);
+  QR_LAUNCH_CHECK("qrlsh_index_build");
+  return QRLSH_OK;
+}
+
+// ---- probe: count / fill ------------------------------------------------------------------------------------------
+__device__ static inline uint32_t ix_top32(uint64_t k) { return (uint32_t)(qr_mix64(k) >> 32); }
+
+// [a, e): the records of band bk whose top 32 mix bits equal those of key
+__device__ static inline void ix_run(const uint64_t *bk, const uint32_t *bdir, int d, uint64_t key, uint32_t &a,
+                                     uint32_t &e) {
+  const uint64_t h = qr_mix64(key);
+  const uint64_t slot = h >> (64 - d);
+  const uint32_t T = (uint32_t)(h >> 32);
+  uint32_t L = bdir[slot], R = bdir[slot + 1];
+  const uint32_t hi = R;
+  while (L < R) {
+    const uint32_t mid = L + (R - L) / 2;
+    if (ix_top32(bk[mid]) < T) L = mid + 1;
+    else R = mid;
+  }
+  a = L;
+  R = hi;
+  while (L < R) {
+    const uint32_t mid = L + (R - L) / 2;
+    if (ix_top32(bk[mid]) <= T) L = mid + 1;
+    else R = mid;
+  }
+  e = L;
+}
+
+// one lane per g = q * b + t (new query q, band t).  count: cnt[g] = records of band t with key == probe key;
+// fill: the same records, raw[cnt[g] + c] = g << 32 | id (cnt = exclusive scan)
+template <bool FILL>
+__global__ __launch_bounds__(256) void index_probe_kernel(const uint64_t *__restrict__ skeys,
+                                                          const uint32_t *__restrict__ sids, int64_t n, int b, int r,
+                                                          int d, const uint32_t *__restrict__ dir,
+                                                          const uint64_t *__restrict__ pkeys, int64_t m,
+                                                          uint64_t *__restrict__ cnt, uint64_t *__restrict__ raw) {
+  const int lane = lane_id();
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = g < m * b;
+  const int64_t q = live ? g / b : 0;
+  const int t = live ? (int)(g - q * b) : 0;
+  const uint64_t key = live ? pkeys[(int64_t)t * m + q] : 0;
+  const bool act = live && key != qr_empty_key(r);
+  const int64_t dw = (1ll << d) + 1;
+  uint32_t a = 0, e = 0;
+  if (act) ix_run(skeys + (int64_t)t * n, dir + (int64_t)t * dw, d, key, a, e);
+  const uint64_t pos = (FILL && live) ? cnt[g] : 0;
+  const uint64_t tag = (uint64_t)g << 32;
+  uint64_t c = 0;
+  const bool longrun = act && e - a > (uint32_t)IX_SERIAL;
+  if (act && !longrun) {
+    const uint64_t *bk = skeys + (int64_t)t * n;
+    const uint32_t *bi = sids + (int64_t)t * n;
+    for (uint32_t x = a; x < e; ++x)
+      if (bk[x] == key) {
+        if (FILL) raw[pos + c] = tag | bi[x];
+        ++c;
+      }
+  }
+  // popular keys: the wave takes the long runs of its lanes one after the other, 64 records per step
+  uint64_t lm = __ballot(longrun);
+  while (lm) {
+    const int src = __ffsll((long long)lm) - 1;
+    lm &= lm - 1;
+    const uint32_t ra = __shfl(a, src, WAVE), re = __shfl(e, src, WAVE);
+    const uint64_t rk = __shfl(key, src, WAVE);
+    const int rt = __shfl(t, src, WAVE);
+    const uint64_t rpos = __shfl(pos, src, WAVE), rtag = __shfl(tag, src, WAVE);
+    const uint64_t *bk = skeys + (int64_t)rt * n;
+    const uint32_t *bi = sids + (int64_t)rt * n;
+    uint64_t rc = 0;
+    for (uint32_t x0 = ra; x0 < re; x0 += WAVE) {
+      const uint32_t x = x0 + lane;
+      const bool hit = x < re && bk[x] == rk;
+      const uint64_t hm = __ballot(hit);
+      if (FILL && hit) raw[rpos + rc + __popcll(hm & ((1ull << lane) - 1))] = rtag | bi[x];
+      rc += __popcll(hm);
+    }
+    if (lane == src) c = rc;
+  }
+  if (!FILL && live) cnt[g] = c;
+}
+
+// workspace: cnt / offsets u64 [m * b + 1] | scan sums
+QRLSH_EXPORT size_t qrlsh_index_probe_workspace_bytes(int64_t m, int32_t b) {
+  if (m <= 0 || b <= 0) return 0;
+  const int64_t mb = m * b;
+  return (size_t)(mb + 1) * sizeof(uint64_t) + (size_t)(ceil_div64(mb, SCANL_CHUNK) + 1) * sizeof(uint64_t);
+}
+
+static int probe_args(const char *who, const uint64_t *skeys, const uint32_t *dir, int64_t n, int32_t b, int32_t r,
+                      const uint64_t *pkeys, int64_t m, const void *workspace, size_t workspace_bytes) {
+  QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && b > 0 && b <= 65535 && r > 0 && m >= 0, "%s: bad sizes n=%lld b=%d r=%d m=%lld",
+               who, (long long)n, b, r, (long long)m);
+  QR_CHECK_ARG(m * (int64_t)b < (1ll << 32), "%s: m * b = %lld must stay below 2^32", who, (long long)(m * (int64_t)b));
+  if (m == 0) return QRLSH_OK;
+  QR_CHECK_ARG(pkeys && workspace && (n == 0 || (skeys && dir)), "%s: null pointer", who);
+  if (workspace_bytes < qrlsh_index_probe_workspace_bytes(m, b)) {
+    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, qrlsh_index_probe_workspace_bytes(m, b));
+    return QRLSH_EWORKSPACE;
+  }
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_index_probe_count(const uint64_t *sorted_keys, const uint32_t *dir, int64_t n, int32_t b, int32_t r,
+                                         const uint64_t *probe_keys, int64_t m, void *workspace, size_t workspace_bytes,
+                                         uint64_t *total_out, void *stream) {
+  QR_CHECK_ARG(total_out, "qrlsh_index_probe_count: null total_out");
+  const int rc = probe_args("qrlsh_index_probe_count", sorted_keys, dir, n, b, r, probe_keys, m, workspace, workspace_bytes);
+  if (rc != QRLSH_OK) return rc;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (m == 0) {
+    if (hipMemsetAsync(total_out, 0, sizeof(uint64_t), st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_index_probe_count: hipMemsetAsync failed");
+      return QRLSH_EHIP;
+    }
+    return QRLSH_OK;
+  }
+  const int64_t mb = m * b;
+  uint64_t *cnt = static_cast<uint64_t *>(workspace);
+  uint64_t *sums = cnt + mb + 1;
+  if (n == 0) {
+    if (hipMemsetAsync(cnt, 0, (size_t)(mb + 1) * sizeof(uint64_t), st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_index_probe_count: hipMemsetAsync failed");
+      return QRLSH_EHIP;
+    }
+  } else {
+    QR_LAUNCH("index_probe_count", index_probe_kernel<false>, dim3((unsigned)ceil_div64(mb, 256)), dim3(256), 0, st,
+              sorted_keys, nullptr, n, b, r, qrlsh_index_dir_bits(n), dir, probe_keys, m, cnt, nullptr);
+    qr_scan_u64(cnt, mb, cnt + mb, sums, st);
+  }
+  if (hipMemcpyAsync(total_out, cnt + mb, sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_index_probe_count: hipMemcpyAsync failed");
+    return QRLSH_EHIP;
+  }
+  QR_LAUNCH_CHECK("qrlsh_index_probe_count");
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_index_probe_fill(const uint64_t *sorted_keys, const uint32_t *sorted_ids, const uint32_t *dir,
+                                        int64_t n, int32_t b, int32_t r, const uint64_t *probe_keys, int64_t m,
+                                        const void *workspace, size_t workspace_bytes, uint64_t *raw_out, void *stream) {
+  const int rc = probe_args("qrlsh_index_probe_fill", sorted_keys, dir, n, b, r, probe_keys, m, workspace, workspace_bytes);
+  if (rc != QRLSH_OK) return rc;
+  if (m == 0 || n == 0) return QRLSH_OK;
+  QR_CHECK_ARG(sorted_ids && raw_out, "qrlsh_index_probe_fill: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int64_t mb = m * b;
+  QR_LAUNCH("index_probe_fill", index_probe_kernel<true>, dim3((unsigned)ceil_div64(mb, 256)), dim3(256), 0, st,
+            sorted_keys, sorted_ids, n, b, r, qrlsh_index_dir_bits(n), dir, probe_keys, m,
+            static_cast<uint64_t *>(const_cast<void *>(workspace)), raw_out);
+  QR_LAUNCH_CHECK("qrlsh_index_probe_fill");
+  return QRLSH_OK;
+}
+
+// ---- finish: dedupe + verify + score, select, cut ------------------------------------------------------------------
+__device__ static inline int64_t ix_val(int32_t v) { return v; }
+__device__ static inline int64_t ix_val(uint16_t v) { return v == 0xFFFFu ? -1 : (int64_t)v; }
+
+// one lane per raw word g << 32 | id: key (1000 - milli) << 32 | id if band g % b is the first band the two rows
+// share, else ~0 (a duplicate, or a key collision)
+template <typename SigT>
+__global__ __launch_bounds__(256) void index_score_kernel(const SigT *__restrict__ sig, const int64_t *__restrict__ norm2,
+                                                          int64_t n, const SigT *__restrict__ psig,
+                                                          const int64_t *__restrict__ pnorm2, int P, int b, int64_t m,
+                                                          const uint64_t *__restrict__ raw, int64_t n_raw,
+                                                          uint64_t *__restrict__ keys_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_raw) return;
+  const uint64_t w = raw[i];
+  const uint32_t id = (uint32_t)w;
+  const int64_t g = (int64_t)(w >> 32);
+  const int64_t q = g / b;
+  const int t = (int)(g - q * b);
+  if ((int64_t)id >= n || q >= m) {  // not a word the fill pass writes
+    keys_out[i] = ~0ull;
+    return;
+  }
+  const SigT *a = sig + (int64_t)id * P;
+  const SigT *c = psig + q * P;
+  const int r = P / b;
+  int first = -1;
+  int64_t dot = 0, na = 0, nb = 0;
+  for (int band = 0; band < b; ++band) {
+    bool eq = true, empty = true;
+    for (int k = 0; k < r; ++k) {
+      const SigT x = a[band * r + k], y = c[band * r + k];
+      const uint32_t ux = (uint32_t)x & 0xFFFFu, uy = (uint32_t)y & 0xFFFFu;
+      eq &= ux == uy;
+      empty &= ux == 0xFFFFu;
+      const int64_t vx = ix_val(x), vy = ix_val(y);
+      dot += vx * vy;
+      na += vx * vx;
+      nb += vy * vy;
+    }
+    if (first < 0 && eq && !empty) {
+      first = band;
+      if (first != t) break;  // not this word's band: dropped, no score needed
+    }
+  }
+  if (first != t) {
+    keys_out[i] = ~0ull;
+    return;
+  }
+  if (norm2) na = norm2[id];
+  if (pnorm2) nb = pnorm2[q];
+  double cs = 0.0;
+  if (na != 0 && nb != 0) cs = (double)dot / (sqrt((double)na) * sqrt((double)nb));
+  const int32_t mi = (int32_t)rint(cs * 1000.0);
+  keys_out[i] = ((uint64_t)(uint32_t)(1000 - mi) << 32) | id;
+}
+
+// exclusive prefix of p over the 256-thread block; *total = number of p
+__device__ static inline uint32_t ix_block_prefix(bool p, uint32_t *wc, uint32_t *total) {
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const uint64_t bal = __ballot(p);
+  if (lane == 0) wc[w] = (uint32_t)__popcll(bal);
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    if (k < w) base += wc[k];
+    tot += wc[k];
+  }
+  __syncthreads();
+  *total = tot;
+  return base + (uint32_t)__popcll(bal & ((1ull << lane) - 1));
+}
+
+// ascending bitonic sort of buf[0 .. cnt) (padded to a power of two with ~0)
+__device__ static inline void ix_sort(uint64_t *buf, uint32_t cnt) {
+  uint32_t n2 = 2;
+  while (n2 < cnt) n2 <<= 1;
+  for (uint32_t x = cnt + threadIdx.x; x < n2; x += blockDim.x) buf[x] = ~0ull;
+  __syncthreads();
+  for (uint32_t k = 2; k <= n2; k <<= 1)
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t x = threadIdx.x; x < n2; x += blockDim.x) {
+        const uint32_t y = x ^ j;
+        if (y > x) {
+          const uint64_t u = buf[x], v = buf[y];
+          if ((u > v) == ((x & k) == 0)) {
+            buf[x] = v;
+            buf[y] = u;
+          }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// one workgroup per new query: the K smallest keys of its raw segment (and how many were kept) -> pidx / pmilli [m][K],
+// avail[q], cut[q] = min(K, avail)
+__global__ __launch_bounds__(256) void index_select_kernel(const uint64_t *__restrict__ keys,
+                                                           const uint64_t *__restrict__ seg, int b, int K,
+                                                           int32_t *__restrict__ pidx, int32_t *__restrict__ pmilli,
+                                                           int32_t *__restrict__ avail, uint64_t *__restrict__ cut) {
+  __shared__ uint64_t buf[IX_CAP];
+  __shared__ uint32_t wc[4];
+  const int64_t q = blockIdx.x;
+  const uint64_t s0 = seg[q * b], s1 = seg[(q + 1) * b];
+  uint32_t fill = 0;            // uniform
+  uint64_t thresh = ~0ull;      // uniform: keys at or above it cannot make the cut
+  uint32_t kept = 0;
+  for (uint64_t base = s0; base < s1; base += blockDim.x) {
+    const uint64_t x = base + threadIdx.x;
+    const uint64_t v = x < s1 ? keys[x] : ~0ull;
+    kept += v != ~0ull;
+    bool take = v < thresh;
+    uint32_t ns;
+    uint32_t pos = ix_block_prefix(take, wc, &ns);
+    if (fill + ns > (uint32_t)IX_CAP) {  // the image is full: keep its K best, raise the bar
+      ix_sort(buf, fill);
+      fill = fill < (uint32_t)K ? fill : (uint32_t)K;
+      if (fill == (uint32_t)K) thresh = buf[K - 1];
+      __syncthreads();
+      take = v < thresh;
+      pos = ix_block_prefix(take, wc, &ns);
+    }
+    if (take) buf[fill + pos] = v;
+    fill += ns;
+    __syncthreads();
+  }
+  ix_sort(buf, fill);
+  const uint32_t nout = fill < (uint32_t)K ? fill : (uint32_t)K;
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    const bool in = (uint32_t)k < nout;
+    const uint64_t v = buf[in ? k : 0];
+    pidx[q * K + k] = in ? (int32_t)(uint32_t)v : -1;
+    pmilli[q * K + k] = in ? 1000 - (int32_t)(v >> 32) : 0;
+  }
+  // kept total: a wave sum, then the block's (ix_sort ended on a barrier: wc is free)
+  uint32_t s = kept;
+#pragma unroll
+  for (int o = 1; o < WAVE; o <<= 1) s += __shfl_xor(s, o, WAVE);
+  if (lane_id() == 0) wc[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const uint32_t all = wc[0] + wc[1] + wc[2] + wc[3];
+    avail[q] = (int32_t)all;
+    cut[q] = nout;
+  }
+}
+
+// lists of the padded [m][K] image -> CSR at off[q]
+__global__ __launch_bounds__(256) void index_compact_kernel(const int32_t *__restrict__ pidx,
+                                                            const int32_t *__restrict__ pmilli, int64_t m, int K,
+                                                            const int64_t *__restrict__ off, int32_t *__restrict__ idx,
+                                                            int32_t *__restrict__ milli) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= m * K) return;
+  const int64_t q = g / K, k = g - q * K;
+  const int64_t lo = off[q];
+  if (k < off[q + 1] - lo) {
+    idx[lo + k] = pidx[g];
+    milli[lo + k] = pmilli[g];
+  }
+}
+
+static inline size_t ix_al16(size_t x) { return (x + 15) / 16 * 16; }
+
+// workspace: keys u64 [n_raw] | pidx i32 [m][K] | pmilli i32 [m][K] | scan sums
+QRLSH_EXPORT size_t qrlsh_index_finish_workspace_bytes(int64_t m, int32_t K, int64_t n_raw) {
+  if (m <= 0 || K <= 0 || K > IX_MAXK || n_raw < 0) return 0;
+  return ix_al16((size_t)n_raw * 8) + 2 * ix_al16((size_t)m * K * 4) + (size_t)(ceil_div64(m, SCANL_CHUNK) + 1) * 8;
+}
+
+QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                                          const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
+                                          const void *probe_workspace, const uint64_t *raw, int64_t n_raw, int32_t K,
+                                          int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
+                                          void *workspace, size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(K >= 1 && K <= IX_MAXK, "qrlsh_index_probe_finish: K=%d not in [1, %d]", K, IX_MAXK);
+  QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && m >= 0 && n_raw >= 0 && P > 0 && b > 0 && b <= 65535 && P % b == 0,
+               "qrlsh_index_probe_finish: bad sizes n=%lld m=%lld n_raw=%lld P=%d b=%d", (long long)n, (long long)m,
+               (long long)n_raw, P, b);
+  QR_CHECK_ARG(m * (int64_t)b < (1ll << 32), "qrlsh_index_probe_finish: m * b must stay below 2^32");
+  QR_CHECK_ARG(sig_dtype == QRLSH_SIG_I32 || sig_dtype == QRLSH_SIG_U16, "qrlsh_index_probe_finish: bad sig_dtype %d",
+               sig_dtype);
+  QR_CHECK_ARG(off_out, "qrlsh_index_probe_finish: null off_out");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (m == 0) {
+    if (hipMemsetAsync(off_out, 0, sizeof(int64_t), st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_index_probe_finish: hipMemsetAsync failed");
+      return QRLSH_EHIP;
+    }
+    return QRLSH_OK;
+  }
+  QR_CHECK_ARG(probe_workspace && idx_out && milli_out && avail_out && workspace && (n_raw == 0 || (sig && probe_sig && raw)),
+               "qrlsh_index_probe_finish: null pointer");
+  if (workspace_bytes < qrlsh_index_finish_workspace_bytes(m, K, n_raw)) {
+    qrlsh_set_error("qrlsh_index_probe_finish: workspace %zu < %zu bytes", workspace_bytes,
+                    qrlsh_index_finish_workspace_bytes(m, K, n_raw));
+    return QRLSH_EWORKSPACE;
+  }
+  char *ws = static_cast<char *>(workspace);
+  uint64_t *keys = reinterpret_cast<uint64_t *>(ws);
+  int32_t *pidx = reinterpret_cast<int32_t *>(ws + ix_al16((size_t)n_raw * 8));
+  int32_t *pmilli = reinterpret_cast<int32_t *>(ws + ix_al16((size_t)n_raw * 8) + ix_al16((size_t)m * K * 4));
+  uint64_t *sums = reinterpret_cast<uint64_t *>(ws + ix_al16((size_t)n_raw * 8) + 2 * ix_al16((size_t)m * K * 4));
+  if (n_raw > 0) {
+    const dim3 grid((unsigned)ceil_div64(n_raw, 256)), block(256);
+    if (sig_dtype == QRLSH_SIG_U16)
+      QR_LAUNCH("index_score", index_score_kernel<uint16_t>, grid, block, 0, st, static_cast<const uint16_t *>(sig), norm2, n,
+                static_cast<const uint16_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, keys);
+    else
+      QR_LAUNCH("index_score", index_score_kernel<int32_t>, grid, block, 0, st, static_cast<const int32_t *>(sig), norm2, n,
+                static_cast<const int32_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, keys);
+  }
+  uint64_t *cut = reinterpret_cast<uint64_t *>(off_out);
+  QR_LAUNCH("index_select", index_select_kernel, dim3((unsigned)m), dim3(256), 0, st, (const uint64_t *)keys,
+            static_cast<const uint64_t *>(probe_workspace), b, K, pidx, pmilli, avail_out, cut);
+  qr_scan_u64(cut, m, cut + m, sums, st);
+  QR_LAUNCH("index_compact", index_compact_kernel, dim3((unsigned)ceil_div64(m * K, 256)), dim3(256), 0, st,
+            (const int32_t *)pidx, (const int32_t *)pmilli, m, K, (const int64_t *)off_out, idx_out, milli_out);
+  QR_LAUNCH_CHECK("qrlsh_index_probe_finish");
+  return QRLSH_OK;
+}

@@ -489,3 +489,71 @@ QRLSH_EXPORT int qrlsh_predict(const int32_t *ratings, int64_t nu, int64_t nq, c
   QR_LAUNCH_CHECK("qrlsh_predict");
   return QRLSH_OK;
 }
+
+// ---- column prediction: the cells of NEW queries (qrlsh_predict_columns) --------------------------------------------
+// A query x that is not a column of the matrix has no ratings, so the user side of every cell (u, x) is 0
+// (weighted_average over an all-zero column, recommender.py:320) and only the query side decides:
+//     out[x][u] = qp == 0 ? 0 : rint(qp * (qw + (uw * 0.5)) + dmean * (uw * 0.5)),  qp = weighted_average(ratings[u],
+// x's list) -- predict_kernel's expression with up = 0.  One workgroup per (new query, block of 256 users): the list
+// (<= 64 entries; similarity = milli / 1000.0, a true division) sits in LDS, lane = user.
+constexpr int PC_THREADS = 256;
+__global__ __launch_bounds__(PC_THREADS) void predict_columns_kernel(const int32_t *__restrict__ ratings, int64_t nu,
+                                                                     int64_t nq, const int64_t *__restrict__ off,
+                                                                     const int32_t *__restrict__ idx,
+                                                                     const int32_t *__restrict__ milli, double qw,
+                                                                     double uw, double dmean, int sequential,
+                                                                     int32_t *__restrict__ out,
+                                                                     uint32_t *__restrict__ flags) {
+  __shared__ int32_t lidx[PRED_MAXK];
+  __shared__ double lval[PRED_MAXK];
+  __shared__ int bad;
+  const int64_t x = blockIdx.x;
+  const int t = threadIdx.x;
+  const int64_t u = (int64_t)blockIdx.y * PC_THREADS + t;
+  const int64_t lo = off[x], n64 = off[x + 1] - lo;
+  const bool fits = n64 >= 0 && n64 <= PRED_MAXK;
+  if (t == 0) bad = fits ? 0 : 1;
+  __syncthreads();
+  if (fits && t < n64) {
+    const int32_t ix = idx[lo + t];
+    if (ix < 0 || ix >= nq) bad = 2;   // never gathered
+    lidx[t] = ix;
+    lval[t] = (double)milli[lo + t] / 1000.0;
+  }
+  __syncthreads();
+  const int why = bad;
+  if (why) {  // too long (bit 0) or an index outside the matrix (bit 1): flagged, the column gets 0
+    if (t == 0 && blockIdx.y == 0) atomicOr(flags, (uint32_t)why);
+    if (u < nu) out[x * nu + u] = 0;
+    return;
+  }
+  if (u >= nu) return;
+  const int32_t *row = ratings + u * nq;
+  const double qp = weighted_average(
+      (int)n64, sequential != 0, [&](int k) { return row[lidx[k]]; }, [&](int k) { return lval[k]; });
+  const double r = qp == 0.0 ? 0.0 : qp * (qw + (uw * 0.5)) + dmean * (uw * 0.5);
+  out[x * nu + u] = (int32_t)rint(r);
+}
+
+QRLSH_EXPORT int qrlsh_predict_columns(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *off,
+                                       const int32_t *idx, const int32_t *milli, int64_t m, double query_weight,
+                                       double user_weight, double default_mean, int32_t sum_order, int32_t *out,
+                                       uint32_t *flags_out, void *stream) {
+  QR_CHECK_ARG(nu >= 0 && nq >= 0 && m >= 0 && ceil_div64(nu, PC_THREADS) <= 65535 && m <= 2147483647ll,
+               "qrlsh_predict_columns: bad sizes nu=%lld nq=%lld m=%lld", (long long)nu, (long long)nq, (long long)m);
+  QR_CHECK_ARG(sum_order == QRLSH_SUM_PAIRWISE || sum_order == QRLSH_SUM_SEQUENTIAL,
+               "qrlsh_predict_columns: bad sum_order %d", sum_order);
+  QR_CHECK_ARG(flags_out, "qrlsh_predict_columns: flags_out is required");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_predict_columns: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  if (nu == 0 || m == 0) return QRLSH_OK;
+  QR_CHECK_ARG(off && out && (nq == 0 || (ratings && idx && milli)), "qrlsh_predict_columns: null pointer");
+  QR_LAUNCH("predict_columns", predict_columns_kernel, dim3((unsigned)m, (unsigned)ceil_div64(nu, PC_THREADS)),
+            dim3(PC_THREADS), 0, st, ratings, nu, nq, off, idx, milli, query_weight, user_weight, default_mean,
+            (int)(sum_order == QRLSH_SUM_SEQUENTIAL), out, flags_out);
+  QR_LAUNCH_CHECK("qrlsh_predict_columns");
+  return QRLSH_OK;
+}

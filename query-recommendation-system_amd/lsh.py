@@ -99,6 +99,33 @@ class LSH:
         keys = ops.band_keys(sig, self.b)
         return ops.candidate_pairs(keys, P // self.b, stats, sig=sig)
 
+    def query(self, signatures):
+        """For each new signature (not registered), the set of registered ids it shares a non-empty band with:
+        get_candidates' rule for a probe (lsh.py:40-55), through a band-key index of the registered signatures
+        (qrlsh.QueryIndex, built on first use and kept until the next compute_buckets*)."""
+        if isinstance(signatures, torch.Tensor):
+            t = signatures
+            t = t.to(torch.int64).bitwise_and(0xFFFFFFFF).to(torch.int32) if t.dtype == torch.int64 else t.to(torch.int32)
+            t = t.to(self.device).contiguous()
+            if t.dim() == 1:
+                t = t[None, :]
+        else:
+            t = self._to_device(np.asarray(signatures))
+        sig = self.signatures_tensor()
+        if t.shape[1] != sig.shape[1] or t.shape[1] % self.b != 0:
+            raise ValueError("new signatures have %d values, the registered ones %d (b=%d)" % (t.shape[1], sig.shape[1], self.b))
+        m = t.shape[0]
+        out = [set() for _ in range(m)]
+        if m == 0 or sig.shape[0] == 0:
+            return out
+        idx = getattr(self, "_index", None)
+        if idx is None or idx.n != sig.shape[0]:
+            idx = self._index = qrlsh.QueryIndex(sig, None, self.b)
+        q, ids = idx.candidates(t)
+        for x, i in zip(ops.to_host(q).tolist(), ops.to_host(ids).tolist()):
+            out[x].add(i)
+        return out
+
     # -- internals ---------------------------------------------------------------
     def _to_device(self, a):
         if a.ndim == 1:

@@ -27,6 +27,7 @@ SORT_HOST = 16
 SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
+INDEX_MAX_K = 256
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -99,6 +100,18 @@ SIGNATURES = {
     "qrlsh_predict_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "qrlsh_predict": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, _i32, _vp, _vp, _i32, _vp, _sz, _vp]),
+    "qrlsh_predict_columns": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, ctypes.c_double, ctypes.c_double,
+                                             ctypes.c_double, _i32, _vp, _vp, _vp]),
+    "qrlsh_index_dir_bits": (_i32, [_i64]),
+    "qrlsh_index_dir_words": (_sz, [_i64, _i32]),
+    "qrlsh_index_build_workspace_bytes": (_sz, [_i64, _i32]),
+    "qrlsh_index_build": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "qrlsh_index_probe_workspace_bytes": (_sz, [_i64, _i32]),
+    "qrlsh_index_probe_count": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "qrlsh_index_probe_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "qrlsh_index_finish_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "qrlsh_index_probe_finish": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _i32,
+                                                _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_recommend_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "qrlsh_recommend_topk": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                             _vp]),

@@ -1,0 +1,193 @@
+"""Serving new queries: a band-key index of a finished hot-path run, probed many times (csrc/index.hip).
+
+The hot path (pipeline.query_similarities) answers a closed set of queries.  A QueryIndex keeps what a new query needs
+from such a run -- the permutation table, the signature rows, their norms, b and r = P / b, and the indexed band keys
+sorted per band with a directory -- and answers, for a batch of new queries:
+
+    neighbours       the K best indexed queries sharing a non-empty band (lsh.py:40-55, recommender.py:187-214 for
+                     the query appended alone, K held fixed; milli descending, then id ascending)
+    predict_columns  the hybrid prediction of every user's cell of each new query (recommender.py:313-331 with a
+                     zero column: the user side is 0)
+    top_users        the users with the largest non-zero predictions (qrlsh_recommend_topk on those rows)
+
+Everything runs on the device; the indexed data never leaves it."""
+import numpy as np
+import torch
+
+from . import _lib, ops
+from .pipeline import max_candidates
+from .predict import QUERY_WEIGHT, USER_WEIGHT, DEFAULT_MEAN
+
+MAX_K = _lib.INDEX_MAX_K
+SUM_ORDERS = {"pairwise": _lib.SUM_PAIRWISE, "sequential": _lib.SUM_SEQUENTIAL}
+
+
+def _int_arg(v, name, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
+        raise ValueError("%s must be an integer in %d..%d, got %r" % (name, lo, hi, v))
+    return int(v)
+
+
+class QueryIndex:
+    """sig: the indexed signature rows (int32 [n, P], or compact uint16 rows carried as torch.int16) on the device;
+    norm2: int64 [n] (None: computed); b: bands (P % b == 0); table: the ops.PermTable the rows were drawn with
+    (needed only by .signatures); keys: int64 [b, n] band keys (default: qrlsh_band_keys of sig; caller keys only
+    filter -- every candidate is checked against the rows); K: default list length (round(log_1.5 n))."""
+
+    def __init__(self, sig, norm2, b, table=None, keys=None, K=None):
+        if not isinstance(sig, torch.Tensor) or sig.dtype not in (torch.int32, torch.int16) or sig.dim() != 2:
+            raise TypeError("sig must be a 2-D int32 or int16 (compact) tensor")
+        ops._need(sig, sig.dtype, "sig", 2)
+        n, P = sig.shape
+        b = _int_arg(b, "b", 1, 65535)
+        if P % b != 0:
+            raise ValueError("signature length %d not divisible by b=%d" % (P, b))
+        if n >= 2**32 - 1:
+            raise ValueError("at most 2^32 - 2 indexed queries")
+        if norm2 is not None:
+            ops._need(norm2, torch.int64, "norm2", 1)
+            if norm2.numel() != n or norm2.device != sig.device:
+                raise ValueError("norm2 must hold one int64 per signature row, on the rows' device")
+        if keys is not None:
+            ops._need(keys, torch.int64, "keys", 2)
+            if tuple(keys.shape) != (b, n) or keys.device != sig.device:
+                raise ValueError("keys must be int64 [b, n] = [%d, %d] on the rows' device" % (b, n))
+        if table is not None and (table.P != P or (sig.dtype == torch.int16 and not ops.can_compact(table))):
+            raise ValueError("the permutation table does not match the signature rows")
+        if K is None:
+            K = min(max(max_candidates(n) if n > 1 else 1, 1), MAX_K)
+        self.K = _int_arg(K, "K", 1, MAX_K)
+        self.sig, self.n, self.P, self.b, self.r = sig, n, P, b, P // b
+        self.table = table
+        self.norm2 = norm2 if norm2 is not None else ops.row_norms(ops.sig_to_int32(sig))
+        keys = ops.band_keys(ops.sig_to_int32(sig), b) if keys is None else keys.clone()
+        self.keys, self.ids, self.dir = ops.index_build(keys)
+
+    @classmethod
+    def from_result(cls, res, table):
+        """the index of a finished run: pipeline.query_similarities' HotPathResult and the table it was drawn with"""
+        return cls(res.sig, res.norm2, res.b, table=table, K=res.K if res.K else None)
+
+    # ---- new queries -----------------------------------------------------------------------------------------------
+    def signatures(self, offsets, rows):
+        """MinHash rows of new queries (CSR answer sets) under the held table, in the index's row dtype:
+        -> (sig, norm2, keys [b, m])"""
+        if self.table is None:
+            raise ValueError("this index holds no permutation table; pass signatures to neighbours()")
+        return ops.minhash(offsets, rows, self.table, b=self.b, want_norm=True, compact=self.sig.dtype == torch.int16)
+
+    def _probe_rows(self, sig, norm2, keys):
+        if not isinstance(sig, torch.Tensor) or sig.dtype not in (torch.int32, torch.int16) or sig.dim() != 2:
+            raise TypeError("sig must be a 2-D int32 or int16 (compact) tensor")
+        if sig.shape[1] != self.P:
+            raise ValueError("new signatures have %d values, the index %d" % (sig.shape[1], self.P))
+        sig = sig.to(self.sig.device).contiguous()
+        if sig.dtype != self.sig.dtype:     # same values, the index's row format
+            sig = ops.sig_to_int32(sig) if self.sig.dtype == torch.int32 else \
+                sig.to(torch.int32).bitwise_and(0xFFFF).to(torch.int16)
+        m = sig.shape[0]
+        if norm2 is not None:
+            ops._need(norm2, torch.int64, "norm2", 1)
+            if norm2.numel() != m:
+                raise ValueError("norm2 must hold one int64 per new signature")
+        if keys is not None:
+            ops._need(keys, torch.int64, "keys", 2)
+            if tuple(keys.shape) != (self.b, m):
+                raise ValueError("keys must be int64 [b, m] = [%d, %d]" % (self.b, m))
+        if norm2 is None:
+            norm2 = ops.row_norms(ops.sig_to_int32(sig))
+        if keys is None:
+            keys = ops.band_keys(ops.sig_to_int32(sig), self.b)
+        return sig, norm2, keys
+
+    def _run(self, sig, norm2, keys, K):
+        raw, pws = ops.index_probe(self.keys, self.ids, self.dir, self.r, keys)
+        return ops.index_finish(self.sig, self.norm2, sig, norm2, self.b, pws, raw, K), raw
+
+    def neighbours(self, sig, norm2=None, keys=None, K=None):
+        """sig: signature rows of m new queries (int32 or compact int16; converted to the index's format); norm2 /
+        keys: theirs, or None (computed).  K: list length, default the index's (1..256).
+        -> (off int64 [m + 1], idx int32, milli int32, avail int32 [m]) device tensors: CSR lists of indexed ids by
+        milli descending, then id ascending; avail = distinct candidates before the cut."""
+        K = self.K if K is None else _int_arg(K, "K", 1, MAX_K)
+        sig, norm2, keys = self._probe_rows(sig, norm2, keys)
+        m = sig.shape[0]
+        dev = self.sig.device
+        if m == 0:
+            z = torch.zeros((1,), dtype=torch.int64, device=dev)
+            e = torch.empty((0,), dtype=torch.int32, device=dev)
+            return z, e, e.clone(), e.clone()
+        step = max(1, (2**32 - 1) // self.b)      # m * b < 2^32 per library call; results do not depend on the batch
+        parts = []
+        for q0 in range(0, m, step):
+            q1 = min(m, q0 + step)
+            (off, idx, milli, avail, _), _ = self._run(sig[q0:q1], norm2[q0:q1], keys[:, q0:q1].contiguous(), K)
+            parts.append((off, idx, milli, avail))
+        if len(parts) == 1:
+            return parts[0]
+        base = 0
+        offs = [torch.zeros((1,), dtype=torch.int64, device=dev)]
+        for off, idx, _, _ in parts:
+            offs.append(off[1:] + base)
+            base += idx.numel()
+        return (torch.cat(offs), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]),
+                torch.cat([p[3] for p in parts]))
+
+    def candidates(self, sig, norm2=None, keys=None):
+        """every candidate of every new query, uncut: -> (query int64, id int64) device tensors, ordered by query,
+        then the band that first brought the id"""
+        sig, norm2, keys = self._probe_rows(sig, norm2, keys)
+        m = sig.shape[0]
+        dev = self.sig.device
+        if m == 0:
+            e = torch.empty((0,), dtype=torch.int64, device=dev)
+            return e, e.clone()
+        if m * self.b >= 2**32:
+            raise ValueError("at most %d new queries per call" % ((2**32 - 1) // self.b))
+        (_, _, _, _, skeys), raw = self._run(sig, norm2, keys, 1)
+        kept = skeys != -1
+        q = torch.div((raw[kept] >> 32) & 0xFFFFFFFF, self.b, rounding_mode="floor")
+        return q, raw[kept] & 0xFFFFFFFF
+
+    def predict_columns(self, ratings, off, idx, milli, sum_order="pairwise", query_weight=QUERY_WEIGHT,
+                        user_weight=USER_WEIGHT, default_mean=DEFAULT_MEAN):
+        """ratings: (nu, n) utility matrix of the indexed queries (0 = missing; array or tensor); (off, idx, milli):
+        neighbours()' lists.  -> int32 device tensor [m, nu]: every user's predicted cell of each new query."""
+        if sum_order not in SUM_ORDERS:
+            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        if isinstance(ratings, torch.Tensor):
+            if ratings.dim() != 2 or ratings.dtype.is_floating_point or ratings.dtype == torch.bool:
+                raise ValueError("ratings must be a 2-D integer matrix")
+            r = ratings
+        else:
+            a = np.asarray(ratings.to_numpy() if hasattr(ratings, "to_numpy") else ratings)
+            if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("ratings must be a 2-D integer matrix")
+            if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
+                raise ValueError("ratings hold values outside int32")
+            r = a
+        if r.shape[1] != self.n:
+            raise ValueError("ratings have %d columns, the index %d queries" % (r.shape[1], self.n))
+        if r.shape[0] > 65535 * 256:
+            raise ValueError("at most %d users" % (65535 * 256))
+        for t, name in ((off, "off"), (idx, "idx"), (milli, "milli")):
+            if not isinstance(t, torch.Tensor) or t.dim() != 1:
+                raise ValueError("%s must be a 1-D device tensor (neighbours()' output)" % name)
+        dev = self.sig.device
+        if not isinstance(r, torch.Tensor):
+            r = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32))
+        r = r.to(device=dev, dtype=torch.int32).contiguous()
+        return ops.predict_columns(r, off.to(dev, torch.int64).contiguous(), idx.to(dev, torch.int32).contiguous(),
+                                   milli.to(dev, torch.int32).contiguous(), query_weight, user_weight, default_mean,
+                                   SUM_ORDERS[sum_order])
+
+    @staticmethod
+    def top_users(columns, k):
+        """columns: predict_columns' [m, nu] output.  -> (users int32 [m, k], values int32 [m, k], avail int32 [m]): per
+        new query the users with the largest non-zero predictions, value descending then user ascending (-1 / 0
+        padding), and how many users have one (qrlsh_recommend_topk over the rows, nothing rated)."""
+        from .recommend import top_k
+        if not isinstance(columns, torch.Tensor) or columns.dim() != 2:
+            raise ValueError("columns must be predict_columns' 2-D device tensor")
+        zeros = torch.zeros_like(columns, dtype=torch.int32)
+        return top_k(zeros, columns, k, device=columns.device)

@@ -915,3 +915,82 @@ def topk_edges(edges, K, id_bits):
     val = torch.empty((m,), dtype=torch.int32, device=dev)
     _lib.check(lib.qrlsh_topk_fill(_ptr(se), _ptr(sd), n, K, kb, _ptr(ws), _ptr(src), _ptr(dst), _ptr(val), _stream()))
     return src, dst, val
+
+
+# ---------------------------------------------------------------------------
+# serving new queries: band-key index, probe, column prediction (csrc/index.hip, csrc/predict.hip)
+# ---------------------------------------------------------------------------
+def index_build(keys):
+    """keys int64 [b, n] band keys of the indexed queries (consumed) -> (sorted keys int64 [b, n], ids int32 [b, n],
+    directory int32 [qrlsh_index_dir_words])"""
+    lib = _lib.load()
+    _need(keys, torch.int64, "keys", 2)
+    b, n = keys.shape
+    dev = keys.device
+    ids = torch.empty((b, n), dtype=torch.int32, device=dev)
+    ktmp, itmp = torch.empty_like(keys), torch.empty_like(ids)
+    dirw = torch.empty((max(int(lib.qrlsh_index_dir_words(n, b)), 1),), dtype=torch.int32, device=dev)
+    ws = _ws(lib.qrlsh_index_build_workspace_bytes(n, b), dev)
+    _lib.check(lib.qrlsh_index_build(_ptr(keys), _ptr(ktmp), _ptr(ids), _ptr(itmp), n, b, _ptr(dirw), _ptr(ws),
+                                     ws.numel(), _stream()))
+    return keys, ids, dirw
+
+
+def index_probe(sorted_keys, ids, dirw, r, probe_keys):
+    """raw candidate words (q * b + band) << 32 | id of every (new query, band) key hit, and the probe workspace
+    (per-(query, band) offsets) that index_finish reads"""
+    lib = _lib.load()
+    b, n = sorted_keys.shape
+    _need(probe_keys, torch.int64, "probe_keys", 2)
+    m = probe_keys.shape[1]
+    dev = probe_keys.device
+    ws = _ws(lib.qrlsh_index_probe_workspace_bytes(m, b), dev)
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_index_probe_count(_ptr(sorted_keys), _ptr(dirw), n, b, r, _ptr(probe_keys), m, _ptr(ws),
+                                           ws.numel(), _ptr(total), _stream()))
+    n_raw = int(total.item())
+    raw = torch.empty((max(n_raw, 1),), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_index_probe_fill(_ptr(sorted_keys), _ptr(ids), _ptr(dirw), n, b, r, _ptr(probe_keys), m,
+                                          _ptr(ws), ws.numel(), _ptr(raw), _stream()))
+    return raw[:n_raw], ws
+
+
+def index_finish(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K):
+    """-> (off int64 [m + 1], idx int32, milli int32, avail int32 [m], keys int64 [n_raw]): the CSR neighbour lists
+    and, per raw word, its select key ((1000 - milli) << 32 | id, or -1 for a dropped word)"""
+    lib = _lib.load()
+    n, P = sig.shape
+    m = probe_sig.shape[0]
+    dev = sig.device
+    n_raw = raw.numel()
+    code = _lib.SIG_U16 if sig.dtype == torch.int16 else _lib.SIG_I32
+    ws = _ws(lib.qrlsh_index_finish_workspace_bytes(m, K, n_raw), dev)
+    off = torch.empty((m + 1,), dtype=torch.int64, device=dev)
+    idx = torch.empty((max(m * K, 1),), dtype=torch.int32, device=dev)
+    milli = torch.empty((max(m * K, 1),), dtype=torch.int32, device=dev)
+    avail = torch.empty((m,), dtype=torch.int32, device=dev)
+    _lib.check(lib.qrlsh_index_probe_finish(_ptr(sig), _ptr(norm2), n, _ptr(probe_sig), _ptr(probe_norm2), code, P, b,
+                                            m, _ptr(probe_ws), _ptr(raw), n_raw, K, _ptr(off), _ptr(idx), _ptr(milli),
+                                            _ptr(avail), _ptr(ws), ws.numel(), _stream()))
+    cnt = int(off[m].item()) if m else 0
+    return off, idx[:cnt], milli[:cnt], avail, ws[:n_raw * 8].view(torch.int64)
+
+
+def predict_columns(ratings, off, idx, milli, query_weight, user_weight, default_mean, sum_order):
+    """int32 [m, nu]: the predicted cells of m new queries for every user (qrlsh_predict_columns); raises ValueError
+    when a list is longer than 64 entries or names a query outside the matrix"""
+    lib = _lib.load()
+    _need(ratings, torch.int32, "ratings", 2)
+    nu, nq = ratings.shape
+    m = off.numel() - 1
+    out = torch.empty((m, nu), dtype=torch.int32, device=ratings.device)
+    flags = torch.zeros((1,), dtype=torch.int32, device=ratings.device)
+    _lib.check(lib.qrlsh_predict_columns(_ptr(ratings), nu, nq, _ptr(off), _ptr(idx), _ptr(milli), m,
+                                         float(query_weight), float(user_weight), float(default_mean), int(sum_order),
+                                         _ptr(out), _ptr(flags), _stream()))
+    f = int(flags.item())
+    if f & 1:
+        raise ValueError("a neighbour list is longer than 64 entries; the prediction kernel handles at most 64")
+    if f & 2:
+        raise ValueError("a neighbour index lies outside the %d columns of the ratings" % nq)
+    return out

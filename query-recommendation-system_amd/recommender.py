@@ -180,9 +180,78 @@ class Recommender:
         torch.cuda.synchronize()
         self._log("Candidate pairs [{}s]: {}".format(round(time.time() - initial, 3), res.pairs.numel()))
         self.last_result = res
+        self.last_table = table      # kept for serving new queries (similar_queries & co.)
+        self._query_index = None
         query_sim = pipeline.sims_to_dict(res.src, res.dst, res.val)
         self._log("\n" + str(round(time.time() - queryTime, 3)) + "s for overall queries_similarity scores")
         return query_sim
+
+    # ---- new queries: probes of the index of the last compute_querySimilarities run (device) ---------------------------
+    def _new_query_rows(self, queries):
+        """(index, sig, norm2, keys) of new queries given in parse_queries' form (one column per dataset feature,
+        "" = unconstrained): answer sets through the cached AnswerIndex, MinHash under the run's own table"""
+        from qrlsh import answers
+        from qrlsh.index import QueryIndex
+        res = getattr(self, "last_result", None)
+        if res is None or getattr(self, "last_table", None) is None:
+            raise ValueError("compute_querySimilarities has not run: there is no index to look new queries up in")
+        q = np.asarray(_as_numpy(queries), dtype=object)
+        if q.ndim != 2 or q.shape[1] != len(self.datasetFeatures):
+            raise ValueError("queries must have one column per dataset feature (%d)" % len(self.datasetFeatures))
+        if getattr(self, "_query_index", None) is None:
+            self._query_index = QueryIndex.from_result(res, self.last_table)
+        qi = self._query_index
+        if getattr(self, "_answer_index", None) is None or getattr(self, "_answer_index_key", None) != id(self.dataset):
+            self.answer_sets_device()  # (re)builds the cached AnswerIndex of this dataset
+        offsets, rows = answers.answer_sets(self._answer_index, answers.encode_queries(self._answer_index, q))
+        sig, norm2, keys = qi.signatures(offsets, rows)
+        return qi, sig, norm2, keys
+
+    def similar_queries(self, queries):
+        """{x: {'indexes': int64[<=K], 'values': float64[<=K]}} for new queries x = 0 .. m-1 (rows of `queries`): the
+        indexed queries each would get as neighbours if appended alone (K of the last run; value descending, then id
+        ascending); queries without candidates are absent, as in compute_querySimilarities."""
+        qi, sig, norm2, keys = self._new_query_rows(queries)
+        off, idx, milli, _ = qi.neighbours(sig, norm2, keys)
+        off, idx, milli = ops.to_host(off), ops.to_host(idx), ops.to_host(milli)
+        out = {}
+        for x in range(len(off) - 1):
+            if off[x + 1] > off[x]:
+                out[x] = {"indexes": idx[off[x]:off[x + 1]].astype(np.int64),
+                          "values": milli[off[x]:off[x + 1]].astype(np.float64) / 1000.0}
+        return out
+
+    def _new_query_columns(self, queries, sum_order):
+        if sum_order not in ("pairwise", "sequential"):
+            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        qi, sig, norm2, keys = self._new_query_rows(queries)
+        off, idx, milli, _ = qi.neighbours(sig, norm2, keys)
+        return qi.predict_columns(self.ratings, off, idx, milli, sum_order, QUERY_WEIGHT, USER_WEIGHT, DEFAULT_MEAN)
+
+    def predict_new_queries(self, queries, sum_order=None):
+        """DataFrame usersIDs x new queries (0 .. m-1): the prediction compute_scores would give each user's cell of a
+        new query appended as an unrated column (recommender.py:313-331; its user side is 0)."""
+        cols = self._new_query_columns(queries, self.sum_order if sum_order is None else sum_order)
+        final = ops.to_host(cols).T
+        return pd.DataFrame(final, index=self.usersIDs, columns=range(final.shape[1])).astype(int)
+
+    def recommend_new_queries(self, queries, k, sum_order=None):
+        """{x: {'users': int64[user rows, 0-based], 'values': int64[predicted values], 'available': int}}: per new query
+        the k users with the largest non-zero predictions (value descending, then user ascending) and how many users
+        have one."""
+        from qrlsh import recommend as rec
+        from qrlsh.index import QueryIndex
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= rec.MAX_K:
+            raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
+        cols = self._new_query_columns(queries, self.sum_order if sum_order is None else sum_order)
+        users, vals, avail = QueryIndex.top_users(cols, int(k))
+        users, vals, avail = ops.to_host(users), ops.to_host(vals), ops.to_host(avail)
+        out = {}
+        for x in range(len(avail)):
+            n = min(int(k), int(avail[x]))
+            out[x] = {"users": users[x, :n].astype(np.int64), "values": vals[x, :n].astype(np.int64),
+                      "available": int(avail[x])}
+        return out
 
     # ---- N4: user similarity (clustering = the reference's sklearn call on the host; the rest on the device) ----
     def compute_userSimilarities(self):
