@@ -132,39 +132,28 @@ int qrlsh_pairs_fill(const uint64_t *sorted_keys, const uint32_t *sorted_ids, in
                      void *stream);
 
 /* Fast form of the same step for keys straight from qrlsh_minhash / qrlsh_band_keys (band-major
- * [b][nq], NOT sorted): radix partition on the top part_bits (8..16) bits of mix64(key) -- one
- * pass for 8 bits, two above (tmp_keys / tmp_ids are the intermediate buffers, may be NULL for
- * 8) -- into part_keys / part_ids, then an LDS hash-group finish per (part, band).  Pick
- * part_bits so that nq / 2^part_bits is ~2-4 K.  count leaves {total pairs, overflow flag} in
- * total_overflow_out[2] (device uint64 x2); overflow != 0 means a part exceeded the LDS image
- * (6144 records; heavily skewed data): ignore the total and use the general path
- * (qrlsh_sort_u64 + qrlsh_pairs_count/fill) instead.  fill must follow a count on the same
- * workspace.  Same pairs as the general path, in a different (still duplicate-carrying) order.
- */
-size_t qrlsh_bucket_workspace_bytes(int64_t nq, int32_t b, int32_t part_bits);
-int qrlsh_bucket_pairs_count(const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids,
-                             uint64_t *tmp_keys, uint32_t *tmp_ids, int64_t nq, int32_t b, int32_t r,
-                             int32_t part_bits, void *workspace, size_t workspace_bytes,
-                             uint64_t *total_overflow_out, void *stream);
-int qrlsh_bucket_pairs_fill(const uint64_t *part_keys, const uint32_t *part_ids, int64_t nq, int32_t b,
-                            int32_t r, int32_t part_bits, void *workspace, uint64_t *pairs_out,
-                            void *stream);
-/* One-pass form of the two calls above: every part reserves its output range on a device cursor, so
- * the count pass (and its scan) disappears -- at the price of sizing pairs_out by a guess.  At most
- * `capacity` words of pairs_out are written; total_overflow_out[0] receives the exact number of pairs
- * whether or not they fitted (if it exceeds capacity: allocate that many and call again), [1] the same
- * oversized-part flag as qrlsh_bucket_pairs_count.  The pairs come out in no particular order.
- * part_keys / part_ids must hold qrlsh_bucket_part_words(nq, b, part_bits) words and, for part_bits > 8,
- * tmp_keys / tmp_ids qrlsh_bucket_tmp_words(...): the partition is ONE kernel per level (one level for
- * part_bits = 8, two of about part_bits / 2 bits each beyond) that gives every part a fixed region of ONE LDS image
- * of the finish and reserves room in it with an atomic per (tile, part) -- no histogram pass, no scan, no bounds
- * search.  Behind the regions the same buffers hold an OVERFLOW POOL (1/16 of the records, at least 1 M): a part
+ * [b][nq], NOT sorted): a hash partition on the top part_bits (8..16) bits of mix64(key) into
+ * part_keys / part_ids, then an LDS hash-group finish per (part, band).  Pick part_bits so that
+ * nq / 2^part_bits is ~2-4 K.  Same pairs as the general path, in no particular (still
+ * duplicate-carrying) order.
+ * Output: every part reserves its output range on a device cursor, so there is no count pass -- at the price
+ * of sizing pairs_out by a guess.  At most `capacity` words of pairs_out are written; total_overflow_out[2]
+ * (device uint64 x2) receives {the exact number of pairs whether or not they fitted, overflow flag}.  A total
+ * beyond capacity: allocate that many and call again.  Overflow flag != 0 (heavily skewed data): nothing of the
+ * call is usable, take the general path (qrlsh_sort_u64 + qrlsh_pairs_count / _fill) instead.
+ * Partition: ONE kernel per level (one level for part_bits = 8, two of about part_bits / 2 bits each beyond:
+ * tmp_keys / tmp_ids are the buffers in between, may be NULL for 8) that gives every part a fixed region of ONE
+ * LDS image of the finish and reserves room in it with an atomic per (tile, part) -- no histogram pass, no scan, no
+ * bounds search.  part_keys / part_ids must hold qrlsh_bucket_part_words(nq, b, part_bits) words and, for
+ * part_bits > 8, tmp_keys / tmp_ids qrlsh_bucket_tmp_words(...).
+ * Pool: behind the regions the same buffers hold an OVERFLOW POOL (1/16 of the records, at least 1 M): a part
  * swollen by a popular key (lsh.py:42-49 makes a bucket of m queries m(m-1)/2 pairs whatever m is; at 100 M queries
  * over 32768 table rows m reaches ~20 000) spills there and is worked in blocks of one image; only a part beyond
  * qrlsh_set_big_part_limit records (default 16 images = 98 304), more than 4096 such parts per band group, or an
  * exhausted pool raise the overflow flag.  Reserved: ~1.4 - 2 x the b * nq records.  These buffers are scratch:
  * what they hold afterwards is mix64(key) (a bijection of the keys, which is all the pairing needs), not the keys,
  * and the records of empty bands are gone. */
+size_t qrlsh_bucket_workspace_bytes(int64_t nq, int32_t b, int32_t part_bits);
 size_t qrlsh_bucket_part_words(int64_t nq, int32_t b, int32_t part_bits);
 /* records a part beyond the LDS image may hold and stay on the partition path (<= 0 or beyond the maximum: the
  * default, 98 304); returns the previous limit.  Process-wide; a tuning / test knob. */

@@ -46,28 +46,16 @@ template <int MODE> __device__ static inline uint32_t digit_of(uint64_t key, int
   return (uint32_t)(x >> shift) & (RADIX - 1);
 }
 
-// Partition digit of the fast bucket path: records holding the "empty" key (all -1 band,
-// never a candidate: lsh.py:47) are dealt round the parts by their index instead of all
-// landing in one part, so a data set with many empty answer sets cannot overflow a part.
-template <bool SPREAD>
-__device__ static inline uint32_t part_digit(uint64_t key, int64_t idx, int shift, uint64_t ek, uint32_t dmask) {
-  const uint64_t x = (SPREAD && key == ek) ? qr_mix64((uint64_t)idx) : qr_mix64(key);
-  return (uint32_t)(x >> shift) & dmask;
-}
-
 // ghist layout: [batch][digit][tile]
-template <int MIX, bool SPREAD = false>
+template <int MIX>
 __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const uint64_t *__restrict__ keys, int64_t n,
                                                                  int ntiles, int shift,
-                                                                 uint32_t *__restrict__ ghist, uint64_t ek = 0,
-                                                                 uint32_t fold = 0, uint32_t dmask = RADIX - 1,
-                                                                 const uint32_t *__restrict__ vals = nullptr) {
+                                                                 uint32_t *__restrict__ ghist, uint32_t fold) {
   __shared__ uint32_t h[RADIX];
   const int tile = blockIdx.x, batch = blockIdx.y;
   h[threadIdx.x] = 0;
   __syncthreads();
   const uint64_t *k = keys + (size_t)batch * n;
-  const uint32_t *v = vals ? vals + (size_t)batch * n : nullptr;
   const int64_t base = (int64_t)tile * SORT_TILE;
   // two keys per lane per step (16-byte loads) when the batch base is 16-byte aligned
   const bool wide = ((((uintptr_t)k) & 15) == 0);
@@ -89,12 +77,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const uint64_t 
       const int64_t idx = idx0 + e;
       uint32_t dd = 0;
       if (idx < n) {
-        const uint64_t key = kk[e];
-        uint32_t d;
-        if (SPREAD)
-          d = part_digit<SPREAD>(key, (key == ek && v) ? (int64_t)v[idx] : idx, shift, ek, dmask);
-        else
-          d = digit_of<MIX>(key, shift, fold);
+        const uint32_t d = digit_of<MIX>(kk[e], shift, fold);
         if (MIX != SM_OWNER && MIX != SM_HOST) atomicAdd(&h[d], 1u);
         dd = d;
       }
@@ -199,7 +182,7 @@ static void launch_rowscan(uint32_t *ghist, int ntiles, uint32_t *rtot, int nbat
     QR_LAUNCH("sort_rowscan", sort_rowscan_kernel<1024>, dim3(RADIX, nbatch), dim3(1024), 0, st, ghist, ntiles, rtot);
 }
 
-template <int MIX, bool HAS_VAL, bool IOTA, bool SPREAD = false>
+template <int MIX, bool HAS_VAL, bool IOTA>
 __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const uint64_t *__restrict__ keys_in,
                                                                     const uint32_t *__restrict__ vals_in,
                                                                     uint64_t *__restrict__ keys_out,
@@ -207,8 +190,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const uint64
                                                                     int ntiles, int shift,
                                                                     const uint32_t *__restrict__ goff,
                                                                     const uint32_t *__restrict__ rtot,
-                                                                    uint64_t ek = 0, uint32_t fold = 0,
-                                                                    uint32_t dmask = RADIX - 1) {
+                                                                    uint32_t fold) {
   __shared__ uint32_t cnt[SORT_THREADS / WAVE][RADIX];
   __shared__ uint32_t dsum[SORT_THREADS / WAVE];
   const int tile = xcd_tile(blockIdx.x, ntiles), batch = blockIdx.y;
@@ -235,8 +217,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const uint64
   for (int k = 0; k < SORT_IPT; ++k) {
     const int64_t idx = wbase + (int64_t)k * WAVE + lane;
     const bool valid = idx < n;
-    const uint32_t d = SPREAD ? part_digit<SPREAD>(key[k], HAS_VAL ? (int64_t)val[k] : idx, shift, ek, dmask)
-                              : digit_of<MIX>(key[k], shift, fold);
+    const uint32_t d = digit_of<MIX>(key[k], shift, fold);
     uint64_t m = __ballot(valid);
 #pragma unroll
     for (int bit = 0; bit < 8; ++bit) {
@@ -401,121 +382,7 @@ __global__ __launch_bounds__(SORT_THREADS, 4) void sort_scatter_staged_kernel(co
   }
 }
 
-// The same staging for the key + id partition passes of the fast bucket path (digit = part_digit,
-// SPREAD).  Ids are < 2^24 there (the host checks nq), so the digit rides in the top byte of the
-// staged id and is not recomputed (mix64 again) when the tile is written out.
-template <bool IOTA>
-__global__ __launch_bounds__(SORT_THREADS, 3) void part_scatter_staged_kernel(
-    const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, uint64_t *__restrict__ keys_out,
-    uint32_t *__restrict__ vals_out, int64_t n, int ntiles, int shift, const uint32_t *__restrict__ goff,
-    const uint32_t *__restrict__ rtot, uint64_t ek, uint32_t dmask) {
-  __shared__ uint32_t cnt[SORT_THREADS / WAVE][RADIX];
-  __shared__ uint32_t dsum[SORT_THREADS / WAVE];
-  __shared__ uint32_t lsum[SORT_THREADS / WAVE];
-  __shared__ uint32_t gdelta[RADIX];
-  __shared__ uint64_t skey[SORT_TILE];
-  __shared__ uint32_t sval[SORT_TILE];
-  const int tile = xcd_tile(blockIdx.x, ntiles), batch = blockIdx.y;
-  const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < SORT_THREADS / WAVE; ++i) cnt[i][threadIdx.x] = 0;
-  __syncthreads();
-  const size_t boff = (size_t)batch * n;
-  const int64_t tbase = (int64_t)tile * SORT_TILE;
-  const int64_t wbase = tbase + (int64_t)w * (WAVE * SORT_IPT);
-  uint64_t key[SORT_IPT];
-  uint32_t val[SORT_IPT];
-  uint32_t dr[SORT_IPT];
-  const uint64_t lt_mask = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int k = 0; k < SORT_IPT; ++k) {
-    const int64_t idx = wbase + (int64_t)k * WAVE + lane;
-    const bool valid = idx < n;
-    key[k] = valid ? keys_in[boff + idx] : 0;
-    val[k] = IOTA ? (uint32_t)idx : (valid ? vals_in[boff + idx] : 0);
-  }
-#pragma unroll
-  for (int k = 0; k < SORT_IPT; ++k) {
-    const int64_t idx = wbase + (int64_t)k * WAVE + lane;
-    const bool valid = idx < n;
-    const uint32_t d = part_digit<true>(key[k], (int64_t)val[k], shift, ek, dmask);
-    uint64_t m = __ballot(valid);
-#pragma unroll
-    for (int bit = 0; bit < 8; ++bit) {
-      const bool one = (d >> bit) & 1u;
-      const uint64_t bal = __ballot(one);
-      m &= one ? bal : ~bal;
-    }
-    const uint32_t below = (uint32_t)__popcll(m & lt_mask);
-    uint32_t prev = 0;
-    if (valid) {
-      prev = cnt[w][d];
-      if (below == 0) cnt[w][d] = prev + (uint32_t)__popcll(m);
-    }
-    dr[k] = (d << 16) | (prev + below);
-  }
-  __syncthreads();
-  {
-    const int d = threadIdx.x;
-    const uint32_t tot = rtot[(size_t)batch * RADIX + d];
-    uint32_t tc = 0;
-#pragma unroll
-    for (int i = 0; i < SORT_THREADS / WAVE; ++i) tc += cnt[i][d];
-    uint32_t inc = tot, linc = tc;
-#pragma unroll
-    for (int k = 1; k < WAVE; k <<= 1) {
-      const uint32_t o = __shfl_up(inc, k, WAVE), lo = __shfl_up(linc, k, WAVE);
-      if (lane >= k) {
-        inc += o;
-        linc += lo;
-      }
-    }
-    if (lane == WAVE - 1) {
-      dsum[w] = inc;
-      lsum[w] = linc;
-    }
-    __syncthreads();
-    uint32_t dbase = inc - tot, lstart = linc - tc;
-#pragma unroll
-    for (int k = 0; k < SORT_THREADS / WAVE; ++k)
-      if (k < w) {
-        dbase += dsum[k];
-        lstart += lsum[k];
-      }
-    gdelta[d] = dbase + goff[((size_t)batch * RADIX + d) * ntiles + tile] - lstart;
-    uint32_t run = lstart;
-#pragma unroll
-    for (int i = 0; i < SORT_THREADS / WAVE; ++i) {
-      const uint32_t c = cnt[i][d];
-      cnt[i][d] = run;
-      run += c;
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < SORT_IPT; ++k) {
-    const int64_t idx = wbase + (int64_t)k * WAVE + lane;
-    if (idx < n) {
-      const uint32_t d = dr[k] >> 16, lp = cnt[w][d] + (dr[k] & 0xFFFFu);
-      skey[lp] = key[k];
-      sval[lp] = val[k] | d << 24;
-    }
-  }
-  __syncthreads();
-  const int ntile = (int)min((int64_t)SORT_TILE, n - tbase);
-#pragma unroll
-  for (int k = 0; k < SORT_IPT; ++k) {
-    const int p = k * SORT_THREADS + threadIdx.x;
-    if (p < ntile) {
-      const uint32_t vv = sval[p];
-      const size_t dst = boff + gdelta[vv >> 24] + (uint32_t)p;
-      keys_out[dst] = skey[p];
-      vals_out[dst] = vv & 0xFFFFFFu;
-    }
-  }
-}
-
-// One-kernel partition for the one-pass bucket path (256 parts): every part owns a fixed region of
+// One-kernel partition of the bucket path (256 parts): every part owns a fixed region of
 // `cap` records, a tile reserves room in each part with one atomicAdd per (tile, part) on the part's
 // cursor, and writes its records there through the same LDS staging as above.  No histogram pass, no
 // row scan, no bounds search; the order of the records inside a part is whatever the atomics gave
@@ -893,20 +760,20 @@ static int sort_passes(uint64_t *ka, uint64_t *kb, uint32_t *va, uint32_t *vb, i
   for (int shift = bit_lo; shift < bit_hi; shift += 8) {
     uint64_t *kin = cur ? kb : ka, *kout = cur ? ka : kb;
     uint32_t *vin = cur ? vb : va, *vout = cur ? va : vb;
-    QR_LAUNCH("sort_hist", (sort_hist_kernel<MIX>), grid, block, 0, st, kin, n, ntiles, shift, ghist, (uint64_t)0, fold);
+    QR_LAUNCH("sort_hist", (sort_hist_kernel<MIX>), grid, block, 0, st, kin, n, ntiles, shift, ghist, fold);
     launch_rowscan(ghist, ntiles, rtot, nbatch, st);
     if (!has_val && (MIX == SM_PLAIN || MIX == SM_FOLD))
       QR_LAUNCH("sort_scatter_k", (sort_scatter_staged_kernel<MIX>), grid, block, 0, st, kin, kout, n, ntiles, shift,
                 ghist, rtot, fold);
     else if (!has_val)
       QR_LAUNCH("sort_scatter_k", (sort_scatter_kernel<MIX, false, false>), grid, block, 0, st, kin, vin, kout, vout, n,
-                         ntiles, shift, ghist, rtot, (uint64_t)0, fold);
+                         ntiles, shift, ghist, rtot, fold);
     else if (iota && shift == bit_lo)
       QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<MIX, true, true>), grid, block, 0, st, kin, vin, kout, vout, n,
-                         ntiles, shift, ghist, rtot, (uint64_t)0, fold);
+                         ntiles, shift, ghist, rtot, fold);
     else
       QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<MIX, true, false>), grid, block, 0, st, kin, vin, kout, vout, n,
-                         ntiles, shift, ghist, rtot, (uint64_t)0, fold);
+                         ntiles, shift, ghist, rtot, fold);
     cur ^= 1;
   }
   hipError_t e = hipGetLastError();
@@ -989,17 +856,17 @@ QRLSH_EXPORT int qrlsh_owner_bounds(const uint64_t *words, int64_t n, int32_t bi
 // ==========================================================================================
 // Fast bucket path (a2/a3): a T-bit hash PARTITION + an LDS finish, instead of a full sort.
 //
-//   partition : one or two of the radix passes above on the top T bits of mix64(key)
+//   partition : one or two steps of part_scatter_atomic_kernel on the top T bits of mix64(key)
 //               (T = 8 .. 16, chosen by the host so that a part holds ~2-4 K records)
-//               -> per band 2^T parts, contiguous in HBM, ids ascending inside a part;
-//   bounds    : one thread per (band, part) binary-searches the part's first record;
-//   finish    : one 1024-thread workgroup per (part, band) stages the part's keys in LDS, links
-//               equal keys through an LDS hash table (atomicExch chains) and, per record,
-//               pairs it with every EARLIER record of the part that has the same FULL key --
-//               exactly the (i < j) pairs of that bucket (lsh.py:47-49).
+//               -> per band 2^T parts, each in a fixed region of its own, records in any order;
+//               what a region cannot hold spills into a pool behind the regions;
+//   finish    : one workgroup per (part, band) stages the part's records in LDS, groups equal
+//               keys through an LDS hash table and pairs every record with the EARLIER arrivals
+//               that have the same FULL key -- exactly the (i < j) pairs of that bucket
+//               (lsh.py:47-49); parts beyond one LDS image are worked in blocks.
 //
-// Count-then-fill like the general path; a part larger than FIN_CAP records (heavily skewed
-// data) raises the overflow word and the host falls back to the general sort path.
+// Every workgroup reserves its output range on a device cursor.  What none of this can hold
+// (heavily skewed data) raises the overflow word and the host falls back to the general sort path.
 // ==========================================================================================
 #ifndef QR_FIN_THREADS
 #define QR_FIN_THREADS 1024
@@ -1010,37 +877,17 @@ QRLSH_EXPORT int qrlsh_owner_bounds(const uint64_t *words, int64_t n, int32_t bi
 constexpr int FIN_THREADS = QR_FIN_THREADS;
 constexpr int FIN_CAP = QR_FIN_CAP;   // records per part that fit the LDS image
 constexpr int FIN_IPT = FIN_CAP / FIN_THREADS;
-constexpr int FIN_SMALL_THREADS = 512, FIN_SMALL_CAP = 4096;  // the small-part form of the one-pass finish
+constexpr int FIN_SMALL_THREADS = 512, FIN_SMALL_CAP = 4096;  // the small-part form of the finish
 constexpr int FIN_SMALL_MEAN = 2800;                          // mean records per part up to which it is used
-
-// starts[band][f] = first position of band `band` whose T-bit part number is >= f (f = 0 .. 2^T)
-__global__ __launch_bounds__(256) void bucket_bounds_kernel(const uint64_t *__restrict__ keys,
-                                                            const uint32_t *__restrict__ ids, int64_t nq, int T,
-                                                            uint64_t ek, uint32_t *__restrict__ starts) {
-  const int nparts = 1 << T;
-  const int f = blockIdx.x * blockDim.x + threadIdx.x, band = blockIdx.y;
-  if (f > nparts) return;
-  const uint64_t *k = keys + (size_t)band * nq;
-  const uint32_t *id = ids + (size_t)band * nq;
-  int64_t lo = 0, hi = nq;  // first t with part(t) >= f
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    const uint64_t key = k[mid];
-    const uint32_t part = part_digit<true>(key, key == ek ? (int64_t)id[mid] : 0, 64 - T, ek, (uint32_t)nparts - 1u);
-    if ((int)part >= f) hi = mid;
-    else lo = mid + 1;
-  }
-  starts[(size_t)band * (nparts + 1) + f] = (uint32_t)lo;
-}
 
 // Finish of one (part, band): an open-addressing hash table in LDS keyed by the FULL 64-bit key
 // (ds_cmpst_b64 claims a slot or finds the key present; the empty-band key, which never enters a
 // bucket, doubles as the "free slot" marker).  A record's arrival number o in its slot's counter
 // says how many records of its bucket came before it, so
-//     pairs of the part = sum of o          (count kernel: that is all it needs)
-// and, for the fill, the ids of every bucket are laid out next to each other in LDS (run start =
-// exclusive scan of the slot counters, place = o) and a record pairs with the o ids in front of
-// it in its run, ordered (smaller id, larger id).  No chains, no walks, no key re-compares.
+//     pairs of the part = sum of o
+// and the ids of every bucket are laid out next to each other in LDS (run start = exclusive
+// scan of the slot counters, place = o): a record pairs with the o ids in front of it in its
+// run, ordered (smaller id, larger id).  No chains, no walks, no key re-compares.
 // LDS: table 48 KB + counters 24 KB = 72 KB -> two 1024-thread workgroups per CU (which also
 // needs <= 64 VGPRs: __launch_bounds__(1024, 8)).  Arrival order varies from run to run, so the
 // pairs of a part come out in varying order -- as a set they are exact, and the next step sorts.
@@ -1084,30 +931,19 @@ __device__ static inline void emit_run(uint64_t *__restrict__ dst, uint32_t pos,
   }
 }
 
-// MODE: FIN_COUNT leaves the part's pair count in blk; FIN_FILL writes the pairs at the offset the
-// scanned blk holds; FIN_EMIT does both in one go -- the workgroup reserves its output range with
-// one atomicAdd on a global cursor (blk[0]) and writes only if the range fits `capacity`; the cursor
-// ends up holding the exact total either way, so a caller whose guess was too small retries once.
-enum { FIN_COUNT = 0, FIN_FILL = 1, FIN_EMIT = 2 };
+// The records of part `bslot` are the first counts[bslot] of its own region of `cap` records.  The workgroup reserves
+// its output range with one atomicAdd on a global cursor (blk[0]) and writes only if the range fits `capacity`; the
+// cursor ends up holding the exact total either way, so a caller whose guess was too small retries once.
 // THREADS / CAP: the workgroup and its LDS image.  1024 / 6144 (72 KB: two workgroups per CU) is the general form; when
 // the parts are small (mean <= FIN_SMALL_MEAN records: 10 M queries and beyond), 512 / 4096 (48 KB) puts THREE
 // independent chains of phases on a CU instead of two (2.51 -> 2.12 ms at 10 M), and a part between 4096 and 6144
 // records joins the ones the big kernel works in blocks.
-template <int MODE, int THREADS = FIN_THREADS, int CAP = FIN_CAP>
-__global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finish_kernel(const uint64_t *__restrict__ keys,
-                                                                       const uint32_t *__restrict__ ids, int64_t nq,
-                                                                       const uint32_t *__restrict__ starts,
-                                                                       int nparts, uint64_t ek,
-                                                                       uint64_t *__restrict__ blk,
-                                                                       uint32_t *__restrict__ overflow,
-                                                                       uint64_t *__restrict__ out,
-                                                                       uint64_t capacity,
-                                                                       const uint32_t *__restrict__ counts = nullptr,
-                                                                       uint32_t cap = 0,
-                                                                       uint64_t *__restrict__ biglist = nullptr,
-                                                                       unsigned long long *__restrict__ nbig = nullptr,
-                                                                       uint32_t big_max = 0, uint32_t big_base = 0) {
-  constexpr bool FILL = MODE != FIN_COUNT;
+template <int THREADS = FIN_THREADS, int CAP = FIN_CAP>
+__global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finish_kernel(
+    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ids, int nparts, uint64_t ek, uint64_t *__restrict__ blk,
+    uint32_t *__restrict__ overflow, uint64_t *__restrict__ out, uint64_t capacity, const uint32_t *__restrict__ counts,
+    uint32_t cap, uint64_t *__restrict__ biglist, unsigned long long *__restrict__ nbig, uint32_t big_max,
+    uint32_t big_base) {
   constexpr int IPT = CAP / THREADS;
   static_assert(CAP % THREADS == 0 && CAP <= 65535, "image = whole records per thread, slots fit 16 bits");
   __shared__ unsigned long long gbase;
@@ -1117,33 +953,23 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
   const int part = blockIdx.x, band = blockIdx.y;
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid >> 6;
   const size_t bslot = (size_t)band * nparts + part;
-  // records of the part: [start, start + m) of the band's nq sorted records, or (counts given) the first
-  // counts[part] records of the part's own region of cap records
-  const uint32_t start = counts ? 0u : starts[(size_t)band * (nparts + 1) + part];
-  const uint32_t m = counts ? counts[bslot] : starts[(size_t)band * (nparts + 1) + part + 1] - start;
-  const size_t first = counts ? bslot * cap : (size_t)band * nq + start;
-  if (m > (uint32_t)CAP || (counts && m > cap)) {  // uniform over the workgroup
+  const uint32_t m = counts[bslot];
+  const size_t first = bslot * cap;
+  if (m > (uint32_t)CAP || m > cap) {  // uniform over the workgroup
     if (tid == 0) {
       // a part that holds more records than the LDS image (a popular key with thousands of copies, mostly), in its
-      // region or spilled into the pool: left to bucket_finish_big_kernel, which works it in blocks -- one-pass form only
+      // region or spilled into the pool: left to bucket_finish_big_kernel, which works it in blocks
       bool listed = false;
-      if (MODE == FIN_EMIT && biglist && counts) {
-        const unsigned long long at =
-            __hip_atomic_fetch_add(nbig, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (at < (unsigned long long)big_max) {
-          biglist[at] = (uint64_t)(big_base + bslot);
-          listed = true;
-        }
+      const unsigned long long at = __hip_atomic_fetch_add(nbig, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if (at < (unsigned long long)big_max) {
+        biglist[at] = (uint64_t)(big_base + bslot);
+        listed = true;
       }
       if (!listed) atomicOr(overflow, 1u);
-      if (MODE == FIN_COUNT) blk[bslot] = 0;
     }
     return;
   }
-  if (m == 0) {
-    if (MODE == FIN_COUNT && tid == 0) blk[bslot] = 0;
-    return;
-  }
+  if (m == 0) return;
   const uint64_t *k = keys + first;
   const uint32_t *id = ids + first;
   uint64_t kreg[IPT];
@@ -1152,7 +978,7 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
   for (int j = 0; j < IPT; ++j) {
     const uint32_t i = tid + j * THREADS;
     kreg[j] = i < m ? k[i] : ek;
-    if (FILL) ireg[j] = i < m ? id[i] : 0u;  // coalesced, in flight together with the keys
+    ireg[j] = i < m ? id[i] : 0u;  // coalesced, in flight together with the keys
   }
 #pragma unroll
   for (int j = 0; j < IPT; ++j) {
@@ -1209,16 +1035,10 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
     if (i < w) base += x;
     tot += x;
   }
-  if (MODE == FIN_COUNT) {
-    if (tid == 0) blk[bslot] = (uint64_t)tot;
-    return;
-  }
-  if (MODE == FIN_EMIT) {
-    if (tot == 0) return;  // uniform
-    if (tid == 0)
-      gbase = __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(blk), (unsigned long long)tot,
-                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (tot == 0) return;  // uniform
+  if (tid == 0)
+    gbase = __hip_atomic_fetch_add(reinterpret_cast<unsigned long long *>(blk), (unsigned long long)tot, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
   const uint32_t pos0 = base + inc - mine;
   {
     // run starts: exclusive scan of the slot counters, blocked layout (IPT consecutive slots per thread)
@@ -1255,8 +1075,8 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
     if (so[j] != 0xFFFFFFFFu) grp[cnt[so[j] & 0xFFFFu] + (so[j] >> 16)] = ireg[j];
   __syncthreads();
   {
-    const uint64_t obase = MODE == FIN_EMIT ? (uint64_t)gbase : blk[bslot];
-    if (MODE == FIN_EMIT && obase + tot > capacity) return;  // uniform: counted, not written
+    const uint64_t obase = (uint64_t)gbase;
+    if (obase + tot > capacity) return;  // uniform: counted, not written
     uint64_t *dst = out + obase;
     uint32_t pos = pos0;
 #pragma unroll
@@ -1710,12 +1530,6 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
   }
 }
 
-// the packed-counter form of the small-part finish (QRLSH_FIN_PACKED=0: the separate-counter form; an A/B knob)
-static int g_fin_packed = [] {
-  const char *e = getenv("QRLSH_FIN_PACKED");
-  return !(e && e[0] == '0') ? 1 : 0;
-}();
-
 // records a listed part may hold (qrlsh_set_big_part_limit; default and maximum: FIN_BIG_BLOCKS images)
 static uint32_t g_big_limit = (uint32_t)FIN_BIG_BLOCKS * FIN_CAP;
 QRLSH_EXPORT int64_t qrlsh_set_big_part_limit(int64_t records) {
@@ -1724,37 +1538,34 @@ QRLSH_EXPORT int64_t qrlsh_set_big_part_limit(int64_t records) {
   return old;
 }
 
-// workspace: [ghist + rtot of one sort pass][starts: b*(2^T+1) u32][blk: b*2^T u64][16 B tail]
-//            [fill: b*2^T u32][pool cursor, run count: 2 u64][runs: POOL_RUNS x 16 B][desc: 16 x FIN_BIG_LIST x 16 B]
+// workspace: [step-1 cursors: b << c1 u32 (two-step partitions only)][step-2 cursors = records per part: b << T u32]
+//            [big parts: one counter per band group, then their lists: b << T u64 in all][fill: b << T u32]
+//            [pool cursor, run count: 2 u64][runs: POOL_RUNS x 16 B][desc: 2 x FIN_BIG_LIST x 16 B]
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-constexpr int EMIT_MAX_GROUPS = 16;  // band groups of one qrlsh_bucket_pairs_emit call
+static int coarse_bits(int T);
+constexpr int EMIT_MAX_GROUPS = 2;  // band groups of one qrlsh_bucket_pairs_emit call
 struct BucketWs {
-  uint32_t *ghist, *rtot, *starts;
-  uint64_t *blk;
-  uint32_t *tail;
+  uint32_t *cur1, *counts;  // (a one-step partition, T = 8, has one set of cursors: cur1 == counts)
+  uint64_t *big;
   uint32_t *fill;
   unsigned long long *poolctl;
   uint4 *runs;
   BigDesc *desc;
   size_t bytes;
 };
-static BucketWs bucket_ws(void *workspace, int64_t nq, int32_t b, int32_t T) {
+static BucketWs bucket_ws(void *workspace, int32_t b, int32_t T) {
   BucketWs w;
-  const size_t nparts = (size_t)1 << T;
-  const int64_t ntiles = ceil_div64(nq, SORT_TILE);
+  const size_t slots = (size_t)b << T;
   char *p = static_cast<char *>(workspace);
   size_t off = 0;
-  w.ghist = reinterpret_cast<uint32_t *>(p + off);
-  w.rtot = w.ghist + (size_t)b * RADIX * ntiles;
-  off += align16(qrlsh_sort_workspace_bytes(nq, b));
-  w.starts = reinterpret_cast<uint32_t *>(p + off);
-  off += align16((size_t)b * (nparts + 1) * sizeof(uint32_t));
-  w.blk = reinterpret_cast<uint64_t *>(p + off);
-  off += (size_t)b * nparts * sizeof(uint64_t);
-  w.tail = reinterpret_cast<uint32_t *>(p + off);
-  off += 16;
+  w.cur1 = reinterpret_cast<uint32_t *>(p + off);
+  if (T > 8) off += align16(((size_t)b << coarse_bits(T)) * sizeof(uint32_t));
+  w.counts = reinterpret_cast<uint32_t *>(p + off);
+  off += align16(slots * sizeof(uint32_t));
+  w.big = reinterpret_cast<uint64_t *>(p + off);
+  off += slots * sizeof(uint64_t);
   w.fill = reinterpret_cast<uint32_t *>(p + off);
-  off += align16((size_t)b * nparts * sizeof(uint32_t));
+  off += align16(slots * sizeof(uint32_t));
   w.poolctl = reinterpret_cast<unsigned long long *>(p + off);
   off += 16;
   w.runs = reinterpret_cast<uint4 *>(p + off);
@@ -1767,55 +1578,7 @@ static BucketWs bucket_ws(void *workspace, int64_t nq, int32_t b, int32_t T) {
 
 QRLSH_EXPORT size_t qrlsh_bucket_workspace_bytes(int64_t nq, int32_t b, int32_t part_bits) {
   if (nq <= 0 || b <= 0 || part_bits < 8 || part_bits > 16) return 64;
-  return bucket_ws(nullptr, nq, b, part_bits).bytes;
-}
-
-// partition (one or two radix passes on the T-bit part number) + part bounds
-static void bucket_partition(const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids, uint64_t *tmp_keys,
-                             uint32_t *tmp_ids, int64_t nq, int32_t b, int32_t r, int32_t part_bits, const BucketWs &w,
-                             hipStream_t st) {
-  const int T = part_bits, nparts = 1 << T;
-  const int ntiles = (int)ceil_div64(nq, SORT_TILE);
-  const dim3 grid(ntiles, b), block(SORT_THREADS);
-  const uint64_t ek = qr_empty_key(r);
-  const uint32_t *no_vals = nullptr;
-  const bool staged = nq <= (1ll << 24);  // ids fit 24 bits: the LDS-staged scatter carries the digit beside them
-  if (T == 8) {
-    QR_LAUNCH("sort_hist", (sort_hist_kernel<SM_MIX, true>), grid, block, 0, st, keys, nq, ntiles, 56, w.ghist, ek, 0,
-              (uint32_t)RADIX - 1u, no_vals);
-    launch_rowscan(w.ghist, ntiles, w.rtot, b, st);
-    if (staged)
-      QR_LAUNCH("sort_scatter_kv", (part_scatter_staged_kernel<true>), grid, block, 0, st, keys, no_vals, part_keys,
-                part_ids, nq, ntiles, 56, w.ghist, w.rtot, ek, (uint32_t)RADIX - 1u);
-    else
-      QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<SM_MIX, true, true, true>), grid, block, 0, st, keys, no_vals,
-                part_keys, part_ids, nq, ntiles, 56, w.ghist, w.rtot, ek, 0, (uint32_t)RADIX - 1u);
-  } else {
-    // LSD over the T-bit part number: low T-8 bits first, then the top 8
-    const uint32_t lowmask = (1u << (T - 8)) - 1u;
-    QR_LAUNCH("sort_hist", (sort_hist_kernel<SM_MIX, true>), grid, block, 0, st, keys, nq, ntiles, 64 - T, w.ghist, ek, 0,
-              lowmask, no_vals);
-    launch_rowscan(w.ghist, ntiles, w.rtot, b, st);
-    if (staged)
-      QR_LAUNCH("sort_scatter_kv", (part_scatter_staged_kernel<true>), grid, block, 0, st, keys, no_vals, tmp_keys,
-                tmp_ids, nq, ntiles, 64 - T, w.ghist, w.rtot, ek, lowmask);
-    else
-      QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<SM_MIX, true, true, true>), grid, block, 0, st, keys, no_vals,
-                tmp_keys, tmp_ids, nq, ntiles, 64 - T, w.ghist, w.rtot, ek, 0, lowmask);
-    QR_LAUNCH("sort_hist", (sort_hist_kernel<SM_MIX, true>), grid, block, 0, st, (const uint64_t *)tmp_keys, nq, ntiles,
-              56, w.ghist, ek, 0, (uint32_t)RADIX - 1u, (const uint32_t *)tmp_ids);
-    launch_rowscan(w.ghist, ntiles, w.rtot, b, st);
-    if (staged)
-      QR_LAUNCH("sort_scatter_kv", (part_scatter_staged_kernel<false>), grid, block, 0, st, (const uint64_t *)tmp_keys,
-                (const uint32_t *)tmp_ids, part_keys, part_ids, nq, ntiles, 56, w.ghist, w.rtot, ek,
-                (uint32_t)RADIX - 1u);
-    else
-      QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<SM_MIX, true, false, true>), grid, block, 0, st,
-                (const uint64_t *)tmp_keys, (const uint32_t *)tmp_ids, part_keys, part_ids, nq, ntiles, 56, w.ghist,
-                w.rtot, ek, 0, (uint32_t)RADIX - 1u);
-  }
-  QR_LAUNCH("bucket_bounds", bucket_bounds_kernel, dim3((nparts + 1 + 255) / 256, b), dim3(256), 0, st,
-            (const uint64_t *)part_keys, (const uint32_t *)part_ids, nq, T, ek, w.starts);
+  return bucket_ws(nullptr, b, part_bits).bytes;
 }
 
 static int bucket_check(const char *name, const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids,
@@ -1840,27 +1603,7 @@ static int bucket_check(const char *name, const uint64_t *keys, uint64_t *part_k
   return QRLSH_OK;
 }
 
-QRLSH_EXPORT int qrlsh_bucket_pairs_count(const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids,
-                                          uint64_t *tmp_keys, uint32_t *tmp_ids, int64_t nq, int32_t b, int32_t r,
-                                          int32_t part_bits, void *workspace, size_t workspace_bytes,
-                                          uint64_t *total_overflow_out, void *stream) {
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const int rc = bucket_check("qrlsh_bucket_pairs_count", keys, part_keys, part_ids, tmp_keys, tmp_ids, nq, b, r,
-                              part_bits, workspace, workspace_bytes, total_overflow_out, st);
-  if (rc != QRLSH_OK || nq == 0) return rc;
-  const int nparts = 1 << part_bits;
-  const uint64_t ek = qr_empty_key(r);
-  const BucketWs w = bucket_ws(workspace, nq, b, part_bits);
-  bucket_partition(keys, part_keys, part_ids, tmp_keys, tmp_ids, nq, b, r, part_bits, w, st);
-  QR_LAUNCH("bucket_count", (bucket_finish_kernel<FIN_COUNT>), dim3(nparts, b), dim3(FIN_THREADS), 0, st,
-            (const uint64_t *)part_keys, (const uint32_t *)part_ids, nq, (const uint32_t *)w.starts, nparts, ek, w.blk,
-            reinterpret_cast<uint32_t *>(total_overflow_out + 1), (uint64_t *)nullptr, (uint64_t)0);
-  QR_LAUNCH("scan_blocks", scan_u64_kernel, dim3(1), dim3(1024), 0, st, w.blk, (int64_t)b * nparts, total_overflow_out);
-  QR_LAUNCH_CHECK("qrlsh_bucket_pairs_count");
-  return QRLSH_OK;
-}
-
-// records every part's region holds in the one-kernel partition (256 parts): the LDS image of the
+// records every part's region holds in a one-step partition (256 parts): the LDS image of the
 // finish for full-size inputs, mean + 50 % + 512 for small ones
 static uint32_t part_region(int64_t nq) {
   const int64_t c = ((nq / RADIX) * 3 / 2 + 512 + 63) / 64 * 64;
@@ -1891,7 +1634,6 @@ static uint32_t fine_region(int64_t nq, int T) {
   const int64_t c = ((nq >> T) * 2 + 128 + 63) / 64 * 64;
   return (uint32_t)(c < FIN_CAP ? c : FIN_CAP);
 }
-static bool one_kernel_partition(int64_t nq, int part_bits) { return nq < (1ll << 32) && part_bits >= 8; }
 // records of the overflow pool behind the regions: 1/16 of the records of the call (what popular keys spill, plus the
 // gathered copies of the spilled parts), at least 1 M, below 2^32
 static size_t pool_records(int64_t nq, int32_t b) {
@@ -1908,20 +1650,18 @@ static size_t region_words(int64_t nq, int32_t b, int32_t part_bits) {
 QRLSH_EXPORT size_t qrlsh_bucket_part_words(int64_t nq, int32_t b, int32_t part_bits) {
   if (nq <= 0 || b <= 0) return 0;
   const size_t plain = (size_t)b * nq;
-  if (!one_kernel_partition(nq, part_bits)) return plain;
   const size_t regions = region_words(nq, b, part_bits) + pool_records(nq, b);   // [regions][overflow pool]
   return regions > plain ? regions : plain;
 }
 QRLSH_EXPORT size_t qrlsh_bucket_tmp_words(int64_t nq, int32_t b, int32_t part_bits) {
   if (nq <= 0 || b <= 0 || part_bits <= 8) return 0;
   const size_t plain = (size_t)b * nq;
-  if (!one_kernel_partition(nq, part_bits)) return plain;
   const int c1 = coarse_bits(part_bits);
   const size_t regions = ((size_t)b << c1) * coarse_region(nq, c1);
   return regions > plain ? regions : plain;
 }
 
-// One-pass form: partition + finish with the output range of every part reserved on a device cursor.
+// Partition + finish with the output range of every part reserved on a device cursor.
 // total_overflow_out[0] ends up holding the exact number of pairs whether or not they fitted
 // `capacity` words of pairs_out (nothing is written past it); [1] != 0 flags an oversized part.
 QRLSH_EXPORT int qrlsh_bucket_pairs_emit(const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids,
@@ -1952,168 +1692,136 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
   QR_CHECK_ARG(pairs_out || capacity == 0, "qrlsh_bucket_pairs_emit: null output with capacity %llu",
                (unsigned long long)capacity);
   const int nparts = 1 << part_bits;
-  const BucketWs w = bucket_ws(workspace, nq, b, part_bits);
+  const BucketWs w = bucket_ws(workspace, b, part_bits);
   // the atomic partition hands the finish x = mix64(key): its free-slot marker is mix64(empty key)
   const uint64_t ekx = qr_mix64(qr_empty_key(r));
 #define QR_PART_SCATTER(LEVEL2_, ...) QR_LAUNCH("part_scatter", (part_scatter_atomic_kernel<LEVEL2_>), __VA_ARGS__)
-  if (one_kernel_partition(nq, part_bits)) {
-    // One-kernel partition(s) into fixed regions + the LDS finish.  The bands are independent of each other all the
-    // way to the pair cursor, so they are worked in GROUPS that alternate between the caller's stream and an
-    // auxiliary one (api.hip: qr_aux_fork): while one group sits in the finish -- a chain of LDS phases that
-    // leaves most of the memory system idle -- the next group's partition, which is nothing but memory traffic,
-    // shares the device with it.  Same kernels, same buffers (every group touches only its own bands' regions,
-    // cursors and counts), results as unordered as before; QRLSH_OVERLAP=0 (or an active profiler) runs the
-    // groups one after the other on the caller's stream.
-    const int T = part_bits;
-    const bool two = T > 8;
-    const int c1 = two ? coarse_bits(T) : 8;
-    const uint32_t cap1 = two ? coarse_region(nq, c1) : part_region(nq), cap2 = two ? fine_region(nq, T) : cap1;
-    const uint32_t lowmask = (1u << (T - c1)) - 1u;
-    // step-1 cursors: the histogram area (two steps) or `starts` (one step, read by the finish); step-2: `starts`
-    uint32_t *cur1 = two ? w.ghist : w.starts, *cur2 = w.starts;
-    if (hipMemsetAsync(cur1, 0, ((size_t)b << c1) * sizeof(uint32_t), st) != hipSuccess ||
-        (two && hipMemsetAsync(cur2, 0, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess)) {
-      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
-    uint32_t *ovf = reinterpret_cast<uint32_t *>(total_overflow_out + 1);
-    // the overflow pool behind the regions of the part buffers (PartPool above); the step that fills the parts the
-    // finish reads spills into it (the coarse step of a two-step partition does not: its regions have their own slack)
-    const size_t reg_words = region_words(nq, b, T);
-    PartPool pool;
-    pool.keys = part_keys + reg_words;
-    pool.vals = part_ids + reg_words;
-    pool.cursor = w.poolctl;
-    pool.nruns = w.poolctl + 1;
-    pool.cap = (uint32_t)pool_records(nq, b);
-    pool.runs = w.runs;
-    pool.runs_max = POOL_RUNS;
-    pool.fill = w.fill;
-    pool.slot_base = 0;
-    PartPool no_pool = pool;
-    no_pool.keys = nullptr;
-    no_pool.vals = nullptr;
-    if (hipMemsetAsync(w.fill, 0xFF, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess ||
-        hipMemsetAsync(w.poolctl, 0, 16, st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
-    // lists of the parts that outgrow the LDS image (bucket_finish_big_kernel), one per band group, in the count /
-    // fill form's block area: [16 counters][group 0's list][group 1's list] ...
-    constexpr int MAX_GROUPS = EMIT_MAX_GROUPS;
-    unsigned long long *nbig0 = reinterpret_cast<unsigned long long *>(w.blk);
-    uint64_t *biglist0 = w.blk + MAX_GROUPS;
-    const uint64_t slots = (uint64_t)b << T;  // >= 256 words in the block area
-    if (hipMemsetAsync(nbig0, 0, MAX_GROUPS * sizeof(unsigned long long), st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
-    // small parts: the 512-thread / 4096-slot finish
-    const bool small_parts = two && small_form(nq, T);
-    const int ntiles = (int)ceil_div64(nq, PS_TILE);
-    const int64_t band_words = key_band_stride ? key_band_stride : nq;  // words between two bands of the key matrix
-    static int groups_env = -1;
-    if (groups_env < 0) {
-      const char *e = getenv("QRLSH_EMIT_GROUPS");
-      groups_env = e ? atoi(e) : 2;  // 10 M queries x 32 bands: 18.84 ms per step with 1 group, 18.42 with 2, 18.9 with 4, 19.2 with 8
-      if (groups_env < 1) groups_env = 1;
-    }
-    // small inputs: one group (the second stream's fork / join and the extra launches cost more than the overlap
-    // gives: 1.71 against 1.67 ms per step at 1 M queries x 32 bands)
-    int GROUPS = (int64_t)b * nq >= (64ll << 20) ? groups_env : 1;
-    if (GROUPS > MAX_GROUPS) GROUPS = MAX_GROUPS;
-    const int per = (b + GROUPS - 1) / GROUPS;
-    const int ngroups = (b + per - 1) / per;
-    const uint64_t list_room = (slots - MAX_GROUPS) / (uint64_t)ngroups;
-    const uint32_t big_max = (uint32_t)(list_room < FIN_BIG_LIST ? list_room : FIN_BIG_LIST);
-    // With two or more groups, a group's gather (bucket_big_gather_kernel) scans the run descriptors while the next
-    // group's partition, on the other stream, counts new runs in before it writes their descriptors: a slot in
-    // between still holds what an earlier call left there, and one that names a part of this group would be counted
-    // twice (the overflow flag, and the step on the general path).  Cleared, such a slot reads {0, 0 records}: it
-    // matches at most slot 0 and adds nothing.
-    if (ngroups > 1 && hipMemsetAsync(w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
-    hipStream_t aux = nullptr;
-    int gi = 0;
-    for (int g0 = 0; g0 < b; g0 += per, ++gi) {
-      const int nb = (b - g0 < per) ? b - g0 : per;
-      hipStream_t s = (aux && (gi & 1)) ? aux : st;
-      uint64_t *biglist = biglist0 + (size_t)gi * big_max;
-      unsigned long long *nbig = nbig0 + gi;
-      uint64_t *k1 = two ? tmp_keys : part_keys;
-      uint32_t *v1 = two ? tmp_ids : part_ids;
-      pool.slot_base = (uint32_t)((size_t)g0 << T);
-      BigDesc *desc = w.desc + (size_t)gi * FIN_BIG_LIST;
-      QR_PART_SCATTER(false, dim3(ntiles, nb), dim3(SORT_THREADS), 0, s, keys + (size_t)g0 * band_words,
-                      (const uint32_t *)nullptr, k1 + ((size_t)g0 << c1) * cap1, v1 + ((size_t)g0 << c1) * cap1, nq,
-                      ntiles, 64 - c1, (1u << c1) - 1u, cur1 + ((size_t)g0 << c1), cap1, ovf, qr_empty_key(r),
-                      (const uint32_t *)nullptr, 0u, key_chunk, key_chunk_stride, key_band_stride, two ? no_pool : pool);
-      if (two)
-        QR_PART_SCATTER(true, dim3((unsigned)ceil_div64(cap1, PS_TILE), nb << c1), dim3(SORT_THREADS), 0, s,
-                        (const uint64_t *)tmp_keys + ((size_t)g0 << c1) * cap1,
-                        (const uint32_t *)tmp_ids + ((size_t)g0 << c1) * cap1, part_keys + ((size_t)g0 << T) * cap2,
-                        part_ids + ((size_t)g0 << T) * cap2, (int64_t)0, 0, 64 - T, lowmask, cur2 + ((size_t)g0 << T),
-                        cap2, ovf, qr_empty_key(r), (const uint32_t *)cur1 + ((size_t)g0 << c1), cap1, (int64_t)0,
-                        (int64_t)0, (int64_t)0, pool);
-      // the auxiliary stream is forked once the first group's partition is queued and before its finish is: the
-      // second group's partition then starts beside the first group's finish, and the two streams stay half a
-      // group out of step
-      if (gi == 0 && b > per) aux = qr_aux_fork(st);
-      if (small_parts && T >= 12 && g_fin_packed)
-        QR_LAUNCH("bucket_emit", bucket_finish_packed_kernel, dim3(nparts, nb), dim3(FIN_PK_THREADS), 0, s,
-                  (const uint64_t *)part_keys + ((size_t)g0 << T) * cap2, (const uint32_t *)part_ids + ((size_t)g0 << T) * cap2,
-                  nparts, total_overflow_out, ovf, pairs_out, capacity, (const uint32_t *)cur2 + ((size_t)g0 << T), cap2, biglist,
-                  nbig, big_max, (uint32_t)((size_t)g0 << T));
-      else if (small_parts)
-        QR_LAUNCH("bucket_emit", (bucket_finish_kernel<FIN_EMIT, FIN_SMALL_THREADS, FIN_SMALL_CAP>), dim3(nparts, nb),
-                  dim3(FIN_SMALL_THREADS), 0, s, (const uint64_t *)part_keys + ((size_t)g0 << T) * cap2,
-                  (const uint32_t *)part_ids + ((size_t)g0 << T) * cap2, nq, (const uint32_t *)nullptr, nparts, ekx,
-                  total_overflow_out, ovf, pairs_out, capacity, (const uint32_t *)cur2 + ((size_t)g0 << T), cap2, biglist, nbig,
-                  big_max, (uint32_t)((size_t)g0 << T));
-      else
-        QR_LAUNCH("bucket_emit", (bucket_finish_kernel<FIN_EMIT>), dim3(nparts, nb), dim3(FIN_THREADS), 0, s,
-                  (const uint64_t *)part_keys + ((size_t)g0 << T) * cap2, (const uint32_t *)part_ids + ((size_t)g0 << T) * cap2,
-                  nq, (const uint32_t *)nullptr, nparts, ekx, total_overflow_out, ovf, pairs_out, capacity,
-                  (const uint32_t *)cur2 + ((size_t)g0 << T), cap2, biglist, nbig, big_max, (uint32_t)((size_t)g0 << T));
-      // the parts of this group the finish listed as larger than its LDS image (usually none: the kernel then finds
-      // an empty list), on the group's own stream: they are worked beside the next group
-      QR_LAUNCH("bucket_emit_big", bucket_big_gather_kernel, dim3(64), dim3(256), 0, s, (const uint64_t *)biglist,
-                (const unsigned long long *)nbig, big_max, desc, (const uint64_t *)part_keys, (const uint32_t *)part_ids,
-                (const uint32_t *)cur2, cap2, pool, g_big_limit, ovf);
-      QR_LAUNCH("bucket_emit_big", bucket_finish_big_kernel, dim3(FIN_BIG_GRID), dim3(FIN_THREADS), 0, s,
-                (const uint64_t *)part_keys, (const uint32_t *)part_ids, (const uint64_t *)pool.keys,
-                (const uint32_t *)pool.vals, ekx, (const BigDesc *)desc, (const unsigned long long *)nbig, big_max,
-                total_overflow_out, pairs_out, capacity);
-    }
-    if (aux && qr_aux_join(st) != QRLSH_OK) return QRLSH_EHIP;
-    QR_LAUNCH_CHECK("qrlsh_bucket_pairs_emit");
-    return QRLSH_OK;
+  // Partition(s) into fixed regions + the LDS finish.  The bands are independent of each other all the way to the
+  // pair cursor, so they are worked in GROUPS that alternate between the caller's stream and an auxiliary one
+  // (api.hip: qr_aux_fork): while one group sits in the finish -- a chain of LDS phases that leaves most of the
+  // memory system idle -- the next group's partition, which is nothing but memory traffic, shares the device with
+  // it.  Same kernels, same buffers (every group touches only its own bands' regions, cursors and counts), results
+  // as unordered as before; QRLSH_OVERLAP=0 (or an active profiler) runs the groups one after the other on the
+  // caller's stream.
+  const int T = part_bits;
+  const bool two = T > 8;
+  const int c1 = two ? coarse_bits(T) : 8;
+  const uint32_t cap1 = two ? coarse_region(nq, c1) : part_region(nq), cap2 = two ? fine_region(nq, T) : cap1;
+  const uint32_t lowmask = (1u << (T - c1)) - 1u;
+  // step-2 cursors end up as the parts' record counts, which the finish reads (one step: they are step 1's)
+  uint32_t *cur1 = w.cur1, *cur2 = w.counts;
+  if (hipMemsetAsync(cur1, 0, ((size_t)b << c1) * sizeof(uint32_t), st) != hipSuccess ||
+      (two && hipMemsetAsync(cur2, 0, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess)) {
+    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
+    return QRLSH_EHIP;
   }
-#undef QR_PART_SCATTER
-  QR_CHECK_ARG(key_chunk == 0, "qrlsh_bucket_pairs_emit_chunked: chunked keys need nq < 2^32");
-  bucket_partition(keys, part_keys, part_ids, tmp_keys, tmp_ids, nq, b, r, part_bits, w, st);
-  QR_LAUNCH("bucket_emit", (bucket_finish_kernel<FIN_EMIT>), dim3(nparts, b), dim3(FIN_THREADS), 0, st,
-            (const uint64_t *)part_keys, (const uint32_t *)part_ids, nq, (const uint32_t *)w.starts, nparts,
-            qr_empty_key(r), total_overflow_out, reinterpret_cast<uint32_t *>(total_overflow_out + 1), pairs_out,
-            capacity);
+  uint32_t *ovf = reinterpret_cast<uint32_t *>(total_overflow_out + 1);
+  // the overflow pool behind the regions of the part buffers (PartPool above); the step that fills the parts the
+  // finish reads spills into it (the coarse step of a two-step partition does not: its regions have their own slack)
+  const size_t reg_words = region_words(nq, b, T);
+  PartPool pool;
+  pool.keys = part_keys + reg_words;
+  pool.vals = part_ids + reg_words;
+  pool.cursor = w.poolctl;
+  pool.nruns = w.poolctl + 1;
+  pool.cap = (uint32_t)pool_records(nq, b);
+  pool.runs = w.runs;
+  pool.runs_max = POOL_RUNS;
+  pool.fill = w.fill;
+  pool.slot_base = 0;
+  PartPool no_pool = pool;
+  no_pool.keys = nullptr;
+  no_pool.vals = nullptr;
+  if (hipMemsetAsync(w.fill, 0xFF, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess ||
+      hipMemsetAsync(w.poolctl, 0, 16, st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  // lists of the parts that outgrow the LDS image (bucket_finish_big_kernel), one per band group:
+  // [2 counters][group 0's list][group 1's list]
+  constexpr int MAX_GROUPS = EMIT_MAX_GROUPS;
+  unsigned long long *nbig0 = reinterpret_cast<unsigned long long *>(w.big);
+  uint64_t *biglist0 = w.big + MAX_GROUPS;
+  const uint64_t slots = (uint64_t)b << T;  // >= 256 words in that area
+  if (hipMemsetAsync(nbig0, 0, MAX_GROUPS * sizeof(unsigned long long), st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  // small parts: the 512-thread / 4096-slot finish
+  const bool small_parts = two && small_form(nq, T);
+  const int ntiles = (int)ceil_div64(nq, PS_TILE);
+  const int64_t band_words = key_band_stride ? key_band_stride : nq;  // words between two bands of the key matrix
+  // two groups (10 M queries x 32 bands: 18.84 ms per step with 1 group, 18.42 with 2, 18.9 with 4, 19.2 with 8);
+  // small inputs: one (the second stream's fork / join and the extra launches cost more than the overlap
+  // gives: 1.71 against 1.67 ms per step at 1 M queries x 32 bands)
+  const int GROUPS = (int64_t)b * nq >= (64ll << 20) ? MAX_GROUPS : 1;
+  const int per = (b + GROUPS - 1) / GROUPS;
+  const int ngroups = (b + per - 1) / per;
+  const uint64_t list_room = (slots - MAX_GROUPS) / (uint64_t)ngroups;
+  const uint32_t big_max = (uint32_t)(list_room < FIN_BIG_LIST ? list_room : FIN_BIG_LIST);
+  // With two or more groups, a group's gather (bucket_big_gather_kernel) scans the run descriptors while the next
+  // group's partition, on the other stream, counts new runs in before it writes their descriptors: a slot in
+  // between still holds what an earlier call left there, and one that names a part of this group would be counted
+  // twice (the overflow flag, and the step on the general path).  Cleared, such a slot reads {0, 0 records}: it
+  // matches at most slot 0 and adds nothing.
+  if (ngroups > 1 && hipMemsetAsync(w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  hipStream_t aux = nullptr;
+  int gi = 0;
+  for (int g0 = 0; g0 < b; g0 += per, ++gi) {
+    const int nb = (b - g0 < per) ? b - g0 : per;
+    hipStream_t s = (aux && (gi & 1)) ? aux : st;
+    uint64_t *biglist = biglist0 + (size_t)gi * big_max;
+    unsigned long long *nbig = nbig0 + gi;
+    uint64_t *k1 = two ? tmp_keys : part_keys;
+    uint32_t *v1 = two ? tmp_ids : part_ids;
+    pool.slot_base = (uint32_t)((size_t)g0 << T);
+    BigDesc *desc = w.desc + (size_t)gi * FIN_BIG_LIST;
+    QR_PART_SCATTER(false, dim3(ntiles, nb), dim3(SORT_THREADS), 0, s, keys + (size_t)g0 * band_words,
+                    (const uint32_t *)nullptr, k1 + ((size_t)g0 << c1) * cap1, v1 + ((size_t)g0 << c1) * cap1, nq,
+                    ntiles, 64 - c1, (1u << c1) - 1u, cur1 + ((size_t)g0 << c1), cap1, ovf, qr_empty_key(r),
+                    (const uint32_t *)nullptr, 0u, key_chunk, key_chunk_stride, key_band_stride, two ? no_pool : pool);
+    if (two)
+      QR_PART_SCATTER(true, dim3((unsigned)ceil_div64(cap1, PS_TILE), nb << c1), dim3(SORT_THREADS), 0, s,
+                      (const uint64_t *)tmp_keys + ((size_t)g0 << c1) * cap1,
+                      (const uint32_t *)tmp_ids + ((size_t)g0 << c1) * cap1, part_keys + ((size_t)g0 << T) * cap2,
+                      part_ids + ((size_t)g0 << T) * cap2, (int64_t)0, 0, 64 - T, lowmask, cur2 + ((size_t)g0 << T),
+                      cap2, ovf, qr_empty_key(r), (const uint32_t *)cur1 + ((size_t)g0 << c1), cap1, (int64_t)0,
+                      (int64_t)0, (int64_t)0, pool);
+    // the auxiliary stream is forked once the first group's partition is queued and before its finish is: the
+    // second group's partition then starts beside the first group's finish, and the two streams stay half a
+    // group out of step
+    if (gi == 0 && b > per) aux = qr_aux_fork(st);
+    if (small_parts && T >= 12)
+      QR_LAUNCH("bucket_emit", bucket_finish_packed_kernel, dim3(nparts, nb), dim3(FIN_PK_THREADS), 0, s,
+                (const uint64_t *)part_keys + ((size_t)g0 << T) * cap2, (const uint32_t *)part_ids + ((size_t)g0 << T) * cap2,
+                nparts, total_overflow_out, ovf, pairs_out, capacity, (const uint32_t *)cur2 + ((size_t)g0 << T), cap2, biglist,
+                nbig, big_max, (uint32_t)((size_t)g0 << T));
+    else if (small_parts)
+      QR_LAUNCH("bucket_emit", (bucket_finish_kernel<FIN_SMALL_THREADS, FIN_SMALL_CAP>), dim3(nparts, nb),
+                dim3(FIN_SMALL_THREADS), 0, s, (const uint64_t *)part_keys + ((size_t)g0 << T) * cap2,
+                (const uint32_t *)part_ids + ((size_t)g0 << T) * cap2, nparts, ekx,
+                total_overflow_out, ovf, pairs_out, capacity, (const uint32_t *)cur2 + ((size_t)g0 << T), cap2, biglist, nbig,
+                big_max, (uint32_t)((size_t)g0 << T));
+    else
+      QR_LAUNCH("bucket_emit", (bucket_finish_kernel<>), dim3(nparts, nb), dim3(FIN_THREADS), 0, s,
+                (const uint64_t *)part_keys + ((size_t)g0 << T) * cap2, (const uint32_t *)part_ids + ((size_t)g0 << T) * cap2,
+                nparts, ekx, total_overflow_out, ovf, pairs_out, capacity,
+                (const uint32_t *)cur2 + ((size_t)g0 << T), cap2, biglist, nbig, big_max, (uint32_t)((size_t)g0 << T));
+    // the parts of this group the finish listed as larger than its LDS image (usually none: the kernel then finds
+    // an empty list), on the group's own stream: they are worked beside the next group
+    QR_LAUNCH("bucket_emit_big", bucket_big_gather_kernel, dim3(64), dim3(256), 0, s, (const uint64_t *)biglist,
+              (const unsigned long long *)nbig, big_max, desc, (const uint64_t *)part_keys, (const uint32_t *)part_ids,
+              (const uint32_t *)cur2, cap2, pool, g_big_limit, ovf);
+    QR_LAUNCH("bucket_emit_big", bucket_finish_big_kernel, dim3(FIN_BIG_GRID), dim3(FIN_THREADS), 0, s,
+              (const uint64_t *)part_keys, (const uint32_t *)part_ids, (const uint64_t *)pool.keys,
+              (const uint32_t *)pool.vals, ekx, (const BigDesc *)desc, (const unsigned long long *)nbig, big_max,
+              total_overflow_out, pairs_out, capacity);
+  }
+  if (aux && qr_aux_join(st) != QRLSH_OK) return QRLSH_EHIP;
   QR_LAUNCH_CHECK("qrlsh_bucket_pairs_emit");
   return QRLSH_OK;
-}
-
-QRLSH_EXPORT int qrlsh_bucket_pairs_fill(const uint64_t *part_keys, const uint32_t *part_ids, int64_t nq, int32_t b,
-                                         int32_t r, int32_t part_bits, void *workspace, uint64_t *pairs_out,
-                                         void *stream) {
-  QR_CHECK_ARG(nq >= 0 && b > 0 && r > 0 && part_bits >= 8 && part_bits <= 16,
-               "qrlsh_bucket_pairs_fill: bad sizes");
-  if (nq == 0) return QRLSH_OK;
-  QR_CHECK_ARG(part_keys && part_ids && workspace && pairs_out, "qrlsh_bucket_pairs_fill: null pointer");
-  const int nparts = 1 << part_bits;
-  const BucketWs w = bucket_ws(workspace, nq, b, part_bits);
-  QR_LAUNCH("bucket_fill", (bucket_finish_kernel<FIN_FILL>), dim3(nparts, b), dim3(FIN_THREADS), 0,
-            static_cast<hipStream_t>(stream), part_keys, part_ids, nq, (const uint32_t *)w.starts, nparts,
-            qr_empty_key(r), w.blk, w.tail, pairs_out, (uint64_t)0);
-  QR_LAUNCH_CHECK("qrlsh_bucket_pairs_fill");
-  return QRLSH_OK;
+#undef QR_PART_SCATTER
 }

@@ -501,15 +501,15 @@ def part_bits_for(n):
 _EMIT_HINT = {}   # (nq, b, r) -> pairs emitted by the last call of that shape: the next call's capacity guess
 
 
-def emit_pairs_fast(keys, r, part_bits=None, one_pass=True, capacity=None, chunks=None):
+def emit_pairs_fast(keys, r, part_bits=None, capacity=None, chunks=None):
     """emit_pairs for unsorted band-major keys through the partition + LDS-finish path.
     Returns the pairs tensor, or None when a part overflowed the LDS image (skewed data).
-    one_pass: the parts reserve their output ranges on a device cursor (qrlsh_bucket_pairs_emit), so
+    The parts reserve their output ranges on a device cursor (qrlsh_bucket_pairs_emit), so
     no count pass runs; the output buffer is sized by `capacity` (default: 1.25 x what the last call
     of this shape emitted, else 24 pairs per query) and the call is repeated once, exactly sized,
-    if that was too small.  one_pass=False is the count-then-fill form.
+    if that was too small.
     chunks=(world, nb, nql[, stride]): `keys` is the [world][nb][nql] buffer a band-partitioned all-to-all delivers
-    (band t, query q at [q // nql][t][q % nql]); it is read in place (one-pass form).  stride (default nb * nql):
+    (band t, query q at [q // nql][t][q % nql]); it is read in place.  stride (default nb * nql):
     words between two ranks' chunks -- nb of each rank's b bands, read out of a [world][b][nql] buffer."""
     lib = _lib.load()
     if chunks is not None:
@@ -517,8 +517,8 @@ def emit_pairs_fast(keys, r, part_bits=None, one_pass=True, capacity=None, chunk
         stride = chunks[3] if len(chunks) > 3 else b * nql     # words between the chunks of two ranks
         nq = world * nql
         _need(keys, torch.int64, "keys")
-        if stride < b * nql or keys.numel() < (world - 1) * stride + b * nql or not one_pass:
-            raise ValueError("chunked keys: need (world - 1) * stride + nb * nql words and the one-pass form")
+        if stride < b * nql or keys.numel() < (world - 1) * stride + b * nql:
+            raise ValueError("chunked keys: need (world - 1) * stride + nb * nql words")
         layout = (nql, stride, nql)
     else:
         _need(keys, torch.int64, "keys", 2)
@@ -528,41 +528,30 @@ def emit_pairs_fast(keys, r, part_bits=None, one_pass=True, capacity=None, chunk
     T = part_bits if part_bits is not None else part_bits_for(nq)
     if nq > 6144 * (1 << T):
         return None  # cannot fit even with the finest partition
-    words = lib.qrlsh_bucket_part_words(nq, b, T) if one_pass else b * nq
+    words = lib.qrlsh_bucket_part_words(nq, b, T)
     pk = torch.empty((words,), dtype=torch.int64, device=dev)
     pid = torch.empty((words,), dtype=torch.int32, device=dev)
-    twords = (lib.qrlsh_bucket_tmp_words(nq, b, T) if one_pass else b * nq) if T > 8 else 0
+    twords = lib.qrlsh_bucket_tmp_words(nq, b, T) if T > 8 else 0
     tk = torch.empty((twords,), dtype=torch.int64, device=dev) if T > 8 else None
     tid = torch.empty((twords,), dtype=torch.int32, device=dev) if T > 8 else None
     ws = _ws(lib.qrlsh_bucket_workspace_bytes(nq, b, T), dev)
     tot = torch.zeros(2, dtype=torch.int64, device=dev)
-    if one_pass:
-        shape = (nq, b, r)
-        if capacity is None:
-            capacity = _EMIT_HINT[shape] * 5 // 4 + 1024 if shape in _EMIT_HINT else 24 * nq + 1024
-        while True:
-            pairs = torch.empty((capacity,), dtype=torch.int64, device=dev)
-            _lib.check(lib.qrlsh_bucket_pairs_emit_chunked(_ptr(keys), layout[0], layout[1], layout[2], _ptr(pk),
-                                                           _ptr(pid), _ptr(tk), _ptr(tid), nq, b, r, T, _ptr(ws),
-                                                           ws.numel(), _ptr(pairs), capacity, _ptr(tot), _stream()))
-            n, overflow = tot.tolist()
-            if overflow:
-                return None
-            _EMIT_HINT[shape] = n
-            if n <= capacity:
-                return pairs[:n]
-            del pairs
-            capacity = n       # the cursor counted everything: the second run fits exactly
-    _lib.check(lib.qrlsh_bucket_pairs_count(_ptr(keys), _ptr(pk), _ptr(pid), _ptr(tk), _ptr(tid), nq, b, r, T,
-                                            _ptr(ws), ws.numel(), _ptr(tot), _stream()))
-    n, overflow = tot.tolist()
-    if overflow:
-        return None
-    del tk, tid
-    pairs = torch.empty((n,), dtype=torch.int64, device=dev)
-    if n:
-        _lib.check(lib.qrlsh_bucket_pairs_fill(_ptr(pk), _ptr(pid), nq, b, r, T, _ptr(ws), _ptr(pairs), _stream()))
-    return pairs
+    shape = (nq, b, r)
+    if capacity is None:
+        capacity = _EMIT_HINT[shape] * 5 // 4 + 1024 if shape in _EMIT_HINT else 24 * nq + 1024
+    while True:
+        pairs = torch.empty((capacity,), dtype=torch.int64, device=dev)
+        _lib.check(lib.qrlsh_bucket_pairs_emit_chunked(_ptr(keys), layout[0], layout[1], layout[2], _ptr(pk),
+                                                       _ptr(pid), _ptr(tk), _ptr(tid), nq, b, r, T, _ptr(ws),
+                                                       ws.numel(), _ptr(pairs), capacity, _ptr(tot), _stream()))
+        n, overflow = tot.tolist()
+        if overflow:
+            return None
+        _EMIT_HINT[shape] = n
+        if n <= capacity:
+            return pairs[:n]
+        del pairs
+        capacity = n       # the cursor counted everything: the second run fits exactly
 
 
 def emit_pairs_any(keys, r, stats=None):

@@ -1,6 +1,6 @@
 """Builders of adversarial band-key matrices for the partition + LDS-finish bucket path (csrc/sort.hip): planted
 multiplicities, several popular keys hashed into ONE part, a part filled to exactly N records.  Shared by
-tests/test_gpu_buckets.py, tests/forms_worker.py and tools/stress_buckets.py.
+tests/test_gpu_buckets.py and tools/stress_buckets.py.
 
 Every builder returns a BucketCase: the band-major int64 keys [b][nq] and what it meant to build -- the partition depth
 T, the band and part it aimed at and the exact number of records that part holds (its background records included).

@@ -1,12 +1,8 @@
 """Boundary cases of the candidate-pair path on the GPU: adversarial bucket structures through the partition + overflow
-pool + LDS finish (every form) + block kernel, the pair de-duplication on their output, the alternate forms chosen at
-library load (in a child process) and the two forms of pair scoring -- all against the oracle.  The cases come from
-tests/bucket_cases.py; every one is checked on the host first, so it cannot quietly stop aiming at its boundary."""
-import json
-import os
-import subprocess
-import sys
-
+pool + LDS finish (every form: the library picks it from the size and the depth) + block kernel, one and two band
+groups, the pair de-duplication on their output and the two forms of pair scoring -- all against the oracle.  The
+cases come from tests/bucket_cases.py; every one is checked on the host first, so it cannot quietly stop aiming at its
+boundary."""
 import numpy as np
 import pytest
 import torch
@@ -20,7 +16,6 @@ from oracle import oracle as O  # noqa: E402  (checker only)
 
 DEV = "cuda"
 R = 4
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 
 def u64(t):
@@ -160,50 +155,6 @@ def test_two_band_groups_with_spills_in_both_stay_exact_and_fast():
         once()
     finally:
         lib.qrlsh_set_overlap(1)
-
-
-# ---- count-then-fill --------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,path", [(6144, "partition+lds"), (6145, "general-sort")])
-def test_count_then_fill_form_at_the_image_boundary(N, path):
-    """emit_pairs_fast(one_pass=False): a part of exactly one image is finished in LDS, one record more overflows (the
-    count-then-fill form has no block kernel) and the general path takes it -- exact either way"""
-    case = B.fill_case(8, N)
-    check_case_on_host(case, count=N)
-    keys = case.keys
-    pairs = ops.emit_pairs_fast(torch.from_numpy(keys).to(DEV), R, one_pass=False)
-    got_path = "partition+lds" if pairs is not None else "general-sort"
-    if pairs is None:
-        sk, sid = ops.bucket_sort(torch.from_numpy(keys).to(DEV))
-        pairs = ops.emit_pairs(sk, sid, R)
-    torch.cuda.synchronize()
-    assert got_path == path
-    kq = np.ascontiguousarray(keys.T).view(np.uint64)
-    assert pairs.numel() == O.emitted_pairs(kq, R)
-    assert np.array_equal(O.sort_unique(u64(pairs)), O.candidates(kq, R))
-
-
-# ---- forms chosen at library load -------------------------------------------------------------------------------------
-@pytest.mark.parametrize("env", [{"QRLSH_FIN_PACKED": "0"}, {"QRLSH_EMIT_GROUPS": "1"}])
-def test_forms_chosen_at_library_load_equal_the_oracle(tmp_path, env):
-    """the separate-counter small-part finish at T = 12 (QRLSH_FIN_PACKED=0) and one band group (QRLSH_EMIT_GROUPS=1)
-    are read once when the library loads: a child process (tests/forms_worker.py) runs the T = 12 exact-fill cases and
-    the two-group case under them and writes the sorted emitted words; they are checked here"""
-    full = dict(os.environ)
-    full.update(env)
-    p = subprocess.run([sys.executable, os.path.join(HERE, "forms_worker.py"), str(tmp_path)], env=full,
-                       capture_output=True, text=True, timeout=600)
-    assert p.returncode == 0, p.stdout[-3000:] + p.stderr[-3000:]
-    done = json.load(open(tmp_path / "cases.json"))
-    cases = [B.fill_case(12, N) for N in B.FILLS[12]] + [B.two_group_case()]
-    assert [c["name"] for c in done] == [c.name for c in cases]
-    for c, d in zip(cases, done):
-        assert d["path"] == "partition+lds", d
-        words = np.fromfile(tmp_path / d["file"], dtype=np.uint64)
-        kq = np.ascontiguousarray(c.keys.T).view(np.uint64)
-        assert len(words) == O.emitted_pairs(kq, R), c.name
-        assert np.all(words[1:] >= words[:-1])
-        uniq = words[np.concatenate(([True], words[1:] != words[:-1]))] if len(words) else words
-        assert np.array_equal(uniq, O.candidates(kq, R)), c.name
 
 
 # ---- scoring forms ----------------------------------------------------------------------------------------------------

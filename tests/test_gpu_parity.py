@@ -614,8 +614,7 @@ def test_full_size_256_perm_64_bands_equals_oracle():
 def test_more_than_2_pow_24_queries_equals_oracle():
     """nq > 2^24 (the per-rank record count of configs 4-5): ids need more than 24 bits of the partition's id
     word (which carries nothing else: the partition stores mix64(key) and takes every part number from it),
-    T = 12; tiny P / b keep it cheap.  Also drives the count-then-fill API, whose sort-based partition takes its non-staged
-    scatter for nq > 2^24 (sort.hip: bucket_partition), and the plain-layout size rules."""
+    T = 12; tiny P / b keep it cheap.  Also reads the same keys in place in the layout an all-to-all delivers."""
     nq, D, P, b = 17_000_000, 32768, 8, 2
     assert nq > (1 << 24)
     K = pipeline.max_candidates(nq)
@@ -627,17 +626,13 @@ def test_more_than_2_pow_24_queries_equals_oracle():
     assert res.stats["bucket_path"] == "partition+lds"
     O.set_threads(16)
     _check_against_oracle(res, off, rows, perms, b, K, nq)
-    # count-then-fill API on the same keys: the sort-based partition, non-staged for nq > 2^24
     _, _, keys = ops.minhash(off, rows, table, b=b, compact=True)
-    slow = ops.emit_pairs_fast(keys, P // b, one_pass=False)
-    assert slow is not None and slow.numel() == res.stats["emitted_pairs"]
-    assert np.array_equal(u64(ops.unique_pairs(slow, nq)), u64(res.pairs))
     # keys as a band-partitioned all-to-all delivers them, read in place at nq > 2^24
     world = 4
     nql = nq // world
     recv = keys.view(b, world, nql).permute(1, 0, 2).contiguous()
     chunked = ops.emit_pairs_fast(recv.view(-1), P // b, chunks=(world, b, nql))
-    assert chunked is not None and chunked.numel() == slow.numel()
+    assert chunked is not None and chunked.numel() == res.stats["emitted_pairs"]
     assert np.array_equal(u64(ops.unique_pairs(chunked, nq)), u64(res.pairs))
 
 
@@ -1306,8 +1301,7 @@ def test_fast_bucket_path_equals_general_path():
         sk, sid = ops.bucket_sort(dev(k.view(np.int64)))
         gen = np.sort(u64(ops.emit_pairs(sk, sid, 4)))
         for T in (None, 9, 12, 16):                               # one- and two-pass partitions
-            for kw in (dict(one_pass=False),                      # count-then-fill
-                       dict(),                                    # cursor-reserved ranges, default capacity guess
+            for kw in (dict(),                                    # cursor-reserved ranges, default capacity guess
                        dict(capacity=max(1, gen.size // 3)),      # guess too small: counted, retried exactly sized
                        dict(capacity=gen.size)):                  # exact
                 fast = ops.emit_pairs_fast(dev(k.view(np.int64)), 4, part_bits=T, **kw)
