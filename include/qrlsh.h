@@ -244,6 +244,25 @@ int qrlsh_pair_regions_scatter(const uint64_t *words, int64_t n, int32_t group_b
 int qrlsh_region_unique_count_regions(const uint64_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
                                       int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp, void *workspace,
                                       size_t workspace_bytes, uint64_t *total_overflow_out, void *stream);
+/* The same with one result buffer for both steps, so that the host reads back once: scatter_overflow is the DEVICE
+ * word qrlsh_pair_regions_scatter wrote on the same stream; out3 (3 words) = {total, distinct-overflow (a region holds
+ * more distinct pairs than the finish can), capacity-overflow (*scatter_overflow)}. */
+int qrlsh_region_unique_count_regions3(const uint64_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
+                                       int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp, void *workspace,
+                                       size_t workspace_bytes, const uint32_t *scatter_overflow, uint64_t *out3,
+                                       void *stream);
+/* The final regions as 32-bit values (i & (2^group_bits - 1)) << id_bits | j instead of pair words: the region already
+ * says every bit of i above the low group_bits, and the finish reduces each word to that value first thing.  For
+ * group_bits + id_bits <= 32 with a value that is never 0xFFFFFFFF (group_bits + id_bits < 32, or nids < 2^id_bits).
+ * Same capacities, counts and tmp_regions as the 8-byte form (qrlsh_pair_regions_words / _cap / _count are in ENTRIES);
+ * `regions` holds qrlsh_pair_regions_words uint32, `tmp` of the count still as many uint64. */
+int qrlsh_pair_regions_scatter32(const uint64_t *words, int64_t n, int32_t group_bits, int32_t id_bits, int64_t nids,
+                                 double words_per_query, uint64_t *tmp_regions, uint32_t *regions, uint32_t *counts,
+                                 uint32_t *overflow_out, void *stream);
+int qrlsh_region_unique_count_regions32(const uint32_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
+                                        int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp, void *workspace,
+                                        size_t workspace_bytes, const uint32_t *scatter_overflow, uint64_t *out3,
+                                        void *stream);
 
 /* ---- a5: pair scoring ------------------------------------------------------------
  * Replaces the cosine of recommender.py:203-204 for one candidate pair:

@@ -736,8 +736,9 @@ __global__ __launch_bounds__(256) void region_bounds_kernel(const uint64_t *__re
 
 // One region, finished by the calling workgroup (RG_THREADS threads).  TAB_LOG2 / SEG size the hash set and the
 // segment array.  Returns false (uniform) when the region holds more than SEG distinct pairs.
-template <int TAB_LOG2, int SEG>
-__device__ static inline bool region_finish(const uint64_t *__restrict__ in, int64_t s0, int64_t s1, int64_t region,
+// W = the word of `in`: the pair word, or the 32-bit value itself (regions of qrlsh_pair_regions_scatter32).
+template <int TAB_LOG2, int SEG, typename W>
+__device__ static inline bool region_finish(const W *__restrict__ in, int64_t s0, int64_t s1, int64_t region,
                                             uint64_t *__restrict__ tmp, uint64_t *__restrict__ counts, int gbits,
                                             int jbits) {
   constexpr int TAB = 1 << TAB_LOG2;
@@ -763,17 +764,23 @@ __device__ static inline bool region_finish(const uint64_t *__restrict__ in, int
   const uint32_t gmask = (1u << gbits) - 1u, jmask = (1u << jbits) - 1u;  // jbits <= 31 (qrlsh_region_unique_count refuses 32)
   // 1. stream the words into the hash set, four independent loads in flight per thread
   for (int64_t p0 = s0 + t; p0 < s1; p0 += 4 * RG_THREADS) {
-    uint64_t x[4];
+    W x[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int64_t p = p0 + (int64_t)k * RG_THREADS;
-      x[k] = p < s1 ? in[p] : ~0ull;
+      x[k] = p < s1 ? in[p] : (W)~(W)0;
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (p0 + (int64_t)k * RG_THREADS >= s1) continue;
-      const uint32_t row = (uint32_t)(x[k] >> 32) & gmask;
-      const uint32_t v = row << jbits | ((uint32_t)x[k] & jmask);
+      uint32_t row, v;
+      if constexpr (sizeof(W) == 4) {
+        v = x[k];
+        row = v >> jbits;
+      } else {
+        row = (uint32_t)(x[k] >> 32) & gmask;
+        v = row << jbits | ((uint32_t)x[k] & jmask);
+      }
       uint32_t slot = (v * 0x9E3779B1u) >> (32 - TAB_LOG2);
       // the set never takes more than SEG values (SEG < TAB: a free slot always turns up); once it would, the
       // region is given up and the remaining words are skipped
@@ -896,7 +903,8 @@ __device__ static inline bool region_finish(const uint64_t *__restrict__ in, int
   return true;
 }
 
-__global__ __launch_bounds__(RG_THREADS, 8) void region_unique_kernel(const uint64_t *__restrict__ in,
+template <typename W>
+__global__ __launch_bounds__(RG_THREADS, 8) void region_unique_kernel(const W *__restrict__ in,
                                                                       const uint64_t *__restrict__ starts,
                                                                       const uint64_t *__restrict__ ends,
                                                                       uint64_t *__restrict__ tmp,
@@ -912,7 +920,7 @@ __global__ __launch_bounds__(RG_THREADS, 8) void region_unique_kernel(const uint
     if (threadIdx.x == 0) counts[region] = 0;
     return;
   }
-  if (!region_finish<13, RG_SEG>(in, s0, s1, region, tmp, counts, gbits, jbits) && threadIdx.x == 0) {
+  if (!region_finish<13, RG_SEG, W>(in, s0, s1, region, tmp, counts, gbits, jbits) && threadIdx.x == 0) {
     // more distinct pairs than this image holds (a few very popular queries): left to the big-image kernel
     counts[region] = 0;
     biglist[__hip_atomic_fetch_add(nbig, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)] = (uint64_t)region;
@@ -924,7 +932,8 @@ __global__ __launch_bounds__(RG_THREADS, 8) void region_unique_kernel(const uint
 // the launch.  A region beyond THAT raises the overflow word (general path).
 constexpr int RG_BIG_SEG = 12288;
 constexpr int RG_BIG_GRID = 256;
-__global__ __launch_bounds__(RG_THREADS, 4) void region_unique_big_kernel(const uint64_t *__restrict__ in,
+template <typename W>
+__global__ __launch_bounds__(RG_THREADS, 4) void region_unique_big_kernel(const W *__restrict__ in,
                                                                           const uint64_t *__restrict__ starts,
                                                                           const uint64_t *__restrict__ ends,
                                                                           uint64_t *__restrict__ tmp,
@@ -937,7 +946,7 @@ __global__ __launch_bounds__(RG_THREADS, 4) void region_unique_big_kernel(const 
   for (unsigned long long e = blockIdx.x; e < nb; e += gridDim.x) {
     const int64_t region = (int64_t)biglist[e];
     const int64_t s0 = (int64_t)starts[region], s1 = (int64_t)ends[region];
-    if (!region_finish<14, RG_BIG_SEG>(in, s0, s1, region, tmp, counts, gbits, jbits) && threadIdx.x == 0)
+    if (!region_finish<14, RG_BIG_SEG, W>(in, s0, s1, region, tmp, counts, gbits, jbits) && threadIdx.x == 0)
       atomicOr((unsigned long long *)overflow, 1ull);
   }
 }
@@ -965,8 +974,11 @@ QRLSH_EXPORT size_t qrlsh_region_unique_workspace_bytes(int64_t nids, int32_t gr
 
 // spans of the fixed regions qrlsh_pair_regions_scatter fills: region r = words [r * cap, r * cap + counts[r])
 __global__ __launch_bounds__(256) void region_spans_kernel(const uint32_t *__restrict__ counts, int64_t nr, uint32_t cap,
-                                                           uint64_t *__restrict__ starts, uint64_t *__restrict__ ends) {
+                                                           uint64_t *__restrict__ starts, uint64_t *__restrict__ ends,
+                                                           const uint32_t *__restrict__ scatter_ovf,
+                                                           uint64_t *__restrict__ ovf_out) {
   const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r == 0 && ovf_out) *ovf_out = *scatter_ovf;   // the scatter's flag rides along: one read-back for both steps
   if (r > nr) return;
   starts[r] = (uint64_t)r * cap;
   ends[r] = (uint64_t)r * cap + (r < nr ? min(counts[r], cap) : 0u);
@@ -974,9 +986,11 @@ __global__ __launch_bounds__(256) void region_spans_kernel(const uint32_t *__res
 
 // shared body of the two count entry points.  regions_counts == NULL: `grouped` holds n words sorted by region (bounds by
 // binary search); else the fixed regions of qrlsh_pair_regions_scatter (region r at r * cap, regions_counts[r] words).
-static int region_unique_count_impl(const char *name, const uint64_t *grouped, int64_t n, const uint32_t *regions_counts,
+template <typename W = uint64_t>
+static int region_unique_count_impl(const char *name, const W *grouped, int64_t n, const uint32_t *regions_counts,
                                     uint32_t cap, int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp,
-                                    void *workspace, size_t workspace_bytes, uint64_t *total_overflow_out, void *stream) {
+                                    void *workspace, size_t workspace_bytes, uint64_t *total_overflow_out, void *stream,
+                                    const uint32_t *scatter_ovf = nullptr) {
   QR_CHECK_ARG(n >= 0 && total_overflow_out && nids > 0 && nids <= (1ll << 32), "%s: bad arguments", name);
   // the 32-bit value (i's low bits, j) must never be the empty-slot marker 0xFFFFFFFF: either it has a spare
   // bit, or the largest j (nids - 1) is not all ones
@@ -986,7 +1000,8 @@ static int region_unique_count_impl(const char *name, const uint64_t *grouped, i
                "%s: group_bits=%d / id_bits=%d (need group_bits <= 8, id_bits <= 31, group_bits + id_bits <= 32)", name,
                group_bits, id_bits);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(total_overflow_out, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
+  // (scatter_ovf: the three-word form, word 2 = the scatter's capacity flag)
+  if (hipMemsetAsync(total_overflow_out, 0, (scatter_ovf ? 3 : 2) * sizeof(uint64_t), st) != hipSuccess) {
     qrlsh_set_error("%s: hipMemsetAsync failed", name);
     return QRLSH_EHIP;
   }
@@ -1009,16 +1024,18 @@ static int region_unique_count_impl(const char *name, const uint64_t *grouped, i
   }
   if (regions_counts) {
     QR_LAUNCH("region_bounds", region_spans_kernel, dim3((unsigned)ceil_div64(nr + 1, 256)), dim3(256), 0, st, regions_counts,
-              nr, cap, starts, ends);
+              nr, cap, starts, ends, scatter_ovf, scatter_ovf ? total_overflow_out + 2 : nullptr);
   } else {
-    QR_LAUNCH("region_bounds", region_bounds_kernel, dim3((unsigned)ceil_div64(nr + 1, 256)), dim3(256), 0, st, grouped, n,
-              32 + group_bits, nr, starts);
+    if constexpr (sizeof(W) == 8) {   // (words sorted by region are always pair words)
+      QR_LAUNCH("region_bounds", region_bounds_kernel, dim3((unsigned)ceil_div64(nr + 1, 256)), dim3(256), 0, st, grouped, n,
+                32 + group_bits, nr, starts);
+    }
     ends = starts + 1;
   }
-  QR_LAUNCH("region_unique", region_unique_kernel, dim3((unsigned)nr), dim3(RG_THREADS), 0, st, grouped,
+  QR_LAUNCH("region_unique", region_unique_kernel<W>, dim3((unsigned)nr), dim3(RG_THREADS), 0, st, grouped,
             (const uint64_t *)starts, (const uint64_t *)ends, tmp, counts, biglist,
             reinterpret_cast<unsigned long long *>(nbig), group_bits, id_bits);
-  QR_LAUNCH("region_unique_big", region_unique_big_kernel, dim3((unsigned)(nr < RG_BIG_GRID ? nr : RG_BIG_GRID)),
+  QR_LAUNCH("region_unique_big", region_unique_big_kernel<W>, dim3((unsigned)(nr < RG_BIG_GRID ? nr : RG_BIG_GRID)),
             dim3(RG_THREADS), 0, st, grouped, (const uint64_t *)starts, (const uint64_t *)ends, tmp, counts,
             (const uint64_t *)biglist, (const unsigned long long *)nbig, total_overflow_out + 1, group_bits, id_bits);
   qr_scan_u64(counts, nr + 1, total_overflow_out, sums, st);
@@ -1042,6 +1059,28 @@ QRLSH_EXPORT int qrlsh_region_unique_count_regions(const uint64_t *regions, cons
   QR_CHECK_ARG(counts && cap > 0 && cap < (1ll << 32), "qrlsh_region_unique_count_regions: bad arguments");
   return region_unique_count_impl("qrlsh_region_unique_count_regions", regions, n, counts, (uint32_t)cap, group_bits, id_bits,
                                   nids, tmp, workspace, workspace_bytes, total_overflow_out, stream);
+}
+
+// The same with ONE result buffer for the grouping and the finish: out3 = {total, distinct-overflow, capacity-overflow},
+// the last copied from the flag word qrlsh_pair_regions_scatter wrote on the same stream (a device pointer).
+QRLSH_EXPORT int qrlsh_region_unique_count_regions3(const uint64_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
+                                                    int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp,
+                                                    void *workspace, size_t workspace_bytes, const uint32_t *scatter_overflow,
+                                                    uint64_t *out3, void *stream) {
+  QR_CHECK_ARG(counts && scatter_overflow && cap > 0 && cap < (1ll << 32), "qrlsh_region_unique_count_regions3: bad arguments");
+  return region_unique_count_impl("qrlsh_region_unique_count_regions3", regions, n, counts, (uint32_t)cap, group_bits, id_bits,
+                                  nids, tmp, workspace, workspace_bytes, out3, stream, scatter_overflow);
+}
+
+// The same on regions of 32-bit values (qrlsh_pair_regions_scatter32 with the same group_bits / id_bits); tmp still
+// takes 8-byte pair words, as many as the region buffer has entries.
+QRLSH_EXPORT int qrlsh_region_unique_count_regions32(const uint32_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
+                                                     int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp,
+                                                     void *workspace, size_t workspace_bytes,
+                                                     const uint32_t *scatter_overflow, uint64_t *out3, void *stream) {
+  QR_CHECK_ARG(counts && scatter_overflow && cap > 0 && cap < (1ll << 32), "qrlsh_region_unique_count_regions32: bad arguments");
+  return region_unique_count_impl<uint32_t>("qrlsh_region_unique_count_regions32", regions, n, counts, (uint32_t)cap, group_bits,
+                                            id_bits, nids, tmp, workspace, workspace_bytes, out3, stream, scatter_overflow);
 }
 
 QRLSH_EXPORT int qrlsh_region_unique_fill(const uint64_t *tmp, int64_t n, int32_t group_bits, int64_t nids,
@@ -1113,8 +1152,11 @@ __device__ static inline uint32_t rev_src(uint64_t w, int id_bits, bool wide) {
 // fills the (usually 1 - 2) entries up to its src; a long stretch of queries without any edge (the ids beyond
 // the last i, below the first j, ...) is left at SEL_UNSET for edge_bounds_fix_kernel, whose threads find their
 // entry by binary search -- one thread walking a million-entry gap was the whole cost of this step.
+// A thread takes EB_RUN consecutive words (16-byte loads) and walks the changes of src inside them: one thread per
+// word read every word twice, 8 bytes at a time, and ran at under half the rate of the streaming kernels here.
 constexpr uint32_t SEL_UNSET = 0xFFFFFFFFu;  // n < 2^31: never a position
 constexpr int SEL_GAP = 32;
+constexpr int EB_RUN = 4;   // (even: the loads are pairs of words)
 __device__ static inline int64_t edge_src(const uint64_t *__restrict__ a, int64_t t, bool fwd, int id_bits, bool wide) {
   return (int64_t)(fwd ? (uint32_t)(a[t] >> 32) : rev_src(a[t], id_bits, wide));
 }
@@ -1125,15 +1167,40 @@ __global__ __launch_bounds__(256) void edge_bounds_kernel(const uint64_t *__rest
   const bool fwd = blockIdx.y + y0 == 0;  // (y0 = 1: reverse words only, no forward list)
   const uint64_t *a = fwd ? pairs : rev;
   uint32_t *start = fwd ? fstart : rstart;
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (t > n) return;
-  const int64_t s = t < n ? edge_src(a, t, fwd, id_bits, wide != 0) : nq;
-  const int64_t p = t > 0 ? edge_src(a, t - 1, fwd, id_bits, wide != 0) : -1;
-  if (s - p > SEL_GAP) {
-    if (s <= nq) start[s] = (uint32_t)t;  // the entry of s itself; the stretch below it stays unset
-    return;
+  const bool w = wide != 0;
+  // positions t0 .. t0 + EB_RUN - 1 of 0 .. n (position n stands for the end: src = nq)
+  const int64_t t0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * EB_RUN;
+  uint64_t x[EB_RUN];
+  if (t0 + EB_RUN <= n && ((uintptr_t)a & 15) == 0) {   // whole run inside the list: 16-byte loads
+    const ulonglong2 *v = reinterpret_cast<const ulonglong2 *>(a + t0);
+#pragma unroll
+    for (int k = 0; k < EB_RUN; k += 2) {
+      const ulonglong2 u = v[k >> 1];
+      x[k] = u.x;
+      x[k + 1] = u.y;
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < EB_RUN; ++k) x[k] = t0 + k < n ? a[t0 + k] : 0ull;
   }
-  for (int64_t q = p + 1; q <= s && q <= nq; ++q) start[q] = (uint32_t)t;
+  int64_t s[EB_RUN];
+#pragma unroll
+  for (int k = 0; k < EB_RUN; ++k)
+    s[k] = t0 + k < n ? (int64_t)(fwd ? (uint32_t)(x[k] >> 32) : rev_src(x[k], id_bits, w)) : nq;
+  // the src in front of the run: the neighbouring lane's last, one more load for the first lane of a wave
+  int64_t p = __shfl_up(s[EB_RUN - 1], 1, WAVE);
+  if ((threadIdx.x & (WAVE - 1)) == 0) p = t0 > 0 && t0 <= n ? edge_src(a, t0 - 1, fwd, id_bits, w) : -1;
+#pragma unroll
+  for (int k = 0; k < EB_RUN; ++k) {
+    const int64_t t = t0 + k;
+    if (t > n) break;
+    if (s[k] - p > SEL_GAP) {
+      if (s[k] <= nq) start[s[k]] = (uint32_t)t;  // the entry of s itself; the stretch below it stays unset
+    } else {
+      for (int64_t q = p + 1; q <= s[k] && q <= nq; ++q) start[q] = (uint32_t)t;
+    }
+    p = s[k];
+  }
 }
 
 __global__ __launch_bounds__(256) void edge_bounds_fix_kernel(const uint64_t *__restrict__ pairs,
@@ -1168,12 +1235,15 @@ __global__ __launch_bounds__(256) void topk_len_kernel(const uint32_t *__restric
                                                        const uint32_t *__restrict__ rstart, int64_t nq, int K,
                                                        uint64_t *__restrict__ cnt, uint32_t *__restrict__ medlist,
                                                        uint32_t *__restrict__ longlist,
-                                                       unsigned long long *__restrict__ nlists) {
-  __shared__ uint32_t smed[LEN_QPB], slng[LEN_QPB];
+                                                       unsigned long long *__restrict__ nlists,
+                                                       uint64_t *__restrict__ wgsum) {
+  __shared__ uint32_t smed[LEN_QPB], slng[LEN_QPB], sval[LEN_QPB + LEN_QPB / 16];   // (sval: padded, see lpad)
+  __shared__ uint64_t sscan[4];
   __shared__ uint32_t nmed, nlng;
   __shared__ unsigned long long bmed, blng;
   const int lane = threadIdx.x & (WAVE - 1);
   const uint64_t lt_mask = (1ull << lane) - 1ull;
+  auto lpad = [](int i) { return i + (i >> 4); };   // a word of padding per 16: a thread's 16 consecutive counts meet no bank twice
   if (threadIdx.x == 0) {
     nmed = 0;
     nlng = 0;
@@ -1185,7 +1255,7 @@ __global__ __launch_bounds__(256) void topk_len_kernel(const uint32_t *__restric
     const int64_t q = q0 + it * 256 + threadIdx.x;
     uint64_t c = 0;
     if (q < nq) c = (uint64_t)(fstart[q + 1] - fstart[q]) + (rstart[q + 1] - rstart[q]);
-    if (q <= nq) cnt[q] = c > (uint64_t)K ? (uint64_t)K : c;  // one word past the end (0): the scan leaves the total there
+    sval[lpad(it * 256 + threadIdx.x)] = (uint32_t)(c > (uint64_t)K ? (uint64_t)K : c);  // (0 past the end)
     const bool med = c > (uint64_t)SEL_SHORT && c <= (uint64_t)SEL_LONG, lng = c > (uint64_t)SEL_LONG;
     const uint64_t mm = __ballot(med), ml = __ballot(lng);
     uint32_t pm = 0, pl = 0;
@@ -1206,6 +1276,39 @@ __global__ __launch_bounds__(256) void topk_len_kernel(const uint32_t *__restric
   __syncthreads();
   for (uint32_t k = threadIdx.x; k < nmed; k += 256) medlist[bmed + k] = smed[k];
   for (uint32_t k = threadIdx.x; k < nlng; k += 256) longlist[blng + k] = slng[k];
+  // the workgroup's own exclusive scan of its counts (16 consecutive per thread; at most 4096 * 256: 32 bits hold
+  // it), and its total next to them: topk_off_add_kernel adds the scanned totals, so the 10 M-entry array is
+  // written once and rewritten once instead of written, scanned in chunks and rewritten
+  constexpr int PER = LEN_QPB / 256;
+  uint32_t v[PER], sum = 0;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    v[k] = sval[lpad(threadIdx.x * PER + k)];
+    sum += v[k];
+  }
+  uint64_t total;
+  uint32_t run = (uint32_t)block_excl_scan_u64_256((uint64_t)sum, sscan, &total);   // (its barriers end the reads)
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {
+    sval[lpad(threadIdx.x * PER + k)] = run;
+    run += v[k];
+  }
+  __syncthreads();
+  // cnt[nq], one word past the end: its count is 0, so the total ends up there
+  for (int k = threadIdx.x; k < LEN_QPB; k += 256)
+    if (q0 + k <= nq) cnt[q0 + k] = sval[lpad(k)];
+  if (threadIdx.x == 0) wgsum[blockIdx.x] = total;
+}
+
+// off[q] += the scanned total of the workgroups in front of q's (wgsum after its exclusive scan)
+__global__ __launch_bounds__(256) void topk_off_add_kernel(uint64_t *__restrict__ off, int64_t m,
+                                                           const uint64_t *__restrict__ wgsum) {
+  const uint64_t add = wgsum[blockIdx.x];
+  const int64_t q0 = (int64_t)blockIdx.x * LEN_QPB;
+  if (add == 0) return;   // (uniform)
+#pragma unroll 4
+  for (int k = threadIdx.x; k < LEN_QPB; k += 256)
+    if (q0 + k < m) off[q0 + k] += add;
 }
 
 // (inv << 32 | dst) of element x of a query's list: x < nr -> reverse run, else forward run
@@ -1467,7 +1570,7 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
 }
 
 // workspace: fstart u32[nq + 1] | rstart u32[nq + 1] | medlist u32[nq] | longlist u32[nq] | off u64[nq + 2] |
-//            list lengths u64[2] | chunk totals of the scan
+//            list lengths u64[2] | totals of topk_len_kernel's workgroups
 struct SelWs {
   uint32_t *fstart, *rstart, *medlist, *longlist;
   uint64_t *off, *nlong, *sums;
@@ -1490,7 +1593,7 @@ static SelWs sel_ws(void *workspace, int64_t nq) {
   w.nlong = reinterpret_cast<uint64_t *>(p + o);
   o += 16;
   w.sums = reinterpret_cast<uint64_t *>(p + o);
-  o += (size_t)(ceil_div64(nq + 1, SCANL_CHUNK) + 2) * 8;
+  o += (size_t)(ceil_div64(nq + 1, LEN_QPB) + 2) * 8;   // (one per workgroup of topk_len_kernel)
   w.bytes = o;
   return w;
 }
@@ -1535,14 +1638,19 @@ QRLSH_EXPORT int qrlsh_topk_select_count(const uint64_t *pairs, int64_t n, const
     qrlsh_set_error("qrlsh_topk_select_count: hipMemsetAsync failed");   // every forward run is empty
     return QRLSH_EHIP;
   }
-  QR_LAUNCH("topk_bounds", edge_bounds_kernel, dim3((unsigned)ceil_div64(n + 1, 256), lists), blk, 0, st, pairs, rev_sorted, n,
-            nq, id_bits, rev_dst ? 1 : 0, w.fstart, w.rstart, y0);
+  QR_LAUNCH("topk_bounds", edge_bounds_kernel, dim3((unsigned)ceil_div64(n + 1, 256 * EB_RUN), lists), blk, 0, st, pairs,
+            rev_sorted, n, nq, id_bits, rev_dst ? 1 : 0, w.fstart, w.rstart, y0);
   QR_LAUNCH("topk_bounds", edge_bounds_fix_kernel, dim3((unsigned)ceil_div64(nq + 1, 256), lists), blk, 0, st, pairs,
             rev_sorted, n, nq, id_bits, rev_dst ? 1 : 0, w.fstart, w.rstart, y0);
   QR_LAUNCH("topk_len", topk_len_kernel, dim3((unsigned)ceil_div64(nq + 1, LEN_QPB)), blk, 0, st, (const uint32_t *)w.fstart,
             (const uint32_t *)w.rstart, nq, K, w.off, w.medlist, w.longlist,
-            reinterpret_cast<unsigned long long *>(w.nlong));
-  qr_scan_u64(w.off, nq + 1, total_out, w.sums, st);
+            reinterpret_cast<unsigned long long *>(w.nlong), w.sums);
+  // offsets: the workgroups left their own exclusive scans in w.off and their totals in w.sums -- the small scan of
+  // the totals (2 442 words at 10 M queries; one workgroup) and one add pass.  The fix kernel stays a pass of its
+  // own: its binary searches must all be over before any length is taken.
+  const int64_t nwg = ceil_div64(nq + 1, LEN_QPB);
+  QR_LAUNCH("scan_blocks", scan_u64_kernel, dim3(1), dim3(1024), 0, st, w.sums, nwg, total_out);
+  QR_LAUNCH("scan_blocks", topk_off_add_kernel, dim3((unsigned)nwg), blk, 0, st, w.off, nq + 1, (const uint64_t *)w.sums);
   QR_LAUNCH_CHECK("qrlsh_topk_select_count");
   return QRLSH_OK;
 }

@@ -566,11 +566,16 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
 constexpr int PG_IPT = QR_PG_IPT;                 // words per thread of the pair-grouping partition
 constexpr int PG_TILE = SORT_THREADS * PG_IPT;
 constexpr int PG_WGS = PG_IPT <= 16 ? 4 : PG_IPT <= 40 ? 2 : 1;      // workgroups per CU the staged tile allows
-template <bool LEVEL2>
+// W = the word written: uint64_t, the pair word as it came, or (the last level only) uint32_t, the value
+// (i & gmask) << jbits | j the region finish reduces every word to as its first step -- the region already says every bit
+// of i above the low g, so the final regions need 4 bytes per entry: 0.76 GB less written here and as much less read by
+// the finish at 10 M queries.  The tile is still staged as 8-byte words: the digit of a staged word (bits of i ABOVE the
+// low g) is read back from it when the runs are written, and the 32-bit value no longer holds it.
+template <bool LEVEL2, typename W>
 __global__ __launch_bounds__(SORT_THREADS, PG_WGS) void pair_group_scatter_kernel(
-    const uint64_t *__restrict__ in, uint64_t *__restrict__ out, int64_t n_in, int ntiles, int shift, uint32_t dmask,
+    const uint64_t *__restrict__ in, W *__restrict__ out, int64_t n_in, int ntiles, int shift, uint32_t dmask,
     uint32_t *__restrict__ cursors, uint32_t cap, uint32_t *__restrict__ overflow, const uint32_t *__restrict__ in_counts,
-    uint32_t in_cap) {
+    uint32_t in_cap, int gbits, int jbits) {
   __shared__ uint32_t cnt[RADIX];
   __shared__ uint32_t lsum[SORT_THREADS / WAVE];
   __shared__ uint32_t gdelta[RADIX];
@@ -640,7 +645,13 @@ __global__ __launch_bounds__(SORT_THREADS, PG_WGS) void pair_group_scatter_kerne
     if (p < nstaged) {
       const uint64_t x = skey[p];
       const uint32_t d = (uint32_t)(x >> shift) & dmask;
-      if (gok[d]) out[obase + (uint32_t)(gdelta[d] + p)] = x;
+      if (gok[d]) {
+        if constexpr (sizeof(W) == 4)
+          out[obase + (uint32_t)(gdelta[d] + p)] =
+              (((uint32_t)(x >> 32) & ((1u << gbits) - 1u)) << jbits) | ((uint32_t)x & ((1u << jbits) - 1u));   // jbits <= 31
+        else
+          out[obase + (uint32_t)(gdelta[d] + p)] = x;
+      }
     }
   }
 }
@@ -708,9 +719,10 @@ QRLSH_EXPORT int64_t qrlsh_pair_regions_count(int64_t n, int64_t nids, int32_t g
 // words (n pair words i << 32 | j, any order) -> regions[r * cap + k], k < counts[r], r = i >> group_bits; counts:
 // uint32 [qrlsh_pair_regions_count + 256] (the tail is level 1's cursors); overflow_out: uint32, != 0 when a region
 // outgrew its capacity (nothing usable then).  tmp_regions may be NULL when qrlsh_pair_regions_tmp_words is 0.
-QRLSH_EXPORT int qrlsh_pair_regions_scatter(const uint64_t *words, int64_t n, int32_t group_bits, int64_t nids,
-                                            double words_per_query, uint64_t *tmp_regions, uint64_t *regions,
-                                            uint32_t *counts, uint32_t *overflow_out, void *stream) {
+template <typename W>
+static int pair_regions_scatter_impl(const uint64_t *words, int64_t n, int32_t group_bits, int32_t id_bits, int64_t nids,
+                                     double words_per_query, uint64_t *tmp_regions, W *regions, uint32_t *counts,
+                                     uint32_t *overflow_out, void *stream) {
   QR_CHECK_ARG(n >= 0 && n < (1ll << 32) && nids > 0 && group_bits >= 0 && group_bits <= 8 && counts && overflow_out,
                "qrlsh_pair_regions_scatter: bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -729,18 +741,41 @@ QRLSH_EXPORT int qrlsh_pair_regions_scatter(const uint64_t *words, int64_t n, in
   const int ntiles = (int)ceil_div64(n, PG_TILE);
   const int sh = 32 + group_bits;
   if (r.ra == 0) {
-    QR_LAUNCH("pair_group", (pair_group_scatter_kernel<false>), dim3(ntiles, 1), dim3(SORT_THREADS), 0, st, words, regions, n,
-              ntiles, sh, (1u << r.rb) - 1u, counts, r.cap_b, overflow_out, (const uint32_t *)nullptr, 0u);
+    QR_LAUNCH("pair_group", (pair_group_scatter_kernel<false, W>), dim3(ntiles, 1), dim3(SORT_THREADS), 0, st, words, regions, n,
+              ntiles, sh, (1u << r.rb) - 1u, counts, r.cap_b, overflow_out, (const uint32_t *)nullptr, 0u, (int)group_bits,
+              (int)id_bits);
   } else {
-    uint32_t *cur_a = counts + r.nregions;
-    QR_LAUNCH("pair_group", (pair_group_scatter_kernel<false>), dim3(ntiles, 1), dim3(SORT_THREADS), 0, st, words, tmp_regions,
-              n, ntiles, sh + r.rb, (1u << r.ra) - 1u, cur_a, r.cap_a, overflow_out, (const uint32_t *)nullptr, 0u);
-    QR_LAUNCH("pair_group", (pair_group_scatter_kernel<true>), dim3((unsigned)ceil_div64(r.cap_a, PG_TILE), (unsigned)r.na),
+    uint32_t *cur_a = counts + r.nregions;   // (level 1's tmp regions keep the whole word: 40 bits of it are live there)
+    QR_LAUNCH("pair_group", (pair_group_scatter_kernel<false, uint64_t>), dim3(ntiles, 1), dim3(SORT_THREADS), 0, st, words,
+              tmp_regions, n, ntiles, sh + r.rb, (1u << r.ra) - 1u, cur_a, r.cap_a, overflow_out, (const uint32_t *)nullptr, 0u,
+              0, 0);
+    QR_LAUNCH("pair_group", (pair_group_scatter_kernel<true, W>), dim3((unsigned)ceil_div64(r.cap_a, PG_TILE), (unsigned)r.na),
               dim3(SORT_THREADS), 0, st, (const uint64_t *)tmp_regions, regions, (int64_t)0, 0, sh, (1u << r.rb) - 1u, counts,
-              r.cap_b, overflow_out, (const uint32_t *)cur_a, r.cap_a);
+              r.cap_b, overflow_out, (const uint32_t *)cur_a, r.cap_a, (int)group_bits, (int)id_bits);
   }
   QR_LAUNCH_CHECK("qrlsh_pair_regions_scatter");
   return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_pair_regions_scatter(const uint64_t *words, int64_t n, int32_t group_bits, int64_t nids,
+                                            double words_per_query, uint64_t *tmp_regions, uint64_t *regions,
+                                            uint32_t *counts, uint32_t *overflow_out, void *stream) {
+  return pair_regions_scatter_impl<uint64_t>(words, n, group_bits, 0, nids, words_per_query, tmp_regions, regions, counts,
+                                             overflow_out, stream);
+}
+
+// The same into regions of 32-bit values (i & (2^group_bits - 1)) << id_bits | j: capacities and counts are those of the
+// 8-byte form, in entries; only the bytes per entry of `regions` differ.  Needs group_bits + id_bits <= 32 and a value
+// that is never 0xFFFFFFFF (qrlsh_region_unique_count_regions32, the only reader, marks empty slots with it).
+QRLSH_EXPORT int qrlsh_pair_regions_scatter32(const uint64_t *words, int64_t n, int32_t group_bits, int32_t id_bits,
+                                              int64_t nids, double words_per_query, uint64_t *tmp_regions, uint32_t *regions,
+                                              uint32_t *counts, uint32_t *overflow_out, void *stream) {
+  QR_CHECK_ARG(group_bits >= 0 && group_bits <= 8 && id_bits >= 1 && id_bits <= 31 && nids > 0 && nids <= (1ll << id_bits) &&
+                   (group_bits + id_bits < 32 || (group_bits + id_bits == 32 && nids < (1ll << id_bits))),
+               "qrlsh_pair_regions_scatter32: group_bits=%d / id_bits=%d / nids=%lld do not fit a 32-bit value", group_bits,
+               id_bits, (long long)nids);
+  return pair_regions_scatter_impl<uint32_t>(words, n, group_bits, id_bits, nids, words_per_query, tmp_regions, regions,
+                                             counts, overflow_out, stream);
 }
 
 QRLSH_EXPORT size_t qrlsh_sort_workspace_bytes(int64_t n, int32_t nbatch) {
@@ -1245,6 +1280,10 @@ constexpr int FIN_BIG_GRID = 256;
 constexpr int FIN_BIG_BLOCKS = 16;        // blocks of FIN_CAP records a listed part may hold (98 304); beyond: overflow flag
 constexpr uint32_t FIN_BIG_LIST = 4096;   // listed parts per band group and call; beyond: overflow flag (general path)
 constexpr int FIN_BIG_SLICES = 8;         // workgroups that share a block pair's pairs (a power of two)
+// own-pair ranks of a block: runs up to here are walked by a lane per record; longer ones are sorted in LDS by the
+// workgroup (~log2(c)^2 / 2 barrier steps against c^2 / 64 wave-wide LDS reads: by that count the two meet near
+// 256 -- 36 steps of ~250 cycles against ~8 000 cycles of reads; the flagship has one run of ~1 700, where the sort wins 5x)
+constexpr int FIN_RANK_SORT = 256;
 constexpr uint32_t POOL_RUNS = 1u << 20;  // spilled-run descriptors per call; beyond: overflow flag
 
 // where the records of a listed part sit: `pool` = 0: in the part buffers at `where` (its own region), 1: in the
@@ -1338,6 +1377,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
   __shared__ uint32_t grp[FIN_CAP];
   __shared__ uint32_t srt[FIN_CAP];   // the runs in id order (own pairs of a block)
   __shared__ uint32_t wsum[FIN_THREADS / WAVE];
+  __shared__ uint32_t lrun[FIN_CAP / (FIN_RANK_SORT + 1) + 1], nlrun;   // slots of the runs longer than FIN_RANK_SORT
   const int tid = threadIdx.x, lane = tid & (WAVE - 1), w = tid >> 6;
   unsigned long long nb = *nbig;
   if (nb > big_max) nb = big_max;
@@ -1442,16 +1482,61 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
       if (bj_only == bi) {
         // this block's own pairs.  Rank of every record's id among its run (ids are distinct inside a bucket), the runs
         // re-laid in id order, then a record of rank r pairs with the r mates in front of it -- if r mod 8 is this slice
+        // A run longer than FIN_RANK_SORT (the key shared by ~1 700 queries) is first sorted by the whole workgroup,
+        // straight into its place in srt, and a record's rank is its id's position there: walking such a run once per
+        // record was 1 700^2 LDS reads in every one of the eight slice workgroups, 0.2 of this kernel's 0.3 ms.
+        if (tid == 0) nlrun = 0;
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < FIN_IPT; ++q) {
+          const uint32_t slot = tid * FIN_IPT + q;
+          if (cnt[slot + 1] - cnt[slot] > (uint32_t)FIN_RANK_SORT) lrun[atomicAdd(&nlrun, 1u)] = slot;
+        }
+        __syncthreads();
+        const uint32_t nl = nlrun;
+        for (uint32_t r = 0; r < nl; ++r) {  // (uniform; the list's order differs from build to build, the sorted runs do not)
+          const uint32_t s0 = cnt[lrun[r]], c = cnt[lrun[r] + 1] - s0;
+          for (uint32_t i = tid; i < c; i += FIN_THREADS) srt[s0 + i] = grp[s0 + i];
+          uint32_t nn = 2;
+          while (nn < c) nn <<= 1;
+          // bitonic network on nn >= c places, every exchange leaving the smaller id at the lower place (a merge opens
+          // with the mirrored partner): the places from c on stand for +infinity, never move, and are never touched
+          for (uint32_t k = 2; k <= nn; k <<= 1)
+            for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+              __syncthreads();
+              for (uint32_t t = tid; t < (nn >> 1); t += FIN_THREADS) {
+                const uint32_t i = ((t & ~(j - 1)) << 1) | (t & (j - 1));   // bit j clear
+                const uint32_t l = j == (k >> 1) ? i ^ (k - 1) : i | j;
+                if (l < c) {
+                  const uint32_t a = srt[s0 + i], b = srt[s0 + l];
+                  if (a > b) {
+                    srt[s0 + i] = b;
+                    srt[s0 + l] = a;
+                  }
+                }
+              }
+            }
+        }
+        __syncthreads();
         uint32_t rk[FIN_IPT];
 #pragma unroll
         for (int j = 0; j < FIN_IPT; ++j) {
           rk[j] = 0;
           if (so[j] != 0xFFFFFFFFu) {
-            // (a lane per record: the copies of a popular key fill whole waves, which then walk the run in step --
-            // counting a long run with the whole wave, one record after the other, was 2.5x slower)
             const uint32_t sl0 = so[j] & 0xFFFFu, s0 = cnt[sl0], c = cnt[sl0 + 1] - s0, me = ireg[j];
             uint32_t r = 0;
-            for (uint32_t u = 0; u < c; ++u) r += grp[s0 + u] < me;
+            if (c > (uint32_t)FIN_RANK_SORT) {
+              uint32_t hi = c;   // first place of the sorted run whose id is >= me: the ids in front are the smaller ones
+              while (r < hi) {
+                const uint32_t mid = (r + hi) >> 1;
+                if (srt[s0 + mid] < me) r = mid + 1;
+                else hi = mid;
+              }
+            } else {
+              // (a lane per record: the copies of a key fill whole waves, which then walk the run in step --
+              // counting a run with the whole wave, one record after the other, was 2.5x slower)
+              for (uint32_t u = 0; u < c; ++u) r += grp[s0 + u] < me;
+            }
             rk[j] = r;
           }
         }

@@ -403,13 +403,20 @@ REGION_MIN_GROUP_BITS = 6               # below: the general sort + unique inste
 REGION_SCATTER_MAX_BYTES = 48 << 30    # the fixed-region grouping is skipped when its buffers would exceed this
 
 
-def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=0.0):
+def region_values_fit(group_bits, id_bits, nids):
+    """the final regions can hold the 32-bit value (i's low group_bits, j) instead of the pair word: it fits, and is
+    never the finish's empty-slot marker 0xFFFFFFFF"""
+    return group_bits + id_bits < 32 or (group_bits + id_bits == 32 and nids < (1 << id_bits))
+
+
+def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=0.0, values32=None):
     """Sorted unique pairs straight from the emitted words: dealt into fixed regions of 2^group_bits queries by two
     histogram-free partition steps (qrlsh_pair_regions_scatter: nothing inside a region is ordered -- the region
     finish does not need it), then the region finish on those regions.  -> (pairs, "") or (None, why): "cap" when a
     region outgrew its capacity or the buffers would be too large (the caller then groups by sorting), "distinct" when
     a region holds more distinct pairs than the finish's LDS set (sorting by region would meet the same: the caller
-    sorts everything)."""
+    sorts everything).  values32: the final regions as 32-bit values (default: whenever region_values_fit; half the
+    bytes of the last grouping level and of the finish's read), False: as 8-byte pair words."""
     lib = _lib.load()
     _need(emitted, torch.int64, "emitted", 1)
     n = emitted.numel()
@@ -419,29 +426,39 @@ def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=
     wpq = float(words_per_query)
     words = lib.qrlsh_pair_regions_words(n, nids, group_bits, wpq)
     twords = lib.qrlsh_pair_regions_tmp_words(n, nids, group_bits, wpq)
-    if words == 0 or n >= (1 << 32) or (2 * words + twords) * 8 > REGION_SCATTER_MAX_BYTES:
+    if values32 is None:
+        values32 = region_values_fit(group_bits, id_bits, nids)
+    elif values32 and not region_values_fit(group_bits, id_bits, nids):
+        raise ValueError("group_bits=%d + id_bits=%d (nids=%d) do not fit a 32-bit region value" % (group_bits, id_bits, nids))
+    rbytes = 4 if values32 else 8       # per entry of the final regions; tmp (the finish's output) keeps pair words
+    if words == 0 or n >= (1 << 32) or words * (rbytes + 8) + twords * 8 > REGION_SCATTER_MAX_BYTES:
         return None, "cap"          # (words == 0: more than 65536 regions -- two levels of 256 digits do not reach)
     cap = lib.qrlsh_pair_regions_cap(n, nids, group_bits, wpq)
     nreg = lib.qrlsh_pair_regions_count(n, nids, group_bits, wpq)
     try:      # fixed regions trade memory for passes: when the device is short of it, group by sorting instead
-        regions = torch.empty((words,), dtype=torch.int64, device=dev)
+        regions = torch.empty((words,), dtype=torch.int32 if values32 else torch.int64, device=dev)
         tmpr = torch.empty((twords,), dtype=torch.int64, device=dev) if twords else None
-        tmp = torch.empty_like(regions)
+        tmp = torch.empty((words,), dtype=torch.int64, device=dev)
     except torch.cuda.OutOfMemoryError:
         regions = tmpr = tmp = None
         torch.cuda.empty_cache()
         return None, "cap"
     counts = torch.empty((nreg + 256,), dtype=torch.int32, device=dev)
     ovf = torch.empty((1,), dtype=torch.int32, device=dev)
-    _lib.check(lib.qrlsh_pair_regions_scatter(_ptr(emitted), n, int(group_bits), int(nids), wpq, _ptr(tmpr), _ptr(regions),
-                                              _ptr(counts), _ptr(ovf), _stream()))
+    if values32:
+        _lib.check(lib.qrlsh_pair_regions_scatter32(_ptr(emitted), n, int(group_bits), int(id_bits), int(nids), wpq, _ptr(tmpr),
+                                                    _ptr(regions), _ptr(counts), _ptr(ovf), _stream()))
+    else:
+        _lib.check(lib.qrlsh_pair_regions_scatter(_ptr(emitted), n, int(group_bits), int(nids), wpq, _ptr(tmpr), _ptr(regions),
+                                                  _ptr(counts), _ptr(ovf), _stream()))
     del tmpr
     ws = _ws(lib.qrlsh_region_unique_workspace_bytes(nids, group_bits), dev)
-    tot = torch.empty(2, dtype=torch.int64, device=dev)
-    _lib.check(lib.qrlsh_region_unique_count_regions(_ptr(regions), _ptr(counts), cap, n, int(group_bits), int(id_bits),
-                                                     int(nids), _ptr(tmp), _ptr(ws), ws.numel(), _ptr(tot), _stream()))
-    total, overflow = tot.tolist()          # (the stream is in order: the scatter's flag is final by now as well)
-    if int(ovf.item()):
+    tot = torch.empty(3, dtype=torch.int64, device=dev)
+    count = lib.qrlsh_region_unique_count_regions32 if values32 else lib.qrlsh_region_unique_count_regions3
+    _lib.check(count(_ptr(regions), _ptr(counts), cap, n, int(group_bits), int(id_bits), int(nids), _ptr(tmp), _ptr(ws),
+                     ws.numel(), _ptr(ovf), _ptr(tot), _stream()))
+    total, overflow, capped = tot.tolist()  # one read-back: the scatter's flag is the third word
+    if capped:
         return None, "cap"
     if overflow:
         return None, "distinct"
