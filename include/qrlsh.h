@@ -457,8 +457,8 @@ int qrlsh_predict_columns(const int32_t *ratings, int64_t nu, int64_t nq, const 
  * recommender.py:187-214 for x appended alone, K held fixed): its candidates are the indexed ids that share with x a
  * band whose r = P / b values are equal after the int16 cast and not all -1 (65535 counts as -1); each once, however
  * many bands it shares.  Score: milli = rint(1000 * dot / (sqrt(na) * sqrt(nb))), qrlsh_score_pairs bit for bit.
- * List: the K best candidates by milli descending, then id ascending.  New queries never see each other, so a
- * query's result does not depend on the batch around it.
+ * List: the K best candidates by milli descending, then id ascending.  New queries of one probe never see each other,
+ * so a query's result does not depend on the batch around it; they become visible to later probes through append.
  *   build: keys [b][n] (band keys of the n indexed queries: qrlsh_band_keys / qrlsh_minhash keys_out, or the
  *     caller's own -- keys only filter, every candidate is checked against the rows) are sorted in place per band with
  *     their ids (ids [b][n] uint32 output; keys_tmp / ids_tmp scratch of the same size; qrlsh_sort_u64 over the top
@@ -495,6 +495,19 @@ int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2, int64_t n, c
                              const void *probe_workspace, const uint64_t *raw, int64_t n_raw, int32_t K,
                              int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
                              void *workspace, size_t workspace_bytes, void *stream);
+/*   append: m new queries enter a built index without a rebuild.  keys / ids / dir: a built index of n queries
+ *     (qrlsh_index_build's outputs, or an earlier append's; read only; may be NULL when n == 0); new_keys [b][m]: the
+ *     band keys of the new queries (consumed: sorted in place).  keys_out [b][n + m], ids_out [b][n + m] and dir_out
+ *     (qrlsh_index_dir_words(n + m, b)) receive the grown index, out of place (the band-major layout moves every band's
+ *     base when n changes): the new queries get the ids n .. n + m - 1 in the order given, and the three arrays are byte
+ *     for byte what qrlsh_index_build makes of the concatenated [b][n + m] keys (the batch is sorted as the build sorts
+ *     it, then merged stably behind the old records of equal mix bits; the directory is written in the same pass).
+ *     No allocation, no read-back.  n + m < 2^32 - 1.  m == 0 returns at once and writes nothing.  workspace:
+ *     qrlsh_index_append_workspace_bytes(m, b). */
+size_t qrlsh_index_append_workspace_bytes(int64_t m, int32_t b);
+int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
+                       uint64_t *new_keys, int64_t m, uint64_t *keys_out, uint32_t *ids_out, uint32_t *dir_out,
+                       void *workspace, size_t workspace_bytes, void *stream);
 #define QRLSH_INDEX_MAX_K 256
 
 /* ---- recommendations: top-k unrated queries per user (the consumer of N1's output) ---------------------

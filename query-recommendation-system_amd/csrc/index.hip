@@ -467,3 +467,202 @@ QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2,
   QR_LAUNCH_CHECK("qrlsh_index_probe_finish");
   return QRLSH_OK;
 }
+
+// ---- append: new queries enter a built index ----------------------------------------------------------------------
+// The build's order is "top 32 bits of mix64(key), then id ascending" and appended ids (n .. n + m - 1) are larger than
+// every indexed id, so the grown index is the STABLE MERGE of the old band and the sorted batch, old records first
+// among equal mix bits -- byte for byte what qrlsh_index_build makes of the concatenated [b][n + m] keys.
+//   sort:   the batch, exactly as the build sorts it (qrlsh_sort_u64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, bits 32..64).
+//   rank:   one lane per (band, sorted batch record j): p_j = old records of the band whose top-32 mix bits are <= the
+//           record's (old directory + a binary search inside the slot); q_j = p_j + j, strictly increasing per band,
+//           is the record's output position.
+//   merge:  one workgroup per tile of IA_TILE consecutive output positions of one band.  Two binary searches in q
+//           give the batch records [j0, j1) that land in the tile.  j0 == j1 (the common case): a copy of the old
+//           records shifted by j0.  Otherwise a flag bitmap of the tile in LDS and a scan over its words tell every
+//           position how many batch records lie before it in the tile: a flagged position takes batch record
+//           j0 + before, any other old record x - j0 - before.  Old reads and all writes are consecutive per lane.
+//           The same pass writes the directory at d = qrlsh_index_dir_bits(n + m) bits as index_dir_kernel does:
+//           each record compares its top d mix bits with its predecessor's (the lane below; a wave's first lane
+//           fetches it, the tile's first record reads one record before the tile).
+constexpr int IA_TILE = 4096;          // output positions per merge workgroup
+constexpr int IA_WORDS = IA_TILE / 32; // words of its flag bitmap
+
+// q[t][j] = output position of sorted batch record j of band t
+__global__ __launch_bounds__(256) void index_rank_kernel(const uint64_t *__restrict__ okeys,
+                                                         const uint32_t *__restrict__ odir, int64_t n, int d,
+                                                         const uint64_t *__restrict__ skeys, int64_t m,
+                                                         uint32_t *__restrict__ q) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const int64_t t = blockIdx.y;
+  uint32_t p = 0;
+  if (n > 0) {
+    const uint64_t *bk = okeys + t * n;
+    const uint32_t *bd = odir + t * ((1ll << d) + 1);
+    const uint64_t h = qr_mix64(skeys[t * m + j]);
+    const uint32_t T = (uint32_t)(h >> 32);
+    uint32_t L = bd[h >> (64 - d)], R = bd[(h >> (64 - d)) + 1];
+    while (L < R) {
+      const uint32_t mid = L + (R - L) / 2;
+      if (ix_top32(bk[mid]) <= T) L = mid + 1;
+      else R = mid;
+    }
+    p = L;
+  }
+  q[t * m + j] = p + (uint32_t)j;
+}
+
+// the source of tile position k: how many batch records of the tile lie before it, and whether it is one
+__device__ static inline bool ia_source(bool mixed, const uint32_t *flags, const uint32_t *wpre, uint32_t k,
+                                        uint32_t &before) {
+  before = 0;
+  if (!mixed) return false;
+  const uint32_t f = flags[k >> 5], bit = k & 31u;
+  before = wpre[k >> 5] + (uint32_t)__popc(f & ((1u << bit) - 1u));
+  return (f >> bit) & 1u;
+}
+
+__global__ __launch_bounds__(256) void index_merge_kernel(const uint64_t *__restrict__ okeys,
+                                                          const uint32_t *__restrict__ oids, int64_t n,
+                                                          const uint64_t *__restrict__ skeys,
+                                                          const uint32_t *__restrict__ sids,
+                                                          const uint32_t *__restrict__ q, int64_t m, int d,
+                                                          uint64_t *__restrict__ keys_out, uint32_t *__restrict__ ids_out,
+                                                          uint32_t *__restrict__ dir_out) {
+  __shared__ uint32_t flags[IA_WORDS];
+  __shared__ uint32_t wpre[IA_WORDS];
+  __shared__ uint64_t sc[4];
+  const int64_t N = n + m, t = blockIdx.y;
+  const int64_t o = (int64_t)blockIdx.x * IA_TILE;
+  const int64_t oe = o + IA_TILE < N ? o + IA_TILE : N;
+  const uint64_t *ok = okeys + t * n;
+  const uint32_t *oi = oids + t * n;
+  const uint64_t *sk = skeys + t * m;
+  const uint32_t *si = sids + t * m;
+  const uint32_t *bq = q + t * m;
+  uint64_t *ko = keys_out + t * N;
+  uint32_t *io = ids_out + t * N;
+  uint32_t *dr = dir_out + t * ((1ll << d) + 1);
+  const int lane = lane_id();
+  // [j0, j1): the batch records with o <= q < oe (uniform; q is strictly increasing, so j1 <= j0 + oe - o)
+  int64_t lo = 0, hi = m;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if ((int64_t)bq[mid] < o) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t j0 = lo;
+  hi = j0 + (oe - o) < m ? j0 + (oe - o) : m;
+  while (lo < hi) {
+    const int64_t mid = lo + (hi - lo) / 2;
+    if ((int64_t)bq[mid] < oe) lo = mid + 1;
+    else hi = mid;
+  }
+  const int64_t j1 = lo;
+  const bool mixed = j1 > j0;
+  if (mixed) {
+    if (threadIdx.x < IA_WORDS) flags[threadIdx.x] = 0;
+    __syncthreads();
+    for (int64_t j = j0 + threadIdx.x; j < j1; j += blockDim.x) {
+      const uint32_t k = (uint32_t)((int64_t)bq[j] - o);
+      if (k < (uint32_t)IA_TILE) atomicOr(&flags[k >> 5], 1u << (k & 31u));
+    }
+    __syncthreads();
+    uint64_t tot;
+    const uint64_t c = threadIdx.x < IA_WORDS ? (uint64_t)__popc(flags[threadIdx.x]) : 0;
+    const uint64_t pre = block_excl_scan_u64_256(c, sc, &tot);
+    if (threadIdx.x < IA_WORDS) wpre[threadIdx.x] = (uint32_t)pre;
+    __syncthreads();
+  }
+  // top d mix bits of the record before the tile (-1 before a band's first record)
+  int64_t htile = -1;
+  if (o > 0) {
+    const bool isnew = j0 > 0 && (int64_t)bq[j0 - 1] == o - 1;
+    const uint64_t kp = isnew ? sk[j0 - 1] : (o - 1 - j0 >= 0 && o - 1 - j0 < n ? ok[o - 1 - j0] : 0);
+    htile = (int64_t)(qr_mix64(kp) >> (64 - d));
+  }
+  for (int k0 = 0; k0 < IA_TILE && o + k0 < oe; k0 += 256) {
+    const uint32_t k = (uint32_t)k0 + threadIdx.x;
+    const int64_t x = o + k;
+    const bool live = x < oe;
+    uint64_t key = 0;
+    uint32_t id = 0;
+    if (live) {
+      uint32_t before;
+      if (ia_source(mixed, flags, wpre, k, before)) {
+        const int64_t j = j0 + before;
+        if (j < m) {
+          key = sk[j];
+          id = (uint32_t)n + si[j];
+        }
+      } else {
+        const int64_t i = x - j0 - before;
+        if (i >= 0 && i < n) {  // always, for a q the rank kernel wrote
+          key = ok[i];
+          id = oi[i];
+        }
+      }
+    }
+    const int64_t h = (int64_t)(qr_mix64(key) >> (64 - d));
+    int64_t hp = __shfl_up(h, 1, WAVE);
+    if (lane == 0) {
+      if (k == 0) hp = htile;
+      else if (live) {
+        uint32_t before;
+        const bool isnew = ia_source(mixed, flags, wpre, k - 1, before);
+        const int64_t i = isnew ? j0 + before : x - 1 - j0 - before;
+        const uint64_t kp = i >= 0 && i < (isnew ? m : n) ? (isnew ? sk[i] : ok[i]) : 0;
+        hp = (int64_t)(qr_mix64(kp) >> (64 - d));
+      }
+    }
+    if (live) {
+      ko[x] = key;
+      io[x] = id;
+      for (int64_t s = hp + 1; s <= h; ++s) dr[s] = (uint32_t)x;
+      if (x == N - 1)
+        for (int64_t s = h + 1; s <= (1ll << d); ++s) dr[s] = (uint32_t)N;
+    }
+  }
+}
+
+// workspace: batch keys_tmp u64 [b][m] | batch ids u32 [b][m] | ids_tmp u32 [b][m] | q u32 [b][m] | sort workspace
+QRLSH_EXPORT size_t qrlsh_index_append_workspace_bytes(int64_t m, int32_t b) {
+  if (m <= 0 || b <= 0) return 0;
+  const size_t bm = (size_t)b * (size_t)m;
+  return ix_al16(bm * 8) + 3 * ix_al16(bm * 4) + qrlsh_sort_workspace_bytes(m, b);
+}
+
+QRLSH_EXPORT int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
+                                    uint64_t *new_keys, int64_t m, uint64_t *keys_out, uint32_t *ids_out,
+                                    uint32_t *dir_out, void *workspace, size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(n >= 0 && m >= 0 && n < (1ll << 32) - 1 && m < (1ll << 32) - 1 && b > 0 && b <= 65535,
+               "qrlsh_index_append: bad sizes n=%lld m=%lld b=%d", (long long)n, (long long)m, b);
+  QR_CHECK_ARG(n + m < (1ll << 32) - 1, "qrlsh_index_append: n + m = %lld must stay below 2^32 - 1", (long long)(n + m));
+  if (m == 0) return QRLSH_OK;  // nothing to add: the outputs are not written
+  QR_CHECK_ARG(new_keys && keys_out && ids_out && dir_out && workspace && (n == 0 || (keys && ids && dir)),
+               "qrlsh_index_append: null pointer");
+  if (workspace_bytes < qrlsh_index_append_workspace_bytes(m, b)) {
+    qrlsh_set_error("qrlsh_index_append: workspace %zu < %zu bytes", workspace_bytes,
+                    qrlsh_index_append_workspace_bytes(m, b));
+    return QRLSH_EWORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const size_t bm = (size_t)b * (size_t)m;
+  char *ws = static_cast<char *>(workspace);
+  uint64_t *ktmp = reinterpret_cast<uint64_t *>(ws);
+  uint32_t *bids = reinterpret_cast<uint32_t *>(ws + ix_al16(bm * 8));
+  uint32_t *itmp = reinterpret_cast<uint32_t *>(ws + ix_al16(bm * 8) + ix_al16(bm * 4));
+  uint32_t *q = reinterpret_cast<uint32_t *>(ws + ix_al16(bm * 8) + 2 * ix_al16(bm * 4));
+  void *sws = ws + ix_al16(bm * 8) + 3 * ix_al16(bm * 4);
+  const int rc = qrlsh_sort_u64(new_keys, ktmp, bids, itmp, m, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0, sws,
+                                qrlsh_sort_workspace_bytes(m, b), stream);
+  if (rc < 0) return rc;
+  const uint64_t *sk = rc == 1 ? ktmp : new_keys;
+  const uint32_t *si = rc == 1 ? itmp : bids;
+  QR_LAUNCH("index_rank", index_rank_kernel, dim3((unsigned)ceil_div64(m, 256), (unsigned)b), dim3(256), 0, st, keys, dir,
+            n, (int)qrlsh_index_dir_bits(n), sk, m, q);
+  QR_LAUNCH("index_merge", index_merge_kernel, dim3((unsigned)ceil_div64(n + m, IA_TILE), (unsigned)b), dim3(256), 0, st,
+            keys, ids, n, sk, si, (const uint32_t *)q, m, (int)qrlsh_index_dir_bits(n + m), keys_out, ids_out, dir_out);
+  QR_LAUNCH_CHECK("qrlsh_index_append");
+  return QRLSH_OK;
+}

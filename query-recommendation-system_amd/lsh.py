@@ -102,7 +102,10 @@ class LSH:
     def query(self, signatures):
         """For each new signature (not registered), the set of registered ids it shares a non-empty band with:
         get_candidates' rule for a probe (lsh.py:40-55), through a band-key index of the registered signatures
-        (qrlsh.QueryIndex, built on first use and kept until the next compute_buckets*)."""
+        (qrlsh.QueryIndex, built on first use; rows registered since are appended to it, without a rebuild of the
+        sorted band keys.  The rows themselves are held twice from the first append on: signatures_tensor()
+        concatenates every registered row into its own tensor, as get_candidates needs them, and the index keeps the
+        rows it serves in its capacity buffers -- so this route saves the sort, not the row copy or the memory)."""
         if isinstance(signatures, torch.Tensor):
             t = signatures
             t = t.to(torch.int64).bitwise_and(0xFFFFFFFF).to(torch.int32) if t.dtype == torch.int64 else t.to(torch.int32)
@@ -119,8 +122,10 @@ class LSH:
         if m == 0 or sig.shape[0] == 0:
             return out
         idx = getattr(self, "_index", None)
-        if idx is None or idx.n != sig.shape[0]:
+        if idx is None or idx.n > sig.shape[0]:
             idx = self._index = qrlsh.QueryIndex(sig, None, self.b)
+        elif idx.n < sig.shape[0]:          # registered rows are only ever added: append the new ones, no rebuild
+            idx.append(sig[idx.n:])
         q, ids = idx.candidates(t)
         for x, i in zip(ops.to_host(q).tolist(), ops.to_host(ids).tolist()):
             out[x].add(i)

@@ -25,6 +25,7 @@ from .ops import (  # noqa: F401
     score_pairs,
     topk_edges,
     id_bits_for,
+    index_append,
 )
 from .pipeline import (  # noqa: F401
     select_bands,

@@ -109,6 +109,8 @@ SIGNATURES = {
     "qrlsh_index_dir_words": (_sz, [_i64, _i32]),
     "qrlsh_index_build_workspace_bytes": (_sz, [_i64, _i32]),
     "qrlsh_index_build": (ctypes.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "qrlsh_index_append_workspace_bytes": (_sz, [_i64, _i32]),
+    "qrlsh_index_append": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_index_probe_workspace_bytes": (_sz, [_i64, _i32]),
     "qrlsh_index_probe_count": (ctypes.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),
     "qrlsh_index_probe_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _i64, _vp, _sz, _vp, _vp]),

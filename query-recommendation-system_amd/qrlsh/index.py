@@ -10,6 +10,10 @@ sorted per band with a directory -- and answers, for a batch of new queries:
                      zero column: the user side is 0)
     top_users        the users with the largest non-zero predictions (qrlsh_recommend_topk on those rows)
 
+New queries enter the index with append / add (qrlsh_index_append: the batch is sorted and merged into the sorted
+band keys, byte for byte what a fresh build of all n + m rows gives, without sorting the n indexed records again);
+afterwards they are indexed queries like the others, with the ids n .. n + m - 1.
+
 Everything runs on the device; the indexed data never leaves it."""
 import numpy as np
 import torch
@@ -32,7 +36,12 @@ class QueryIndex:
     """sig: the indexed signature rows (int32 [n, P], or compact uint16 rows carried as torch.int16) on the device;
     norm2: int64 [n] (None: computed); b: bands (P % b == 0); table: the ops.PermTable the rows were drawn with
     (needed only by .signatures); keys: int64 [b, n] band keys (default: qrlsh_band_keys of sig; caller keys only
-    filter -- every candidate is checked against the rows); K: default list length (round(log_1.5 n))."""
+    filter -- every candidate is checked against the rows); K: default list length (round(log_1.5 n); a defaulted K
+    follows n when queries are appended, a given K stays).
+
+    .sig and .norm2 are contiguous views of the first n rows of capacity buffers: append copies the m new rows behind
+    them and the buffers grow geometrically (reserve pre-sizes them).  The tensors given to the constructor are never
+    written: the first append or reserve moves the rows into a buffer of the index's own."""
 
     def __init__(self, sig, norm2, b, table=None, keys=None, K=None):
         if not isinstance(sig, torch.Tensor) or sig.dtype not in (torch.int32, torch.int16) or sig.dim() != 2:
@@ -54,14 +63,20 @@ class QueryIndex:
                 raise ValueError("keys must be int64 [b, n] = [%d, %d] on the rows' device" % (b, n))
         if table is not None and (table.P != P or (sig.dtype == torch.int16 and not ops.can_compact(table))):
             raise ValueError("the permutation table does not match the signature rows")
+        self._default_K = K is None
         if K is None:
-            K = min(max(max_candidates(n) if n > 1 else 1, 1), MAX_K)
+            K = self._K_rule(n)
         self.K = _int_arg(K, "K", 1, MAX_K)
         self.sig, self.n, self.P, self.b, self.r = sig, n, P, b, P // b
         self.table = table
         self.norm2 = norm2 if norm2 is not None else ops.row_norms(ops.sig_to_int32(sig))
+        self._sig_buf, self._norm2_buf = self.sig, self.norm2      # capacity buffers; .sig / .norm2 = their first n rows
         keys = ops.band_keys(ops.sig_to_int32(sig), b) if keys is None else keys.clone()
         self.keys, self.ids, self.dir = ops.index_build(keys)
+
+    @staticmethod
+    def _K_rule(n):
+        return min(max(max_candidates(n) if n > 1 else 1, 1), MAX_K)
 
     @classmethod
     def from_result(cls, res, table):
@@ -99,6 +114,49 @@ class QueryIndex:
         if keys is None:
             keys = ops.band_keys(ops.sig_to_int32(sig), self.b)
         return sig, norm2, keys
+
+    # ---- growing the index -----------------------------------------------------------------------------------------
+    def reserve(self, total):
+        """room for `total` indexed queries in the row and norm buffers (no effect when they already hold as many)"""
+        total = _int_arg(total, "total", 0, 2**32 - 2)
+        if total <= self._sig_buf.shape[0]:
+            return
+        dev = self.sig.device
+        sig_buf = torch.empty((total, self.P), dtype=self.sig.dtype, device=dev)
+        norm2_buf = torch.empty((total,), dtype=torch.int64, device=dev)
+        sig_buf[:self.n].copy_(self.sig)
+        norm2_buf[:self.n].copy_(self.norm2)
+        self._sig_buf, self._norm2_buf = sig_buf, norm2_buf
+        self.sig, self.norm2 = sig_buf[:self.n], norm2_buf[:self.n]
+
+    def append(self, sig, norm2=None, keys=None):
+        """index m more queries: sig as in neighbours() (int32 or compact int16 rows, converted to the index's format);
+        norm2 / keys [b, m]: theirs, or None (computed; caller keys only filter, as in the constructor).
+        -> (first_id, m): the new queries are the indexed queries first_id .. first_id + m - 1.  Afterwards .n, .sig,
+        .norm2, .keys, .ids and .dir describe the grown index -- the arrays a fresh QueryIndex over all rows holds --
+        and a defaulted K is round(log_1.5 n) of the new n."""
+        given = keys is not None
+        sig, norm2, keys = self._probe_rows(sig, norm2, keys)
+        n, m = self.n, sig.shape[0]
+        if n + m >= 2**32 - 1:
+            raise ValueError("at most 2^32 - 2 indexed queries")
+        if m == 0:
+            return n, 0
+        grown = ops.index_append(self.keys, self.ids, self.dir, keys.clone() if given else keys)
+        if n + m > self._sig_buf.shape[0]:
+            self.reserve(max(n + m, 2 * self._sig_buf.shape[0]))
+        self._sig_buf[n:n + m].copy_(sig)
+        self._norm2_buf[n:n + m].copy_(norm2)
+        self.keys, self.ids, self.dir = grown
+        self.n = n + m
+        self.sig, self.norm2 = self._sig_buf[:self.n], self._norm2_buf[:self.n]
+        if self._default_K:
+            self.K = self._K_rule(self.n)
+        return n, m
+
+    def add(self, offsets, rows):
+        """signatures() of CSR answer sets, then append(): -> (first_id, m)"""
+        return self.append(*self.signatures(offsets, rows))
 
     def _run(self, sig, norm2, keys, K):
         raw, pws = ops.index_probe(self.keys, self.ids, self.dir, self.r, keys)

@@ -942,6 +942,36 @@ def index_build(keys):
     return keys, ids, dirw
 
 
+def index_append(keys, ids, dirw, new_keys):
+    """a built index (index_build's or an earlier index_append's keys int64 [b, n], ids int32 [b, n], directory) and
+    the band keys int64 [b, m] of m new queries (consumed) -> (keys [b, n + m], ids [b, n + m], directory) of the
+    grown index: the new queries get the ids n .. n + m - 1, and the arrays are byte for byte index_build's of the
+    concatenated keys.  m == 0 returns the arguments."""
+    lib = _lib.load()
+    _need(keys, torch.int64, "keys", 2)
+    _need(ids, torch.int32, "ids", 2)
+    _need(dirw, torch.int32, "dirw", 1)
+    _need(new_keys, torch.int64, "new_keys", 2)
+    b, n = keys.shape
+    m = new_keys.shape[1]
+    if tuple(ids.shape) != (b, n) or new_keys.shape[0] != b or new_keys.device != keys.device:
+        raise ValueError("ids must be [b, n] and new_keys [b, m] = [%d, m] on the index's device" % b)
+    if n and dirw.numel() < int(lib.qrlsh_index_dir_words(n, b)):
+        raise ValueError("the directory is shorter than qrlsh_index_dir_words(n, b)")
+    if n + m >= 2**32 - 1:
+        raise ValueError("at most 2^32 - 2 indexed queries")
+    if m == 0:
+        return keys, ids, dirw
+    dev = keys.device
+    keys_out = torch.empty((b, n + m), dtype=torch.int64, device=dev)
+    ids_out = torch.empty((b, n + m), dtype=torch.int32, device=dev)
+    dir_out = torch.empty((int(lib.qrlsh_index_dir_words(n + m, b)),), dtype=torch.int32, device=dev)
+    ws = _ws(lib.qrlsh_index_append_workspace_bytes(m, b), dev)
+    _lib.check(lib.qrlsh_index_append(_ptr(keys), _ptr(ids), _ptr(dirw), n, b, _ptr(new_keys), m, _ptr(keys_out),
+                                      _ptr(ids_out), _ptr(dir_out), _ptr(ws), ws.numel(), _stream()))
+    return keys_out, ids_out, dir_out
+
+
 def index_probe(sorted_keys, ids, dirw, r, probe_keys):
     """raw candidate words (q * b + band) << 32 | id of every (new query, band) key hit, and the probe workspace
     (per-(query, band) offsets) that index_finish reads"""

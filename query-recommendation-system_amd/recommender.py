@@ -207,6 +207,52 @@ class Recommender:
         sig, norm2, keys = qi.signatures(offsets, rows)
         return qi, sig, norm2, keys
 
+    def add_queries(self, queries, ratings=None, ids=None):
+        """Take m new queries (parse_queries' form) into the served set without a new run: their answer sets and
+        signatures under the last run's table are appended to the run's index (QueryIndex.append: no rebuild), and
+        self.queries, self.queriesIDs and self.ratings grow by the same m.  ratings: integer [users, m] block of their
+        ratings (default: zeros, nothing rated); ids: their labels (default: their positions).  queriesIDs keeps
+        its kind: in a string-labelled set (parse_queries' ids) labels are stored as strings, the default ones as
+        str(position); integer queriesIDs take integer labels only, any other dtype (object, float) takes what
+        converts to it (ValueError otherwise).  -> int64 [m], the
+        positions assigned.  Afterwards similar_queries, predict_new_queries and recommend_new_queries see them as
+        indexed queries.  last_result stays the closed-set run's output; the next compute_querySimilarities starts
+        afresh over all queries.  (Nothing per query is cached on the device between calls: the cached AnswerIndex
+        belongs to the dataset and stays.)"""
+        qi, sig, norm2, keys = self._new_query_rows(queries)
+        q = np.asarray(_as_numpy(queries), dtype=object)
+        m = q.shape[0]
+        nu = self.usersIDs.size
+        if ratings is None:
+            block = np.zeros((nu, m), dtype=np.int64)
+        else:
+            block = np.asarray(_as_numpy(ratings))
+            if block.ndim != 2 or block.shape != (nu, m) or not np.issubdtype(block.dtype, np.integer):
+                raise ValueError("ratings must be an integer [users, m] = [%d, %d] block" % (nu, m))
+            block = block.astype(np.int64)
+        if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
+            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        pos = np.arange(qi.n, qi.n + m, dtype=np.int64)
+        labels = pos if ids is None else np.asarray(ids)
+        if labels.ndim != 1 or labels.size != m:
+            raise ValueError("ids must hold one label per new query (%d)" % m)
+        cur = self.queriesIDs
+        if cur.dtype.kind in "US":
+            labels = labels.astype(str)           # a string-labelled set stays one: default labels are str(position)
+        elif cur.dtype.kind in "iu":
+            if labels.dtype.kind not in "iu":
+                raise ValueError("ids of dtype %s do not fit queriesIDs of dtype %s" % (labels.dtype, cur.dtype))
+        else:                                     # object, float, ...: labels (the positions by default) in that dtype
+            try:
+                labels = labels.astype(cur.dtype)
+            except (TypeError, ValueError):
+                raise ValueError("ids of dtype %s do not fit queriesIDs of dtype %s" % (labels.dtype, cur.dtype))
+        first, _ = qi.append(sig, norm2, keys)
+        self.queries = np.concatenate((np.asarray(self.queries, dtype=object), q), axis=0)
+        self.queriesIDs = np.concatenate((cur, labels))
+        self.ratings = np.hstack((self.ratings, block))
+        return pos
+
     def similar_queries(self, queries):
         """{x: {'indexes': int64[<=K], 'values': float64[<=K]}} for new queries x = 0 .. m-1 (rows of `queries`): the
         indexed queries each would get as neighbours if appended alone (K of the last run; value descending, then id
