@@ -100,8 +100,10 @@ int qrlsh_band_keys(const int32_t *sig, int64_t nq, int32_t P, int32_t b, uint64
  * Stable LSD radix sort of nbatch independent arrays of n uint64 keys (+ optional
  * uint32 payload), 8 bits per pass over bits [bit_lo, bit_hi) of the key (or of
  * mix64(key) with QRLSH_SORT_MIX: equal keys still end up adjacent, in payload
- * order, after 32 bits instead of 64).  Buffers a/b ping-pong; the return value
- * (>= 0) says where the result is: 0 = a, 1 = b.  vals_a/vals_b may both be NULL.
+ * order, after 32 bits instead of 64).  The range is exact: the order is that of ONE
+ * stable sort by bits [bit_lo, bit_hi) alone, whatever the bits at and above bit_hi hold
+ * (a last pass narrower than 8 bits masks its digit).  Buffers a/b ping-pong; the return
+ * value (>= 0) says where the result is: 0 = a, 1 = b.  vals_a/vals_b may both be NULL.
  */
 size_t qrlsh_sort_workspace_bytes(int64_t n, int32_t nbatch);
 int qrlsh_sort_u64(uint64_t *keys_a, uint64_t *keys_b, uint32_t *vals_a, uint32_t *vals_b, int64_t n,

@@ -34,8 +34,10 @@ __device__ static inline int xcd_tile(int bid, int ntiles) {
 // (contiguous shards of aux ids each; at most 256 ranks).
 // 4 = host: the word is a pair i << 32 | j; digit = the rank that scores it (qr_pair_host: the owner of i
 // or of j, chosen by one bit of mix64(pair) so that every rank gets an equal share whatever the data).
+// dmask: the digit mask of the pass, RADIX - 1 except in a last pass narrower than 8 bits ((1 << (bit_hi - shift)) - 1):
+// the sort orders by bits [bit_lo, bit_hi) and by nothing above them.  Owner and host digits are not masked.
 enum { SM_PLAIN = 0, SM_MIX = 1, SM_FOLD = 2, SM_OWNER = 3, SM_HOST = 4 };
-template <int MODE> __device__ static inline uint32_t digit_of(uint64_t key, int shift, uint32_t fold = 0) {
+template <int MODE> __device__ static inline uint32_t digit_of(uint64_t key, int shift, uint32_t fold, uint32_t dmask) {
   if (MODE == SM_OWNER || MODE == SM_HOST) {
     const uint64_t o = MODE == SM_HOST ? qr_pair_host(key, fold) : (key >> shift) / fold;
     return o < RADIX ? (uint32_t)o : RADIX - 1;
@@ -43,14 +45,15 @@ template <int MODE> __device__ static inline uint32_t digit_of(uint64_t key, int
   uint64_t x = key;
   if (MODE == SM_MIX) x = qr_mix64(key);
   if (MODE == SM_FOLD) x = ((key >> 32) << fold) | (key & ((1ull << fold) - 1ull));
-  return (uint32_t)(x >> shift) & (RADIX - 1);
+  return (uint32_t)(x >> shift) & dmask;
 }
 
 // ghist layout: [batch][digit][tile]
 template <int MIX>
 __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const uint64_t *__restrict__ keys, int64_t n,
                                                                  int ntiles, int shift,
-                                                                 uint32_t *__restrict__ ghist, uint32_t fold) {
+                                                                 uint32_t *__restrict__ ghist, uint32_t fold,
+                                                                 uint32_t dmask) {
   __shared__ uint32_t h[RADIX];
   const int tile = blockIdx.x, batch = blockIdx.y;
   h[threadIdx.x] = 0;
@@ -77,7 +80,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_hist_kernel(const uint64_t 
       const int64_t idx = idx0 + e;
       uint32_t dd = 0;
       if (idx < n) {
-        const uint32_t d = digit_of<MIX>(kk[e], shift, fold);
+        const uint32_t d = digit_of<MIX>(kk[e], shift, fold, dmask);
         if (MIX != SM_OWNER && MIX != SM_HOST) atomicAdd(&h[d], 1u);
         dd = d;
       }
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const uint64
                                                                     int ntiles, int shift,
                                                                     const uint32_t *__restrict__ goff,
                                                                     const uint32_t *__restrict__ rtot,
-                                                                    uint32_t fold) {
+                                                                    uint32_t fold, uint32_t dmask) {
   __shared__ uint32_t cnt[SORT_THREADS / WAVE][RADIX];
   __shared__ uint32_t dsum[SORT_THREADS / WAVE];
   const int tile = xcd_tile(blockIdx.x, ntiles), batch = blockIdx.y;
@@ -217,7 +220,7 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const uint64
   for (int k = 0; k < SORT_IPT; ++k) {
     const int64_t idx = wbase + (int64_t)k * WAVE + lane;
     const bool valid = idx < n;
-    const uint32_t d = digit_of<MIX>(key[k], shift, fold);
+    const uint32_t d = digit_of<MIX>(key[k], shift, fold, dmask);
     uint64_t m = __ballot(valid);
 #pragma unroll
     for (int bit = 0; bit < 8; ++bit) {
@@ -283,7 +286,7 @@ __global__ __launch_bounds__(SORT_THREADS, 4) void sort_scatter_staged_kernel(co
                                                                            int ntiles, int shift,
                                                                            const uint32_t *__restrict__ goff,
                                                                            const uint32_t *__restrict__ rtot,
-                                                                           uint32_t fold) {
+                                                                           uint32_t fold, uint32_t dmask) {
   __shared__ uint32_t cnt[SORT_THREADS / WAVE][RADIX];
   __shared__ uint32_t dsum[SORT_THREADS / WAVE];
   __shared__ uint32_t lsum[SORT_THREADS / WAVE];
@@ -309,7 +312,7 @@ __global__ __launch_bounds__(SORT_THREADS, 4) void sort_scatter_staged_kernel(co
   for (int k = 0; k < SORT_IPT; ++k) {
     const int64_t idx = wbase + (int64_t)k * WAVE + lane;
     const bool valid = idx < n;
-    const uint32_t d = digit_of<MODE>(key[k], shift, fold);
+    const uint32_t d = digit_of<MODE>(key[k], shift, fold, dmask);
     uint64_t m = __ballot(valid);
 #pragma unroll
     for (int bit = 0; bit < 8; ++bit) {
@@ -377,7 +380,7 @@ __global__ __launch_bounds__(SORT_THREADS, 4) void sort_scatter_staged_kernel(co
     const int p = k * SORT_THREADS + threadIdx.x;
     if (p < ntile) {
       const uint64_t kk = skey[p];
-      keys_out[boff + gdelta[digit_of<MODE>(kk, shift, fold)] + (uint32_t)p] = kk;
+      keys_out[boff + gdelta[digit_of<MODE>(kk, shift, fold, dmask)] + (uint32_t)p] = kk;
     }
   }
 }
@@ -795,20 +798,21 @@ static int sort_passes(uint64_t *ka, uint64_t *kb, uint32_t *va, uint32_t *vb, i
   for (int shift = bit_lo; shift < bit_hi; shift += 8) {
     uint64_t *kin = cur ? kb : ka, *kout = cur ? ka : kb;
     uint32_t *vin = cur ? vb : va, *vout = cur ? va : vb;
-    QR_LAUNCH("sort_hist", (sort_hist_kernel<MIX>), grid, block, 0, st, kin, n, ntiles, shift, ghist, fold);
+    const uint32_t dmask = (1u << (bit_hi - shift < 8 ? bit_hi - shift : 8)) - 1u;   // the last pass may be narrower
+    QR_LAUNCH("sort_hist", (sort_hist_kernel<MIX>), grid, block, 0, st, kin, n, ntiles, shift, ghist, fold, dmask);
     launch_rowscan(ghist, ntiles, rtot, nbatch, st);
     if (!has_val && (MIX == SM_PLAIN || MIX == SM_FOLD))
       QR_LAUNCH("sort_scatter_k", (sort_scatter_staged_kernel<MIX>), grid, block, 0, st, kin, kout, n, ntiles, shift,
-                ghist, rtot, fold);
+                ghist, rtot, fold, dmask);
     else if (!has_val)
       QR_LAUNCH("sort_scatter_k", (sort_scatter_kernel<MIX, false, false>), grid, block, 0, st, kin, vin, kout, vout, n,
-                         ntiles, shift, ghist, rtot, fold);
+                         ntiles, shift, ghist, rtot, fold, dmask);
     else if (iota && shift == bit_lo)
       QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<MIX, true, true>), grid, block, 0, st, kin, vin, kout, vout, n,
-                         ntiles, shift, ghist, rtot, fold);
+                         ntiles, shift, ghist, rtot, fold, dmask);
     else
       QR_LAUNCH("sort_scatter_kv", (sort_scatter_kernel<MIX, true, false>), grid, block, 0, st, kin, vin, kout, vout, n,
-                         ntiles, shift, ghist, rtot, fold);
+                         ntiles, shift, ghist, rtot, fold, dmask);
     cur ^= 1;
   }
   hipError_t e = hipGetLastError();

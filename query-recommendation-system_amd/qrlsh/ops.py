@@ -208,8 +208,10 @@ def row_norms(sig):
 # ---------------------------------------------------------------------------
 def sort_u64(keys, vals=None, bit_lo=0, bit_hi=64, mix=False, iota=False, fold=0, owner_shard=0, host_shard=0):
     """Stable LSD radix sort of each row of keys (int64 bit patterns, unsigned order) over
-    bits [bit_lo, bit_hi) (of mix64(key) when mix).  `keys` (and vals) are consumed as one
-    of the two ping-pong buffers.  Returns (sorted_keys, sorted_vals | None)."""
+    bits [bit_lo, bit_hi) (of mix64(key) when mix, of i << fold | j when fold).  The range is exact:
+    bits at and above bit_hi never influence the order, also when bit_hi - bit_lo is no multiple of 8.
+    `keys` (and vals) are consumed as one of the two ping-pong buffers.
+    Returns (sorted_keys, sorted_vals | None)."""
     lib = _lib.load()
     _need(keys, torch.int64, "keys")
     k2 = keys if keys.dim() == 2 else keys.view(1, -1)
