@@ -67,12 +67,7 @@ __global__ __launch_bounds__(256) void answer_sets_kernel(const uint32_t *__rest
       total += pc;
     } else {
       // exclusive prefix of the lanes' popcounts: where this lane's rows start
-      uint32_t inc = pc;
-#pragma unroll
-      for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t o = __shfl_up(inc, d, WAVE);
-        if (lane >= d) inc += o;
-      }
+      const uint32_t inc = wave_incl_scan(pc);
       const uint32_t step_total = __shfl(inc, WAVE - 1, WAVE);
       if (MODE == 2) {
         uint32_t p = total + (inc - pc);  // total is wave-uniform here

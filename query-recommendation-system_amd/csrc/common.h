@@ -110,22 +110,59 @@ template <bool NT, typename T> __device__ static inline T qr_load(const T *p) {
 
 __device__ static inline int lane_id() { return threadIdx.x & (WAVE - 1); }
 
-// wave-level inclusive scan of a u64 via shuffles
-__device__ static inline uint64_t wave_incl_scan_u64(uint64_t v) {
+// radix sort, bucket partition and pair grouping all deal 256 ways with 256-thread workgroups
+constexpr int SORT_THREADS = 256;
+constexpr int RADIX = 256;
+
+// Workgroups b and b+8 share an XCD (round-robin dispatch; speed only, never correctness).
+// Remap so each XCD works on a contiguous range of tiles: the runs that neighbouring tiles
+// write for one digit are adjacent in memory, and their shared 64-B sectors then merge in
+// ONE L2 instead of being written back partially by two.
+__device__ static inline int xcd_tile(int bid, int ntiles) {
+  const int q = ntiles >> 3, r = ntiles & 7, x = bid & 7, y = bid >> 3;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + y;
+}
+
+// wave-level inclusive scan (sum) of a uint32_t or uint64_t via shuffles; every lane of the wave calls it
+template <typename T> __device__ static inline T wave_incl_scan(T v) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 8, "uint32_t or uint64_t");
   const int lane = lane_id();
 #pragma unroll
   for (int d = 1; d < WAVE; d <<= 1) {
-    uint64_t o = __shfl_up(v, d, WAVE);
+    const T o = __shfl_up(v, d, WAVE);
     if (lane >= d) v += o;
   }
   return v;
 }
 
+// block-level exclusive scan of one u32 per thread over THREADS threads (all of them call it); returns the
+// exclusive prefix for this thread, and the block total in `total`.  Barrier contract: barrier (wsum may still
+// be read from an earlier scan, and whatever the caller wrote to LDS before the call is visible after it),
+// store the wave totals to wsum[THREADS / WAVE], barrier.  NO barrier after wsum is read: a caller that
+// rewrites wsum itself puts one in between.
+template <int THREADS> __device__ static inline uint32_t block_excl_scan(uint32_t v, uint32_t *wsum, uint32_t &total) {
+  const int lane = lane_id(), w = threadIdx.x >> 6;
+  const uint32_t inc = wave_incl_scan(v);
+  __syncthreads();
+  if (lane == WAVE - 1) wsum[w] = inc;
+  __syncthreads();
+  uint32_t base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < THREADS / WAVE; ++i) {
+    const uint32_t x = wsum[i];
+    if (i < w) base += x;
+    tot += x;
+  }
+  total = tot;
+  return base + inc - v;
+}
+
 // block-level exclusive scan of one u64 per thread (blockDim.x = 256); returns the
 // exclusive prefix for this thread and the block total in *total.  smem: >= 4 u64.
+// Its barriers are not those of block_excl_scan: none before the store, one after the reads.
 __device__ static inline uint64_t block_excl_scan_u64_256(uint64_t v, uint64_t *smem, uint64_t *total) {
   const int lane = lane_id(), w = threadIdx.x >> 6;
-  uint64_t inc = wave_incl_scan_u64(v);
+  uint64_t inc = wave_incl_scan(v);
   if (lane == WAVE - 1) smem[w] = inc;
   __syncthreads();
   uint64_t base = 0, tot = 0;
@@ -156,12 +193,7 @@ static __global__ __launch_bounds__(SCANL_THREADS) void scan_chunks_kernel(uint6
   for (int k = 0; k < SCANL_PER; ++k) held[k] = lo + k < m ? a[lo + k] : 0;
 #pragma unroll
   for (int k = 0; k < SCANL_PER; ++k) s += held[k];
-  uint64_t inc = s;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint64_t o = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += o;
-  }
+  const uint64_t inc = wave_incl_scan(s);
   if (lane == 63) wsum[w] = inc;
   __syncthreads();
   uint64_t run = inc - s, tot = 0;
@@ -209,7 +241,7 @@ static __global__ __launch_bounds__(1024) void scan_u64_kernel(uint64_t *__restr
   } else {
     for (int64_t i = lo; i < hi; ++i) s += a[i];
   }
-  const uint64_t inc = wave_incl_scan_u64(s);
+  const uint64_t inc = wave_incl_scan(s);
   if (lane == WAVE - 1) wsum[w] = inc;
   __syncthreads();
   uint64_t base = 0, tot = 0;

@@ -487,21 +487,8 @@ __global__ __launch_bounds__(RD_THREADS) void row_unique_kernel(const uint64_t *
       val[k] = p < m ? tab[p] : RD_EMPTY;
       sum += val[k] != RD_EMPTY;
     }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, WAVE);
-      if (lane >= d) inc += o;
-    }
-    __syncthreads();  // every wave is done with wsum (row starts) and with lo
-    if (lane == WAVE - 1) wsum[w] = inc;
-    __syncthreads();
-    uint32_t run = inc - sum;
-    total = 0;
-    for (int k = 0; k < RD_THREADS / WAVE; ++k) {
-      if (k < w) run += wsum[k];
-      total += wsum[k];
-    }
+    // (the scan's first barrier: every wave is done with wsum (row starts) and with lo)
+    uint32_t run = block_excl_scan<RD_THREADS>(sum, wsum, total);
 #pragma unroll
     for (int k = 0; k < RD_PER; ++k) {
       const int p = b0 + k;
@@ -600,12 +587,7 @@ __global__ __launch_bounds__(RL_THREADS) void row_unique_long_kernel(const uint6
       val[k] = tab[b0 + k];
       sum += val[k] != RD_EMPTY;
     }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, WAVE);
-      if (lane >= d) inc += o;
-    }
+    const uint32_t inc = wave_incl_scan(sum);
     if (lane == WAVE - 1) wsum[w] = inc;
     __syncthreads();
     uint32_t run = inc - sum, u = 0;
@@ -802,12 +784,7 @@ __device__ static inline bool region_finish(const W *__restrict__ in, int64_t s0
   uint32_t c = 0, inc = 0;
   if (t < RG_ROWS) {
     c = rowcnt[t];
-    inc = c;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, WAVE);
-      if (lane >= d) inc += o;
-    }
+    inc = wave_incl_scan(c);
     if (lane == WAVE - 1) wsum[wv] = inc;
   }
   __syncthreads();
@@ -867,12 +844,7 @@ __device__ static inline bool region_finish(const W *__restrict__ in, int64_t s0
     uint32_t c2 = 0, inc2 = 0;
     if (t < RG_ROWS) {
       c2 = sub[t];
-      inc2 = c2;
-#pragma unroll
-      for (int d = 1; d < WAVE; d <<= 1) {
-        const uint32_t o = __shfl_up(inc2, d, WAVE);
-        if (lane >= d) inc2 += o;
-      }
+      inc2 = wave_incl_scan(c2);
       if (lane == WAVE - 1) wsum[wv] = inc2;
     }
     __syncthreads();
@@ -1465,12 +1437,7 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
     // v* = smallest v with count(inv <= v) >= K; below = count(inv < v*).  Lane l owns values [32 l, 32 l + 32).
     uint32_t mysum = 0;
     for (int v = 0; v < NV / WAVE; ++v) mysum += hist[lane * (NV / WAVE) + v];
-    uint32_t inc = mysum;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-      const uint32_t o = __shfl_up(inc, d, WAVE);
-      if (lane >= d) inc += o;
-    }
+    const uint32_t inc = wave_incl_scan(mysum);
     const uint64_t reach = __ballot(inc >= (uint32_t)K);  // len > SEL_LONG >= ... may still be < K: then keep all
     uint32_t vstar = NV, below = 0;
     if (reach) {
@@ -1512,12 +1479,7 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
         __builtin_amdgcn_wave_barrier();
         uint32_t ms = 0;
         for (int v = 0; v < NV / WAVE; ++v) ms += hist[lane * (NV / WAVE) + v];
-        uint32_t ic = ms;
-#pragma unroll
-        for (int d = 1; d < WAVE; d <<= 1) {
-          const uint32_t o = __shfl_up(ic, d, WAVE);
-          if (lane >= d) ic += o;
-        }
+        const uint32_t ic = wave_incl_scan(ms);
         const int owner = __ffsll((long long)__ballot(ic >= need)) - 1;  // (need <= the number of undecided ids)
         uint32_t run = __shfl(ic - ms, owner, WAVE), dg = 0, bl = 0;
         if (lane == owner) {

@@ -328,7 +328,7 @@ __global__ __launch_bounds__(RC_THREADS) void recommend_threshold_kernel(int64_t
 __device__ __forceinline__ void rc_append(uint32_t *cnt, uint64_t *out, const uint64_t *sk, uint32_t mask) {
   const int n = __popc(mask);
   if (!__any(n > 0)) return;
-  const uint64_t inc = wave_incl_scan_u64((uint64_t)n);
+  const uint64_t inc = wave_incl_scan((uint64_t)n);
   const uint64_t tot = __shfl(inc, WAVE - 1, WAVE);
   uint32_t base = 0;
   if (lane_id() == WAVE - 1) base = atomicAdd(cnt, (uint32_t)tot);

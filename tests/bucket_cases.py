@@ -1,4 +1,4 @@
-"""Builders of adversarial band-key matrices for the partition + LDS-finish bucket path (csrc/sort.hip): planted
+"""Builders of adversarial band-key matrices for the partition + LDS-finish bucket path (csrc/bucket.hip): planted
 multiplicities, several popular keys hashed into ONE part, a part filled to exactly N records.  Shared by
 tests/test_gpu_buckets.py and tools/stress_buckets.py.
 

@@ -23,7 +23,7 @@ def u64(t):
 
 
 def coarse_region(nq, c1):
-    """records a coarse region of the two-step partition holds (sort.hip: coarse_region); it does not spill"""
+    """records a coarse region of the two-step partition holds (bucket.hip: coarse_region); it does not spill"""
     a = nq / (1 << c1)
     slack = 0.25 * a + 8192.0 if a >= 4096.0 else 6.0 * a ** 0.5 + 2.0 * a + 64.0
     return (int(a + slack) + 63) // 64 * 64

@@ -1,4 +1,4 @@
-"""Own-pair ranks of the block kernel of the bucket finish (csrc/sort.hip: bucket_finish_big_kernel).  A record's rank
+"""Own-pair ranks of the block kernel of the bucket finish (csrc/bucket.hip: bucket_finish_big_kernel).  A record's rank
 among its bucket-mates decides which of the eight slice workgroups writes its pairs; runs up to FIN_RANK_SORT copies
 are ranked by a lane per record, longer ones are sorted in LDS by the workgroup and ranked by position.  One part of a
 one-band key matrix is filled to just beyond the LDS image, so that the block kernel works it and its first block holds
@@ -20,7 +20,7 @@ DEV = "cuda"
 R = 4
 T, NQ = 8, 1_000_000      # one-step partition, parts of ~3 900 background records, regions of one 6144-record image
 FIN_CAP = 6144            # csrc/common.h: records of an LDS image = a block of the big kernel
-FIN_RANK_SORT = 256       # csrc/sort.hip: runs beyond this are sorted
+FIN_RANK_SORT = 256       # csrc/bucket.hip: runs beyond this are sorted
 
 
 def planted_part(seed, sizes, total):
