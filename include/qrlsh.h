@@ -152,9 +152,13 @@ int qrlsh_pairs_fill(const uint64_t *sorted_keys, const uint32_t *sorted_ids, in
  * swollen by a popular key (lsh.py:42-49 makes a bucket of m queries m(m-1)/2 pairs whatever m is; at 100 M queries
  * over 32768 table rows m reaches ~20 000) spills there and is worked in blocks of one image; only a part beyond
  * qrlsh_set_big_part_limit records (default 16 images = 98 304), more than 4096 such parts per band group, or an
- * exhausted pool raise the overflow flag.  Reserved: ~1.4 - 2 x the b * nq records.  These buffers are scratch:
- * what they hold afterwards is mix64(key) (a bijection of the keys, which is all the pairing needs), not the keys,
- * and the records of empty bands are gone. */
+ * exhausted pool raise the overflow flag.  Reserved: ~1.4 - 2 x the b * nq records.  These buffers are scratch.
+ * What they hold afterwards are 10-byte records, not keys and ids: part_keys a 64-bit word per record -- the low
+ * 64 - part_bits bits of mix64(key) (a bijection of the keys; the top part_bits bits are the part number, which the
+ * record's place says) with the query id's bits from 16 up above them -- and part_ids, used as uint16_t storage, the
+ * id's low 16 bits at the record's index (the first half of the buffer; the sizes stay counted in 32-bit words).
+ * tmp_keys / tmp_ids hold the same form after the first level, per slab of 2^(16 + first level's bits) consecutive
+ * queries.  The records of empty bands are gone.  nq beyond 2^(16 + part_bits) raises the overflow flag. */
 size_t qrlsh_bucket_workspace_bytes(int64_t nq, int32_t b, int32_t part_bits);
 size_t qrlsh_bucket_part_words(int64_t nq, int32_t b, int32_t part_bits);
 /* records a part beyond the LDS image may hold and stay on the partition path (<= 0 or beyond the maximum: the

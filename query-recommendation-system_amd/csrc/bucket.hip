@@ -37,9 +37,27 @@
 // The finish lists such parts like every part beyond its image; bucket_big_gather_kernel then puts each one's records
 // (region prefix + its runs) next to each other in the pool, where the block kernel works them.  No pool (keys ==
 // nullptr: the coarse step of a two-step partition): an overflowing part raises the flag, as before.
+// NARROW RECORDS (round 6).  A record is a 64-bit word and a 16-bit tail, 10 bytes instead of 12.  Where a record sits
+// already says `used` top bits of x -- the part number: c1 bits after the first of two steps, T bits after the last
+// step -- so those bits of the word carry the id's bits from 16 up instead, and the tail its low 16:
+//     word = x's low (64 - used) bits | (id >> 16) << (64 - used),    tail = (uint16_t)id
+// After the last step id >> 16 always fits (the path serves nq <= 2^(16+T) only).  After the first of two steps it need
+// not (10 M queries: 24-bit ids, 16 + c1 = 22), so that step deals every SLAB of 2^(16+c1) consecutive queries to
+// regions of its own -- (band, slab, part) -- and the id bits above 16 + c1 are the slab number, which the second step
+// knows from its batch.  A tile of the first step is PS_TILE consecutive queries and PS_TILE divides 2^16: a tile lies
+// in one slab, its records share id >> 16, and its runs per (tile, part) are as long as without slabs.
+// xbits = 64 - used everywhere below.
+__device__ static inline uint64_t rec_x(uint64_t word, int xbits) { return word & ((1ull << xbits) - 1ull); }
+__device__ static inline uint64_t rec_word(uint64_t x, uint32_t id_hi, int xbits) {
+  return rec_x(x, xbits) | (uint64_t)id_hi << xbits;
+}
+__device__ static inline uint32_t rec_id(uint64_t word, uint16_t tail, int xbits) {
+  return (uint32_t)(word >> xbits) << 16 | tail;
+}
+
 struct PartPool {
-  uint64_t *keys;               // pool records (the x words) ...
-  uint32_t *vals;               // ... and their ids
+  uint64_t *keys;               // pool records (the words) ...
+  uint16_t *vals;               // ... and their tails
   unsigned long long *cursor;   // records handed out so far
   uint32_t cap;                 // records the pool holds (< 2^32)
   uint4 *runs;                  // {part slot, records, pool position, 0} per spilled run
@@ -54,19 +72,24 @@ struct PartPool {
 #endif
 constexpr int PS_IPT = QR_PS_IPT;  // records per thread of the atomic partition (8, six workgroups per CU: 3.9 ms against 3.4)
 constexpr int PS_TILE = SORT_THREADS * PS_IPT;
-constexpr int PS_WGS = PS_IPT <= 16 ? 3 : 2;   // workgroups per CU the LDS image (12 B per record) allows
+static_assert(65536 % PS_TILE == 0, "a tile of the first step lies in one slab and its records share id >> 16");
+// workgroups per CU the LDS image (10 B per record + 2.3 KB of counters) allows: 42.3 KB at 16 records per thread --
+// three; four would need 4 x 42.3 = 169 KB of the CU's 160
+constexpr int PS_WGS = PS_IPT <= 16 ? 3 : 2;
+// LEVEL2 = false: batch = band; its tiles go to the regions of (band, slab of the tile) -- nslabs = 1, slab_shift = 63
+// for a one-step partition.  LEVEL2 = true: batch = ((band * nslabs + slab) << c1) + coarse part, dealt to the fine
+// parts of (band, coarse part) whatever the slab.
 template <bool LEVEL2>
 __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kernel(
-    const uint64_t *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, uint64_t *__restrict__ keys_out,
-    uint32_t *__restrict__ vals_out, int64_t n_in, int ntiles, int shift, uint32_t dmask,
+    const uint64_t *__restrict__ keys_in, const uint16_t *__restrict__ tails_in, uint64_t *__restrict__ keys_out,
+    uint16_t *__restrict__ tails_out, int64_t n_in, int ntiles, int shift, uint32_t dmask,
     uint32_t *__restrict__ cursors, uint32_t cap, uint32_t *__restrict__ overflow, uint64_t ek,
     const uint32_t *__restrict__ in_counts, uint32_t in_cap, int64_t chunk_len, int64_t chunk_stride,
-    int64_t band_stride, PartPool pool) {
+    int64_t band_stride, int c1, int nslabs, int slab_shift, PartPool pool) {
   // What travels through the partition is x = mix64(key), not the key: mix64 is a bijection, so equal x <=> equal
   // keys and the finish can pair on x; the part number of either step is then a shift of the staged word (no
-  // second hash in the second step, none at the write-out, nothing to carry in the id word -- ids keep all 32
-  // bits for any number of queries).  Records of empty bands (key == ek) never pair (lsh.py:47) and are dropped
-  // here; mix64(ek), which no other key maps to, is the finish's free-slot marker.
+  // second hash in the second step, none at the write-out).  Records of empty bands (key == ek) never pair
+  // (lsh.py:47) and are dropped here.
   // The order of the records inside a part is free, so a record's place in its tile's share of a part is the old
   // value of an LDS counter (one returning ds_add per record), not the eight ballots + popcount a stable rank
   // costs: the kernel was VALU-bound on those (2200 vector instructions per wave, 66 % VALU-busy).
@@ -75,7 +98,7 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
   __shared__ uint32_t gdelta[RADIX];
   __shared__ uint8_t gok[RADIX];
   __shared__ uint64_t skey[PS_TILE];
-  __shared__ uint32_t sval[PS_TILE];
+  __shared__ uint16_t sval[PS_TILE];
   const int tile = LEVEL2 ? (int)blockIdx.x : xcd_tile(blockIdx.x, ntiles), batch = blockIdx.y;
   const int lane = threadIdx.x & (WAVE - 1), w = threadIdx.x >> 6;
   const int64_t n = LEVEL2 ? (int64_t)min(in_counts[batch], in_cap) : n_in;
@@ -83,6 +106,17 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
   if (tbase >= n) return;  // LEVEL2: the grid covers a full region, this one holds fewer records (uniform)
   cnt[threadIdx.x] = 0;
   __syncthreads();
+  // the batch the records go to, and the id bits from 16 up that the written word carries: the tile's own (first
+  // step: ids are positions), or slab number : what the read word carries (second step)
+  uint32_t obatch, id_hi;
+  if (LEVEL2) {
+    const uint32_t bs = (uint32_t)batch >> c1, band = bs / (uint32_t)nslabs, slab = bs - band * (uint32_t)nslabs;
+    obatch = band << c1 | ((uint32_t)batch & ((1u << c1) - 1u));
+    id_hi = slab << c1;
+  } else {
+    obatch = (uint32_t)batch * (uint32_t)nslabs + (uint32_t)(tbase >> slab_shift);
+    id_hi = (uint32_t)(tbase >> 16) & dmask;
+  }
   // first step: band `batch` of the key matrix, either plain ([b][n]: band_stride = n) or in chunks of
   // chunk_len queries chunk_stride words apart (what a band-partitioned all-to-all delivers: [rank][band][nql])
   const size_t boff = LEVEL2 ? (size_t)batch * in_cap : (size_t)batch * (size_t)(band_stride ? band_stride : n);
@@ -90,14 +124,14 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
   const int64_t wbase = tbase + (int64_t)w * (WAVE * PS_IPT);
   const uint32_t nd = dmask + 1u;  // parts per batch
   uint64_t key[PS_IPT];
-  uint32_t val[PS_IPT];
+  uint16_t val[PS_IPT];
   uint32_t dr[PS_IPT];  // part << 16 | place among the tile's records of that part; 0xFFFFFFFF = no record
 #pragma unroll
   for (int k = 0; k < PS_IPT; ++k) {
     const int64_t idx = wbase + (int64_t)k * WAVE + lane;
     const size_t at = chunked ? boff + (size_t)(idx / chunk_len) * chunk_stride + (size_t)(idx % chunk_len) : boff + idx;
     key[k] = idx < n ? keys_in[at] : ek;
-    val[k] = LEVEL2 ? (idx < n ? vals_in[boff + idx] : 0u) : (uint32_t)idx;
+    val[k] = LEVEL2 ? (idx < n ? tails_in[boff + idx] : (uint16_t)0) : (uint16_t)idx;
   }
 #pragma unroll
   for (int k = 0; k < PS_IPT; ++k) {
@@ -112,7 +146,7 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
   // tile has been laid out in LDS (which needs local positions only): the atomic's round trip to memory
   // runs beside the scan and the staging.
   const uint32_t tc = cnt[threadIdx.x];
-  const uint32_t gb = tc ? atomicAdd(&cursors[(size_t)batch * nd + threadIdx.x], tc) : 0u;
+  const uint32_t gb = tc ? atomicAdd(&cursors[(size_t)obatch * nd + threadIdx.x], tc) : 0u;
   uint32_t lstart;
   {
     const uint32_t linc = wave_incl_scan(tc);
@@ -144,7 +178,7 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
         if (pb + tc <= (unsigned long long)pool.cap) {
           const unsigned long long ri = __hip_atomic_fetch_add(pool.nruns, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
           if (ri < (unsigned long long)pool.runs_max) {
-            const uint32_t slot = pool.slot_base + (uint32_t)batch * nd + (uint32_t)d;
+            const uint32_t slot = pool.slot_base + obatch * nd + (uint32_t)d;
             pool.runs[ri] = make_uint4(slot, tc, (uint32_t)pb, 0u);
             atomicMin(&pool.fill[slot], gb);
             where = 2u;
@@ -161,21 +195,22 @@ __global__ __launch_bounds__(SORT_THREADS, PS_WGS) void part_scatter_atomic_kern
   uint32_t nstaged = 0;  // records of the tile that are not of an empty band
 #pragma unroll
   for (int k = 0; k < SORT_THREADS / WAVE; ++k) nstaged += lsum[k];
-  const size_t obase = (size_t)batch * nd * cap;
+  const size_t obase = (size_t)obatch * nd * cap;
 #pragma unroll
   for (int k = 0; k < PS_IPT; ++k) {
     const uint32_t p = k * SORT_THREADS + threadIdx.x;
     if (p < nstaged) {
-      const uint64_t x = skey[p];
+      const uint64_t x = skey[p];  // (second step: the first step's word -- the digit's bits are x's in both)
       const uint32_t d = (uint32_t)(x >> shift) & dmask;
       const uint32_t where = gok[d];
+      const uint64_t word = rec_word(x, LEVEL2 ? id_hi | (uint32_t)(x >> (64 - c1)) : id_hi, shift);
       if (where == 1u) {
         const size_t dst = obase + (uint32_t)(gdelta[d] + p);
-        keys_out[dst] = x;
-        vals_out[dst] = sval[p];
+        keys_out[dst] = word;
+        tails_out[dst] = sval[p];
       } else if (where == 2u) {
         const uint32_t dst = gdelta[d] + p;
-        pool.keys[dst] = x;
+        pool.keys[dst] = word;
         pool.vals[dst] = sval[p];
       }
     }
@@ -194,9 +229,9 @@ constexpr int FIN_IPT = FIN_CAP / FIN_THREADS;
 constexpr int FIN_SMALL_THREADS = 512, FIN_SMALL_CAP = 4096;  // the small-part form of the finish
 constexpr int FIN_SMALL_MEAN = 2800;                          // mean records per part up to which it is used
 
-// Finish of one (part, band): an open-addressing hash table in LDS keyed by the FULL 64-bit key
-// (ds_cmpst_b64 claims a slot or finds the key present; the empty-band key, which never enters a
-// bucket, doubles as the "free slot" marker).  A record's arrival number o in its slot's counter
+// Finish of one (part, band): an open-addressing hash table in LDS keyed by the x bits of the record's word -- inside a
+// part they tell the full 64-bit keys apart -- (ds_cmpst_b64 claims a slot or finds the key present; FIN_FREE, which
+// has bits set above the x bits and so equals no key, is the "free slot" marker).  A record's arrival number o in its slot's counter
 // says how many records of its bucket came before it, so
 //     pairs of the part = sum of o
 // and the ids of every bucket are laid out next to each other in LDS (run start = exclusive
@@ -205,6 +240,8 @@ constexpr int FIN_SMALL_MEAN = 2800;                          // mean records pe
 // LDS: table 48 KB + counters 24 KB = 72 KB -> two 1024-thread workgroups per CU (which also
 // needs <= 64 VGPRs: __launch_bounds__(1024, 8)).  Arrival order varies from run to run, so the
 // pairs of a part come out in varying order -- as a set they are exact, and the next step sorts.
+constexpr unsigned long long FIN_FREE = ~0ull;
+// (key: the x bits only -- the id bits above them differ between the records of a bucket)
 template <int CAP = FIN_CAP> __device__ static inline uint32_t fin_home(uint64_t key) {
   uint32_t h = (uint32_t)key * 0x9E3779B1u;
   h ^= h >> 15;
@@ -338,11 +375,12 @@ __device__ static inline void fin_emit(uint64_t *__restrict__ dst, uint32_t pos,
 // records joins the ones the big kernel works in blocks.
 template <int THREADS = FIN_THREADS, int CAP = FIN_CAP>
 __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finish_kernel(
-    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ids, int nparts, uint64_t ek, uint64_t *__restrict__ blk,
+    const uint64_t *__restrict__ keys, const uint16_t *__restrict__ tails, int nparts, int xbits, uint64_t *__restrict__ blk,
     uint32_t *__restrict__ overflow, uint64_t *__restrict__ out, uint64_t capacity, const uint32_t *__restrict__ counts,
     uint32_t cap, uint64_t *__restrict__ biglist, unsigned long long *__restrict__ nbig, uint32_t big_max,
     uint32_t big_base) {
   constexpr int IPT = CAP / THREADS;
+  constexpr uint64_t ek = FIN_FREE;
   static_assert(CAP % THREADS == 0 && CAP <= 65535, "image = whole records per thread, slots fit 16 bits");
   __shared__ unsigned long long gbase;
   __shared__ __attribute__((aligned(16))) unsigned long long tab[CAP];
@@ -359,18 +397,22 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
   }
   if (m == 0) return;
   const uint64_t *k = keys + first;
-  const uint32_t *id = ids + first;
+  const uint16_t *tl = tails + first;
   uint64_t kreg[IPT];
   uint32_t ireg[IPT];
 #pragma unroll
   for (int j = 0; j < IPT; ++j) {
     const uint32_t i = tid + j * THREADS;
     kreg[j] = i < m ? k[i] : ek;
-    ireg[j] = i < m ? id[i] : 0u;  // coalesced, in flight together with the keys
+    ireg[j] = i < m ? tl[i] : 0u;  // coalesced, in flight together with the words
   }
 #pragma unroll
   for (int j = 0; j < IPT; ++j) {
     const uint32_t i = tid + j * THREADS;
+    if (i < m) {
+      ireg[j] = rec_id(kreg[j], (uint16_t)ireg[j], xbits);
+      kreg[j] = rec_x(kreg[j], xbits);
+    }
     tab[i] = ek;
     cnt[i] = 0;
   }
@@ -421,8 +463,8 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
 }
 
 // The small-part finish with the arrival counters INSIDE the table words (round 4; partitions of 12 bits and more: 10 M
-// queries and up).  Inside a part all words share their top T >= 12 bits (the part number), so a slot needs only the
-// low 52 bits of the word to tell keys apart, and the 12 bits above hold the number of records that found it: a slot is
+// queries and up).  Inside a part the x bits of a word (64 - T <= 52 of them) tell keys apart, so a slot holds them
+// in its low 52 bits, and the 12 bits above hold the number of records that found it: a slot is
 // claimed with one CAS (0 -> key52 | 1 << 52: arrival number 0), joined with one returning 64-bit add of 1 << 52 (the old
 // count is the arrival number).  No counter array: the image is 32 KB instead of 48 -- FOUR workgroups per CU instead of
 // three (the kernel is a chain of barrier-separated phases; what hides one workgroup's latency is another workgroup).
@@ -431,12 +473,12 @@ __global__ __launch_bounds__(THREADS, THREADS >= 1024 ? 8 : 6) void bucket_finis
 // kernel like every part beyond the image.
 constexpr int FIN_PK_THREADS = 512, FIN_PK_CAP = 4096, FIN_PK_MAX = 4095;
 __global__ __launch_bounds__(FIN_PK_THREADS, 8) void bucket_finish_packed_kernel(
-    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ids, int nparts, uint64_t *__restrict__ blk,
+    const uint64_t *__restrict__ keys, const uint16_t *__restrict__ tails, int nparts, int xbits, uint64_t *__restrict__ blk,
     uint32_t *__restrict__ overflow, uint64_t *__restrict__ out, uint64_t capacity, const uint32_t *__restrict__ counts,
     uint32_t cap, uint64_t *__restrict__ biglist, unsigned long long *__restrict__ nbig, uint32_t big_max,
     uint32_t big_base) {
   constexpr int THREADS = FIN_PK_THREADS, CAP = FIN_PK_CAP, IPT = CAP / THREADS;
-  constexpr unsigned long long KMASK = (1ull << 52) - 1ull, ONE = 1ull << 52;
+  constexpr unsigned long long KMASK = (1ull << 52) - 1ull, ONE = 1ull << 52;  // (xbits <= 52: the host's rule)
   __shared__ unsigned long long gbase;
   __shared__ __attribute__((aligned(16))) unsigned long long tab[CAP];
   __shared__ uint32_t wsum[THREADS / WAVE];
@@ -451,14 +493,14 @@ __global__ __launch_bounds__(FIN_PK_THREADS, 8) void bucket_finish_packed_kernel
   if (m == 0) return;
   const size_t first = bslot * cap;
   const uint64_t *k = keys + first;
-  const uint32_t *id = ids + first;
+  const uint16_t *tl = tails + first;
   uint64_t kreg[IPT];
   uint32_t ireg[IPT];
 #pragma unroll
   for (int j = 0; j < IPT; ++j) {
     const uint32_t i = tid + j * THREADS;
     kreg[j] = i < m ? k[i] : 0ull;
-    ireg[j] = i < m ? id[i] : 0u;
+    ireg[j] = i < m ? tl[i] : 0u;
   }
 #pragma unroll
   for (int j = 0; j < IPT; ++j) tab[tid + j * THREADS] = 0ull;
@@ -469,8 +511,9 @@ __global__ __launch_bounds__(FIN_PK_THREADS, 8) void bucket_finish_packed_kernel
   for (int j = 0; j < IPT; ++j) {
     so[j] = 0xFFFFFFFFu;
     if (tid + j * THREADS < (int)m) {
-      const unsigned long long k52 = kreg[j] & KMASK;
-      uint32_t slot = fin_home<CAP>(kreg[j]);
+      const unsigned long long k52 = rec_x(kreg[j], xbits);
+      ireg[j] = rec_id(kreg[j], (uint16_t)ireg[j], xbits);  // (the tail was waiting there)
+      uint32_t slot = fin_home<CAP>(k52);
       uint32_t o;
       for (;;) {  // at most 4095 records for 4096 slots: a free one always turns up
         const unsigned long long old = atomicCAS(&tab[slot], 0ull, k52 | ONE);
@@ -504,7 +547,7 @@ __global__ __launch_bounds__(FIN_PK_THREADS, 8) void bucket_finish_packed_kernel
 
 // Parts the kernel above listed (more records than its LDS image): worked in BLOCKS of
 // FIN_CAP records by workgroups that walk the device-side list (fixed grid; nothing is read back to size the
-// launch).  Block bi is finished exactly like a small part (hash table on the full word, arrival numbers, bucket
+// launch).  Block bi is finished exactly like a small part (hash table on the word's x bits, arrival numbers, bucket
 // runs laid out in LDS -> its own pairs); then every EARLIER block's records are streamed past bi's table: a
 // record whose word is in the table pairs with every id of that bucket's run.  Together: every pair of equal words
 // of the part, once -- a key with any number of copies up to FIN_BIG_BLOCKS images is no special case any more.
@@ -529,10 +572,11 @@ struct BigDesc {
 // One workgroup per listed part: a part that spilled (fill mark set) gets m records of room at the pool's cursor and
 // its records -- the prefix its region holds and every run of the descriptor list that names it -- are copied there,
 // next to each other in any order (the finish does not care); a part that fits its region is described in place.
+// Region and pool records have the same form (word, tail): they are copied as they are.
 __global__ __launch_bounds__(256) void bucket_big_gather_kernel(const uint64_t *__restrict__ biglist,
                                                                 const unsigned long long *__restrict__ nbig, uint32_t big_max,
                                                                 BigDesc *__restrict__ desc, const uint64_t *__restrict__ part_keys,
-                                                                const uint32_t *__restrict__ part_ids,
+                                                                const uint16_t *__restrict__ part_ids,
                                                                 const uint32_t *__restrict__ counts, uint32_t cap, PartPool pool,
                                                                 uint32_t max_records, uint32_t *__restrict__ overflow) {
   __shared__ unsigned long long base_s;
@@ -601,8 +645,8 @@ __global__ __launch_bounds__(256) void bucket_big_gather_kernel(const uint64_t *
 }
 
 __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
-    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ids, const uint64_t *pool_keys, const uint32_t *pool_ids,
-    uint64_t ek, const BigDesc *__restrict__ desc, const unsigned long long *__restrict__ nbig, uint32_t big_max,
+    const uint64_t *__restrict__ keys, const uint16_t *__restrict__ ids, const uint64_t *pool_keys, const uint16_t *pool_ids,
+    int xbits, const BigDesc *__restrict__ desc, const unsigned long long *__restrict__ nbig, uint32_t big_max,
     uint64_t *__restrict__ blk, uint64_t *__restrict__ out, uint64_t capacity) {
   __shared__ unsigned long long gbase;
   __shared__ __attribute__((aligned(16))) unsigned long long tab[FIN_CAP];
@@ -612,6 +656,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
   __shared__ uint32_t wsum[FIN_THREADS / WAVE];
   __shared__ uint32_t lrun[FIN_CAP / (FIN_RANK_SORT + 1) + 1], nlrun;   // slots of the runs longer than FIN_RANK_SORT
   const int tid = threadIdx.x;
+  constexpr uint64_t ek = FIN_FREE;
   unsigned long long nb = *nbig;
   if (nb > big_max) nb = big_max;
   // work items: (listed part, block bi, block bj <= bi, slice sl) -- the table of bi is built, then an eighth of bi's
@@ -636,7 +681,7 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
     const BigDesc de = desc[e];
     const uint32_t m = de.m;
     const uint64_t *k = (de.pool ? pool_keys : keys) + de.where;
-    const uint32_t *id = (de.pool ? pool_ids : ids) + de.where;
+    const uint16_t *id = (de.pool ? pool_ids : ids) + de.where;
     const uint32_t nblk = (m + FIN_CAP - 1) / FIN_CAP;
     if (bi >= nblk) continue;  // uniform
     {
@@ -647,8 +692,13 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
 #pragma unroll
       for (int j = 0; j < FIN_IPT; ++j) {
         const uint32_t i = tid + j * FIN_THREADS;
-        kreg[j] = i < mb ? k[lo + i] : ek;
-        ireg[j] = i < mb ? id[lo + i] : 0u;
+        kreg[j] = ek;
+        ireg[j] = 0u;
+        if (i < mb) {
+          const uint64_t word = k[lo + i];
+          kreg[j] = rec_x(word, xbits);
+          ireg[j] = rec_id(word, id[lo + i], xbits);
+        }
         tab[i] = ek;
         cnt[i] = 0;
       }
@@ -772,8 +822,8 @@ __global__ __launch_bounds__(FIN_THREADS) void bucket_finish_big_kernel(
 #pragma unroll
         for (int j = 0; j < FIN_IPT; ++j) {
           const uint32_t i = tid + j * FIN_THREADS;
-          const uint64_t x = k[lo2 + i];
-          ireg[j] = id[lo2 + i];
+          const uint64_t word = k[lo2 + i], x = rec_x(word, xbits);
+          ireg[j] = rec_id(word, id[lo2 + i], xbits);
           uint32_t slot = fin_home(x), found = 0xFFFFFFFFu;
           const bool my_slice = (uint32_t)(tid & (FIN_BIG_SLICES - 1)) == sl;
           for (int step = 0; my_slice && step < FIN_CAP; ++step) {  // (bounded: a full table has no free slot to stop at)
@@ -820,38 +870,46 @@ QRLSH_EXPORT int64_t qrlsh_set_big_part_limit(int64_t records) {
   return old;
 }
 
-// workspace: [step-1 cursors: b << c1 u32 (two-step partitions only)][step-2 cursors = records per part: b << T u32]
-//            [big parts: one counter per band group, then their lists: b << T u64 in all][fill: b << T u32]
-//            [pool cursor, run count: 2 u64][runs: POOL_RUNS x 16 B][desc: 2 x FIN_BIG_LIST x 16 B]
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
+// Slabs of the first step of a two-step partition (narrow records, above): 2^(16+c1) consecutive queries each
 static int coarse_bits(int T);
+static int slab_bits(int T) { return 16 + coarse_bits(T); }
+static int n_slabs(int64_t nq, int T) { return T > 8 ? (int)((nq + (1ll << slab_bits(T)) - 1) >> slab_bits(T)) : 1; }
+
+// workspace: [fill: b << T u32]
+//            [step-1 cursors: b x slabs << c1 u32 (two-step partitions only)][step-2 cursors = records per part: b << T u32]
+//            [big parts: one counter per band group][pool cursor, run count: 2 u64][runs: POOL_RUNS x 16 B]
+//            [the big parts' lists: b << T u64 in all][desc: 2 x FIN_BIG_LIST x 16 B]
+// Every area starts on a multiple of 16 bytes.
+static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr int EMIT_MAX_GROUPS = 2;  // band groups of one qrlsh_bucket_pairs_emit call
 struct BucketWs {
-  uint32_t *cur1, *counts;  // (a one-step partition, T = 8, has one set of cursors: cur1 == counts)
-  uint64_t *big;
   uint32_t *fill;
-  unsigned long long *poolctl;
+  uint32_t *cur1, *counts;  // (a one-step partition, T = 8, has one set of cursors: cur1 == counts)
+  unsigned long long *nbig, *poolctl;
   uint4 *runs;
+  uint64_t *biglist;
   BigDesc *desc;
   size_t bytes;
 };
-static BucketWs bucket_ws(void *workspace, int32_t b, int32_t T) {
+static BucketWs bucket_ws(void *workspace, int64_t nq, int32_t b, int32_t T) {
   BucketWs w;
   const size_t slots = (size_t)b << T;
   char *p = static_cast<char *>(workspace);
   size_t off = 0;
-  w.cur1 = reinterpret_cast<uint32_t *>(p + off);
-  if (T > 8) off += align16(((size_t)b << coarse_bits(T)) * sizeof(uint32_t));
-  w.counts = reinterpret_cast<uint32_t *>(p + off);
-  off += align16(slots * sizeof(uint32_t));
-  w.big = reinterpret_cast<uint64_t *>(p + off);
-  off += slots * sizeof(uint64_t);
   w.fill = reinterpret_cast<uint32_t *>(p + off);
   off += align16(slots * sizeof(uint32_t));
+  w.cur1 = reinterpret_cast<uint32_t *>(p + off);
+  if (T > 8) off += align16((((size_t)b * n_slabs(nq, T)) << coarse_bits(T)) * sizeof(uint32_t));
+  w.counts = reinterpret_cast<uint32_t *>(p + off);
+  off += align16(slots * sizeof(uint32_t));
+  w.nbig = reinterpret_cast<unsigned long long *>(p + off);
+  off += align16(EMIT_MAX_GROUPS * sizeof(unsigned long long));
   w.poolctl = reinterpret_cast<unsigned long long *>(p + off);
   off += 16;
   w.runs = reinterpret_cast<uint4 *>(p + off);
   off += (size_t)POOL_RUNS * sizeof(uint4);
+  w.biglist = reinterpret_cast<uint64_t *>(p + off);
+  off += align16(slots * sizeof(uint64_t));
   w.desc = reinterpret_cast<BigDesc *>(p + off);
   off += (size_t)EMIT_MAX_GROUPS * FIN_BIG_LIST * sizeof(BigDesc);
   w.bytes = off;
@@ -860,7 +918,7 @@ static BucketWs bucket_ws(void *workspace, int32_t b, int32_t T) {
 
 QRLSH_EXPORT size_t qrlsh_bucket_workspace_bytes(int64_t nq, int32_t b, int32_t part_bits) {
   if (nq <= 0 || b <= 0 || part_bits < 8 || part_bits > 16) return 64;
-  return bucket_ws(nullptr, b, part_bits).bytes;
+  return bucket_ws(nullptr, nq, b, part_bits).bytes;
 }
 
 static int bucket_check(const char *name, const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids,
@@ -929,6 +987,7 @@ static size_t region_words(int64_t nq, int32_t b, int32_t part_bits) {
 }
 
 // words part_keys / part_ids (and, for part_bits > 8, tmp_keys / tmp_ids) must hold for qrlsh_bucket_pairs_emit
+// (the id buffers are sized in 32-bit words as before; the records' 16-bit tails use the first half of them)
 QRLSH_EXPORT size_t qrlsh_bucket_part_words(int64_t nq, int32_t b, int32_t part_bits) {
   if (nq <= 0 || b <= 0) return 0;
   const size_t plain = (size_t)b * nq;
@@ -939,7 +998,9 @@ QRLSH_EXPORT size_t qrlsh_bucket_tmp_words(int64_t nq, int32_t b, int32_t part_b
   if (nq <= 0 || b <= 0 || part_bits <= 8) return 0;
   const size_t plain = (size_t)b * nq;
   const int c1 = coarse_bits(part_bits);
-  const size_t regions = ((size_t)b << c1) * coarse_region(nq, c1);
+  const int64_t slab = 1ll << slab_bits(part_bits);
+  // a region of its own per (band, slab, coarse part), each with the room a whole slab asks for
+  const size_t regions = (((size_t)b * n_slabs(nq, part_bits)) << c1) * coarse_region(nq < slab ? nq : slab, c1);
   return regions > plain ? regions : plain;
 }
 
@@ -973,10 +1034,16 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
   if (rc != QRLSH_OK || nq == 0) return rc;
   QR_CHECK_ARG(pairs_out || capacity == 0, "qrlsh_bucket_pairs_emit: null output with capacity %llu",
                (unsigned long long)capacity);
+  uint32_t *ovf = reinterpret_cast<uint32_t *>(total_overflow_out + 1);
+  if (nq > (1ll << (16 + part_bits))) {  // ids beyond what a record of the last step carries: the general path
+    if (hipMemsetAsync(ovf, 1, 1, st) != hipSuccess) {
+      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
+      return QRLSH_EHIP;
+    }
+    return QRLSH_OK;
+  }
   const int nparts = 1 << part_bits;
-  const BucketWs w = bucket_ws(workspace, b, part_bits);
-  // the atomic partition hands the finish x = mix64(key): its free-slot marker is mix64(empty key)
-  const uint64_t ekx = qr_mix64(qr_empty_key(r));
+  const BucketWs w = bucket_ws(workspace, nq, b, part_bits);
 #define QR_PART_SCATTER(LEVEL2_, ...) QR_LAUNCH("part_scatter", (part_scatter_atomic_kernel<LEVEL2_>), __VA_ARGS__)
   // Partition(s) into fixed regions + the LDS finish.  The bands are independent of each other all the way to the
   // pair cursor, so they are worked in GROUPS that alternate between the caller's stream and an auxiliary one
@@ -988,22 +1055,20 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
   const int T = part_bits;
   const bool two = T > 8;
   const int c1 = two ? coarse_bits(T) : 8;
-  const uint32_t cap1 = two ? coarse_region(nq, c1) : part_region(nq), cap2 = two ? fine_region(nq, T) : cap1;
+  const int nslabs = n_slabs(nq, T), slab_shift = two ? slab_bits(T) : 63;
+  const int64_t slab_nq = two && nq > (1ll << slab_shift) ? 1ll << slab_shift : nq;
+  const uint32_t cap1 = two ? coarse_region(slab_nq, c1) : part_region(nq), cap2 = two ? fine_region(nq, T) : cap1;
   const uint32_t lowmask = (1u << (T - c1)) - 1u;
   // step-2 cursors end up as the parts' record counts, which the finish reads (one step: they are step 1's)
   uint32_t *cur1 = w.cur1, *cur2 = w.counts;
-  if (hipMemsetAsync(cur1, 0, ((size_t)b << c1) * sizeof(uint32_t), st) != hipSuccess ||
-      (two && hipMemsetAsync(cur2, 0, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess)) {
-    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
-  uint32_t *ovf = reinterpret_cast<uint32_t *>(total_overflow_out + 1);
+  // the records' 16-bit tails live in the id buffers
+  uint16_t *part_tails = reinterpret_cast<uint16_t *>(part_ids), *tmp_tails = reinterpret_cast<uint16_t *>(tmp_ids);
   // the overflow pool behind the regions of the part buffers (PartPool above); the step that fills the parts the
   // finish reads spills into it (the coarse step of a two-step partition does not: its regions have their own slack)
   const size_t reg_words = region_words(nq, b, T);
   PartPool pool;
   pool.keys = part_keys + reg_words;
-  pool.vals = part_ids + reg_words;
+  pool.vals = part_tails + reg_words;
   pool.cursor = w.poolctl;
   pool.nruns = w.poolctl + 1;
   pool.cap = (uint32_t)pool_records(nq, b);
@@ -1014,21 +1079,11 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
   PartPool no_pool = pool;
   no_pool.keys = nullptr;
   no_pool.vals = nullptr;
-  if (hipMemsetAsync(w.fill, 0xFF, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess ||
-      hipMemsetAsync(w.poolctl, 0, 16, st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
-  // lists of the parts that outgrow the LDS image (bucket_finish_big_kernel), one per band group:
-  // [2 counters][group 0's list][group 1's list]
+  // lists of the parts that outgrow the LDS image (bucket_finish_big_kernel), one counter and one list per band group
   constexpr int MAX_GROUPS = EMIT_MAX_GROUPS;
-  unsigned long long *nbig0 = reinterpret_cast<unsigned long long *>(w.big);
-  uint64_t *biglist0 = w.big + MAX_GROUPS;
+  unsigned long long *nbig0 = w.nbig;
+  uint64_t *biglist0 = w.biglist;
   const uint64_t slots = (uint64_t)b << T;  // >= 256 words in that area
-  if (hipMemsetAsync(nbig0, 0, MAX_GROUPS * sizeof(unsigned long long), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
   // small parts: the 512-thread / 4096-slot finish
   const bool small_parts = two && small_form(nq, T);
   const int ntiles = (int)ceil_div64(nq, PS_TILE);
@@ -1041,12 +1096,19 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
   const int ngroups = (b + per - 1) / per;
   const uint64_t list_room = (slots - MAX_GROUPS) / (uint64_t)ngroups;
   const uint32_t big_max = (uint32_t)(list_room < FIN_BIG_LIST ? list_room : FIN_BIG_LIST);
-  // With two or more groups, a group's gather (bucket_big_gather_kernel) scans the run descriptors while the next
-  // group's partition, on the other stream, counts new runs in before it writes their descriptors: a slot in
-  // between still holds what an earlier call left there, and one that names a part of this group would be counted
-  // twice (the overflow flag, and the step on the general path).  Cleared, such a slot reads {0, 0 records}: it
-  // matches at most slot 0 and adds nothing.
-  if (ngroups > 1 && hipMemsetAsync(w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st) != hipSuccess) {
+  // What the call counts in is cleared first: fill marks (0xFF), both steps' cursors, the big-part counters, the
+  // pool's cursor and run count -- and, with two or more groups, the run descriptors.  A group's gather
+  // (bucket_big_gather_kernel) scans the descriptors while the next group's partition, on the other stream, counts
+  // new runs in before it writes their descriptors: a slot in between still holds what an earlier call left there,
+  // and one that names a part of this group would be counted twice (the overflow flag, and the step on the general
+  // path).  Cleared, such a slot reads {0, 0 records}: it matches at most slot 0 and adds nothing.
+  // (One kernel that clears all of it in a single launch measured slower than these calls: DESIGN section 6, round 6.)
+  if (hipMemsetAsync(cur1, 0, (((size_t)b * nslabs) << c1) * sizeof(uint32_t), st) != hipSuccess ||
+      (two && hipMemsetAsync(cur2, 0, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess) ||
+      hipMemsetAsync(w.fill, 0xFF, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess ||
+      hipMemsetAsync(w.poolctl, 0, 16, st) != hipSuccess ||
+      hipMemsetAsync(nbig0, 0, MAX_GROUPS * sizeof(unsigned long long), st) != hipSuccess ||
+      (ngroups > 1 && hipMemsetAsync(w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st) != hipSuccess)) {
     qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
     return QRLSH_EHIP;
   }
@@ -1058,20 +1120,20 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
     uint64_t *biglist = biglist0 + (size_t)gi * big_max;
     unsigned long long *nbig = nbig0 + gi;
     uint64_t *k1 = two ? tmp_keys : part_keys;
-    uint32_t *v1 = two ? tmp_ids : part_ids;
+    uint16_t *v1 = two ? tmp_tails : part_tails;
     pool.slot_base = (uint32_t)((size_t)g0 << T);
     BigDesc *desc = w.desc + (size_t)gi * FIN_BIG_LIST;
+    const size_t in0 = ((size_t)g0 * nslabs) << c1;  // the group's first region / cursor of the first step
     QR_PART_SCATTER(false, dim3(ntiles, nb), dim3(SORT_THREADS), 0, s, keys + (size_t)g0 * band_words,
-                    (const uint32_t *)nullptr, k1 + ((size_t)g0 << c1) * cap1, v1 + ((size_t)g0 << c1) * cap1, nq,
-                    ntiles, 64 - c1, (1u << c1) - 1u, cur1 + ((size_t)g0 << c1), cap1, ovf, qr_empty_key(r),
-                    (const uint32_t *)nullptr, 0u, key_chunk, key_chunk_stride, key_band_stride, two ? no_pool : pool);
+                    (const uint16_t *)nullptr, k1 + in0 * cap1, v1 + in0 * cap1, nq, ntiles, 64 - c1, (1u << c1) - 1u,
+                    cur1 + in0, cap1, ovf, qr_empty_key(r), (const uint32_t *)nullptr, 0u, key_chunk, key_chunk_stride,
+                    key_band_stride, c1, nslabs, slab_shift, two ? no_pool : pool);
     if (two)
-      QR_PART_SCATTER(true, dim3((unsigned)ceil_div64(cap1, PS_TILE), nb << c1), dim3(SORT_THREADS), 0, s,
-                      (const uint64_t *)tmp_keys + ((size_t)g0 << c1) * cap1,
-                      (const uint32_t *)tmp_ids + ((size_t)g0 << c1) * cap1, part_keys + ((size_t)g0 << T) * cap2,
-                      part_ids + ((size_t)g0 << T) * cap2, (int64_t)0, 0, 64 - T, lowmask, cur2 + ((size_t)g0 << T),
-                      cap2, ovf, qr_empty_key(r), (const uint32_t *)cur1 + ((size_t)g0 << c1), cap1, (int64_t)0,
-                      (int64_t)0, (int64_t)0, pool);
+      QR_PART_SCATTER(true, dim3((unsigned)ceil_div64(cap1, PS_TILE), (nb * nslabs) << c1), dim3(SORT_THREADS), 0, s,
+                      (const uint64_t *)tmp_keys + in0 * cap1, (const uint16_t *)tmp_tails + in0 * cap1,
+                      part_keys + ((size_t)g0 << T) * cap2, part_tails + ((size_t)g0 << T) * cap2, (int64_t)0, 0, 64 - T,
+                      lowmask, cur2 + ((size_t)g0 << T), cap2, ovf, qr_empty_key(r), (const uint32_t *)cur1 + in0, cap1,
+                      (int64_t)0, (int64_t)0, (int64_t)0, c1, nslabs, slab_shift, pool);
     // the auxiliary stream is forked once the first group's partition is queued and before its finish is: the
     // second group's partition then starts beside the first group's finish, and the two streams stay half a
     // group out of step
@@ -1079,25 +1141,26 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
     // the group's parts: regions, record counts (step 2's cursors) and first slot
     const uint32_t slot0 = (uint32_t)((size_t)g0 << T);
     const uint64_t *gkeys = part_keys + (size_t)slot0 * cap2;
-    const uint32_t *gids = part_ids + (size_t)slot0 * cap2, *gcounts = cur2 + slot0;
+    const uint16_t *gids = part_tails + (size_t)slot0 * cap2;
+    const uint32_t *gcounts = cur2 + slot0;
     if (small_parts && T >= 12)
       QR_LAUNCH("bucket_emit", bucket_finish_packed_kernel, dim3(nparts, nb), dim3(FIN_PK_THREADS), 0, s, gkeys, gids, nparts,
-                total_overflow_out, ovf, pairs_out, capacity, gcounts, cap2, biglist, nbig, big_max, slot0);
+                64 - T, total_overflow_out, ovf, pairs_out, capacity, gcounts, cap2, biglist, nbig, big_max, slot0);
     else if (small_parts)
       QR_LAUNCH("bucket_emit", (bucket_finish_kernel<FIN_SMALL_THREADS, FIN_SMALL_CAP>), dim3(nparts, nb),
-                dim3(FIN_SMALL_THREADS), 0, s, gkeys, gids, nparts, ekx, total_overflow_out, ovf, pairs_out, capacity, gcounts,
+                dim3(FIN_SMALL_THREADS), 0, s, gkeys, gids, nparts, 64 - T, total_overflow_out, ovf, pairs_out, capacity, gcounts,
                 cap2, biglist, nbig, big_max, slot0);
     else
-      QR_LAUNCH("bucket_emit", (bucket_finish_kernel<>), dim3(nparts, nb), dim3(FIN_THREADS), 0, s, gkeys, gids, nparts, ekx,
+      QR_LAUNCH("bucket_emit", (bucket_finish_kernel<>), dim3(nparts, nb), dim3(FIN_THREADS), 0, s, gkeys, gids, nparts, 64 - T,
                 total_overflow_out, ovf, pairs_out, capacity, gcounts, cap2, biglist, nbig, big_max, slot0);
     // the parts of this group the finish listed as larger than its LDS image (usually none: the kernel then finds
     // an empty list), on the group's own stream: they are worked beside the next group
     QR_LAUNCH("bucket_emit_big", bucket_big_gather_kernel, dim3(64), dim3(256), 0, s, (const uint64_t *)biglist,
-              (const unsigned long long *)nbig, big_max, desc, (const uint64_t *)part_keys, (const uint32_t *)part_ids,
+              (const unsigned long long *)nbig, big_max, desc, (const uint64_t *)part_keys, (const uint16_t *)part_tails,
               (const uint32_t *)cur2, cap2, pool, g_big_limit, ovf);
     QR_LAUNCH("bucket_emit_big", bucket_finish_big_kernel, dim3(FIN_BIG_GRID), dim3(FIN_THREADS), 0, s,
-              (const uint64_t *)part_keys, (const uint32_t *)part_ids, (const uint64_t *)pool.keys,
-              (const uint32_t *)pool.vals, ekx, (const BigDesc *)desc, (const unsigned long long *)nbig, big_max,
+              (const uint64_t *)part_keys, (const uint16_t *)part_tails, (const uint64_t *)pool.keys,
+              (const uint16_t *)pool.vals, 64 - T, (const BigDesc *)desc, (const unsigned long long *)nbig, big_max,
               total_overflow_out, pairs_out, capacity);
   }
   if (aux && qr_aux_join(st) != QRLSH_OK) return QRLSH_EHIP;
