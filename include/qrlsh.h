@@ -515,6 +515,52 @@ int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, const uint32_t
                        uint64_t *new_keys, int64_t m, uint64_t *keys_out, uint32_t *ids_out, uint32_t *dir_out,
                        void *workspace, size_t workspace_bytes, void *stream);
 #define QRLSH_INDEX_MAX_K 256
+/*   finish for probe rows that ARE indexed: qrlsh_index_probe_finish with one more argument, first_id: probe row q is
+ *     indexed query first_id + q (0 <= first_id, first_id + m <= n; probe_sig = rows first_id .. of sig, or a copy).  A
+ *     raw word that names the query itself is dropped like a duplicate -- select key ~0, not counted in avail_out --
+ *     so a query is never in its own list; everything else is the plain finish (rows with identical signatures and
+ *     different ids stay each other's neighbours, at 1000).  Probed against the index they are in, this gives the
+ *     lists of a range of indexed queries: new queries of one appended batch do see each other. */
+int qrlsh_index_probe_finish_indexed(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                                     const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
+                                     int64_t first_id, const void *probe_workspace, const uint64_t *raw, int64_t n_raw,
+                                     int32_t K, int64_t *off_out, int32_t *idx_out, int32_t *milli_out,
+                                     int32_t *avail_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- keeping the top-K lists current when queries are appended (csrc/lists.hip) ---------------------------------
+ * Input: the lists of a run over queries 0 .. n-1 with list length K -- COO src / dst / val int32 [n_edges] as
+ * qrlsh_topk_*_fill writes them: ordered by src, then value descending, then dst ascending, at most K per src, queries
+ * without candidates absent -- and a batch of m queries n .. n+m-1 that was appended to the index (qrlsh_index_append)
+ * and then probed against the GROWN index: raw [n_raw] from qrlsh_index_probe_fill, select_keys [n_raw] = the first
+ * n_raw words qrlsh_index_probe_finish_indexed (first_id = n, the same K) leaves in its workspace, new_off [m + 1] /
+ * new_idx / new_milli its lists.  Output: src_out / dst_out / val_out, element for element the lists of a run over all
+ * n + m queries with the same K and b:
+ *   old row i < n:  the first K of the merge (value descending, then id ascending) of its stored row and its new
+ *     neighbours (milli, n + x) for every kept raw word of probe query x that names i; a new id is larger than every
+ *     old id and loses ties; a row that did not exist may appear;
+ *   new row n + x:  the finish's list of x.
+ * K is held fixed: a stored row was cut at K and cannot be regrown, so the result is that of a run with the SAME K over
+ * the n + m queries, not with the K a fresh run would default to.  Splitting a batch into successive appends-with-update
+ * gives the same lists; n = 0 (from empty lists), m > n and m = 0 (the stored lists, unchanged) are served.
+ * count: the reverse records (one per kept raw word with id < n: id << 11 | (1000 - milli), payload x) are sorted with
+ *   qrlsh_sort_u64 over bits [0, 11 + bits(n)), rows get their stored and reverse extents, a scan their output offsets;
+ *   *total_out (device uint64; the one read-back) = the number of output entries -- or ~0 when the stored lists break
+ *   the contract in a way the kernels see (src not ascending, src or dst outside [0, n)); nothing may be filled then.
+ * fill: follows a count on the same workspace and arguments; writes exactly `total` entries.  Every stored entry and
+ *   every record ranks itself (place in its own sequence + a binary search in the other); no row is walked serially.
+ * No allocation, one stream.  Limits: 1 <= K <= QRLSH_INDEX_MAX_K, n + m < 2^31, n_edges < 2^31, n_raw < 2^32,
+ * m * b < 2^32 per call (QRLSH_EINVAL otherwise).  workspace: qrlsh_lists_update_workspace_bytes(n, m, n_edges, n_raw)
+ * (two record + payload buffers of n_raw, 24 bytes per row, the sort's workspace). */
+size_t qrlsh_lists_update_workspace_bytes(int64_t n, int64_t m, int64_t n_edges, int64_t n_raw);
+int qrlsh_lists_update_count(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                             int64_t m, int32_t b, int32_t K, const uint64_t *raw, const uint64_t *select_keys,
+                             int64_t n_raw, const int64_t *new_off, void *workspace, size_t workspace_bytes,
+                             uint64_t *total_out, void *stream);
+int qrlsh_lists_update_fill(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                            int64_t m, int32_t b, int32_t K, int64_t n_raw, const int64_t *new_off,
+                            const int32_t *new_idx, const int32_t *new_milli, const void *workspace,
+                            size_t workspace_bytes, int64_t total, int32_t *src_out, int32_t *dst_out, int32_t *val_out,
+                            void *stream);
 
 /* ---- recommendations: top-k unrated queries per user (the consumer of N1's output) ---------------------
  * Replaces the selection of the interactive prompt, recommender.py:357-375 (just_scored of :361, the argsort of

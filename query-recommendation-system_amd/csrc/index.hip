@@ -249,13 +249,14 @@ __device__ static inline int64_t ix_val(int32_t v) { return v; }
 __device__ static inline int64_t ix_val(uint16_t v) { return v == 0xFFFFu ? -1 : (int64_t)v; }
 
 // one lane per raw word g << 32 | id: key (1000 - milli) << 32 | id if band g % b is the first band the two rows
-// share, else ~0 (a duplicate, or a key collision)
+// share, else ~0 (a duplicate, or a key collision).  first_id >= 0: probe row q IS indexed query first_id + q, and the
+// word that names it (the query finding itself) is dropped like a duplicate; first_id < 0: the probe rows are strangers
 template <typename SigT>
 __global__ __launch_bounds__(256) void index_score_kernel(const SigT *__restrict__ sig, const int64_t *__restrict__ norm2,
                                                           int64_t n, const SigT *__restrict__ psig,
                                                           const int64_t *__restrict__ pnorm2, int P, int b, int64_t m,
                                                           const uint64_t *__restrict__ raw, int64_t n_raw,
-                                                          uint64_t *__restrict__ keys_out) {
+                                                          int64_t first_id, uint64_t *__restrict__ keys_out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_raw) return;
   const uint64_t w = raw[i];
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(256) void index_score_kernel(const SigT *__restrict
   const int64_t g = (int64_t)(w >> 32);
   const int64_t q = g / b;
   const int t = (int)(g - q * b);
-  if ((int64_t)id >= n || q >= m) {  // not a word the fill pass writes
+  if ((int64_t)id >= n || q >= m || (first_id >= 0 && (int64_t)id == first_id + q)) {  // not a word the fill pass writes, or q itself
     keys_out[i] = ~0ull;
     return;
   }
@@ -416,11 +417,10 @@ QRLSH_EXPORT size_t qrlsh_index_finish_workspace_bytes(int64_t m, int32_t K, int
   return ix_al16((size_t)n_raw * 8) + 2 * ix_al16((size_t)m * K * 4) + (size_t)(ceil_div64(m, SCANL_CHUNK) + 1) * 8;
 }
 
-QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
-                                          const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
-                                          const void *probe_workspace, const uint64_t *raw, int64_t n_raw, int32_t K,
-                                          int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
-                                          void *workspace, size_t workspace_bytes, void *stream) {
+static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig, const int64_t *probe_norm2,
+                     int32_t sig_dtype, int32_t P, int32_t b, int64_t m, const void *probe_workspace, const uint64_t *raw,
+                     int64_t n_raw, int32_t K, int64_t first_id, int64_t *off_out, int32_t *idx_out, int32_t *milli_out,
+                     int32_t *avail_out, void *workspace, size_t workspace_bytes, void *stream) {
   QR_CHECK_ARG(K >= 1 && K <= IX_MAXK, "qrlsh_index_probe_finish: K=%d not in [1, %d]", K, IX_MAXK);
   QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && m >= 0 && n_raw >= 0 && P > 0 && b > 0 && b <= 65535 && P % b == 0,
                "qrlsh_index_probe_finish: bad sizes n=%lld m=%lld n_raw=%lld P=%d b=%d", (long long)n, (long long)m,
@@ -453,10 +453,10 @@ QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2,
     const dim3 grid((unsigned)ceil_div64(n_raw, 256)), block(256);
     if (sig_dtype == QRLSH_SIG_U16)
       QR_LAUNCH("index_score", index_score_kernel<uint16_t>, grid, block, 0, st, static_cast<const uint16_t *>(sig), norm2, n,
-                static_cast<const uint16_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, keys);
+                static_cast<const uint16_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, first_id, keys);
     else
       QR_LAUNCH("index_score", index_score_kernel<int32_t>, grid, block, 0, st, static_cast<const int32_t *>(sig), norm2, n,
-                static_cast<const int32_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, keys);
+                static_cast<const int32_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, first_id, keys);
   }
   uint64_t *cut = reinterpret_cast<uint64_t *>(off_out);
   QR_LAUNCH("index_select", index_select_kernel, dim3((unsigned)m), dim3(256), 0, st, (const uint64_t *)keys,
@@ -466,6 +466,30 @@ QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2,
             (const int32_t *)pidx, (const int32_t *)pmilli, m, K, (const int64_t *)off_out, idx_out, milli_out);
   QR_LAUNCH_CHECK("qrlsh_index_probe_finish");
   return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                                          const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
+                                          const void *probe_workspace, const uint64_t *raw, int64_t n_raw, int32_t K,
+                                          int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
+                                          void *workspace, size_t workspace_bytes, void *stream) {
+  return ix_finish(sig, norm2, n, probe_sig, probe_norm2, sig_dtype, P, b, m, probe_workspace, raw, n_raw, K, -1, off_out,
+                   idx_out, milli_out, avail_out, workspace, workspace_bytes, stream);
+}
+
+// the finish for probe rows that are in the index themselves: row q is indexed query first_id + q and is kept out of
+// its own list
+QRLSH_EXPORT int qrlsh_index_probe_finish_indexed(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                                                  const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b,
+                                                  int64_t m, int64_t first_id, const void *probe_workspace,
+                                                  const uint64_t *raw, int64_t n_raw, int32_t K, int64_t *off_out,
+                                                  int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
+                                                  void *workspace, size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(first_id >= 0 && m >= 0 && first_id + m <= n,
+               "qrlsh_index_probe_finish_indexed: rows %lld .. %lld are not among the %lld indexed queries",
+               (long long)first_id, (long long)(first_id + m), (long long)n);
+  return ix_finish(sig, norm2, n, probe_sig, probe_norm2, sig_dtype, P, b, m, probe_workspace, raw, n_raw, K, first_id,
+                   off_out, idx_out, milli_out, avail_out, workspace, workspace_bytes, stream);
 }
 
 // ---- append: new queries enter a built index ----------------------------------------------------------------------

@@ -763,6 +763,11 @@ __device__ static inline bool region_finish(const W *__restrict__ in, int64_t s0
         row = (uint32_t)(x[k] >> 32) & gmask;
         v = row << jbits | ((uint32_t)x[k] & jmask);
       }
+      // Not a value of this region: a slot of a fixed region that was never written.  After a capacity overflow of
+      // qrlsh_pair_regions_scatter the tiles that did not fit skip their runs, and what the buffer held before is read
+      // here before the host sees the flag.  A row beyond 2^gbits would index past rowcnt / rowstart and send the
+      // placement below to an arbitrary address; the empty marker would be counted without taking a slot.
+      if (row > gmask || v == RD_EMPTY) continue;
       uint32_t slot = (v * 0x9E3779B1u) >> (32 - TAB_LOG2);
       // the set never takes more than SEG values (SEG < TAB: a free slot always turns up); once it would, the
       // region is given up and the remaining words are skipped

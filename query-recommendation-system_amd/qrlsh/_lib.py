@@ -117,6 +117,13 @@ SIGNATURES = {
     "qrlsh_index_finish_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "qrlsh_index_probe_finish": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _i64, _i32,
                                                 _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_index_probe_finish_indexed": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _i64,
+                                                        _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_lists_update_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "qrlsh_lists_update_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _sz,
+                                                _vp, _vp]),
+    "qrlsh_lists_update_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _sz,
+                                               _i64, _vp, _vp, _vp, _vp]),
     "qrlsh_recommend_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "qrlsh_recommend_topk": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                             _vp]),

@@ -12,7 +12,9 @@ sorted per band with a directory -- and answers, for a batch of new queries:
 
 New queries enter the index with append / add (qrlsh_index_append: the batch is sorted and merged into the sorted
 band keys, byte for byte what a fresh build of all n + m rows gives, without sorting the n indexed records again);
-afterwards they are indexed queries like the others, with the ids n .. n + m - 1.
+afterwards they are indexed queries like the others, with the ids n .. n + m - 1.  An index that holds the run's
+top-K lists (lists=...) keeps them current on the way (update_lists=True, csrc/lists.hip): after the append the batch
+is probed against the grown index and every list, old and new, becomes what a run over all rows with the same K gives.
 
 Everything runs on the device; the indexed data never leaves it."""
 import numpy as np
@@ -37,13 +39,17 @@ class QueryIndex:
     norm2: int64 [n] (None: computed); b: bands (P % b == 0); table: the ops.PermTable the rows were drawn with
     (needed only by .signatures); keys: int64 [b, n] band keys (default: qrlsh_band_keys of sig; caller keys only
     filter -- every candidate is checked against the rows); K: default list length (round(log_1.5 n); a defaulted K
-    follows n when queries are appended, a given K stays).
+    follows n when queries are appended, a given K stays); lists: the run's top-K lists (src, dst, val) int32 COO as
+    pipeline.query_similarities returns them (by src, value descending, dst ascending), held in .lists by reference --
+    never written: an update puts new tensors there.  Their list length is the K of the constructor and stays that:
+    stored rows were cut at it and cannot be regrown, so appends with update_lists=True keep .lists equal to a run over
+    all rows WITH THAT K, not with the K a fresh run of the grown set would default to.
 
     .sig and .norm2 are contiguous views of the first n rows of capacity buffers: append copies the m new rows behind
     them and the buffers grow geometrically (reserve pre-sizes them).  The tensors given to the constructor are never
     written: the first append or reserve moves the rows into a buffer of the index's own."""
 
-    def __init__(self, sig, norm2, b, table=None, keys=None, K=None):
+    def __init__(self, sig, norm2, b, table=None, keys=None, K=None, lists=None):
         if not isinstance(sig, torch.Tensor) or sig.dtype not in (torch.int32, torch.int16) or sig.dim() != 2:
             raise TypeError("sig must be a 2-D int32 or int16 (compact) tensor")
         ops._need(sig, sig.dtype, "sig", 2)
@@ -73,15 +79,35 @@ class QueryIndex:
         self._sig_buf, self._norm2_buf = self.sig, self.norm2      # capacity buffers; .sig / .norm2 = their first n rows
         keys = ops.band_keys(ops.sig_to_int32(sig), b) if keys is None else keys.clone()
         self.keys, self.ids, self.dir = ops.index_build(keys)
+        self.lists, self.lists_K = None, None
+        if lists is not None:
+            self.lists, self.lists_K = self._check_lists(lists), self.K
+
+    def _check_lists(self, lists):
+        if not isinstance(lists, (tuple, list)) or len(lists) != 3:
+            raise ValueError("lists must be the (src, dst, val) of a run")
+        for t, name in zip(lists, ("src", "dst", "val")):
+            ops._need(t, torch.int32, "lists " + name, 1)
+            if t.device != self.sig.device or t.numel() != lists[0].numel():
+                raise ValueError("the lists must be three int32 tensors of one length on the rows' device")
+        src, dst, _ = lists
+        if src.numel():
+            ok = bool(((src[1:] >= src[:-1]).all() & (src[0] >= 0) & (src[-1] < self.n) & (dst.min() >= 0)
+                       & (dst.max() < self.n)).item())
+            if not ok:
+                raise ValueError("the lists must be ordered by src and name queries in [0, %d)" % self.n)
+        return tuple(lists)
 
     @staticmethod
     def _K_rule(n):
         return min(max(max_candidates(n) if n > 1 else 1, 1), MAX_K)
 
     @classmethod
-    def from_result(cls, res, table):
-        """the index of a finished run: pipeline.query_similarities' HotPathResult and the table it was drawn with"""
-        return cls(res.sig, res.norm2, res.b, table=table, K=res.K if res.K else None)
+    def from_result(cls, res, table, lists=False):
+        """the index of a finished run: pipeline.query_similarities' HotPathResult and the table it was drawn with;
+        lists=True: with the run's top-K lists in .lists (references to res.src / dst / val), list length res.K"""
+        return cls(res.sig, res.norm2, res.b, table=table, K=res.K if res.K else None,
+                   lists=(res.src, res.dst, res.val) if lists else None)
 
     # ---- new queries -----------------------------------------------------------------------------------------------
     def signatures(self, offsets, rows):
@@ -129,20 +155,36 @@ class QueryIndex:
         self._sig_buf, self._norm2_buf = sig_buf, norm2_buf
         self.sig, self.norm2 = sig_buf[:self.n], norm2_buf[:self.n]
 
-    def append(self, sig, norm2=None, keys=None):
+    def append(self, sig, norm2=None, keys=None, update_lists=False):
         """index m more queries: sig as in neighbours() (int32 or compact int16 rows, converted to the index's format);
         norm2 / keys [b, m]: theirs, or None (computed; caller keys only filter, as in the constructor).
         -> (first_id, m): the new queries are the indexed queries first_id .. first_id + m - 1.  Afterwards .n, .sig,
         .norm2, .keys, .ids and .dir describe the grown index -- the arrays a fresh QueryIndex over all rows holds --
-        and a defaulted K is round(log_1.5 n) of the new n."""
+        and a defaulted K is round(log_1.5 n) of the new n.
+        update_lists=True (an index that holds lists; ValueError otherwise): the batch is then probed against the grown
+        index (every new query kept out of its own list) and .lists is replaced by the lists of all n + m queries at
+        the lists' own K (.lists_K, the run's -- not a defaulted K that follows n); any split of a batch into
+        successive appends gives the same lists.  update_lists=False: held lists would go stale, so .lists becomes None
+        (and a later update_lists=True raises)."""
+        if update_lists and self.lists is None:
+            raise ValueError("this index holds no lists to update (none were given, or an append without "
+                             "update_lists=True dropped them)")
         given = keys is not None
         sig, norm2, keys = self._probe_rows(sig, norm2, keys)
         n, m = self.n, sig.shape[0]
         if n + m >= 2**32 - 1:
             raise ValueError("at most 2^32 - 2 indexed queries")
+        if update_lists and n + m >= 2**31:
+            raise ValueError("lists are kept for fewer than 2^31 queries")
         if m == 0:
             return n, 0
-        grown = ops.index_append(self.keys, self.ids, self.dir, keys.clone() if given else keys)
+        step = max(1, (2**32 - 1) // self.b)      # the probe of an update takes m * b < 2^32 words per call
+        if update_lists and m > step:
+            for q0 in range(0, m, step):
+                q1 = min(m, q0 + step)
+                self.append(sig[q0:q1], norm2[q0:q1].contiguous(), keys[:, q0:q1].contiguous(), update_lists=True)
+            return n, m
+        grown = ops.index_append(self.keys, self.ids, self.dir, keys.clone() if given or update_lists else keys)
         if n + m > self._sig_buf.shape[0]:
             self.reserve(max(n + m, 2 * self._sig_buf.shape[0]))
         self._sig_buf[n:n + m].copy_(sig)
@@ -152,11 +194,40 @@ class QueryIndex:
         self.sig, self.norm2 = self._sig_buf[:self.n], self._norm2_buf[:self.n]
         if self._default_K:
             self.K = self._K_rule(self.n)
+        if update_lists:
+            K = self.lists_K
+            raw, pws = ops.index_probe(self.keys, self.ids, self.dir, self.r, keys)
+            off, idx, milli, _, skeys = ops.index_finish(self.sig, self.norm2, sig, norm2, self.b, pws, raw, K, first_id=n)
+            self.lists = ops.lists_update(*self.lists, n, m, self.b, K, raw, skeys, off, idx, milli)
+        else:
+            self.lists = None
         return n, m
 
-    def add(self, offsets, rows):
+    def add(self, offsets, rows, update_lists=False):
         """signatures() of CSR answer sets, then append(): -> (first_id, m)"""
-        return self.append(*self.signatures(offsets, rows))
+        return self.append(*self.signatures(offsets, rows), update_lists=update_lists)
+
+    def neighbours_of(self, first_id, m, K=None, keys=None):
+        """the lists of the indexed queries first_id .. first_id + m - 1 recomputed from the index: each query's K best
+        among ALL other indexed queries (itself excluded; rows with the same signature and another id stay in, at
+        1000).  keys [b, m]: the band keys these queries were indexed under when they were the caller's (default:
+        computed from the rows, as the constructor does).  -> (off, idx, milli, avail) as neighbours()."""
+        K = self.K if K is None else _int_arg(K, "K", 1, MAX_K)
+        first_id = _int_arg(first_id, "first_id", 0, max(self.n, 0))
+        m = _int_arg(m, "m", 0, self.n - first_id)
+        dev = self.sig.device
+        if m == 0:
+            z = torch.zeros((1,), dtype=torch.int64, device=dev)
+            e = torch.empty((0,), dtype=torch.int32, device=dev)
+            return z, e, e.clone(), e.clone()
+        if m * self.b >= 2**32:
+            raise ValueError("at most %d queries per call" % ((2**32 - 1) // self.b))
+        sig, norm2, keys = self._probe_rows(self.sig[first_id:first_id + m], self.norm2[first_id:first_id + m].contiguous(),
+                                            keys)
+        raw, pws = ops.index_probe(self.keys, self.ids, self.dir, self.r, keys)
+        off, idx, milli, avail, _ = ops.index_finish(self.sig, self.norm2, sig, norm2, self.b, pws, raw, K,
+                                                     first_id=first_id)
+        return off, idx, milli, avail
 
     def _run(self, sig, norm2, keys, K):
         raw, pws = ops.index_probe(self.keys, self.ids, self.dir, self.r, keys)

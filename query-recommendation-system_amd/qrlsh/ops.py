@@ -993,9 +993,11 @@ def index_probe(sorted_keys, ids, dirw, r, probe_keys):
     return raw[:n_raw], ws
 
 
-def index_finish(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K):
+def index_finish(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K, first_id=None):
     """-> (off int64 [m + 1], idx int32, milli int32, avail int32 [m], keys int64 [n_raw]): the CSR neighbour lists
-    and, per raw word, its select key ((1000 - milli) << 32 | id, or -1 for a dropped word)"""
+    and, per raw word, its select key ((1000 - milli) << 32 | id, or -1 for a dropped word).  first_id: probe row q IS
+    indexed query first_id + q and stays out of its own list (qrlsh_index_probe_finish_indexed); None: the probe rows
+    are strangers to the index."""
     lib = _lib.load()
     n, P = sig.shape
     m = probe_sig.shape[0]
@@ -1007,11 +1009,65 @@ def index_finish(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K):
     idx = torch.empty((max(m * K, 1),), dtype=torch.int32, device=dev)
     milli = torch.empty((max(m * K, 1),), dtype=torch.int32, device=dev)
     avail = torch.empty((m,), dtype=torch.int32, device=dev)
-    _lib.check(lib.qrlsh_index_probe_finish(_ptr(sig), _ptr(norm2), n, _ptr(probe_sig), _ptr(probe_norm2), code, P, b,
-                                            m, _ptr(probe_ws), _ptr(raw), n_raw, K, _ptr(off), _ptr(idx), _ptr(milli),
-                                            _ptr(avail), _ptr(ws), ws.numel(), _stream()))
+    if first_id is None:
+        _lib.check(lib.qrlsh_index_probe_finish(_ptr(sig), _ptr(norm2), n, _ptr(probe_sig), _ptr(probe_norm2), code, P,
+                                                b, m, _ptr(probe_ws), _ptr(raw), n_raw, K, _ptr(off), _ptr(idx),
+                                                _ptr(milli), _ptr(avail), _ptr(ws), ws.numel(), _stream()))
+    else:
+        if isinstance(first_id, bool) or not isinstance(first_id, (int, np.integer)) or not 0 <= first_id <= n - m:
+            raise ValueError("rows %r .. are not among the %d indexed queries" % (first_id, n))
+        _lib.check(lib.qrlsh_index_probe_finish_indexed(_ptr(sig), _ptr(norm2), n, _ptr(probe_sig), _ptr(probe_norm2),
+                                                        code, P, b, m, int(first_id), _ptr(probe_ws), _ptr(raw), n_raw,
+                                                        K, _ptr(off), _ptr(idx), _ptr(milli), _ptr(avail), _ptr(ws),
+                                                        ws.numel(), _stream()))
     cnt = int(off[m].item()) if m else 0
     return off, idx[:cnt], milli[:cnt], avail, ws[:n_raw * 8].view(torch.int64)
+
+
+def lists_update(src, dst, val, n, m, b, K, raw, select_keys, new_off, new_idx, new_milli):
+    """The top-K lists (src, dst, val int32 COO: by src, value descending, dst ascending, at most K per src) of a run
+    over queries 0 .. n-1, brought up to date with m appended queries n .. n+m-1 (csrc/lists.hip).  raw: index_probe's
+    words of the batch probed against the GROWN index; select_keys, new_off, new_idx, new_milli: index_finish's keys
+    and lists of that probe with first_id = n and the same K.  -> (src, dst, val): new tensors, element for element the
+    lists of a run over all n + m queries with the same K; the arguments are not written.  Raises ValueError for
+    K > 256, and for stored lists whose src is not ascending or whose ids lie outside [0, n)."""
+    lib = _lib.load()
+    for t, name in ((src, "src"), (dst, "dst"), (val, "val"), (new_idx, "new_idx"), (new_milli, "new_milli")):
+        _need(t, torch.int32, name, 1)
+    for t, name in ((raw, "raw"), (select_keys, "select_keys"), (new_off, "new_off")):
+        _need(t, torch.int64, name, 1)
+    dev = src.device
+    for t in (dst, val, raw, select_keys, new_off, new_idx, new_milli):
+        if t.device != dev:
+            raise ValueError("every tensor of a list update must live on the lists' device")
+    for v, name in ((n, "n"), (m, "m"), (b, "b"), (K, "K")):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < 0:
+            raise ValueError("%s must be a non-negative integer, got %r" % (name, v))
+    n, m, b, K = int(n), int(m), int(b), int(K)
+    if not 1 <= K <= _lib.INDEX_MAX_K:
+        raise ValueError("K must lie in 1..%d, got %d" % (_lib.INDEX_MAX_K, K))
+    n_edges, n_raw = src.numel(), raw.numel()
+    if dst.numel() != n_edges or val.numel() != n_edges:
+        raise ValueError("src, dst and val must have one length")
+    if select_keys.numel() != n_raw or new_off.numel() != m + 1 or new_idx.numel() != new_milli.numel():
+        raise ValueError("select_keys must match raw, new_off hold m + 1 offsets, new_idx match new_milli")
+    if b < 1 or n + m >= 2**31 or n_edges >= 2**31 or m * b >= 2**32:
+        raise ValueError("a list update needs n + m < 2^31, fewer than 2^31 stored entries and m * b < 2^32")
+    if m == 0:
+        return src, dst, val
+    ws = _ws(lib.qrlsh_lists_update_workspace_bytes(n, m, n_edges, n_raw), dev)
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_lists_update_count(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, b, K, _ptr(raw),
+                                            _ptr(select_keys), n_raw, _ptr(new_off), _ptr(ws), ws.numel(), _ptr(total),
+                                            _stream()))
+    cnt = int(total.item())
+    if cnt < 0:     # ~0: the count saw stored lists that break the contract
+        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
+    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
+    _lib.check(lib.qrlsh_lists_update_fill(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, b, K, n_raw, _ptr(new_off),
+                                           _ptr(new_idx), _ptr(new_milli), _ptr(ws), ws.numel(), cnt, _ptr(out[0]),
+                                           _ptr(out[1]), _ptr(out[2]), _stream()))
+    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
 
 
 def predict_columns(ratings, off, idx, milli, query_weight, user_weight, default_mean, sum_order):

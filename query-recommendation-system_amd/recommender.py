@@ -199,7 +199,7 @@ class Recommender:
         if q.ndim != 2 or q.shape[1] != len(self.datasetFeatures):
             raise ValueError("queries must have one column per dataset feature (%d)" % len(self.datasetFeatures))
         if getattr(self, "_query_index", None) is None:
-            self._query_index = QueryIndex.from_result(res, self.last_table)
+            self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
         qi = self._query_index
         if getattr(self, "_answer_index", None) is None or getattr(self, "_answer_index_key", None) != id(self.dataset):
             self.answer_sets_device()  # (re)builds the cached AnswerIndex of this dataset
@@ -207,7 +207,7 @@ class Recommender:
         sig, norm2, keys = qi.signatures(offsets, rows)
         return qi, sig, norm2, keys
 
-    def add_queries(self, queries, ratings=None, ids=None):
+    def add_queries(self, queries, ratings=None, ids=None, update_lists=False):
         """Take m new queries (parse_queries' form) into the served set without a new run: their answer sets and
         signatures under the last run's table are appended to the run's index (QueryIndex.append: no rebuild), and
         self.queries, self.queriesIDs and self.ratings grow by the same m.  ratings: integer [users, m] block of their
@@ -218,8 +218,15 @@ class Recommender:
         positions assigned.  Afterwards similar_queries, predict_new_queries and recommend_new_queries see them as
         indexed queries.  last_result stays the closed-set run's output; the next compute_querySimilarities starts
         afresh over all queries.  (Nothing per query is cached on the device between calls: the cached AnswerIndex
-        belongs to the dataset and stays.)"""
+        belongs to the dataset and stays.)
+        update_lists=True: the index also keeps the run's top-K lists current (QueryIndex.append(update_lists=True)):
+        current_query_similarities() then returns what compute_querySimilarities would over all queries at the run's
+        K, and compute_scores(reuse_lists=True) predicts from them.  last_result is still left alone.  Without the flag
+        the live lists are dropped (they would be stale), and a later update_lists=True raises ValueError."""
         qi, sig, norm2, keys = self._new_query_rows(queries)
+        if update_lists and qi.lists is None:
+            raise ValueError("the live lists were dropped by an add_queries without update_lists=True; "
+                             "compute_querySimilarities starts afresh")
         q = np.asarray(_as_numpy(queries), dtype=object)
         m = q.shape[0]
         nu = self.usersIDs.size
@@ -247,11 +254,31 @@ class Recommender:
                 labels = labels.astype(cur.dtype)
             except (TypeError, ValueError):
                 raise ValueError("ids of dtype %s do not fit queriesIDs of dtype %s" % (labels.dtype, cur.dtype))
-        first, _ = qi.append(sig, norm2, keys)
+        first, _ = qi.append(sig, norm2, keys, update_lists=update_lists)
         self.queries = np.concatenate((np.asarray(self.queries, dtype=object), q), axis=0)
         self.queriesIDs = np.concatenate((cur, labels))
         self.ratings = np.hstack((self.ratings, block))
         return pos
+
+    def _live_lists(self):
+        """(src, dst, val) that know every added query, or None: the run's own lists before any append, the index's
+        while add_queries(update_lists=True) kept them current"""
+        res = getattr(self, "last_result", None)
+        if res is None:
+            return None
+        qi = getattr(self, "_query_index", None)
+        if qi is None:
+            return (res.src, res.dst, res.val) if res.sig.shape[0] == self.queriesIDs.size else None
+        return qi.lists if qi.n == self.queriesIDs.size else None
+
+    def current_query_similarities(self):
+        """the dict compute_querySimilarities returns, from the live lists: before any add_queries the run's own, after
+        add_queries(update_lists=True) those of all queries served now (list length: the run's K).  ValueError when
+        there are none (no run yet, or an add_queries without update_lists dropped them)."""
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        return pipeline.sims_to_dict(*lists)
 
     def similar_queries(self, queries):
         """{x: {'indexes': int64[<=K], 'values': float64[<=K]}} for new queries x = 0 .. m-1 (rows of `queries`): the
@@ -323,12 +350,18 @@ class Recommender:
         return user_sim
 
     # ---- N1: hybrid prediction (device) ------------------------------------------------
-    def compute_scores(self):
-        """(scores_to_predict, finalPredictions DataFrame, scores_missed), recommender.py:292-343."""
+    def compute_scores(self, reuse_lists=False):
+        """(scores_to_predict, finalPredictions DataFrame, scores_missed), recommender.py:292-343.
+        reuse_lists=True with live lists present (current_query_similarities): the query side comes from them instead
+        of from a new compute_querySimilarities run; the user side and the prediction are unchanged.  Without live
+        lists, and by default, the run happens as always."""
         from qrlsh import predict
         self._log("\n========== QUERY SIMILARITY ==========")
-        self.compute_querySimilarities()
-        res = self.last_result
+        lists = self._live_lists() if reuse_lists else None
+        if lists is None:
+            self.compute_querySimilarities()
+            res = self.last_result
+            lists = (res.src, res.dst, res.val)
         self._log("\n========== USER SIMILARITY ==========")
         user_sim = self.compute_userSimilarities()
         self._log("\n========== WEIGHTED AVERAGES ==========")
@@ -339,7 +372,7 @@ class Recommender:
         # "pairwise" is numpy's own np.sum order, what the reference does with @jit removed -- the run the committed
         # fixtures were captured from (numba is not installable here), on which both orders give the same matrices;
         # parity with the numba build itself stays unpinned.
-        final = predict.fill_predictions(self.ratings, res.src, res.dst, res.val, user_sim, QUERY_WEIGHT, USER_WEIGHT,
+        final = predict.fill_predictions(self.ratings, lists[0], lists[1], lists[2], user_sim, QUERY_WEIGHT, USER_WEIGHT,
                                          DEFAULT_MEAN, self.device, sum_order=self.sum_order)
         final = ops.to_host(final)
         self._log(str(round(time.time() - t0, 3)) + "s for weighted averages")
