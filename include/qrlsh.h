@@ -562,6 +562,76 @@ int qrlsh_lists_update_fill(const int32_t *src, const int32_t *dst, const int32_
                             size_t workspace_bytes, int64_t total, int32_t *src_out, int32_t *dst_out, int32_t *val_out,
                             void *stream);
 
+/*   finish for probe rows scattered over the index: qrlsh_index_probe_finish_indexed with self_ids (device uint32 [m]) in
+ *     the place of first_id: probe row q is indexed query self_ids[q].  A raw word that names the row itself is dropped
+ *     like a duplicate; rows with identical signatures and different ids stay neighbours at 1000. */
+int qrlsh_index_probe_finish_rows(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                                  const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
+                                  const uint32_t *self_ids, const void *probe_workspace, const uint64_t *raw, int64_t n_raw,
+                                  int32_t K, int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- removing queries from a built index (csrc/remove.hip) ------------------------------------------------------
+ * A set R of ids leaves 0 .. n-1 and the survivors are renumbered by rank: new id = old id - |{r in R : r < old id}|.
+ * The map is monotone, so every order the index and the lists keep among ids is kept, and ids stay dense.
+ *   id map: a set of ids over [0, n) with O(1) membership and rank: one 8-byte entry {32 bits, members below the word}
+ *     per 32 ids, in caller memory of qrlsh_idmap_workspace_bytes(n) bytes (entries, then scratch of the build).
+ *     build: ids uint32 [m] in any order, duplicates allowed; out2 (device uint64 [2]) receives {the number of distinct
+ *     ids, a flag word: bit 0 = an id >= n was seen -- the map is then not to be used}: the one read-back that sizes
+ *     what follows.  list: the members in ascending order (uint32 [count]).  positions: pos_out int64 [n], the new id
+ *     of every old id, -1 for a member.  n < 2^32 - 1.
+ *   rows: rows [n] of row_bytes (both arrays 16-byte aligned) and norm2 [n] (or NULL) -> rows_out / norm2_out [n - |R|],
+ *     out of place: survivor i goes to row i - rank(i).  A row whose width is a multiple of 16 bytes -- every width the
+ *     hot path makes at P a multiple of 8 -- is moved as 16-byte vectors; any other even width (P = 180 compact rows:
+ *     360 bytes) as the widest of 8, 4 or 2 bytes that divides it.  An odd row_bytes is QRLSH_EINVAL.
+ *   index: keys / ids [b][n] of a built index -> keys_out / ids_out [b][n - n_removed] and dir_out
+ *     (qrlsh_index_dir_words(n - n_removed, b)), byte for byte qrlsh_index_build of the survivors' keys in their order:
+ *     one stable compaction per band (count per tile of 2048 records, one scan, fill), ids remapped, then the directory
+ *     kernel of the build over the output.  Keys are read once, ids twice, every output written once; no read-back.
+ *     n_removed = the map's member count (out2[0]).  pick_map / n_pick / pick_keys_out [b][n_pick] (optional: NULL, 0,
+ *     NULL): a second id map over OLD ids; the key of every surviving record whose id is in it is also written to
+ *     pick_keys_out[band][rank_pick(id)] -- the probe keys of those rows, in qrlsh_idmap_list order, taken from the
+ *     index itself (so an index built on caller keys behaves the same).  n_removed == 0 returns at once and writes
+ *     nothing; n_removed == n writes nothing and succeeds (the caller holds the empty index).  workspace:
+ *     qrlsh_index_remove_workspace_bytes(n, b).
+ *   lists: src / dst / val as qrlsh_lists_update_* take them, list length K.  A stored row with fewer than K entries
+ *     was never cut and holds every candidate of its query: it loses its removed entries and is renumbered.  A
+ *     surviving row of exactly K entries that loses at least one may need candidates the cut threw away:
+ *     mark: every such row enters pick_map_out (an id map over old ids, qrlsh_idmap_workspace_bytes(n) bytes); out2
+ *       (device uint64 [2]) = {picked rows, 0 -- or ~0 when the stored lists break the contract (src not ascending, an
+ *       id outside [0, n)); nothing may follow then}.
+ *     The caller probes the picked rows against the SHRUNK index (pick_keys_out, qrlsh_index_probe_*,
+ *     qrlsh_index_probe_finish_rows with their new ids, the same K): re_off int64 [n_pick + 1] / re_idx / re_milli,
+ *     rows in qrlsh_idmap_list order; re_self uint32 [n_pick] = their new ids.
+ *     count / fill: src_out / dst_out / val_out ordered by new src: an unpicked surviving row becomes its surviving
+ *       entries, remapped, in stored order; a picked row its re-probed list; rows of removed queries and rows left
+ *       empty are absent.  *total_out (device uint64; the one read-back) = the number of entries, or ~0 on a contract
+ *       break.  fill follows a count on the same workspace and arguments and writes exactly `total` entries.  Stored
+ *       entries are compacted like the bands (tiles of 2048, one scan); every entry places itself.
+ * Limits: 1 <= K <= QRLSH_INDEX_MAX_K, n < 2^31 and n_edges < 2^31 with lists, n < 2^32 - 1 without (QRLSH_EINVAL
+ * otherwise).  No allocation, one stream.  workspace: qrlsh_lists_remove_workspace_bytes(n, n_edges). */
+size_t qrlsh_idmap_workspace_bytes(int64_t n);
+int qrlsh_idmap_build(const uint32_t *ids, int64_t m, int64_t n, void *map, size_t map_bytes, uint64_t *out2, void *stream);
+int qrlsh_idmap_list(const void *map, int64_t n, uint32_t *ids_out, void *stream);
+int qrlsh_idmap_positions(const void *map, int64_t n, int64_t *pos_out, void *stream);
+int qrlsh_rows_remove(const void *rows, int64_t row_bytes, const int64_t *norm2, int64_t n, const void *removed_map,
+                      void *rows_out, int64_t *norm2_out, void *stream);
+size_t qrlsh_index_remove_workspace_bytes(int64_t n, int32_t b);
+int qrlsh_index_remove(const uint64_t *keys, const uint32_t *ids, int64_t n, int32_t b, const void *removed_map,
+                       int64_t n_removed, const void *pick_map, int64_t n_pick, uint64_t *keys_out, uint32_t *ids_out,
+                       uint32_t *dir_out, uint64_t *pick_keys_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t qrlsh_lists_remove_workspace_bytes(int64_t n, int64_t n_edges);
+int qrlsh_lists_remove_mark(const int32_t *src, const int32_t *dst, int64_t n_edges, int64_t n, int32_t K,
+                            const void *removed_map, void *pick_map_out, uint64_t *out2, void *stream);
+int qrlsh_lists_remove_count(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                             int32_t K, const void *removed_map, const void *pick_map, const int64_t *re_off,
+                             int64_t n_pick, void *workspace, size_t workspace_bytes, uint64_t *total_out, void *stream);
+int qrlsh_lists_remove_fill(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                            int32_t K, const void *removed_map, const void *pick_map, const int64_t *re_off,
+                            const int32_t *re_idx, const int32_t *re_milli, const uint32_t *re_self, int64_t n_pick,
+                            void *workspace, size_t workspace_bytes, int64_t total, int32_t *src_out, int32_t *dst_out,
+                            int32_t *val_out, void *stream);
+
 /* ---- recommendations: top-k unrated queries per user (the consumer of N1's output) ---------------------
  * Replaces the selection of the interactive prompt, recommender.py:357-375 (just_scored of :361, the argsort of
  * :370), in batch form over the completed matrix.  ratings / pred int32 [nu][nq] (qrlsh_predict's input and output),

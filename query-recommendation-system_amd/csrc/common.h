@@ -44,6 +44,9 @@ int qr_aux_join(hipStream_t st);
     qr_prof_end(ps__, st);                                               \
   } while (0)
 
+// the per-band directory of sorted index bands (index.hip); `who` names the entry point in a launch error
+int qr_index_dir(const uint64_t *keys, int64_t n, int32_t b, uint32_t *dir_out, hipStream_t st, const char *who);
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // 64-bit bijective mixer (splitmix64 finaliser).  Bijective => equal mixes <=> equal keys

@@ -60,6 +60,14 @@ __global__ __launch_bounds__(256) void index_dir_kernel(const uint64_t *__restri
     for (int64_t x = h + 1; x <= (1ll << d); ++x) dr[x] = (uint32_t)n;
 }
 
+// the directory of b sorted bands of n > 0 records (also what qrlsh_index_remove runs over its output)
+int qr_index_dir(const uint64_t *keys, int64_t n, int32_t b, uint32_t *dir_out, hipStream_t st, const char *who) {
+  QR_LAUNCH("index_dir", index_dir_kernel, dim3((unsigned)ceil_div64(n, 256), (unsigned)b), dim3(256), 0, st, keys, n,
+            (int)qrlsh_index_dir_bits(n), dir_out);
+  QR_LAUNCH_CHECK(who);
+  return QRLSH_OK;
+}
+
 QRLSH_EXPORT int qrlsh_index_build(uint64_t *keys, uint64_t *keys_tmp, uint32_t *ids, uint32_t *ids_tmp, int64_t n,
                                    int32_t b, uint32_t *dir_out, void *workspace, size_t workspace_bytes, void *stream) {
   QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && b > 0 && b <= 65535, "qrlsh_index_build: bad sizes n=%lld b=%d",
@@ -84,11 +92,7 @@ QRLSH_EXPORT int qrlsh_index_build(uint64_t *keys, uint64_t *keys_tmp, uint32_t 
       return QRLSH_EHIP;
     }
   }
-  const int d = qrlsh_index_dir_bits(n);
-  QR_LAUNCH("index_dir", index_dir_kernel, dim3((unsigned)ceil_div64(n, 256), (unsigned)b), dim3(256), 0, st,
-            (const uint64_t *)keys, n, d, dir_out);
-  QR_LAUNCH_CHECK("qrlsh_index_build");
-  return QRLSH_OK;
+  return qr_index_dir(keys, n, b, dir_out, st, "qrlsh_index_build");
 }
 
 // ---- probe: count / fill ------------------------------------------------------------------------------------------
@@ -250,13 +254,15 @@ __device__ static inline int64_t ix_val(uint16_t v) { return v == 0xFFFFu ? -1 :
 
 // one lane per raw word g << 32 | id: key (1000 - milli) << 32 | id if band g % b is the first band the two rows
 // share, else ~0 (a duplicate, or a key collision).  first_id >= 0: probe row q IS indexed query first_id + q, and the
-// word that names it (the query finding itself) is dropped like a duplicate; first_id < 0: the probe rows are strangers
+// word that names it (the query finding itself) is dropped like a duplicate; self_ids: probe row q is indexed query
+// self_ids[q] instead (scattered rows); first_id < 0 and no self_ids: the probe rows are strangers
 template <typename SigT>
 __global__ __launch_bounds__(256) void index_score_kernel(const SigT *__restrict__ sig, const int64_t *__restrict__ norm2,
                                                           int64_t n, const SigT *__restrict__ psig,
                                                           const int64_t *__restrict__ pnorm2, int P, int b, int64_t m,
                                                           const uint64_t *__restrict__ raw, int64_t n_raw,
-                                                          int64_t first_id, uint64_t *__restrict__ keys_out) {
+                                                          int64_t first_id, const uint32_t *__restrict__ self_ids,
+                                                          uint64_t *__restrict__ keys_out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_raw) return;
   const uint64_t w = raw[i];
@@ -264,7 +270,12 @@ __global__ __launch_bounds__(256) void index_score_kernel(const SigT *__restrict
   const int64_t g = (int64_t)(w >> 32);
   const int64_t q = g / b;
   const int t = (int)(g - q * b);
-  if ((int64_t)id >= n || q >= m || (first_id >= 0 && (int64_t)id == first_id + q)) {  // not a word the fill pass writes, or q itself
+  if ((int64_t)id >= n || q >= m) {  // not a word the fill pass writes
+    keys_out[i] = ~0ull;
+    return;
+  }
+  const int64_t self = self_ids ? (int64_t)self_ids[q] : (first_id >= 0 ? first_id + q : -1);
+  if ((int64_t)id == self) {  // q itself
     keys_out[i] = ~0ull;
     return;
   }
@@ -419,7 +430,8 @@ QRLSH_EXPORT size_t qrlsh_index_finish_workspace_bytes(int64_t m, int32_t K, int
 
 static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig, const int64_t *probe_norm2,
                      int32_t sig_dtype, int32_t P, int32_t b, int64_t m, const void *probe_workspace, const uint64_t *raw,
-                     int64_t n_raw, int32_t K, int64_t first_id, int64_t *off_out, int32_t *idx_out, int32_t *milli_out,
+                     int64_t n_raw, int32_t K, int64_t first_id, const uint32_t *self_ids, int64_t *off_out, int32_t *idx_out,
+                     int32_t *milli_out,
                      int32_t *avail_out, void *workspace, size_t workspace_bytes, void *stream) {
   QR_CHECK_ARG(K >= 1 && K <= IX_MAXK, "qrlsh_index_probe_finish: K=%d not in [1, %d]", K, IX_MAXK);
   QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && m >= 0 && n_raw >= 0 && P > 0 && b > 0 && b <= 65535 && P % b == 0,
@@ -453,10 +465,10 @@ static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const voi
     const dim3 grid((unsigned)ceil_div64(n_raw, 256)), block(256);
     if (sig_dtype == QRLSH_SIG_U16)
       QR_LAUNCH("index_score", index_score_kernel<uint16_t>, grid, block, 0, st, static_cast<const uint16_t *>(sig), norm2, n,
-                static_cast<const uint16_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, first_id, keys);
+                static_cast<const uint16_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, first_id, self_ids, keys);
     else
       QR_LAUNCH("index_score", index_score_kernel<int32_t>, grid, block, 0, st, static_cast<const int32_t *>(sig), norm2, n,
-                static_cast<const int32_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, first_id, keys);
+                static_cast<const int32_t *>(probe_sig), probe_norm2, P, b, m, raw, n_raw, first_id, self_ids, keys);
   }
   uint64_t *cut = reinterpret_cast<uint64_t *>(off_out);
   QR_LAUNCH("index_select", index_select_kernel, dim3((unsigned)m), dim3(256), 0, st, (const uint64_t *)keys,
@@ -473,8 +485,8 @@ QRLSH_EXPORT int qrlsh_index_probe_finish(const void *sig, const int64_t *norm2,
                                           const void *probe_workspace, const uint64_t *raw, int64_t n_raw, int32_t K,
                                           int64_t *off_out, int32_t *idx_out, int32_t *milli_out, int32_t *avail_out,
                                           void *workspace, size_t workspace_bytes, void *stream) {
-  return ix_finish(sig, norm2, n, probe_sig, probe_norm2, sig_dtype, P, b, m, probe_workspace, raw, n_raw, K, -1, off_out,
-                   idx_out, milli_out, avail_out, workspace, workspace_bytes, stream);
+  return ix_finish(sig, norm2, n, probe_sig, probe_norm2, sig_dtype, P, b, m, probe_workspace, raw, n_raw, K, -1, nullptr,
+                   off_out, idx_out, milli_out, avail_out, workspace, workspace_bytes, stream);
 }
 
 // the finish for probe rows that are in the index themselves: row q is indexed query first_id + q and is kept out of
@@ -489,6 +501,19 @@ QRLSH_EXPORT int qrlsh_index_probe_finish_indexed(const void *sig, const int64_t
                "qrlsh_index_probe_finish_indexed: rows %lld .. %lld are not among the %lld indexed queries",
                (long long)first_id, (long long)(first_id + m), (long long)n);
   return ix_finish(sig, norm2, n, probe_sig, probe_norm2, sig_dtype, P, b, m, probe_workspace, raw, n_raw, K, first_id,
+                   nullptr, off_out, idx_out, milli_out, avail_out, workspace, workspace_bytes, stream);
+}
+
+// the finish for probe rows scattered over the index: row q is indexed query self_ids[q] (device uint32 [m]) and is kept
+// out of its own list
+QRLSH_EXPORT int qrlsh_index_probe_finish_rows(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig,
+                                               const int64_t *probe_norm2, int32_t sig_dtype, int32_t P, int32_t b, int64_t m,
+                                               const uint32_t *self_ids, const void *probe_workspace, const uint64_t *raw,
+                                               int64_t n_raw, int32_t K, int64_t *off_out, int32_t *idx_out,
+                                               int32_t *milli_out, int32_t *avail_out, void *workspace,
+                                               size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(m >= 0 && (m == 0 || self_ids), "qrlsh_index_probe_finish_rows: null self_ids");
+  return ix_finish(sig, norm2, n, probe_sig, probe_norm2, sig_dtype, P, b, m, probe_workspace, raw, n_raw, K, -1, self_ids,
                    off_out, idx_out, milli_out, avail_out, workspace, workspace_bytes, stream);
 }
 

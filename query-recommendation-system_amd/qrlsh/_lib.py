@@ -28,6 +28,7 @@ SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
 INDEX_MAX_K = 256
+REMOVE_TILE = 2048      # records (list entries) per workgroup of the removal's compactions (csrc/remove.hip RM_TILE)
 
 _vp = ctypes.c_void_p
 _i32 = ctypes.c_int32
@@ -123,6 +124,20 @@ SIGNATURES = {
     "qrlsh_lists_update_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _sz,
                                                 _vp, _vp]),
     "qrlsh_lists_update_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _sz,
+                                               _i64, _vp, _vp, _vp, _vp]),
+    "qrlsh_index_probe_finish_rows": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _i64,
+                                                     _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_idmap_workspace_bytes": (_sz, [_i64]),
+    "qrlsh_idmap_build": (ctypes.c_int, [_vp, _i64, _i64, _vp, _sz, _vp, _vp]),
+    "qrlsh_idmap_list": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    "qrlsh_idmap_positions": (ctypes.c_int, [_vp, _i64, _vp, _vp]),
+    "qrlsh_rows_remove": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "qrlsh_index_remove_workspace_bytes": (_sz, [_i64, _i32]),
+    "qrlsh_index_remove": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_lists_remove_workspace_bytes": (_sz, [_i64, _i64]),
+    "qrlsh_lists_remove_mark": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "qrlsh_lists_remove_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _sz, _vp, _vp]),
+    "qrlsh_lists_remove_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz,
                                                _i64, _vp, _vp, _vp, _vp]),
     "qrlsh_recommend_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "qrlsh_recommend_topk": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,

@@ -15,6 +15,8 @@ band keys, byte for byte what a fresh build of all n + m rows gives, without sor
 afterwards they are indexed queries like the others, with the ids n .. n + m - 1.  An index that holds the run's
 top-K lists (lists=...) keeps them current on the way (update_lists=True, csrc/lists.hip): after the append the batch
 is probed against the grown index and every list, old and new, becomes what a run over all rows with the same K gives.
+Queries leave with remove (csrc/remove.hip): the survivors are renumbered by rank, the band arrays are compacted into
+what a fresh build of the surviving rows gives, and held lists are kept exact on the way (update_lists=True).
 
 Everything runs on the device; the indexed data never leaves it."""
 import numpy as np
@@ -80,6 +82,7 @@ class QueryIndex:
         keys = ops.band_keys(ops.sig_to_int32(sig), b) if keys is None else keys.clone()
         self.keys, self.ids, self.dir = ops.index_build(keys)
         self.lists, self.lists_K = None, None
+        self.last_picked = None
         if lists is not None:
             self.lists, self.lists_K = self._check_lists(lists), self.K
 
@@ -206,6 +209,75 @@ class QueryIndex:
     def add(self, offsets, rows, update_lists=False):
         """signatures() of CSR answer sets, then append(): -> (first_id, m)"""
         return self.append(*self.signatures(offsets, rows), update_lists=update_lists)
+
+    # ---- shrinking the index ---------------------------------------------------------------------------------------
+    def remove(self, ids, update_lists=False):
+        """take queries out of the index: ids = their positions (array or tensor of integers, any order, duplicates
+        allowed; ValueError for one outside [0, n), the index unchanged).  The survivors are renumbered by rank, so ids
+        stay dense.  -> new_pos, int64 device tensor [old n]: the new id of every old id, -1 for a removed one.
+        Afterwards .n, .sig, .norm2, .keys, .ids and .dir are the arrays a fresh QueryIndex over the surviving rows holds
+        (built with the surviving keys: one stable compaction per band, no sort), and a defaulted K follows the new n.
+        update_lists=True (an index that holds lists; ValueError otherwise): .lists becomes the lists of a run over the
+        survivors at .lists_K.  Stored rows shorter than K only lose their removed entries; a row of exactly K entries
+        that loses one is probed again against the shrunk index, with the keys it is indexed under.
+        update_lists=False: held lists would go stale, so .lists becomes None.  No ids: nothing happens.
+        .last_picked: how many rows the last remove(update_lists=True) probed again (None after one without)."""
+        if update_lists and self.lists is None:
+            raise ValueError("this index holds no lists to update (none were given, or an append or remove without "
+                             "update_lists=True dropped them)")
+        dev = self.sig.device
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+                raise ValueError("ids must be integers")
+            t = ids.reshape(-1).to(dev, torch.int64)
+        else:
+            a = np.asarray(ids).reshape(-1)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("ids must be integers")
+            t = torch.from_numpy(a.astype(np.int64)).to(dev)
+        n = self.n
+        if update_lists and n >= 2**31:
+            raise ValueError("lists are kept for fewer than 2^31 queries")
+        if t.numel() == 0:
+            return torch.arange(n, dtype=torch.int64, device=dev)
+        # ids beyond uint32 all become 2^32 - 1, which no index holds (n < 2^32 - 1): the map build flags them
+        t = torch.where((t < 0) | (t > 0xFFFFFFFF), torch.full_like(t, 0xFFFFFFFF), t)
+        removed = ops.idmap_build(((t + 2**31) % 2**32 - 2**31).to(torch.int32), n)
+        new_pos = removed.positions()
+        left = n - removed.count
+        pick = None
+        if update_lists:
+            K = self.lists_K
+            pick = ops.lists_remove_mark(self.lists[0], self.lists[1], n, K, removed)
+        keys, ids_, dirw, pick_keys = ops.index_remove(self.keys, self.ids, removed, pick)
+        sig, norm2 = ops.rows_remove(self.sig, self.norm2, removed)
+        if update_lists:
+            self_ids = new_pos[pick.members().to(torch.int64) & 0xFFFFFFFF].to(torch.int32)
+            rows = self_ids.to(torch.int64)
+            psig, pnorm2 = sig[rows], norm2[rows]
+            step = max(1, (2**32 - 1) // self.b)      # the probe takes n_pick * b < 2^32 words per call
+            offs, idxs, millis, base = [torch.zeros((1,), dtype=torch.int64, device=dev)], [], [], 0
+            for q0 in range(0, pick.count, step):
+                q1 = min(pick.count, q0 + step)
+                raw, pws = ops.index_probe(keys, ids_, dirw, self.r, pick_keys[:, q0:q1].contiguous())
+                off, idx, milli, _ = ops.index_finish_rows(sig, norm2, psig[q0:q1], pnorm2[q0:q1].contiguous(), self.b,
+                                                           pws, raw, K, self_ids[q0:q1].contiguous())
+                offs.append(off[1:] + base)
+                idxs.append(idx)
+                millis.append(milli)
+                base += idx.numel()
+            e = torch.empty((0,), dtype=torch.int32, device=dev)
+            lists = ops.lists_remove(*self.lists, n, K, removed, pick, torch.cat(offs), torch.cat(idxs) if idxs else e,
+                                     torch.cat(millis) if millis else e, self_ids)
+        self.keys, self.ids, self.dir = keys, ids_, dirw
+        self.n = left
+        self.sig, self.norm2 = sig, norm2
+        self._sig_buf, self._norm2_buf = sig, norm2
+        if self._default_K:
+            self.K = self._K_rule(self.n)
+        self.lists = lists if update_lists else None
+        self.last_picked = pick.count if update_lists else None
+        return new_pos
 
     def neighbours_of(self, first_id, m, K=None, keys=None):
         """the lists of the indexed queries first_id .. first_id + m - 1 recomputed from the index: each query's K best

@@ -1070,6 +1070,169 @@ def lists_update(src, dst, val, n, m, b, K, raw, select_keys, new_off, new_idx, 
     return out[0][:cnt], out[1][:cnt], out[2][:cnt]
 
 
+# ---------------------------------------------------------------------------
+# removing queries from a built index (csrc/remove.hip)
+# ---------------------------------------------------------------------------
+class IdMap:
+    """a set of ids over [0, n) on the device with O(1) membership and rank (qrlsh_idmap_*): .ws its memory, .count its
+    members"""
+
+    def __init__(self, ws, n, count):
+        self.ws, self.n, self.count = ws, n, count
+
+    def members(self):
+        """the members, ascending: int32 [count] (uint32 bit patterns)"""
+        out = torch.empty((self.count,), dtype=torch.int32, device=self.ws.device)
+        if self.count:
+            _lib.check(_lib.load().qrlsh_idmap_list(_ptr(self.ws), self.n, _ptr(out), _stream()))
+        return out
+
+    def positions(self):
+        """int64 [n]: the rank of every id among the ids outside the set, -1 for a member"""
+        out = torch.empty((self.n,), dtype=torch.int64, device=self.ws.device)
+        _lib.check(_lib.load().qrlsh_idmap_positions(_ptr(self.ws), self.n, _ptr(out), _stream()))
+        return out
+
+
+def idmap_build(ids, n):
+    """ids: int32 device tensor (uint32 bit patterns), any order, duplicates allowed -> IdMap over [0, n); ValueError
+    for an id outside [0, n).  One read-back (the member count and the flag word)."""
+    lib = _lib.load()
+    _need(ids, torch.int32, "ids", 1)
+    dev = ids.device
+    ws = _ws(lib.qrlsh_idmap_workspace_bytes(n), dev)
+    out2 = torch.zeros((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_idmap_build(_ptr(ids), ids.numel(), n, _ptr(ws), ws.numel(), _ptr(out2), _stream()))
+    count, flags = out2.tolist()
+    if flags & 1:
+        raise ValueError("ids must lie in [0, %d)" % n)
+    return IdMap(ws, n, count)
+
+
+def rows_remove(sig, norm2, removed):
+    """the rows (and norms) outside the IdMap `removed`, in order: new tensors [n - removed.count]"""
+    lib = _lib.load()
+    n, P = sig.shape
+    row_bytes = P * sig.element_size()
+    left = n - removed.count
+    sig_out = torch.empty((left, P), dtype=sig.dtype, device=sig.device)
+    norm2_out = torch.empty((left,), dtype=torch.int64, device=sig.device)
+    if left == 0:
+        return sig_out, norm2_out
+    _lib.check(lib.qrlsh_rows_remove(_ptr(sig), row_bytes, _ptr(norm2), n, _ptr(removed.ws), _ptr(sig_out),
+                                     _ptr(norm2_out), _stream()))
+    return sig_out, norm2_out
+
+
+def index_remove(keys, ids, removed, pick=None):
+    """a built index (keys int64 [b, n], ids int32 [b, n]) without the ids of the IdMap `removed`, survivors renumbered
+    by rank -> (keys [b, n'], ids [b, n'], directory, pick_keys): byte for byte index_build of the survivors' keys.
+    pick: an IdMap over old ids; pick_keys int64 [b, pick.count] then holds the keys those rows are indexed under, in
+    pick.members() order (None without pick).  Nothing removed: the arguments come back (directory None)."""
+    lib = _lib.load()
+    _need(keys, torch.int64, "keys", 2)
+    _need(ids, torch.int32, "ids", 2)
+    b, n = keys.shape
+    if tuple(ids.shape) != (b, n) or removed.n != n or (pick is not None and pick.n != n):
+        raise ValueError("ids must be [b, n] and the id maps cover [0, n) = [0, %d)" % n)
+    dev = keys.device
+    left = n - removed.count
+    n_pick = pick.count if pick is not None else 0
+    pick_keys = torch.empty((b, n_pick), dtype=torch.int64, device=dev) if pick is not None else None
+    if removed.count == 0:
+        return keys, ids, None, pick_keys
+    if left == 0:
+        k0 = torch.empty((b, 0), dtype=torch.int64, device=dev)
+        return index_build(k0) + (pick_keys,)
+    keys_out = torch.empty((b, left), dtype=torch.int64, device=dev)
+    ids_out = torch.empty((b, left), dtype=torch.int32, device=dev)
+    dir_out = torch.empty((int(lib.qrlsh_index_dir_words(left, b)),), dtype=torch.int32, device=dev)
+    ws = _ws(lib.qrlsh_index_remove_workspace_bytes(n, b), dev)
+    _lib.check(lib.qrlsh_index_remove(_ptr(keys), _ptr(ids), n, b, _ptr(removed.ws), removed.count,
+                                      _ptr(pick.ws) if n_pick else None, n_pick, _ptr(keys_out), _ptr(ids_out),
+                                      _ptr(dir_out), _ptr(pick_keys) if n_pick else None, _ptr(ws), ws.numel(), _stream()))
+    return keys_out, ids_out, dir_out, pick_keys
+
+
+def index_finish_rows(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K, self_ids):
+    """index_finish for probe rows scattered over the index: row q is indexed query self_ids[q] (int32 device tensor
+    [m]) and stays out of its own list (qrlsh_index_probe_finish_rows) -> (off, idx, milli, avail)"""
+    lib = _lib.load()
+    n, P = sig.shape
+    m = probe_sig.shape[0]
+    _need(self_ids, torch.int32, "self_ids", 1)
+    if self_ids.numel() != m:
+        raise ValueError("self_ids must hold one id per probe row")
+    dev = sig.device
+    n_raw = raw.numel()
+    code = _lib.SIG_U16 if sig.dtype == torch.int16 else _lib.SIG_I32
+    ws = _ws(lib.qrlsh_index_finish_workspace_bytes(m, K, n_raw), dev)
+    off = torch.empty((m + 1,), dtype=torch.int64, device=dev)
+    idx = torch.empty((max(m * K, 1),), dtype=torch.int32, device=dev)
+    milli = torch.empty((max(m * K, 1),), dtype=torch.int32, device=dev)
+    avail = torch.empty((m,), dtype=torch.int32, device=dev)
+    _lib.check(lib.qrlsh_index_probe_finish_rows(_ptr(sig), _ptr(norm2), n, _ptr(probe_sig), _ptr(probe_norm2), code, P, b,
+                                                 m, _ptr(self_ids), _ptr(probe_ws), _ptr(raw), n_raw, K, _ptr(off),
+                                                 _ptr(idx), _ptr(milli), _ptr(avail), _ptr(ws), ws.numel(), _stream()))
+    cnt = int(off[m].item()) if m else 0
+    return off, idx[:cnt], milli[:cnt], avail
+
+
+def _remove_lists_args(src, dst, val, n, K):
+    for t, name in ((src, "src"), (dst, "dst"), (val, "val")):
+        _need(t, torch.int32, name, 1)
+        if t.device != src.device or t.numel() != src.numel():
+            raise ValueError("src, dst and val must have one length and one device")
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= _lib.INDEX_MAX_K:
+        raise ValueError("K must lie in 1..%d, got %r" % (_lib.INDEX_MAX_K, K))
+    if n >= 2**31 or src.numel() >= 2**31:
+        raise ValueError("lists are kept for fewer than 2^31 queries and entries")
+
+
+def lists_remove_mark(src, dst, n, K, removed):
+    """the rows of the stored lists that a removal has to probe again: surviving rows of exactly K entries with at least
+    one removed dst -> IdMap over old ids.  ValueError for stored lists that break the contract."""
+    lib = _lib.load()
+    _remove_lists_args(src, dst, dst, n, K)
+    dev = src.device
+    ws = _ws(lib.qrlsh_idmap_workspace_bytes(n), dev)
+    out2 = torch.zeros((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_lists_remove_mark(_ptr(src), _ptr(dst), src.numel(), n, int(K), _ptr(removed.ws), _ptr(ws),
+                                           _ptr(out2), _stream()))
+    count, bad = out2.tolist()
+    if bad:
+        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
+    return IdMap(ws, n, count)
+
+
+def lists_remove(src, dst, val, n, K, removed, pick, re_off, re_idx, re_milli, re_self):
+    """The stored top-K lists without the queries of `removed` (csrc/remove.hip): rows outside `pick` keep their
+    surviving entries, renumbered; row pick.members()[j] becomes the re-probed list j (re_off int64 [count + 1], re_idx /
+    re_milli int32, re_self int32 [count] = the rows' new ids).  -> (src, dst, val): new tensors ordered by new src."""
+    lib = _lib.load()
+    _remove_lists_args(src, dst, val, n, K)
+    dev = src.device
+    n_edges, n_pick = src.numel(), pick.count
+    _need(re_off, torch.int64, "re_off", 1)
+    for t, name in ((re_idx, "re_idx"), (re_milli, "re_milli"), (re_self, "re_self")):
+        _need(t, torch.int32, name, 1)
+    if re_off.numel() != n_pick + 1 or re_self.numel() != n_pick or re_idx.numel() != re_milli.numel():
+        raise ValueError("re_off must hold count + 1 offsets, re_self count ids, re_idx match re_milli")
+    ws = _ws(lib.qrlsh_lists_remove_workspace_bytes(n, n_edges), dev)
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_lists_remove_count(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, int(K), _ptr(removed.ws),
+                                            _ptr(pick.ws), _ptr(re_off), n_pick, _ptr(ws), ws.numel(), _ptr(total),
+                                            _stream()))
+    cnt = int(total.item())
+    if cnt < 0:
+        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
+    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
+    _lib.check(lib.qrlsh_lists_remove_fill(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, int(K), _ptr(removed.ws),
+                                           _ptr(pick.ws), _ptr(re_off), _ptr(re_idx), _ptr(re_milli), _ptr(re_self), n_pick,
+                                           _ptr(ws), ws.numel(), cnt, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()))
+    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+
+
 def predict_columns(ratings, off, idx, milli, query_weight, user_weight, default_mean, sum_order):
     """int32 [m, nu]: the predicted cells of m new queries for every user (qrlsh_predict_columns); raises ValueError
     when a list is longer than 64 entries or names a query outside the matrix"""

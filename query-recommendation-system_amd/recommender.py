@@ -260,6 +260,37 @@ class Recommender:
         self.ratings = np.hstack((self.ratings, block))
         return pos
 
+    def remove_queries(self, positions, update_lists=False):
+        """Take queries out of the served set without a new run, the mirror of add_queries: positions (integers, any
+        order, duplicates allowed; ValueError for one outside the set, nothing changed) leave self.queries,
+        self.queriesIDs, self.ratings and the run's index (QueryIndex.remove: no rebuild), and the queries left are
+        renumbered by rank.  -> int64 host array [old count]: the new position of every old one, -1 for a removed one.
+        update_lists=True: the index keeps the run's top-K lists exact (QueryIndex.remove(update_lists=True)), so
+        current_query_similarities() and compute_scores(reuse_lists=True) serve the shrunk set at the run's K.  Without
+        the flag the live lists are dropped, and a later update_lists=True raises ValueError.  last_result stays the
+        closed-set run's output."""
+        from qrlsh.index import QueryIndex
+        res = getattr(self, "last_result", None)
+        if res is None or getattr(self, "last_table", None) is None:
+            raise ValueError("compute_querySimilarities has not run: there is no index to take queries out of")
+        if getattr(self, "_query_index", None) is None:
+            self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
+        qi = self._query_index
+        if update_lists and qi.lists is None:
+            raise ValueError("the live lists were dropped by an add_queries or remove_queries without update_lists=True; "
+                             "compute_querySimilarities starts afresh")
+        if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
+            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        pos = np.asarray(_as_numpy(positions)).reshape(-1)
+        if pos.size and not np.issubdtype(pos.dtype, np.integer):
+            raise ValueError("positions must be integers")
+        new_pos = ops.to_host(qi.remove(pos, update_lists=update_lists))
+        keep = new_pos >= 0
+        self.queries = np.asarray(self.queries, dtype=object)[keep]
+        self.queriesIDs = self.queriesIDs[keep]
+        self.ratings = np.ascontiguousarray(self.ratings[:, keep])
+        return new_pos
+
     def _live_lists(self):
         """(src, dst, val) that know every added query, or None: the run's own lists before any append, the index's
         while add_queries(update_lists=True) kept them current"""
