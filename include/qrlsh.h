@@ -3,7 +3,8 @@
  * MinHash-LSH candidate-generation + pair-scoring hot path of
  * wamuumu/query-recommendation-system (lsh.py, recommender.py:105-214), the steps around it (answer sets, the
  * prediction loop, user similarity, recommendations), and the serving of queries that were not in the indexed set
- * (qrlsh_index_*, qrlsh_predict_columns).
+ * (qrlsh_index_*, qrlsh_predict_columns) and of chosen users straight from the live neighbour lists, without a
+ * prediction matrix (qrlsh_predict_users, qrlsh_recommend_users).
  *
  * The reference is pure Python and has no FFI of its own; this header is the
  * boundary its Python call surface (lsh.LSH, Recommender.compute_signatures /
@@ -655,6 +656,49 @@ size_t qrlsh_recommend_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t
 int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pred, int64_t nu, int64_t nq, const int32_t *users,
                          int64_t m, int32_t k, int32_t lo, int32_t slices, int32_t *idx_out, int32_t *val_out,
                          int32_t *avail_out, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- serving chosen users: their rows and their top-k from the live lists, no [nu][nq] prediction matrix ----------
+ * "What do I show user u now?" needs the user's own row, the rows of its <= 64 neighbour users and the query lists:
+ * qrlsh_predict_users computes qrlsh_predict's cells for the requested rows only, qrlsh_recommend_users selects from
+ * them as qrlsh_recommend_topk would from the completed matrix.  Same arithmetic as qrlsh_predict (float64, no FMA,
+ * half to even, both sum orders) cell for cell.
+ * ratings int32 [nu][nq].  Query lists in CSR with integer milli values, as qrlsh_topk_* / a QueryIndex's lists hold
+ * them: q_off int64 [nq + 1], q_idx int32, q_milli int32; the similarity is (double)milli / 1000.0, a true division
+ * (8 bytes per entry; no transposed copy is made).  User lists u_idx / u_val [nu][ku] as qrlsh_predict takes them,
+ * for ALL nu users, indexed by the requested user's id.  users int32 [m]: any order, repeats allowed; NULL = all rows
+ * in order (then m = nu).
+ * qrlsh_predict_users: out int32 [m][nq] = the completed rows (the rating where rated, else the prediction): rows
+ * users[.] of qrlsh_predict's output.  qrlsh_predict_users_workspace_bytes is 0 (the lists are read where they are;
+ * workspace may be NULL).
+ * qrlsh_recommend_users: writes the rows in eligible mode (0 where rated, else the prediction; row stride rounded up to
+ * 16 bytes) into its workspace (qrlsh_recommend_users_workspace_bytes(m, nq, k, slices), 16-byte aligned) and selects
+ * from them; idx_out / val_out [m][k] and avail_out [m] under qrlsh_recommend_topk's contract (value descending, then
+ * column ascending; padding -1 / 0; avail = eligible cells), `lo` and `slices` as there; the result depends on
+ * neither, nor on the form.  A user id outside [0, nu) gives avail_out = -1 and a padded row.
+ * One kernel sweeps (column slice, requested user) workgroups, the users of a slice together so that they share the
+ * slice's lists in L2; per workgroup, decided on the device: the user's row staged in LDS as bytes (nq <= 131072 and
+ * every value of the row in 0 .. 255), or read from memory.
+ * *flags_out (device uint32, required) = 0, or bit 0: a query list longer than 64, bit 1: a list index outside
+ * [0, nq), bit 2: a requested user id outside [0, nu).  Such lists are never walked (their cells get 0) and such rows
+ * are never read (the row is all 0); the result is not to be used -- the caller reads the flags back.
+ * Limits: ku <= 64, 1 <= k <= QRLSH_RECOMMEND_MAX_K, nq < 2^31, sum_order one of the two (QRLSH_EINVAL otherwise);
+ * m <= 2^24 and m x max(slices, 1) <= 2^24 (QRLSH_EUNSUPPORTED above).  Every check precedes any device work.
+ * m = 0 returns at once (nothing is written, *flags_out included); nq = 0 gives avail 0.  No allocation, one stream,
+ * no read-back.
+ */
+size_t qrlsh_predict_users_workspace_bytes(int64_t m, int64_t nq);
+int qrlsh_predict_users(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off, const int32_t *q_idx,
+                        const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                        double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                        const int32_t *users, int64_t m, int32_t *out, uint32_t *flags_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+size_t qrlsh_recommend_users_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices);
+int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off, const int32_t *q_idx,
+                          const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                          double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                          const int32_t *users, int64_t m, int32_t k, int32_t lo, int32_t slices, int32_t *idx_out,
+                          int32_t *val_out, int32_t *avail_out, uint32_t *flags_out, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 /* ---- N4: user similarity, the part after the clustering ----------------------------------------
  * Recommender.compute_userSimilarities, recommender.py:263-288: inside a cluster every user's row is centred on

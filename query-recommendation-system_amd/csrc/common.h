@@ -47,6 +47,14 @@ int qr_aux_join(hipStream_t st);
 // the per-band directory of sorted index bands (index.hip); `who` names the entry point in a launch error
 int qr_index_dir(const uint64_t *keys, int64_t n, int32_t b, uint32_t *dir_out, hipStream_t st, const char *who);
 
+// the rows of chosen users (predict.hip, compiled without FMA contraction): out[x] = the completed (eligible = false)
+// or eligible-only (true: 0 where rated) row of users[x], rows `ostride` words apart; `who` names the entry point
+int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
+                     const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                     double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                     const int32_t *users, int64_t m, bool eligible, int32_t *out, int64_t ostride, uint32_t *flags_out,
+                     hipStream_t st);
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // 64-bit bijective mixer (splitmix64 finaliser).  Bijective => equal mixes <=> equal keys

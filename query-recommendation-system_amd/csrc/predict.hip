@@ -557,3 +557,183 @@ QRLSH_EXPORT int qrlsh_predict_columns(const int32_t *ratings, int64_t nu, int64
   QR_LAUNCH_CHECK("qrlsh_predict_columns");
   return QRLSH_OK;
 }
+
+// ---- the rows of chosen users (qrlsh_predict_users, qrlsh_recommend_users) -------------------------------------------
+// What a server needs to answer "what do I show user u now?": predict_kernel's cells for the requested rows only,
+// straight from the live lists (CSR, similarity = milli / 1000.0, a true division as in predict_columns_kernel) -- no
+// [nu][nq] prediction matrix and no transposed copy of the lists.  One 1024-thread workgroup per (column slice,
+// requested user), the requested users varying fastest so that the workgroups of one slice run together and share that
+// slice's lists in L2.  Two forms, decided on the device, same results:
+//   LDS row form (nq <= PR_MAXQ and every value of the user's row in 0 .. 255): predict_row_kernel's scheme -- the
+//     workgroup stages its user's whole row in LDS as bytes and the query-side gathers become LDS byte reads;
+//   global form otherwise (a wider value anywhere in the row, found while staging, or a longer row): the gathers read
+//     the user's int32 row from memory.
+// The user-side gathers (ratings[u_k][j], consecutive lanes = consecutive j) are coalesced global reads in both.
+// ELIGIBLE = false: completed rows (the rating where rated: the rows qrlsh_predict writes); true: 0 where rated, so
+// that out != 0 is exactly the recommendation's eligibility test (ratings == 0 && pred != 0).
+// Nothing outside the buffers is read whatever the inputs hold: a list longer than PRED_MAXK is not walked, an index
+// outside [0, nq) is not gathered (both: the cell gets 0), the row of a user id outside [0, nu) is not read (the output
+// row gets 0).  predict_users_check_kernel raises the flags for all three, whatever the ratings are.
+constexpr int PU_THREADS = 1024;
+constexpr int PU_AUTO_GROUPS = 4096;   // column slices: about this many workgroups, at least PU_THREADS columns each
+
+template <bool ELIGIBLE>
+__global__ __launch_bounds__(PU_THREADS) void predict_users_kernel(
+    const int32_t *__restrict__ ratings, int64_t nu, int64_t nq, const int64_t *__restrict__ q_off,
+    const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli, const int32_t *__restrict__ u_idx,
+    const double *__restrict__ u_val, int ku, double qw, double uw, double dmean, int sequential,
+    const int32_t *__restrict__ users, int64_t m, int64_t slices, int32_t *__restrict__ out, int64_t ostride) {
+  __shared__ uint8_t lrow[PR_MAXQ];
+  __shared__ int wide;
+  const int64_t s = blockIdx.x / m, x = blockIdx.x - s * m;
+  const int t = threadIdx.x;
+  const int64_t per = (nq + slices - 1) / slices;
+  const int64_t j0 = s * per, j1 = min(nq, j0 + per);
+  int32_t *orow = out + x * ostride;
+  const int64_t i = users ? (int64_t)users[x] : x;
+  if (i < 0 || i >= nu) {  // uniform; flagged (bit 2) by the check kernel
+    for (int64_t j = j0 + t; j < j1; j += PU_THREADS) orow[j] = 0;
+    return;
+  }
+  const int32_t *row = ratings + i * nq;
+  bool in_lds = false;
+  if (nq <= PR_MAXQ) {  // uniform
+    if (t == 0) wide = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int64_t j = t; j < nq; j += PU_THREADS) {
+      const int32_t v = row[j];
+      bad |= (v < 0) | (v > 255);
+      lrow[j] = (uint8_t)v;
+    }
+    if (bad) wide = 1;
+    __syncthreads();
+    in_lds = wide == 0;
+  }
+  const int32_t *ui = u_idx + i * ku;
+  const double *uv = u_val + i * ku;
+  int mu = 0;
+  while (mu < ku && ui[mu] >= 0) ++mu;  // uniform: the user's own neighbour list
+  for (int64_t j = j0 + t; j < j1; j += PU_THREADS) {
+    const int32_t own = in_lds ? (int32_t)lrow[j] : row[j];
+    if (own != 0) {
+      orow[j] = ELIGIBLE ? 0 : own;
+      continue;
+    }
+    const int64_t lo = q_off[j], n64 = q_off[j + 1] - lo;
+    if (n64 < 0 || n64 > PRED_MAXK) {  // flagged (bit 0); never walked
+      orow[j] = 0;
+      continue;
+    }
+    bool outside = false;
+    const double qp = weighted_average(
+        (int)n64, sequential != 0,
+        [&](int k) {
+          const int32_t q = q_idx[lo + k];
+          if ((uint32_t)q >= (uint32_t)nq) {  // flagged (bit 1); never gathered
+            outside = true;
+            return (int32_t)0;
+          }
+          return in_lds ? (int32_t)lrow[q] : row[q];
+        },
+        [&](int k) { return (double)q_milli[lo + k] / 1000.0; });
+    const double up = weighted_average(
+        mu, sequential != 0, [&](int k) { return ratings[(int64_t)ui[k] * nq + j]; }, [&](int k) { return uv[k]; });
+    double r;
+    if (up == 0.0 && qp == 0.0) r = 0.0;
+    else if (up == 0.0) r = qp * (qw + (uw * 0.5)) + dmean * (uw * 0.5);
+    else if (qp == 0.0) r = up * (uw + (qw * 0.5)) + dmean * (qw * 0.5);
+    else r = qp * qw + up * uw;
+    orow[j] = outside ? 0 : (int32_t)rint(r);
+  }
+}
+
+// one thread per query list and per requested user: bit 0 a list longer than PRED_MAXK, bit 1 an index outside
+// [0, nq) (lists within the limit only: longer ones are not walked here either), bit 2 a user id outside [0, nu)
+__global__ __launch_bounds__(256) void predict_users_check_kernel(const int64_t *__restrict__ q_off,
+                                                                  const int32_t *__restrict__ q_idx, int64_t nq,
+                                                                  const int32_t *__restrict__ users, int64_t m,
+                                                                  int64_t nu, uint32_t *__restrict__ flags) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t why = 0;
+  if (t < nq) {
+    const int64_t lo = q_off[t], n = q_off[t + 1] - lo;
+    if (n < 0 || n > PRED_MAXK) {
+      why |= 1u;
+    } else {
+      for (int64_t k = 0; k < n; ++k)
+        if ((uint32_t)q_idx[lo + k] >= (uint32_t)nq) why |= 2u;
+    }
+  }
+  if (users && t < m) {
+    const int64_t u = users[t];
+    if (u < 0 || u >= nu) why |= 4u;
+  }
+  if (why) atomicOr(flags, why);
+}
+
+// Both entry points' common part: every check of the shared arguments (all before any device work), the flags, the
+// check kernel and the sweep.  `out` rows are `ostride` words apart.
+int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
+                     const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                     double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                     const int32_t *users, int64_t m, bool eligible, int32_t *out, int64_t ostride, uint32_t *flags_out,
+                     hipStream_t st) {
+  QR_CHECK_ARG(nu >= 0 && nq >= 0 && nq <= 2147483647ll && m >= 0 && ku >= 0 && ku <= PRED_MAXK,
+               "%s: bad sizes nu=%lld nq=%lld m=%lld ku=%d (<= %d)", who, (long long)nu, (long long)nq, (long long)m, ku,
+               PRED_MAXK);
+  QR_CHECK_ARG(sum_order == QRLSH_SUM_PAIRWISE || sum_order == QRLSH_SUM_SEQUENTIAL, "%s: bad sum_order %d", who,
+               sum_order);
+  QR_CHECK_ARG(users || m == nu, "%s: without a user list m (%lld) must equal nu (%lld)", who, (long long)m,
+               (long long)nu);
+  QR_CHECK_ARG(flags_out, "%s: flags_out is required", who);
+  if (m == 0) return QRLSH_OK;
+  QR_CHECK_ARG(nq == 0 || (q_off && out && (nu == 0 || (ratings && (ku == 0 || (u_idx && u_val))))), "%s: null pointer",
+               who);
+  if (m > (1ll << 24)) {
+    qrlsh_set_error("%s: m=%lld above the %lld rows served per call", who, (long long)m, (long long)(1ll << 24));
+    return QRLSH_EUNSUPPORTED;
+  }
+  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess) {
+    qrlsh_set_error("%s: hipMemsetAsync failed", who);
+    return QRLSH_EHIP;
+  }
+  const int64_t checks = nq > m ? nq : m;
+  QR_LAUNCH("predict_users_check", predict_users_check_kernel, dim3((unsigned)ceil_div64(checks, 256)), dim3(256), 0, st,
+            q_off, q_idx, nq, users, m, nu, flags_out);
+  if (nq > 0) {
+    int64_t slices = ceil_div64(PU_AUTO_GROUPS, m);
+    const int64_t most = ceil_div64(nq, PU_THREADS);
+    if (slices > most) slices = most;   // m x slices <= 2^24 + 2^21 workgroups
+    const dim3 grid((unsigned)(m * slices));
+    const int seq = (int)(sum_order == QRLSH_SUM_SEQUENTIAL);
+    if (eligible)
+      QR_LAUNCH("predict_users", predict_users_kernel<true>, grid, dim3(PU_THREADS), 0, st, ratings, nu, nq, q_off, q_idx,
+                q_milli, u_idx, u_val, (int)ku, query_weight, user_weight, default_mean, seq, users, m, slices, out,
+                ostride);
+    else
+      QR_LAUNCH("predict_users", predict_users_kernel<false>, grid, dim3(PU_THREADS), 0, st, ratings, nu, nq, q_off, q_idx,
+                q_milli, u_idx, u_val, (int)ku, query_weight, user_weight, default_mean, seq, users, m, slices, out,
+                ostride);
+  }
+  QR_LAUNCH_CHECK(who);
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT size_t qrlsh_predict_users_workspace_bytes(int64_t m, int64_t nq) {
+  (void)m;
+  (void)nq;
+  return 0;   // the sweep reads the lists where they are
+}
+
+QRLSH_EXPORT int qrlsh_predict_users(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
+                                     const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx,
+                                     const double *u_val, int32_t ku, double query_weight, double user_weight,
+                                     double default_mean, int32_t sum_order, const int32_t *users, int64_t m, int32_t *out,
+                                     uint32_t *flags_out, void *workspace, size_t workspace_bytes, void *stream) {
+  (void)workspace;
+  (void)workspace_bytes;
+  return qr_predict_users("qrlsh_predict_users", ratings, nu, nq, q_off, q_idx, q_milli, u_idx, u_val, ku, query_weight,
+                          user_weight, default_mean, sum_order, users, m, false, out, nq, flags_out,
+                          static_cast<hipStream_t>(stream));
+}

@@ -20,6 +20,10 @@
 //     emit      -- cells > t (fewer than k) and the slices' ties up to their quotas into the row's k candidates
 //                  (the one slice that takes only part of its ties takes them in column order, block-wide scan);
 //     finish    -- per row, bitonic sort of the <= k candidates in LDS, padded output.
+//
+// COMPACT (qrlsh_recommend_users): the rows come from a compact [m][stride] buffer of eligible-mode predictions
+// (0 where rated: predict_users_kernel) instead of the two matrices -- row x of the buffer is request x, a cell is
+// eligible when it is not 0, and no ratings are read; `users` only tells a bad id (avail -1) from a served one.
 #include "common.h"
 
 namespace {
@@ -58,8 +62,8 @@ __device__ __forceinline__ int32_t rc_key_value(uint64_t sk) { return (int32_t)(
 // and the calls go in column order (head, vector steps, tail; threads in order inside a call), so f may hold
 // block-wide scans.  Rows start anywhere: the body from the first 16-byte-aligned column on is read as int4 (the two
 // matrices have the same alignment phase: both base pointers are 16-byte aligned), the <= 3 columns before it by
-// slice 0, the <= 3 after it by slice S - 1.
-template <typename F>
+// slice 0, the <= 3 after it by slice S - 1.  RATED = false: there is no ratings row (rr is not read, r stays 0).
+template <bool RATED, typename F>
 __device__ __forceinline__ void rc_sweep(const int32_t *__restrict__ rr, const int32_t *__restrict__ pr, int64_t nq,
                                          int s, int S, F &&f) {
   const int tid = threadIdx.x;
@@ -71,22 +75,22 @@ __device__ __forceinline__ void rc_sweep(const int32_t *__restrict__ rr, const i
   if (s == 0 && a0 > 0) {
     const int n = tid < a0 ? 1 : 0;
     if (n) {
-      r[0] = rr[tid];
+      if (RATED) r[0] = rr[tid];
       p[0] = pr[tid];
     }
     f((int64_t)tid, r, p, n);
   }
-  const int4 *rv = reinterpret_cast<const int4 *>(rr + a0);
+  const int4 *rv = RATED ? reinterpret_cast<const int4 *>(rr + a0) : nullptr;
   const int4 *pv = reinterpret_cast<const int4 *>(pr + a0);
   for (int64_t v = vb; v < ve; v += 2 * RC_THREADS) {
     const int64_t va = v + tid, vc = v + RC_THREADS + tid;
     int4 ra = make_int4(0, 0, 0, 0), pa = ra, rc = ra, pc = ra;
     if (va < ve) {
-      ra = rv[va];
+      if (RATED) ra = rv[va];
       pa = pv[va];
     }
     if (vc < ve) {
-      rc = rv[vc];
+      if (RATED) rc = rv[vc];
       pc = pv[vc];
     }
     int r0[4] = {ra.x, ra.y, ra.z, ra.w}, p0[4] = {pa.x, pa.y, pa.z, pa.w};
@@ -99,7 +103,7 @@ __device__ __forceinline__ void rc_sweep(const int32_t *__restrict__ rr, const i
     const int n = t0 + tid < nq ? 1 : 0;
     r[0] = p[0] = 0;
     if (n) {
-      r[0] = rr[t0 + tid];
+      if (RATED) r[0] = rr[t0 + tid];
       p[0] = pr[t0 + tid];
     }
     f(t0 + tid, r, p, n);
@@ -141,9 +145,11 @@ __device__ __forceinline__ int rc_pow2(int n) {
 }
 
 // ---- rows form ---------------------------------------------------------------------------------------------------
+template <bool COMPACT>
 __global__ __launch_bounds__(RC_THREADS) void recommend_rows_kernel(const int32_t *__restrict__ ratings,
                                                                    const int32_t *__restrict__ pred, int64_t nu,
-                                                                   int64_t nq, const int32_t *__restrict__ users, int k,
+                                                                   int64_t nq, int64_t stride,
+                                                                   const int32_t *__restrict__ users, int k,
                                                                    int32_t *__restrict__ idx_out,
                                                                    int32_t *__restrict__ val_out,
                                                                    int32_t *__restrict__ avail_out) {
@@ -155,9 +161,9 @@ __global__ __launch_bounds__(RC_THREADS) void recommend_rows_kernel(const int32_
   if (threadIdx.x == 0) n_s = 0;
   __syncthreads();
   if (!bad) {
-    const int32_t *rr = ratings + u * nq, *pr = pred + u * nq;
+    const int32_t *rr = COMPACT ? nullptr : ratings + u * nq, *pr = pred + (COMPACT ? row : u) * stride;
     for (int64_t c = threadIdx.x; c < nq; c += RC_THREADS) {
-      const int32_t r = rr[c], p = pr[c];
+      const int32_t r = COMPACT ? 0 : rr[c], p = pr[c];
       if (r == 0 && p != 0) keys[atomicAdd(&n_s, 1u)] = rc_sort_key((uint32_t)p ^ 0x80000000u, (uint32_t)c);
     }
   }
@@ -172,9 +178,11 @@ __global__ __launch_bounds__(RC_THREADS) void recommend_rows_kernel(const int32_
 
 // ---- slice form --------------------------------------------------------------------------------------------------
 // pass 0: the window [lo_key, lo_key + RC_BINS); passes 1-3: the radix round st[row] names (rows not pending return)
+template <bool COMPACT>
 __global__ __launch_bounds__(RC_THREADS) void recommend_hist_kernel(const int32_t *__restrict__ ratings,
                                                                    const int32_t *__restrict__ pred, int64_t nu,
-                                                                   int64_t nq, const int32_t *__restrict__ users, int S,
+                                                                   int64_t nq, int64_t stride,
+                                                                   const int32_t *__restrict__ users, int S,
                                                                    int pass, uint32_t lo_key,
                                                                    const RowState *__restrict__ st,
                                                                    uint32_t *__restrict__ hist,
@@ -193,7 +201,8 @@ __global__ __launch_bounds__(RC_THREADS) void recommend_hist_kernel(const int32_
   __syncthreads();
   const int64_t u = users ? (int64_t)users[row] : row;
   if (u >= 0 && u < nu) {
-    rc_sweep(ratings + u * nq, pred + u * nq, nq, s, S, [&](int64_t, const int *r, const int *p, int n) {
+    rc_sweep<!COMPACT>(COMPACT ? nullptr : ratings + u * nq, pred + (COMPACT ? row : u) * stride, nq, s, S,
+                       [&](int64_t, const int *r, const int *p, int n) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         if (j < n && r[j] == 0 && p[j] != 0) {
@@ -339,9 +348,11 @@ __device__ __forceinline__ void rc_append(uint32_t *cnt, uint64_t *out, const ui
     if (mask >> j & 1u) out[pos++] = sk[j];
 }
 
+template <bool COMPACT>
 __global__ __launch_bounds__(RC_THREADS) void recommend_emit_kernel(const int32_t *__restrict__ ratings,
                                                                    const int32_t *__restrict__ pred, int64_t nq,
-                                                                   const int32_t *__restrict__ users, int k, int S,
+                                                                   int64_t stride, const int32_t *__restrict__ users,
+                                                                   int k, int S,
                                                                    RowState *__restrict__ st,
                                                                    const int32_t *__restrict__ tq,
                                                                    uint64_t *__restrict__ cand) {
@@ -358,7 +369,8 @@ __global__ __launch_bounds__(RC_THREADS) void recommend_emit_kernel(const int32_
   uint32_t *cnt = &st[row].cnt;
   uint64_t *out = cand + (size_t)row * k;
   uint64_t taken = 0;   // ordered ties seen so far (block-uniform)
-  rc_sweep(ratings + u * nq, pred + u * nq, nq, s, S, [&](int64_t col0, const int *r, const int *p, int n) {
+  rc_sweep<!COMPACT>(COMPACT ? nullptr : ratings + u * nq, pred + (COMPACT ? row : u) * stride, nq, s, S,
+                     [&](int64_t col0, const int *r, const int *p, int n) {
     uint64_t sk[4];
     uint32_t many = 0, mtie = 0;   // bit j: cell j goes in any order / is a tie of a partially taken slice
 #pragma unroll
@@ -429,6 +441,51 @@ RcLayout rc_layout(int64_t m, int32_t k, int64_t S) {
   L.total = L.tq + rc_round((size_t)m * S * sizeof(int32_t));
   return L;
 }
+
+// The selection over m rows, once the arguments are checked: the rows form (S == 0 or nq == 0; no workspace) or the
+// slice form over `ws` (rc_layout(m, k, S) bytes).  COMPACT = false: rows users[.] of ratings / pred, stride = nq;
+// true: rows 0 .. m - 1 of the compact buffer `pred`.
+template <bool COMPACT>
+int rc_select(const char *who, const int32_t *ratings, const int32_t *pred, int64_t stride, int64_t nu, int64_t nq,
+              const int32_t *users, int64_t m, int32_t k, int32_t lo, int64_t S, int32_t *idx_out, int32_t *val_out,
+              int32_t *avail_out, uint8_t *ws, hipStream_t st) {
+  if (S == 0 || nq == 0) {
+    // rows form (also every row of an empty matrix: avail 0, padded, bad ids flagged)
+    QR_LAUNCH("recommend_rows", recommend_rows_kernel<COMPACT>, dim3((unsigned)m), dim3(RC_THREADS), 0, st, ratings, pred,
+              nu, nq, stride, users, (int)k, idx_out, val_out, avail_out);
+    QR_LAUNCH_CHECK(who);
+    return QRLSH_OK;
+  }
+  const RcLayout L = rc_layout(m, k, S);
+  RowState *rs = reinterpret_cast<RowState *>(ws + L.state);
+  uint64_t *cand = reinterpret_cast<uint64_t *>(ws + L.cand);
+  uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.hist);
+  uint32_t *rowhist = reinterpret_cast<uint32_t *>(ws + L.rowhist);
+  int32_t *tq = reinterpret_cast<int32_t *>(ws + L.tq);
+  if (S > 1 && hipMemsetAsync(rowhist, 0, (size_t)m * RC_HSTRIDE * sizeof(uint32_t), st) != hipSuccess) {
+    qrlsh_set_error("%s: hipMemsetAsync failed", who);
+    return QRLSH_EHIP;
+  }
+  const unsigned groups = (unsigned)(m * S);
+  const uint32_t lo_key = (uint32_t)lo ^ 0x80000000u;
+  for (int pass = 0; pass < 4; ++pass) {
+    // pass 0: the window; 1-3: radix rounds, returning at once for every row the window resolved
+    QR_LAUNCH(pass ? "recommend_refine_hist" : "recommend_hist", recommend_hist_kernel<COMPACT>, dim3(groups),
+              dim3(RC_THREADS), 0, st, ratings, pred, nu, nq, stride, users, (int)S, pass, lo_key, (const RowState *)rs,
+              hist, rowhist);
+    QR_LAUNCH(pass ? "recommend_refine_threshold" : "recommend_threshold", recommend_threshold_kernel, dim3((unsigned)m),
+              dim3(RC_THREADS), 0, st, nu, users, (int)k, (int)S, pass, lo_key, rs, (const uint32_t *)hist, rowhist, tq);
+  }
+  QR_LAUNCH("recommend_emit", recommend_emit_kernel<COMPACT>, dim3(groups), dim3(RC_THREADS), 0, st, ratings, pred, nq,
+            stride, users, (int)k, (int)S, rs, (const int32_t *)tq, cand);
+  QR_LAUNCH("recommend_finish", recommend_finish_kernel, dim3((unsigned)m), dim3(RC_THREADS), 0, st, (int)k,
+            (const RowState *)rs, (const uint64_t *)cand, idx_out, val_out, avail_out);
+  QR_LAUNCH_CHECK(who);
+  return QRLSH_OK;
+}
+
+// qrlsh_recommend_users' compact rows: a stride of whole 16-byte vectors, so that every row starts on one
+int64_t rc_compact_stride(int64_t nq) { return (nq + 3) & ~(int64_t)3; }
 }  // namespace
 
 QRLSH_EXPORT size_t qrlsh_recommend_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices) {
@@ -460,42 +517,61 @@ QRLSH_EXPORT int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pre
                     (long long)S, (long long)RC_MAX_GROUPS);
     return QRLSH_EUNSUPPORTED;
   }
+  if (S > 0 && nq > 0) {
+    const size_t need = rc_layout(m, k, S).total;
+    if (!workspace || workspace_bytes < need) {
+      qrlsh_set_error("qrlsh_recommend_topk: needs %zu workspace bytes, got %zu", need, workspace ? workspace_bytes : 0);
+      return QRLSH_EWORKSPACE;
+    }
+  }
+  return rc_select<false>("qrlsh_recommend_topk", ratings, pred, nq, nu, nq, users, m, k, lo, S, idx_out, val_out,
+                          avail_out, static_cast<uint8_t *>(workspace), static_cast<hipStream_t>(stream));
+}
+
+// workspace: [compact eligible-mode rows: m x round_up(nq, 4) int32][the selection's workspace (slice form)]
+QRLSH_EXPORT size_t qrlsh_recommend_users_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices) {
+  if (m <= 0 || nq <= 0 || k < 1 || k > QRLSH_RECOMMEND_MAX_K || slices < 0 || slices > RC_MAXS) return 0;
+  const int64_t S = rc_slices(m, nq, slices);
+  if (m > RC_MAX_GROUPS || m * (S > 0 ? S : 1) > RC_MAX_GROUPS) return 0;
+  return rc_round((size_t)m * (size_t)rc_compact_stride(nq) * sizeof(int32_t)) + (S > 0 ? rc_layout(m, k, S).total : 0);
+}
+
+QRLSH_EXPORT int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
+                                       const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx,
+                                       const double *u_val, int32_t ku, double query_weight, double user_weight,
+                                       double default_mean, int32_t sum_order, const int32_t *users, int64_t m, int32_t k,
+                                       int32_t lo, int32_t slices, int32_t *idx_out, int32_t *val_out, int32_t *avail_out,
+                                       uint32_t *flags_out, void *workspace, size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(k >= 1 && k <= QRLSH_RECOMMEND_MAX_K, "qrlsh_recommend_users: k=%d outside 1..%d", k,
+               QRLSH_RECOMMEND_MAX_K);
+  QR_CHECK_ARG(m >= 0 && nu >= 0 && nq >= 0 && nq <= 2147483647ll, "qrlsh_recommend_users: bad sizes m=%lld nu=%lld nq=%lld",
+               (long long)m, (long long)nu, (long long)nq);
+  QR_CHECK_ARG(slices >= 0 && slices <= RC_MAXS, "qrlsh_recommend_users: slices=%d outside 0..%d", slices, RC_MAXS);
+  QR_CHECK_ARG(m == 0 || (idx_out && val_out && avail_out), "qrlsh_recommend_users: null output pointer");
+  const int64_t S = rc_slices(m, nq, slices);
+  if (m > RC_MAX_GROUPS || m * (S > 0 ? S : 1) > RC_MAX_GROUPS) {
+    qrlsh_set_error("qrlsh_recommend_users: m=%lld x slices=%lld above the %lld workgroups served", (long long)m,
+                    (long long)S, (long long)RC_MAX_GROUPS);
+    return QRLSH_EUNSUPPORTED;
+  }
+  const size_t need = qrlsh_recommend_users_workspace_bytes(m, nq, k, slices);
+  if (m > 0 && need > 0) {
+    QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_recommend_users: the workspace must be 16-byte aligned");
+    if (!workspace || workspace_bytes < need) {
+      qrlsh_set_error("qrlsh_recommend_users: needs %zu workspace bytes, got %zu", need, workspace ? workspace_bytes : 0);
+      return QRLSH_EWORKSPACE;
+    }
+  }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (S == 0 || nq == 0) {
-    // rows form (also every row of an empty matrix: avail 0, padded, bad ids flagged)
-    QR_LAUNCH("recommend_rows", recommend_rows_kernel, dim3((unsigned)m), dim3(RC_THREADS), 0, st, ratings, pred, nu, nq,
-              users, (int)k, idx_out, val_out, avail_out);
-    QR_LAUNCH_CHECK("qrlsh_recommend_topk");
-    return QRLSH_OK;
-  }
-  const RcLayout L = rc_layout(m, k, S);
-  if (!workspace || workspace_bytes < L.total) {
-    qrlsh_set_error("qrlsh_recommend_topk: needs %zu workspace bytes, got %zu", L.total, workspace ? workspace_bytes : 0);
-    return QRLSH_EWORKSPACE;
-  }
   uint8_t *ws = static_cast<uint8_t *>(workspace);
-  RowState *rs = reinterpret_cast<RowState *>(ws + L.state);
-  uint64_t *cand = reinterpret_cast<uint64_t *>(ws + L.cand);
-  uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.hist);
-  uint32_t *rowhist = reinterpret_cast<uint32_t *>(ws + L.rowhist);
-  int32_t *tq = reinterpret_cast<int32_t *>(ws + L.tq);
-  if (S > 1 && hipMemsetAsync(rowhist, 0, (size_t)m * RC_HSTRIDE * sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_recommend_topk: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
-  const unsigned groups = (unsigned)(m * S);
-  const uint32_t lo_key = (uint32_t)lo ^ 0x80000000u;
-  for (int pass = 0; pass < 4; ++pass) {
-    // pass 0: the window; 1-3: radix rounds, returning at once for every row the window resolved
-    QR_LAUNCH(pass ? "recommend_refine_hist" : "recommend_hist", recommend_hist_kernel, dim3(groups), dim3(RC_THREADS),
-              0, st, ratings, pred, nu, nq, users, (int)S, pass, lo_key, (const RowState *)rs, hist, rowhist);
-    QR_LAUNCH(pass ? "recommend_refine_threshold" : "recommend_threshold", recommend_threshold_kernel, dim3((unsigned)m),
-              dim3(RC_THREADS), 0, st, nu, users, (int)k, (int)S, pass, lo_key, rs, (const uint32_t *)hist, rowhist, tq);
-  }
-  QR_LAUNCH("recommend_emit", recommend_emit_kernel, dim3(groups), dim3(RC_THREADS), 0, st, ratings, pred, nq, users,
-            (int)k, (int)S, rs, (const int32_t *)tq, cand);
-  QR_LAUNCH("recommend_finish", recommend_finish_kernel, dim3((unsigned)m), dim3(RC_THREADS), 0, st, (int)k,
-            (const RowState *)rs, (const uint64_t *)cand, idx_out, val_out, avail_out);
-  QR_LAUNCH_CHECK("qrlsh_recommend_topk");
-  return QRLSH_OK;
+  const int64_t stride = rc_compact_stride(nq);
+  int32_t *rows = reinterpret_cast<int32_t *>(ws);
+  // the remaining checks (sizes, sum_order, pointers) are the sweep's, made before any device work as well; m = 0
+  // returns from there
+  const int rc = qr_predict_users("qrlsh_recommend_users", ratings, nu, nq, q_off, q_idx, q_milli, u_idx, u_val, ku,
+                                  query_weight, user_weight, default_mean, sum_order, users, m, true, rows, stride,
+                                  flags_out, st);
+  if (rc != QRLSH_OK || m == 0) return rc;
+  return rc_select<true>("qrlsh_recommend_users", nullptr, rows, stride, nu, nq, users, m, k, lo, S, idx_out, val_out,
+                         avail_out, nq > 0 ? ws + rc_round((size_t)m * (size_t)stride * sizeof(int32_t)) : nullptr, st);
 }

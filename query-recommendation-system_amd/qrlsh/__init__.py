@@ -36,7 +36,8 @@ from .pipeline import (  # noqa: F401
 )
 from .synth import synth_csr, poisson_cdf_u32  # noqa: F401
 from .answers import build_answer_index, encode_queries, answer_sets, AnswerIndex  # noqa: F401
-from .recommend import top_k  # noqa: F401
+from .recommend import top_k, for_users  # noqa: F401
+from .predict import predict_users, user_lists  # noqa: F401
 from .index import QueryIndex  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

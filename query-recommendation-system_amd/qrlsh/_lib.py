@@ -142,6 +142,13 @@ SIGNATURES = {
     "qrlsh_recommend_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "qrlsh_recommend_topk": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                             _vp]),
+    "qrlsh_predict_users_workspace_bytes": (_sz, [_i64, _i64]),
+    "qrlsh_predict_users": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                           ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_recommend_users_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "qrlsh_recommend_users": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
+                                             _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_center_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "qrlsh_user_gram_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_user_gram": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -113,3 +113,53 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
         bad = int(torch.nonzero(avail < 0)[0, 0].item())
         raise ValueError("user id %d (position %d) outside [0, %d)" % (int(u[bad].item()), bad, nu))
     return idx, val, avail
+
+
+def for_users(ratings, q_src, q_dst, q_milli, user_sims, users, k, lo=0, slices=0, sum_order="pairwise",
+              query_weight=None, user_weight=None, default_mean=None, device="cuda"):
+    """Top-k unrated queries of chosen users from the live lists, without a prediction matrix
+    (qrlsh_recommend_users): what top_k(ratings, fill_predictions(...), k, users=users) returns, output for output.
+    ratings, the lists, user_sims and users as predict.predict_users takes them (tensors are used where they are, host
+    data is uploaded); k, lo and slices as top_k takes them.  Served in row blocks under WORKSPACE_BUDGET.
+    -> (idx int32 (m, k), val int32 (m, k), avail int32 (m,)) device tensors.
+    Raises ValueError for a bad k, slices, lo, shape or sum_order, a list longer than 64, a neighbour index outside
+    [0, nq) and a user id outside [0, nu) (host ids before anything is uploaded; device ids and the lists through
+    the library's flags)."""
+    from . import predict
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
+        raise ValueError("k must be an integer in 1..%d, got %r" % (MAX_K, k))
+    k = int(k)
+    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= MAX_SLICES:
+        raise ValueError("slices must be an integer in 0..%d, got %r" % (MAX_SLICES, slices))
+    if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
+        raise ValueError("lo must be an int32, got %r" % (lo,))
+    a = predict.ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, users, sum_order)
+    m, nq = a.m, a.nq
+    lib = _lib.load()
+    a.upload(device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=device)
+    val = torch.empty((m, k), dtype=torch.int32, device=device)
+    avail = torch.empty((m,), dtype=torch.int32, device=device)
+    if m == 0:
+        return idx, val, avail
+    blk = m
+    while blk > 1 and int(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices))) > WORKSPACE_BUDGET:
+        blk = (blk + 1) // 2
+    ut = a.ut
+    if ut is None and blk < m:
+        ut = torch.arange(a.nu, dtype=torch.int32, device=device)
+    ws = torch.empty((max(int(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices))), 16),),
+                     dtype=torch.uint8, device=device)
+    starts = range(0, m, blk)
+    flags = torch.zeros((len(starts),), dtype=torch.int32, device=device)
+    args = a.lists_args(predict.QUERY_WEIGHT if query_weight is None else query_weight,
+                        predict.USER_WEIGHT if user_weight is None else user_weight,
+                        predict.DEFAULT_MEAN if default_mean is None else default_mean)
+    st = _stream()
+    for b, i0 in enumerate(starts):
+        i1 = min(m, i0 + blk)
+        _lib.check(lib.qrlsh_recommend_users(*args, None if ut is None else _ptr(ut[i0:i1]), i1 - i0, k, int(lo),
+                                             int(slices), _ptr(idx[i0:i1]), _ptr(val[i0:i1]), _ptr(avail[i0:i1]),
+                                             _ptr(flags[b:b + 1]), _ptr(ws), ws.numel(), st))
+    a.raise_flags(flags)
+    return idx, val, avail

@@ -434,6 +434,55 @@ class Recommender:
                       "available": int(avail[i])}
         return out
 
+    # ---- serving chosen users from the live lists: no prediction matrix -------------------------------------------
+    def _serving_inputs(self, sum_order, user_sim, ratings):
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        sum_order = self.sum_order if sum_order is None else sum_order
+        if sum_order not in ("pairwise", "sequential"):
+            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        if user_sim is None:
+            user_sim = self.compute_userSimilarities()
+        return lists, sum_order, user_sim, self.ratings if ratings is None else ratings
+
+    def recommend_users(self, users, k, sum_order=None, user_sim=None, ratings=None):
+        """recommend(compute_scores(reuse_lists=True)[1], k, users) for the requested users only, without the
+        prediction of every user's row: the query side comes from the live lists (current_query_similarities; ValueError
+        when there are none), so the answer is current after add_queries / remove_queries(update_lists=True).
+        user_sim: compute_userSimilarities' dict or qrlsh.user_lists' prepared tuple (default: computed here);
+        ratings: the utility matrix where the caller holds it, e.g. its device copy (default: self.ratings).
+        -> the dict recommend() returns.  Raises ValueError for a bad k, sum_order or user id."""
+        from qrlsh import recommend as rec
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= rec.MAX_K:
+            raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        idx, val, avail = rec.for_users(ratings, lists[0], lists[1], lists[2], user_sim, users, int(k),
+                                        sum_order=sum_order, query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT,
+                                        default_mean=DEFAULT_MEAN, device=self.device)
+        idx, val, avail = ops.to_host(idx), ops.to_host(val), ops.to_host(avail)
+        ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
+        out = {}
+        for i, u in enumerate(ids):
+            n = min(int(k), int(avail[i]))
+            out[u] = {"indexes": idx[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
+                      "available": int(avail[i])}
+        return out
+
+    def predict_users(self, users, sum_order=None, user_sim=None, ratings=None):
+        """DataFrame requested users x queriesIDs: their rows of compute_scores(reuse_lists=True)'s finalPredictions,
+        from the live lists (arguments as recommend_users takes them)."""
+        from qrlsh import predict
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        rows = predict.predict_users(ratings, lists[0], lists[1], lists[2], user_sim, users, QUERY_WEIGHT, USER_WEIGHT,
+                                     DEFAULT_MEAN, self.device, sum_order=sum_order)
+        ids = np.arange(self.usersIDs.size) if users is None else np.asarray(ops.to_host(users), dtype=np.int64)
+        return pd.DataFrame(ops.to_host(rows), index=self.usersIDs[ids], columns=self.queriesIDs).astype(int)
+
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
         """Interactive top-k prompt of recommender.py:345-381 (`ask` is injectable for tests)."""
         pred = predictions.to_numpy()
