@@ -262,7 +262,9 @@ int qrlsh_region_unique_count_regions3(const uint64_t *regions, const uint32_t *
  * says every bit of i above the low group_bits, and the finish reduces each word to that value first thing.  For
  * group_bits + id_bits <= 32 with a value that is never 0xFFFFFFFF (group_bits + id_bits < 32, or nids < 2^id_bits).
  * Same capacities, counts and tmp_regions as the 8-byte form (qrlsh_pair_regions_words / _cap / _count are in ENTRIES);
- * `regions` holds qrlsh_pair_regions_words uint32, `tmp` of the count still as many uint64. */
+ * `regions` holds qrlsh_pair_regions_words uint32, `tmp` of the count still as many uint64.  With two levels the
+ * first writes 5 bytes per entry into tmp_regions (16-byte aligned; same size as for the 8-byte form): the
+ * qrlsh_pair_regions_tmp_words values as uint32, then as many bytes with the low digit of each entry's region id. */
 int qrlsh_pair_regions_scatter32(const uint64_t *words, int64_t n, int32_t group_bits, int32_t id_bits, int64_t nids,
                                  double words_per_query, uint64_t *tmp_regions, uint32_t *regions, uint32_t *counts,
                                  uint32_t *overflow_out, void *stream);
