@@ -231,40 +231,31 @@ int qrlsh_region_unique_fill(const uint64_t *tmp, int64_t n, int32_t group_bits,
  * and nothing about the order inside a group, so the stable radix passes (a histogram pass, a scan and a scatter per 8
  * bits) are replaced by a most-significant-digit-first partition into FIXED regions with one atomic reservation per
  * (tile, digit): one read and one write of the words per level, two levels for up to 65536 regions.
- * qrlsh_pair_regions_scatter deals the n emitted words into regions[r * cap ..) (counts[r] words each; cap =
- * qrlsh_pair_regions_cap, buffers of qrlsh_pair_regions_words / _tmp_words words, counts of _count + 256 uint32);
+ * qrlsh_pair_regions_scatter32 deals the n emitted words into regions[r * cap ..) (counts[r] entries each; cap =
+ * qrlsh_pair_regions_cap, buffers of qrlsh_pair_regions_words / _tmp_words entries, counts of _count + 256 uint32);
  * words_per_query: what a query of the populated id range emits on average (0: n / nids) -- sizes the regions (3 x the
  * mean + 4096: i is the smaller id of a pair, so low ids carry up to twice the mean).  *overflow_out != 0: a region
  * outgrew its capacity (group with qrlsh_sort_u64 instead).  qrlsh_pair_regions_words returns 0 when the id space has
  * more than 65536 regions, or when a level's regions reach 2^32 words -- the scatter places words with 32-bit offsets,
  * so it needs na * cap_a < 2^32 (level 1: na = tmp_words / cap_a coarse digits) and 2^rb * cap_b < 2^32 (the final
  * regions of one coarse digit) -- (not served; the scatter rejects such sizes with QRLSH_EINVAL before any device
- * work; a large words_per_query hint reaches them first).  qrlsh_region_unique_count_regions is qrlsh_region_unique_count on those
- * regions (tmp: as many words as the region buffer); qrlsh_region_unique_fill follows it as usual. */
+ * work; a large words_per_query hint reaches them first).
+ * An entry of a region is the 32-bit value (i & (2^group_bits - 1)) << id_bits | j, not the pair word: the region already
+ * says every bit of i above the low group_bits, and the finish reduces each word to that value first thing.  So the form
+ * needs group_bits + id_bits <= 32 and a value that is never 0xFFFFFFFF, the finish's empty-slot marker (group_bits +
+ * id_bits < 32, or nids < 2^id_bits); both calls return QRLSH_EINVAL otherwise, before any device work.  `regions` holds
+ * qrlsh_pair_regions_words uint32; tmp_regions qrlsh_pair_regions_tmp_words uint64 (16-byte aligned; NULL when that is 0),
+ * of which the first of two levels uses 5 bytes per entry: the values as uint32, then as many bytes with the low digit
+ * of each entry's region id.
+ * qrlsh_region_unique_count_regions32 is qrlsh_region_unique_count on those regions (same group_bits / id_bits / nids,
+ * counts and cap; tmp: as many uint64 as the region buffer has entries) with one result buffer for both steps, so that
+ * the host reads back once: scatter_overflow is the DEVICE word the scatter wrote on the same stream; out3 (3 words) =
+ * {total, distinct-overflow (a region holds more distinct pairs than the finish can), capacity-overflow
+ * (*scatter_overflow)}.  qrlsh_region_unique_fill follows it as usual. */
 size_t qrlsh_pair_regions_words(int64_t n, int64_t nids, int32_t group_bits, double words_per_query);
 size_t qrlsh_pair_regions_tmp_words(int64_t n, int64_t nids, int32_t group_bits, double words_per_query);
 int64_t qrlsh_pair_regions_cap(int64_t n, int64_t nids, int32_t group_bits, double words_per_query);
 int64_t qrlsh_pair_regions_count(int64_t n, int64_t nids, int32_t group_bits, double words_per_query);
-int qrlsh_pair_regions_scatter(const uint64_t *words, int64_t n, int32_t group_bits, int64_t nids, double words_per_query,
-                               uint64_t *tmp_regions, uint64_t *regions, uint32_t *counts, uint32_t *overflow_out,
-                               void *stream);
-int qrlsh_region_unique_count_regions(const uint64_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
-                                      int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp, void *workspace,
-                                      size_t workspace_bytes, uint64_t *total_overflow_out, void *stream);
-/* The same with one result buffer for both steps, so that the host reads back once: scatter_overflow is the DEVICE
- * word qrlsh_pair_regions_scatter wrote on the same stream; out3 (3 words) = {total, distinct-overflow (a region holds
- * more distinct pairs than the finish can), capacity-overflow (*scatter_overflow)}. */
-int qrlsh_region_unique_count_regions3(const uint64_t *regions, const uint32_t *counts, int64_t cap, int64_t n,
-                                       int32_t group_bits, int32_t id_bits, int64_t nids, uint64_t *tmp, void *workspace,
-                                       size_t workspace_bytes, const uint32_t *scatter_overflow, uint64_t *out3,
-                                       void *stream);
-/* The final regions as 32-bit values (i & (2^group_bits - 1)) << id_bits | j instead of pair words: the region already
- * says every bit of i above the low group_bits, and the finish reduces each word to that value first thing.  For
- * group_bits + id_bits <= 32 with a value that is never 0xFFFFFFFF (group_bits + id_bits < 32, or nids < 2^id_bits).
- * Same capacities, counts and tmp_regions as the 8-byte form (qrlsh_pair_regions_words / _cap / _count are in ENTRIES);
- * `regions` holds qrlsh_pair_regions_words uint32, `tmp` of the count still as many uint64.  With two levels the
- * first writes 5 bytes per entry into tmp_regions (16-byte aligned; same size as for the 8-byte form): the
- * qrlsh_pair_regions_tmp_words values as uint32, then as many bytes with the low digit of each entry's region id. */
 int qrlsh_pair_regions_scatter32(const uint64_t *words, int64_t n, int32_t group_bits, int32_t id_bits, int64_t nids,
                                  double words_per_query, uint64_t *tmp_regions, uint32_t *regions, uint32_t *counts,
                                  uint32_t *overflow_out, void *stream);

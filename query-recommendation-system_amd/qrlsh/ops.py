@@ -411,14 +411,14 @@ def region_values_fit(group_bits, id_bits, nids):
     return group_bits + id_bits < 32 or (group_bits + id_bits == 32 and nids < (1 << id_bits))
 
 
-def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=0.0, values32=None):
+def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=0.0):
     """Sorted unique pairs straight from the emitted words: dealt into fixed regions of 2^group_bits queries by two
-    histogram-free partition steps (qrlsh_pair_regions_scatter: nothing inside a region is ordered -- the region
-    finish does not need it), then the region finish on those regions.  -> (pairs, "") or (None, why): "cap" when a
-    region outgrew its capacity or the buffers would be too large (the caller then groups by sorting), "distinct" when
-    a region holds more distinct pairs than the finish's LDS set (sorting by region would meet the same: the caller
-    sorts everything).  values32: the final regions as 32-bit values (default: whenever region_values_fit; half the
-    bytes of the last grouping level and of the finish's read), False: as 8-byte pair words."""
+    histogram-free partition steps (qrlsh_pair_regions_scatter32: nothing inside a region is ordered -- the region
+    finish does not need it; an entry is the 32-bit value (i's low group_bits, j)), then the region finish on those
+    regions.  -> (pairs, "") or (None, why): "cap" when a region outgrew its capacity or the buffers would be too large
+    (the caller then groups by sorting), "distinct" when a region holds more distinct pairs than the finish's LDS set
+    (sorting by region would meet the same: the caller sorts everything).  ValueError unless region_values_fit
+    (region_group_bits never returns such group bits)."""
     lib = _lib.load()
     _need(emitted, torch.int64, "emitted", 1)
     n = emitted.numel()
@@ -428,17 +428,15 @@ def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=
     wpq = float(words_per_query)
     words = lib.qrlsh_pair_regions_words(n, nids, group_bits, wpq)
     twords = lib.qrlsh_pair_regions_tmp_words(n, nids, group_bits, wpq)
-    if values32 is None:
-        values32 = region_values_fit(group_bits, id_bits, nids)
-    elif values32 and not region_values_fit(group_bits, id_bits, nids):
+    if not region_values_fit(group_bits, id_bits, nids):
         raise ValueError("group_bits=%d + id_bits=%d (nids=%d) do not fit a 32-bit region value" % (group_bits, id_bits, nids))
-    rbytes = 4 if values32 else 8       # per entry of the final regions; tmp (the finish's output) keeps pair words
-    if words == 0 or n >= (1 << 32) or words * (rbytes + 8) + twords * 8 > REGION_SCATTER_MAX_BYTES:
+    # per entry: 4 bytes of the final regions + 8 of tmp (the finish's output keeps pair words)
+    if words == 0 or n >= (1 << 32) or words * 12 + twords * 8 > REGION_SCATTER_MAX_BYTES:
         return None, "cap"          # (words == 0: more than 65536 regions -- two levels of 256 digits do not reach)
     cap = lib.qrlsh_pair_regions_cap(n, nids, group_bits, wpq)
     nreg = lib.qrlsh_pair_regions_count(n, nids, group_bits, wpq)
     try:      # fixed regions trade memory for passes: when the device is short of it, group by sorting instead
-        regions = torch.empty((words,), dtype=torch.int32 if values32 else torch.int64, device=dev)
+        regions = torch.empty((words,), dtype=torch.int32, device=dev)
         tmpr = torch.empty((twords,), dtype=torch.int64, device=dev) if twords else None
         tmp = torch.empty((words,), dtype=torch.int64, device=dev)
     except torch.cuda.OutOfMemoryError:
@@ -447,18 +445,14 @@ def region_unique_scattered(emitted, group_bits, id_bits, nids, words_per_query=
         return None, "cap"
     counts = torch.empty((nreg + 256,), dtype=torch.int32, device=dev)
     ovf = torch.empty((1,), dtype=torch.int32, device=dev)
-    if values32:
-        _lib.check(lib.qrlsh_pair_regions_scatter32(_ptr(emitted), n, int(group_bits), int(id_bits), int(nids), wpq, _ptr(tmpr),
-                                                    _ptr(regions), _ptr(counts), _ptr(ovf), _stream()))
-    else:
-        _lib.check(lib.qrlsh_pair_regions_scatter(_ptr(emitted), n, int(group_bits), int(nids), wpq, _ptr(tmpr), _ptr(regions),
-                                                  _ptr(counts), _ptr(ovf), _stream()))
+    _lib.check(lib.qrlsh_pair_regions_scatter32(_ptr(emitted), n, int(group_bits), int(id_bits), int(nids), wpq, _ptr(tmpr),
+                                                _ptr(regions), _ptr(counts), _ptr(ovf), _stream()))
     del tmpr
     ws = _ws(lib.qrlsh_region_unique_workspace_bytes(nids, group_bits), dev)
     tot = torch.empty(3, dtype=torch.int64, device=dev)
-    count = lib.qrlsh_region_unique_count_regions32 if values32 else lib.qrlsh_region_unique_count_regions3
-    _lib.check(count(_ptr(regions), _ptr(counts), cap, n, int(group_bits), int(id_bits), int(nids), _ptr(tmp), _ptr(ws),
-                     ws.numel(), _ptr(ovf), _ptr(tot), _stream()))
+    _lib.check(lib.qrlsh_region_unique_count_regions32(_ptr(regions), _ptr(counts), cap, n, int(group_bits), int(id_bits),
+                                                       int(nids), _ptr(tmp), _ptr(ws), ws.numel(), _ptr(ovf), _ptr(tot),
+                                                       _stream()))
     total, overflow, capped = tot.tolist()  # one read-back: the scatter's flag is the third word
     if capped:
         return None, "cap"
@@ -825,7 +819,7 @@ def score_pairs_rev(sig, norm2, pairs, id_bits, wide=None):
     return milli, ((rev, rdst) if wide else rev)
 
 
-SELECT_MAX_K = 256   # SEL_MAXK in csrc/pairs.hip
+SELECT_MAX_K = 256   # SEL_MAXK in csrc/topk.hip
 
 
 def topk_select(pairs, milli, rev, K, id_bits, nq):

@@ -83,7 +83,7 @@ def query_similarities(offsets, rows, table, b, K, timings=None, compact=None, w
     t0 = tick("candidates", t0)
     ib = ops.id_bits_for(nq)
     if topk == "select" and (K > ops.SELECT_MAX_K or pairs.numel() >= (1 << 31)):
-        topk = "sort"      # the select form's limits (csrc/pairs.hip: SEL_MAXK, 32-bit run starts)
+        topk = "sort"      # the select form's limits (csrc/topk.hip: SEL_MAXK, 32-bit run starts)
     if topk == "select":     # reverse edges sorted on j alone, every edge ranks itself in its query's two runs
         milli, rev = ops.score_pairs_rev(sig, norm2, pairs, ib, wide=wide_ids)
         t0 = tick("scoring", t0)

@@ -15,7 +15,7 @@ from oracle import oracle as O  # noqa: E402  (checker only)
 
 DEV = "cuda"
 GUARD = 64
-GUARD32, GUARD64 = 0x5A5A5A5A, 0x5A5A5A5A5A5A5A5A
+GUARD32 = 0x5A5A5A5A
 
 
 def dev(a):
@@ -63,26 +63,20 @@ class Shape:
         return (np.bincount(r).max() <= self.cap and np.bincount(r >> self.rb).max() <= self.cap_a)
 
 
-def scatter(words, sh, values32=True):
+def scatter(words, sh):
     """the direct call -> (region id << 32 | value of every entry, sorted; counts; overflow word); the guards behind
     regions and counts are checked here"""
     lib = _lib.load()
     n = len(words)
     wd = dev(words.view(np.int64))
     tmp = torch.full((sh.twords,), -1, dtype=torch.int64, device=DEV)                       # 0xFF bytes
-    if values32:
-        regions = torch.full((sh.words + GUARD,), GUARD32, dtype=torch.int32, device=DEV)
-    else:
-        regions = torch.full((sh.words + GUARD,), GUARD64, dtype=torch.int64, device=DEV)
+    regions = torch.full((sh.words + GUARD,), GUARD32, dtype=torch.int32, device=DEV)
     counts = torch.full((sh.nreg + 256 + GUARD,), GUARD32, dtype=torch.int32, device=DEV)
     ovf = torch.full((1 + GUARD,), GUARD32, dtype=torch.int32, device=DEV)
     P, st = ops._ptr, ops._stream()
-    if values32:
-        _lib.check(lib.qrlsh_pair_regions_scatter32(P(wd), n, sh.g, sh.ib, sh.nids, 0.0, P(tmp), P(regions), P(counts), P(ovf), st))
-    else:
-        _lib.check(lib.qrlsh_pair_regions_scatter(P(wd), n, sh.g, sh.nids, 0.0, P(tmp), P(regions), P(counts), P(ovf), st))
+    _lib.check(lib.qrlsh_pair_regions_scatter32(P(wd), n, sh.g, sh.ib, sh.nids, 0.0, P(tmp), P(regions), P(counts), P(ovf), st))
     torch.cuda.synchronize()
-    assert bool((regions[sh.words:] == (GUARD32 if values32 else GUARD64)).all()), "guard behind regions"
+    assert bool((regions[sh.words:] == GUARD32).all()), "guard behind regions"
     assert bool((counts[sh.nreg + 256:] == GUARD32).all()), "guard behind counts"
     assert bool((ovf[1:] == GUARD32).all()), "guard behind the overflow word"
     overflow = int(ovf[0].item())
@@ -93,11 +87,7 @@ def scatter(words, sh, values32=True):
     held = torch.arange(sh.cap, device=DEV)[None, :] < cnt[:, None]
     vals = regions[:sh.words].view(sh.nreg, sh.cap)[held]                                   # region after region
     rid = torch.repeat_interleave(torch.arange(sh.nreg, device=DEV), cnt)
-    if values32:
-        v = vals.to(torch.int64) & 0xFFFFFFFF
-    else:   # the 8-byte form keeps the pair word: its region must be the one it lies in, the rest reduces to the value
-        assert torch.equal(vals >> (32 + sh.g), rid)
-        v = (((vals >> 32) & ((1 << sh.g) - 1)) << sh.ib) | (vals & 0xFFFFFFFF)
+    v = vals.to(torch.int64) & 0xFFFFFFFF
     got = np.sort(((rid << 32) | v).cpu().numpy().view(np.uint64))
     return got, cnt.cpu().numpy(), overflow
 
@@ -110,17 +100,13 @@ def expected(words, sh):
     return np.sort((r << np.uint64(32)) | v), np.bincount(r.astype(np.int64), minlength=sh.nreg)
 
 
-def check(words, sh, both=False):
+def check(words, sh):
     want, want_counts = expected(words, sh)
     got, counts, overflow = scatter(words, sh)
     assert overflow == 0
     assert int(counts.sum()) == len(words)
     assert np.array_equal(counts, want_counts)
     assert np.array_equal(got, want)
-    if both:
-        got64, counts64, overflow64 = scatter(words, sh, values32=False)
-        assert overflow64 == 0 and np.array_equal(counts64, want_counts)
-        assert np.array_equal(got64, got)
 
 
 @pytest.mark.parametrize("n", [1, 8191, 8192, 8193, 200_003])
@@ -133,7 +119,7 @@ def test_digits_narrower_than_a_byte_in_both_levels(n):
     assert (big.cap_a, big.cap) == (103_936, 5_568)        # (3 * 480 + 4096 = 5 536, rounded up to a multiple of 64)
     words = random_words(rng, n, sh.nids)
     assert sh.fits(words)
-    check(words, sh, both=True)
+    check(words, sh)
 
 
 def test_all_32_value_bits_and_full_byte_tails():

@@ -1,9 +1,7 @@
-"""The fixed-region de-duplication with regions of 32-bit values (qrlsh_pair_regions_scatter32 +
-qrlsh_region_unique_count_regions32) beside the 8-byte form (qrlsh_pair_regions_scatter +
-qrlsh_region_unique_count_regions3), both with ONE three-word read-back: the unique pairs of each against the oracle's
-sorted unique words, and the two forms against each other on the same input -- at the empty-marker boundary
-(2^24 - 1 and 2^24 ids at g = 8), with ids too wide for the value, with one grouping level, and with a region filled to
-its capacity and one word beyond."""
+"""The fixed-region de-duplication (regions of 32-bit values: qrlsh_pair_regions_scatter32 +
+qrlsh_region_unique_count_regions32, with ONE three-word read-back): its unique pairs against the oracle's sorted unique
+words -- at the empty-marker boundary (2^24 - 1 and 2^24 ids at g = 8), with ids too wide for the value, with one
+grouping level, and with a region filled to its capacity and one word beyond."""
 import numpy as np
 import pytest
 import torch
@@ -37,16 +35,13 @@ def random_words(rng, n, nids, dup=3):
     return w[rng.integers(0, len(w), size=n)]
 
 
-def both_forms(words, g, ib, nids, wpq=0.0):
-    """-> the unique pairs of the 4-byte form, after checking them and the 8-byte form's against the oracle"""
+def scattered(words, g, ib, nids, wpq=0.0):
+    """-> the unique pairs of the fixed-region form, after checking them against the oracle"""
     want = O.sort_unique(words)
-    got32, why32 = ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids, wpq, values32=True)
-    got64, why64 = ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids, wpq, values32=False)
-    assert why32 == "" and why64 == "", (why32, why64)
-    assert np.array_equal(u64(got32), want)
-    assert np.array_equal(u64(got64), want)
-    assert torch.equal(got32, got64)
-    return got32
+    got, why = ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids, wpq)
+    assert why == "", why
+    assert np.array_equal(u64(got), want)
+    return got
 
 
 def test_largest_value_beside_the_empty_marker():
@@ -60,7 +55,7 @@ def test_largest_value_beside_the_empty_marker():
     edge = pack([top - 1, top - 1, top - 255, 0, 255, 256, top - 256], [top, top, top, top, top, top, top - 1])
     words = np.concatenate([random_words(rng, 2_000_000, nids), edge, edge[:3]])
     words = words[rng.permutation(len(words))]
-    got = both_forms(words, g, ib, nids)
+    got = scattered(words, g, ib, nids)
     assert int(u64(got)[-1]) == ((top - 1) << 32 | top)
     st = {}
     out = ops.unique_pairs(dev(words.view(np.int64)), nids, st)
@@ -69,7 +64,9 @@ def test_largest_value_beside_the_empty_marker():
 
 
 def test_two_to_the_24_ids_leave_no_spare_value_at_g_8():
-    """2^24 ids: (255, 2^24 - 1) would BE the marker, so neither form serves g = 8 and the step groups by 7 bits"""
+    """2^24 ids: (255, 2^24 - 1) would BE the marker, so g = 8 is refused -- by ops and by both library calls, before
+    any device work -- and the step groups by 7 bits"""
+    lib = _lib.load()
     rng = np.random.default_rng(2)
     nids, ib = 1 << 24, 24
     assert ops.id_bits_for(nids) == ib
@@ -77,9 +74,11 @@ def test_two_to_the_24_ids_leave_no_spare_value_at_g_8():
     top = nids - 1
     words = np.concatenate([random_words(rng, 1_000_000, nids), pack([top - 1, 0, top - 255], [top, top, top])])
     with pytest.raises(ValueError):
-        ops.region_unique_scattered(dev(words.view(np.int64)), 8, ib, nids, values32=True)
-    with pytest.raises(_lib.QrlshError):     # the 8-byte finish keeps its own check of the marker
-        ops.region_unique_scattered(dev(words.view(np.int64)), 8, ib, nids, values32=False)
+        ops.region_unique_scattered(dev(words.view(np.int64)), 8, ib, nids)
+    # the library's own refusal: both calls check before any device work, so dummy non-null pointers do
+    p, n = 64, len(words)
+    assert lib.qrlsh_pair_regions_scatter32(p, n, 8, ib, nids, 0.0, p, p, p, p, None) == _lib.QRLSH_EINVAL
+    assert lib.qrlsh_region_unique_count_regions32(p, p, 4096, n, 8, ib, nids, p, p, 1 << 30, p, p, None) == _lib.QRLSH_EINVAL
     assert ops.region_group_bits(ib, nids, len(words) / nids) == 7
     st = {}
     out = ops.unique_pairs(dev(words.view(np.int64)), nids, st)
@@ -93,13 +92,12 @@ def test_ids_of_25_bits_do_not_take_the_value_form_at_g_8():
     assert ops.id_bits_for(nids) == ib and not ops.region_values_fit(8, ib, nids)
     words = random_words(rng, 500_000, nids)
     with pytest.raises(ValueError):
-        ops.region_unique_scattered(dev(words.view(np.int64)), 8, ib, nids, values32=True)
+        ops.region_unique_scattered(dev(words.view(np.int64)), 8, ib, nids)
     # what the step does with such ids: 7 group bits are 2^18 regions, more than two levels of 256 digits reach --
-    # the grouping is not served in either form and the words are grouped by sorting, with the same result
+    # the grouping is not served and the words are grouped by sorting, with the same result
     g = ops.region_group_bits(ib, nids, len(words) / nids)
     assert g == 7
-    for v32 in (True, False):
-        assert ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids, values32=v32) == (None, "cap")
+    assert ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids) == (None, "cap")
     out = ops.unique_pairs(dev(words.view(np.int64)), nids, {})
     assert np.array_equal(u64(out), O.sort_unique(words))
 
@@ -113,7 +111,7 @@ def test_one_grouping_level(nids, g):
     words = random_words(rng, 300_000, nids, dup=5)
     assert lib.qrlsh_pair_regions_tmp_words(len(words), nids, g, 0.0) == 0
     assert lib.qrlsh_pair_regions_count(len(words), nids, g, 0.0) <= 256
-    both_forms(words, g, ib, nids)
+    scattered(words, g, ib, nids)
 
 
 def test_two_grouping_levels_and_popular_queries():
@@ -133,12 +131,12 @@ def test_two_grouping_levels_and_popular_queries():
     per_region = np.bincount((words >> np.uint64(32 + g)).astype(np.int64))
     assert per_region.max() <= lib.qrlsh_pair_regions_cap(len(words), nids, g, wpq)
     assert len(np.unique(words[(words >> np.uint64(32 + g)) == np.uint64(0)])) > 5_400
-    both_forms(words, g, ib, nids, wpq=wpq)
+    scattered(words, g, ib, nids, wpq=wpq)
 
 
 def test_a_region_at_its_capacity_and_one_word_beyond():
-    """region 3 of a one-level grouping receives exactly its capacity in words (both forms serve it), then one word
-    more (both report "cap" through the one read-back, never a wrong list)"""
+    """region 3 of a one-level grouping receives exactly its capacity in words (it is served), then one word
+    more ("cap" through the one read-back, never a wrong list)"""
     lib = _lib.load()
     rng = np.random.default_rng(6)
     nids, g, n = 50_000, 8, 200_000
@@ -155,10 +153,9 @@ def test_a_region_at_its_capacity_and_one_word_beyond():
         assert len(words) == n and int(np.count_nonzero((words >> np.uint64(32 + g)) == np.uint64(3))) == m
         words = words[rng.permutation(n)]
         if extra == 0:
-            both_forms(words, g, ib, nids)
+            scattered(words, g, ib, nids)
         else:
-            for v32 in (True, False):
-                assert ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids, values32=v32) == (None, "cap")
+            assert ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids) == (None, "cap")
 
 
 def test_more_distinct_pairs_than_the_finish_holds_is_reported_in_the_same_read_back():
@@ -168,8 +165,7 @@ def test_more_distinct_pairs_than_the_finish_holds_is_reported_in_the_same_read_
     one = pack(np.full(60_000, 1500), rng.integers(1501, nids, size=60_000))      # ~58 000 distinct partners of one query
     words = np.concatenate([random_words(rng, 400_000, nids - 1), one])
     words = words[rng.permutation(len(words))]
-    for v32 in (True, False):
-        got = ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids - 1, len(words) / 3000, values32=v32)
-        assert got == (None, "distinct") or got == (None, "cap")
+    got = ops.region_unique_scattered(dev(words.view(np.int64)), g, ib, nids - 1, len(words) / 3000)
+    assert got == (None, "distinct") or got == (None, "cap")
     out = ops.unique_pairs(dev(words.view(np.int64)), nids - 1, {})
     assert np.array_equal(u64(out), O.sort_unique(words))

@@ -1,4 +1,4 @@
-"""Run bounds of the select form of the top-K (csrc/pairs.hip: edge_bounds_kernel takes a run of consecutive words per
+"""Run bounds of the select form of the top-K (csrc/topk.hip: edge_bounds_kernel takes a run of consecutive words per
 thread, edge_bounds_fix_kernel fills the long stretches without edges, topk_len_kernel leaves its workgroups' own
 scans and totals for the offsets) through ops.topk_select, against the oracle's top-K: list lengths on every side of
 the per-thread run, a change of source on every word and none at all, stretches without edges of exactly the walked
@@ -13,7 +13,7 @@ from qrlsh import ops  # noqa: E402
 from oracle import oracle as O  # noqa: E402  (checker only)
 
 DEV = "cuda"
-SEL_GAP = 32     # csrc/pairs.hip: stretches of queries without edges up to here are walked, longer ones searched
+SEL_GAP = 32     # csrc/topk.hip: stretches of queries without edges up to here are walked, longer ones searched
 RUN = 4          # words a thread of edge_bounds_kernel takes (EB_RUN)
 
 

@@ -112,12 +112,12 @@ def test_host_size_rules():
 
 def test_pair_region_offsets_stay_below_2_pow_32():
     """pair_group_scatter_kernel places a word at digit * cap + position in 32 bits: with two levels of 256 digits
-    (nids = 2^24 at group_bits = 8) a large words-per-query hint grows the region capacities until a level's regions
+    (nids = 2^24 - 1 at group_bits = 8: 65 536 regions, and a 32-bit value that is never the empty marker) a large words-per-query hint grows the region capacities until a level's regions
     pass 2^32 words.  From the first such hint on, qrlsh_pair_regions_words says "not served" (0, the caller sorts
     instead) and the scatter refuses the sizes -- before any device work, so host buffers and no GPU do here."""
     from qrlsh import _lib
     lib = _lib.load()
-    n, nids, g = 100_000_000, 1 << 24, 8
+    n, nids, g, ib = 100_000_000, (1 << 24) - 1, 8, 24
     assert lib.qrlsh_pair_regions_count(n, nids, g, 0.0) == 65536
 
     def breaks(hint):   # level 1: na x cap_a (na = 256 coarse digits); level 2: 2^8 x cap_b per coarse digit
@@ -134,7 +134,8 @@ def test_pair_region_offsets_stay_below_2_pow_32():
     assert lib.qrlsh_pair_regions_words(n, nids, g, float(lo)) == 65536 * lib.qrlsh_pair_regions_cap(n, nids, g, float(lo))
     counts = np.zeros(65536 + 256, dtype=np.uint32)
     ovf = np.zeros(1, dtype=np.uint32)
-    rc = lib.qrlsh_pair_regions_scatter(None, n, g, nids, float(hi), None, None, counts.ctypes.data, ovf.ctypes.data, None)
+    rc = lib.qrlsh_pair_regions_scatter32(None, n, g, ib, nids, float(hi), None, None, counts.ctypes.data, ovf.ctypes.data,
+                                          None)
     assert rc == _lib.QRLSH_EINVAL
     assert b"2^32" in lib.qrlsh_last_error()
     assert not counts.any() and not ovf.any()          # nothing was touched
@@ -144,9 +145,26 @@ def test_pair_region_offsets_stay_below_2_pow_32():
     h1 = next(h for h in range(1, 1 << 16, 7) if 256 * lib.qrlsh_pair_regions_cap(n1, nids1, g, float(h)) >= 1 << 32)
     assert lib.qrlsh_pair_regions_words(n1, nids1, g, float(h1)) == 0
     assert lib.qrlsh_pair_regions_words(n1, nids1, g, float(h1 - 7)) > 0
-    rc = lib.qrlsh_pair_regions_scatter(None, n1, g, nids1, float(h1), None, None, counts.ctypes.data, ovf.ctypes.data,
-                                        None)
+    rc = lib.qrlsh_pair_regions_scatter32(None, n1, g, 16, nids1, float(h1), None, None, counts.ctypes.data, ovf.ctypes.data,
+                                          None)
     assert rc == _lib.QRLSH_EINVAL and b"2^32" in lib.qrlsh_last_error()
+
+
+def test_region_group_bits_always_fit_the_32_bit_value():
+    """what the single fixed-region form rests on: whenever region_group_bits serves an id space, the value (i's low g
+    bits, j) fits 32 bits and is never the finish's empty-slot marker -- it lowers g in exactly the case where
+    region_values_fit fails (g + id_bits == 32 with nids == 2^id_bits)"""
+    from qrlsh import ops
+    served = 0
+    for bits in range(1, 33):
+        for nq in {1 << bits, (1 << bits) - 1, (1 << (bits - 1)) + 1, (1 << (bits - 1)) + 2}:
+            ib = ops.id_bits_for(nq)
+            for wpq in (0, 1, 19, 100, 2000, 5000):
+                g = ops.region_group_bits(ib, nq, wpq)
+                if g is not None:
+                    served += 1
+                    assert ops.region_values_fit(g, ib, nq), (nq, ib, wpq, g)
+    assert served > 300      # (ids up to 29 bits leave three group bits or more)
 
 
 def test_bucket_case_builders_build_what_they_say():

@@ -3,7 +3,7 @@
     python tools/pair_group_probe.py [nq = 10000000] [reps = 10]
 MinHash + bucket emit of the standard workload once, then qrlsh_pair_regions_scatter32 `reps` times on those words with
 the step's own group bits and capacities; prints min / median / max ms per call (events round the call).  The library
-is the tree's, or the one QRLSH_LIB names: build sort.hip with -DQR_PG_IPT_N1=.. -DQR_PG_IPT_N2=.. into another
+is the tree's, or the one QRLSH_LIB names: build dedup.hip with -DQR_PG_IPT_N1=.. -DQR_PG_IPT_N2=.. into another
 libqrlsh.so to compare tile sizes.  Per-level times: run it under `rocprofv3 --kernel-trace --stats` (two launches of
 pair_group_scatter_kernel per call, 2 warm-up calls + reps)."""
 import os, sys
