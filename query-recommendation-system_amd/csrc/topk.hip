@@ -18,6 +18,8 @@
 // (j << 11 | inv, i) for ids that do not fit.
 #include "common.h"
 
+#include <type_traits>
+
 __device__ static inline uint32_t rev_src(uint64_t w, int id_bits, bool wide) {
   return (uint32_t)(wide ? w >> 11 : w >> (id_bits + 11));
 }
@@ -100,6 +102,7 @@ constexpr int SEL_SHORT = 16;   // lists up to here: one 16-lane group per query
 constexpr int SEL_LONG = 64;    // lists up to here: one wave per query; beyond: the histogram kernel
 constexpr int SEL_MAXK = 256;   // largest K of the select form (the sort form has no limit)
 constexpr int SEL_LIST_GRID = 1024;
+constexpr int64_t SEL_FORK_NQ = 1 << 22;   // from here on the medium and long lists run beside the short ones (qrlsh_topk_select_fill)
 
 // list lengths -> output counts (min(K, length)); queries whose list does not fit a 16-lane group are put on
 // the medium (17 .. 64) or the long list.  A workgroup classifies LEN_QPB consecutive queries, collects its two
@@ -186,17 +189,38 @@ __global__ __launch_bounds__(256) void topk_off_add_kernel(uint64_t *__restrict_
     if (q0 + k < m) off[q0 + k] += add;
 }
 
-// (inv << 32 | dst) of element x of a query's list: x < nr -> reverse run, else forward run
-__device__ static inline uint64_t sel_key(uint32_t x, uint32_t rs, uint32_t nr, uint32_t fs,
-                                          const uint64_t *__restrict__ pairs, const int32_t *__restrict__ milli,
-                                          const uint64_t *__restrict__ rev, const uint32_t *__restrict__ rdst,
-                                          int id_bits, uint64_t idm) {
-  if (x < nr) {
-    const uint64_t w = rev[rs + x];
-    return rdst ? (w & 0x7FFull) << 32 | rdst[rs + x] : ((w >> id_bits) & 0x7FFull) << 32 | (w & idm);
-  }
-  const uint32_t y = fs + (x - nr);
-  return (uint64_t)(uint32_t)(1000 - milli[y]) << 32 | (uint32_t)pairs[y];
+// Element x of a query's list of `len` entries: x < nr -> reverse run, else forward run.  sel_load fetches it and
+// sel_key turns what was fetched into the key (inv << 32 | dst); x >= len -> ~0, the key of an absent element (never
+// smaller than a real one; its inv is no value).
+// One pair of 4-byte loads, without a branch, serves either run: (lo, hi) = the two halves of the reverse word, or
+// (the low half of the pair word = dst, milli); an absent element reads the first reverse word (n > 0).  A caller
+// that takes several keys (the queries of a 16-lane group, the register batch of a long list) calls sel_load for all
+// of them and only then sel_key: all their loads are in flight at once, two registers per key.  Written as one
+// function, `if (x < nr) return ...; return ...;`, the compiler waited for each key inside its branch: the keys of
+// one thread came one memory round trip after the other.
+struct SelRaw {
+  uint32_t lo, hi, wd;
+};
+template <bool WIDE>
+__device__ static inline SelRaw sel_load(uint32_t x, uint32_t len, uint32_t rs, uint32_t nr, uint32_t fs,
+                                         const uint64_t *__restrict__ pairs, const int32_t *__restrict__ milli,
+                                         const uint64_t *__restrict__ rev, const uint32_t *__restrict__ rdst) {
+  const bool inr = x < nr, inf = !inr && x < len;
+  const uint64_t r = inr ? (uint64_t)(rs + x) : 0ull, y = (uint64_t)(fs + (x - nr));
+  const uint32_t *blo = inf ? reinterpret_cast<const uint32_t *>(pairs) : reinterpret_cast<const uint32_t *>(rev);
+  const uint32_t *bhi = inf ? reinterpret_cast<const uint32_t *>(milli) : reinterpret_cast<const uint32_t *>(rev);
+  SelRaw v;
+  v.lo = blo[inf ? 2 * y : 2 * r];
+  v.hi = bhi[inf ? y : 2 * r + 1];
+  v.wd = WIDE ? rdst[r] : 0u;
+  return v;
+}
+template <bool WIDE>
+__device__ static inline uint64_t sel_key(SelRaw v, uint32_t x, uint32_t len, uint32_t nr, int id_bits, uint64_t idm) {
+  const uint64_t w = (uint64_t)v.hi << 32 | v.lo;
+  const uint64_t kr = WIDE ? (w & 0x7FFull) << 32 | v.wd : ((w >> id_bits) & 0x7FFull) << 32 | (w & idm);
+  const uint64_t kf = (uint64_t)(uint32_t)(1000 - (int32_t)v.hi) << 32 | v.lo;
+  return x < nr ? kr : x < len ? kf : ~0ull;
 }
 
 // 64-bit value of the lane S positions further round this lane's 16-lane row (DPP row_ror)
@@ -215,6 +239,7 @@ template <int S> __device__ static inline uint32_t row_rank(uint64_t mine) {
 // lane's rank is the number of smaller keys met while the row rotates past it (15 DPP steps, no memory traffic).
 // Absent elements carry the key ~0: never smaller than a real one.
 constexpr int SEL_QPG = 4;  // queries per 16-lane group: their loads are issued together (latency-bound otherwise)
+template <bool WIDE>
 __global__ __launch_bounds__(256) void topk_select_short_kernel(const uint64_t *__restrict__ pairs,
                                                                 const int32_t *__restrict__ milli,
                                                                 const uint64_t *__restrict__ rev,
@@ -230,27 +255,33 @@ __global__ __launch_bounds__(256) void topk_select_short_kernel(const uint64_t *
   const uint32_t l = threadIdx.x & 15;
   const uint64_t idm = id_bits >= 32 ? 0xFFFFFFFFull : (1ull << id_bits) - 1ull;
   // query c of this group: group + c * ngroups (consecutive groups -> consecutive queries: the start arrays are read in runs)
-  uint32_t fs[SEL_QPG], rs[SEL_QPG], nr[SEL_QPG], len[SEL_QPG];
+  // Both load levels without a branch between the queries: a query past the end reads the last query's entries
+  // (and gets length 0), so the 5 * SEL_QPG loads of the first level and then the keys of the second are each
+  // issued together.  With `if (q < nq) { loads }` per query the compiler waited inside every branch.
+  uint32_t fs[SEL_QPG], fe[SEL_QPG], rs[SEL_QPG], re[SEL_QPG], nr[SEL_QPG], len[SEL_QPG];
   uint64_t o0[SEL_QPG], mine[SEL_QPG];
+  SelRaw raw[SEL_QPG];
 #pragma unroll
   for (int c = 0; c < SEL_QPG; ++c) {
-    const int64_t q = group + (int64_t)c * ngroups;
-    uint32_t nf = 0;
-    fs[c] = rs[c] = nr[c] = 0;
-    o0[c] = 0;
-    if (q < nq) {
-      fs[c] = fstart[q];
-      nf = fstart[q + 1] - fs[c];
-      rs[c] = rstart[q];
-      nr[c] = rstart[q + 1] - rs[c];
-      o0[c] = off[q];
-    }
-    len[c] = nf + nr[c];
-    if (len[c] > (uint32_t)SEL_SHORT) len[c] = 0;  // another kernel's query
+    const int64_t q = group + (int64_t)c * ngroups, qc = q < nq ? q : nq - 1;
+    fs[c] = fstart[qc];
+    fe[c] = fstart[qc + 1];
+    rs[c] = rstart[qc];
+    re[c] = rstart[qc + 1];
+    o0[c] = off[qc];
+  }
+#pragma unroll
+  for (int c = 0; c < SEL_QPG; ++c) {
+    nr[c] = re[c] - rs[c];
+    len[c] = (fe[c] - fs[c]) + nr[c];
+    // (past the end, or another kernel's query)
+    if (group + (int64_t)c * ngroups >= nq || len[c] > (uint32_t)SEL_SHORT) len[c] = 0;
   }
 #pragma unroll
   for (int c = 0; c < SEL_QPG; ++c)
-    mine[c] = l < len[c] ? sel_key(l, rs[c], nr[c], fs[c], pairs, milli, rev, rdst, id_bits, idm) : ~0ull;
+    raw[c] = sel_load<WIDE>(l, len[c], rs[c], nr[c], fs[c], pairs, milli, rev, rdst);
+#pragma unroll
+  for (int c = 0; c < SEL_QPG; ++c) mine[c] = sel_key<WIDE>(raw[c], l, len[c], nr[c], id_bits, idm);
 #pragma unroll
   for (int c = 0; c < SEL_QPG; ++c) {
     const uint32_t rank = row_rank<15>(mine[c]);  // executed by every lane (all lanes of the wave are active here)
@@ -264,6 +295,7 @@ __global__ __launch_bounds__(256) void topk_select_short_kernel(const uint64_t *
 }
 
 // Lists of 17 .. 64 neighbours: one wave per query, from a fixed grid that walks the medium list.
+template <bool WIDE>
 __global__ __launch_bounds__(256) void topk_select_medium_kernel(const uint64_t *__restrict__ pairs,
                                                                  const int32_t *__restrict__ milli,
                                                                  const uint64_t *__restrict__ rev,
@@ -284,7 +316,7 @@ __global__ __launch_bounds__(256) void topk_select_medium_kernel(const uint64_t 
     const uint32_t q = medlist[e];
     const uint32_t fs = fstart[q], nf = fstart[q + 1] - fs, rs = rstart[q], nr = rstart[q + 1] - rs;
     const uint32_t len = nf + nr;  // 17 .. 64
-    const uint64_t mine = (uint32_t)lane < len ? sel_key(lane, rs, nr, fs, pairs, milli, rev, rdst, id_bits, idm) : ~0ull;
+    const uint64_t mine = sel_key<WIDE>(sel_load<WIDE>(lane, len, rs, nr, fs, pairs, milli, rev, rdst), lane, len, nr, id_bits, idm);
     uint32_t rank = 0;
 #pragma unroll 9
     for (int s = 1; s < WAVE; ++s) {  // every other lane's key once (absent elements: ~0, never smaller)
@@ -306,7 +338,15 @@ __global__ __launch_bounds__(256) void topk_select_medium_kernel(const uint64_t 
 // with inv < v* are all kept, and of those with inv == v* the first K - (number below) in list order -- the
 // list order (reverse run, then forward run) IS ascending neighbour id, the tie-break.  The <= K survivors then
 // rank themselves among each other.
-__global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *__restrict__ pairs,
+// The wave holds a register batch of SEL_LK keys per lane (element base + k * 64 + lane in kk[k]): all SEL_LK loads
+// of a batch are issued before the first histogram add, and a list of up to SEL_BATCH entries is read from memory
+// ONCE -- the sweep in list order and the by_id rounds then read the registers.  A longer list is worked in
+// batches of SEL_BATCH in every sweep (re-read, SEL_LK loads in flight).  One load per lane in flight and an LDS
+// atomic behind each made every sweep a chain of len / 64 memory round trips.
+constexpr int SEL_LK = 16;
+constexpr int SEL_BATCH = WAVE * SEL_LK;
+template <bool WIDE>
+__global__ __launch_bounds__(256, 4) void topk_select_long_kernel(const uint64_t *__restrict__ pairs,
                                                                const int32_t *__restrict__ milli,
                                                                const uint64_t *__restrict__ rev,
                                                                const uint32_t *__restrict__ rdst,
@@ -319,7 +359,8 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
                                                                int32_t *__restrict__ dst_out,
                                                                int32_t *__restrict__ milli_out, int by_id) {
   constexpr int NV = 2048;  // inv in [0, 2000]
-  __shared__ uint32_t hist_all[4][NV];
+  constexpr int OWN = NV / WAVE;  // lane l owns values [32 l, 32 l + 32)
+  __shared__ __align__(16) uint32_t hist_all[4][NV];
   __shared__ uint64_t keep_all[4][SEL_MAXK];
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x >> 6;
   uint32_t *hist = hist_all[wv];
@@ -328,18 +369,50 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
   const unsigned long long nl = nlists[1];
   const unsigned long long nwaves = (unsigned long long)gridDim.x * 4;
   const uint64_t lt_mask = (1ull << lane) - 1ull;
+  // the wave's histogram to zero (16-byte stores), and the sum of a lane's OWN words: lane l starts at its word
+  // l mod 32 and goes round, so the lanes of a 32-lane half read 32 different banks (straight, hist[32 l + v], they all
+  // read the same one)
+  auto hist_zero = [&]() {
+    uint4 *h4 = reinterpret_cast<uint4 *>(hist);
+    for (int v = lane; v < NV / 4; v += WAVE) h4[v] = make_uint4(0u, 0u, 0u, 0u);
+  };
+  auto own_sum = [&]() {
+    uint32_t s = 0;
+#pragma unroll 8
+    for (int v = 0; v < OWN; ++v) s += hist[lane * OWN + ((v + lane) & (OWN - 1))];
+    return s;
+  };
   for (unsigned long long e = (unsigned long long)blockIdx.x * 4 + wv; e < nl; e += nwaves) {
     const uint32_t q = longlist[e];
     const uint32_t fs = fstart[q], nf = fstart[q + 1] - fs, rs = rstart[q], nr = rstart[q + 1] - rs;
     const uint32_t len = nf + nr;
-    for (int v = lane; v < NV; v += WAVE) hist[v] = 0;
+    const uint64_t o0 = off[q];
+    const bool fits = len <= (uint32_t)SEL_BATCH;  // (uniform) the registers hold the whole list after the first sweep
+    uint64_t kk[SEL_LK];
+    auto load = [&](uint32_t base) {
+      SelRaw raw[SEL_LK];
+#pragma unroll
+      for (int k = 0; k < SEL_LK; ++k)
+        raw[k] = sel_load<WIDE>(base + (uint32_t)(k * WAVE + lane), len, rs, nr, fs, pairs, milli, rev, rdst);
+#pragma unroll
+      for (int k = 0; k < SEL_LK; ++k)
+        kk[k] = sel_key<WIDE>(raw[k], base + (uint32_t)(k * WAVE + lane), len, nr, id_bits, idm);
+    };
+    // (the sweeps leave a batch at the first row past the list's end: most lists are far shorter than a batch)
+    hist_zero();
     __builtin_amdgcn_wave_barrier();
-    for (uint32_t x = lane; x < len; x += WAVE)
-      atomicAdd(&hist[(uint32_t)(sel_key(x, rs, nr, fs, pairs, milli, rev, rdst, id_bits, idm) >> 32)], 1u);
+    for (uint32_t base = 0; base < len; base += SEL_BATCH) {
+      load(base);
+#pragma unroll
+      for (int k = 0; k < SEL_LK; ++k) {
+        if (base + (uint32_t)(k * WAVE) >= len) break;
+        const uint32_t inv = (uint32_t)(kk[k] >> 32);
+        if (inv < (uint32_t)NV) atomicAdd(&hist[inv], 1u);   // (absent elements: inv = ~0)
+      }
+    }
     __builtin_amdgcn_wave_barrier();
-    // v* = smallest v with count(inv <= v) >= K; below = count(inv < v*).  Lane l owns values [32 l, 32 l + 32).
-    uint32_t mysum = 0;
-    for (int v = 0; v < NV / WAVE; ++v) mysum += hist[lane * (NV / WAVE) + v];
+    // v* = smallest v with count(inv <= v) >= K; below = count(inv < v*)
+    const uint32_t mysum = own_sum();
     const uint32_t inc = wave_incl_scan(mysum);
     const uint64_t reach = __ballot(inc >= (uint32_t)K);  // len > SEL_LONG >= ... may still be < K: then keep all
     uint32_t vstar = NV, below = 0;
@@ -348,10 +421,10 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
       uint32_t run = __shfl(inc - mysum, owner, WAVE);   // count below the owner's first value
       uint32_t vs = NV, bl = 0;
       if (lane == owner) {
-        for (int v = 0; v < NV / WAVE; ++v) {
-          const uint32_t h = hist[lane * (NV / WAVE) + v];
+        for (int v = 0; v < OWN; ++v) {
+          const uint32_t h = hist[lane * OWN + v];
           if (run + h >= (uint32_t)K) {
-            vs = lane * (NV / WAVE) + v;
+            vs = lane * OWN + v;
             bl = run;
             break;
           }
@@ -371,25 +444,28 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
       uint32_t prefix = 0, need = want_eq;          // ids whose top bits equal `prefix` are still undecided
       for (int shift = 22; shift >= 0; shift -= 11) {
         __builtin_amdgcn_wave_barrier();
-        for (int v = lane; v < NV; v += WAVE) hist[v] = 0;
+        hist_zero();
         __builtin_amdgcn_wave_barrier();
-        for (uint32_t x = lane; x < len; x += WAVE) {
-          const uint64_t k = sel_key(x, rs, nr, fs, pairs, milli, rev, rdst, id_bits, idm);
-          const uint32_t idv = (uint32_t)k;
-          if ((uint32_t)(k >> 32) == vstar && (shift == 22 || (idv >> (shift + 11)) == prefix))
-            atomicAdd(&hist[(idv >> shift) & (NV - 1)], 1u);
+        for (uint32_t base = 0; base < len; base += SEL_BATCH) {
+          if (!fits) load(base);
+#pragma unroll
+          for (int k = 0; k < SEL_LK; ++k) {
+            if (base + (uint32_t)(k * WAVE) >= len) break;
+            const uint32_t idv = (uint32_t)kk[k];
+            if ((uint32_t)(kk[k] >> 32) == vstar && (shift == 22 || (idv >> (shift + 11)) == prefix))
+              atomicAdd(&hist[(idv >> shift) & (NV - 1)], 1u);
+          }
         }
         __builtin_amdgcn_wave_barrier();
-        uint32_t ms = 0;
-        for (int v = 0; v < NV / WAVE; ++v) ms += hist[lane * (NV / WAVE) + v];
+        const uint32_t ms = own_sum();
         const uint32_t ic = wave_incl_scan(ms);
         const int owner = __ffsll((long long)__ballot(ic >= need)) - 1;  // (need <= the number of undecided ids)
         uint32_t run = __shfl(ic - ms, owner, WAVE), dg = 0, bl = 0;
         if (lane == owner) {
-          for (int v = 0; v < NV / WAVE; ++v) {
-            const uint32_t h = hist[lane * (NV / WAVE) + v];
+          for (int v = 0; v < OWN; ++v) {
+            const uint32_t h = hist[lane * OWN + v];
             if (run + h >= need) {
-              dg = lane * (NV / WAVE) + v;
+              dg = lane * OWN + v;
               bl = run;
               break;
             }
@@ -403,25 +479,29 @@ __global__ __launch_bounds__(256) void topk_select_long_kernel(const uint64_t *_
       }
       id_cut = prefix;                               // the need-th smallest undecided id itself (need == 1 by now)
     }
-    // second sweep, in list order: collect the survivors
+    // second sweep, in list order (k ascending, then lane, inside a batch): collect the survivors
+    const uint32_t want = len < (uint32_t)K ? len : (uint32_t)K;
     uint32_t nkeep = 0, neq = 0;
-    for (uint32_t x0 = 0; x0 < len; x0 += WAVE) {
-      const uint32_t x = x0 + lane;
-      const uint64_t k = x < len ? sel_key(x, rs, nr, fs, pairs, milli, rev, rdst, id_bits, idm) : ~0ull;
-      const uint32_t inv = (uint32_t)(k >> 32);
-      const bool lt = x < len && inv < vstar;
-      const bool eq = x < len && inv == vstar;
-      const uint64_t meq = __ballot(eq);
-      const bool take_eq = eq && (id_cut != 0xFFFFFFFFu ? (uint32_t)k <= id_cut
-                                                        : neq + (uint32_t)__popcll(meq & lt_mask) < want_eq);
-      const uint64_t mk = __ballot(lt || take_eq);
-      if (lt || take_eq) keep[nkeep + (uint32_t)__popcll(mk & lt_mask)] = k;
-      nkeep += (uint32_t)__popcll(mk);
-      neq += (uint32_t)__popcll(meq);
+    for (uint32_t base = 0; base < len && nkeep < want; base += SEL_BATCH) {   // (all `want` found: none follows)
+      if (!fits) load(base);
+#pragma unroll
+      for (int k = 0; k < SEL_LK; ++k) {
+        if (base + (uint32_t)(k * WAVE) >= len) break;
+        const uint64_t key = kk[k];
+        const uint32_t inv = (uint32_t)(key >> 32);
+        const bool lt = inv < vstar;      // (absent elements: inv = ~0, neither below nor at v* <= NV)
+        const bool eq = inv == vstar;
+        const uint64_t meq = __ballot(eq);
+        const bool take_eq = eq && (id_cut != 0xFFFFFFFFu ? (uint32_t)key <= id_cut
+                                                          : neq + (uint32_t)__popcll(meq & lt_mask) < want_eq);
+        const uint64_t mk = __ballot(lt || take_eq);
+        if (lt || take_eq) keep[nkeep + (uint32_t)__popcll(mk & lt_mask)] = key;
+        nkeep += (uint32_t)__popcll(mk);
+        neq += (uint32_t)__popcll(meq);
+      }
     }
     __builtin_amdgcn_wave_barrier();
     // nkeep == min(K, len); rank the survivors among themselves
-    const uint64_t o0 = off[q];
     for (uint32_t a = lane; a < nkeep; a += WAVE) {
       const uint64_t k = keep[a];
       uint32_t r = 0;
@@ -534,13 +614,27 @@ QRLSH_EXPORT int qrlsh_topk_select_fill(const uint64_t *pairs, const int32_t *mi
   const uint32_t *fsp = w.fstart, *rsp = w.rstart;
   const uint64_t *offp = w.off;
   const unsigned long long *nl = reinterpret_cast<const unsigned long long *>(w.nlong);
-  QR_LAUNCH("topk_select", topk_select_short_kernel, dim3((unsigned)ceil_div64(nq, 16 * SEL_QPG)), dim3(256), 0, st, pairs, milli,
-            rev_sorted, rev_dst, fsp, rsp, offp, nq, K, id_bits, src_out, dst_out, milli_out);
-  QR_LAUNCH("topk_select_medium", topk_select_medium_kernel, dim3(SEL_LIST_GRID), dim3(256), 0, st, pairs, milli,
-            rev_sorted, rev_dst, fsp, rsp, offp, (const uint32_t *)w.medlist, nl, K, id_bits, src_out, dst_out, milli_out);
-  QR_LAUNCH("topk_select_long", topk_select_long_kernel, dim3(SEL_LIST_GRID), dim3(256), 0, st, pairs, milli, rev_sorted,
-            rev_dst, fsp, rsp, offp, (const uint32_t *)w.longlist, nl, K, id_bits, src_out, dst_out, milli_out,
-            pairs ? 0 : 1);
+  // Every query belongs to exactly one of the three kernels and they write disjoint output rows: the two small
+  // fixed grids of the medium and long lists run on the auxiliary stream (api.hip: qr_aux_fork; none with the
+  // profiler on or overlap off -- then all three follow each other on `st`) beside the short kernel, which visits
+  // every query.  Below SEL_FORK_NQ queries they stay on `st` too: the two cross-stream waits of a fork and join cost
+  // about 0.03 ms, what the overlap gains at 3 M queries (0.1 ms of the 0.95 at 10 M; at 1 M the step was 0.027 ms
+  // slower with the fork than without).
+  auto launch = [&](auto wide) -> int {   // (packed or wide reverse words: the kernels' two forms)
+    constexpr bool W = decltype(wide)::value;
+    hipStream_t aux = nq >= SEL_FORK_NQ ? qr_aux_fork(st) : nullptr;
+    hipStream_t sl = aux ? aux : st;
+    QR_LAUNCH("topk_select_long", topk_select_long_kernel<W>, dim3(SEL_LIST_GRID), dim3(256), 0, sl, pairs, milli,
+              rev_sorted, rev_dst, fsp, rsp, offp, (const uint32_t *)w.longlist, nl, K, id_bits, src_out, dst_out, milli_out,
+              pairs ? 0 : 1);
+    QR_LAUNCH("topk_select_medium", topk_select_medium_kernel<W>, dim3(SEL_LIST_GRID), dim3(256), 0, sl, pairs, milli,
+              rev_sorted, rev_dst, fsp, rsp, offp, (const uint32_t *)w.medlist, nl, K, id_bits, src_out, dst_out, milli_out);
+    QR_LAUNCH("topk_select", topk_select_short_kernel<W>, dim3((unsigned)ceil_div64(nq, 16 * SEL_QPG)), dim3(256), 0, st,
+              pairs, milli, rev_sorted, rev_dst, fsp, rsp, offp, nq, K, id_bits, src_out, dst_out, milli_out);
+    if (aux && qr_aux_join(st) != QRLSH_OK) return QRLSH_EHIP;
+    return QRLSH_OK;
+  };
+  if ((rev_dst ? launch(std::true_type{}) : launch(std::false_type{})) != QRLSH_OK) return QRLSH_EHIP;
   QR_LAUNCH_CHECK("qrlsh_topk_select_fill");
   return QRLSH_OK;
 }
