@@ -626,6 +626,57 @@ int qrlsh_lists_remove_fill(const int32_t *src, const int32_t *dst, const int32_
                             void *workspace, size_t workspace_bytes, int64_t total, int32_t *src_out, int32_t *dst_out,
                             int32_t *val_out, void *stream);
 
+/* ---- replacing queries of a built index in place (csrc/replace.hip) -----------------------------------------------------
+ * m distinct ids R of 0 .. n-1 get new rows: batch row x goes to id replaced_ids[x] (device uint32 [m], ASCENDING;
+ * replaced_map = qrlsh_idmap_build over them, whose member count must be m).  n, b, qrlsh_index_dir_bits(n) and every
+ * other id stay as they are.  Afterwards the arrays are byte for byte those of qrlsh_index_build over the key matrix with
+ * columns R overwritten, and the lists element for element those of a run over the row matrix with rows R overwritten.
+ *   rows: new_rows [m] of row_bytes and new_norm2 [m] overwrite rows / norm2 at replaced_ids[x], in place; 16-byte
+ *     vectors, or the widest of 8, 4 or 2 bytes that divides row_bytes, as qrlsh_rows_remove.
+ *   index: keys / ids / dir of the built index, new_keys [b][m] of the batch (consumed: sorted in place) -> keys_out /
+ *     ids_out [b][n], dir_out.  A band's order is "top 32 bits of mix64(key), then id ascending": the new band is the old
+ *     one without the records of R merged with the sorted batch by (mix bits, id), so a new record goes among the
+ *     equal-bit records by its id.  Sort of the batch (bits 32..64, payload = batch index = id order); count per tile of
+ *     2048 records (ids read, one map load each), which also lists the (mix bits, id) of the records that leave, sorted
+ *     on their bits; a scan; rank: one lane per sorted batch record j finds the old records before it (old directory + a
+ *     binary search on (bits, id)) and the leaving ones among them (a search in that list): s_j survivors precede it and
+ *     it lands at s_j + j; fill: every surviving record ranks itself in its tile with ballots and goes to
+ *     s + #{j : s_j <= s} (the batch range narrowed once per tile; a tile without batch records is a shifted copy); then
+ *     the directory kernel of the build.  Keys are read once and written once, ids read twice.  pick_map / n_pick /
+ *     pick_keys_out as qrlsh_index_remove.  m == 0 returns at once and writes nothing; m == n is served.  workspace:
+ *     qrlsh_index_replace_workspace_bytes(n, m, b).
+ *   lists: stored src / dst / val at list length K.  The rows to probe again are those of qrlsh_lists_remove_mark over
+ *     replaced_map: rows outside R with exactly K entries, at least one of them in R (pick_map; pick_ids = its
+ *     qrlsh_idmap_list).  The caller probes the batch against the NEW index with the new rows (raw / select_keys of
+ *     qrlsh_index_probe_fill / qrlsh_index_probe_finish_rows, self ids replaced_ids, m * b < 2^32: r_off / r_idx /
+ *     r_milli) and the picked rows with pick_keys_out (p_off / p_idx / p_milli; may be NULL when n_pick == 0).
+ *     An unpicked row outside R becomes the first K of the merge of its stored entries whose dst is outside R with the
+ *     replaced queries that name it (every kept raw word), by value descending, then id ascending -- ties go by id both
+ *     ways; rows of R and picked rows take the finish's lists.  count leaves the number of entries in *total_out
+ *     (device uint64; the one read-back), or ~0 when the stored lists break the contract (src not ascending, an id
+ *     outside [0, n)); fill follows a count on the same workspace and arguments and writes exactly `total` entries;
+ *     every stored entry and every reverse record ranks itself.  workspace: qrlsh_lists_replace_workspace_bytes.
+ * Limits as for the removal.  No allocation, one stream, no fallback path. */
+int qrlsh_rows_replace(void *rows, int64_t row_bytes, int64_t *norm2, int64_t n, const uint32_t *replaced_ids,
+                       const void *new_rows, const int64_t *new_norm2, int64_t m, void *stream);
+size_t qrlsh_index_replace_workspace_bytes(int64_t n, int64_t m, int32_t b);
+int qrlsh_index_replace(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
+                        const void *replaced_map, const uint32_t *replaced_ids, uint64_t *new_keys, int64_t m,
+                        const void *pick_map, int64_t n_pick, uint64_t *keys_out, uint32_t *ids_out, uint32_t *dir_out,
+                        uint64_t *pick_keys_out, void *workspace, size_t workspace_bytes, void *stream);
+size_t qrlsh_lists_replace_workspace_bytes(int64_t n, int64_t n_edges, int64_t n_raw);
+int qrlsh_lists_replace_count(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                              int64_t m, int32_t b, int32_t K, const void *replaced_map, const uint32_t *replaced_ids,
+                              const void *pick_map, const uint32_t *pick_ids, int64_t n_pick, const uint64_t *raw,
+                              const uint64_t *select_keys, int64_t n_raw, const int64_t *r_off, const int64_t *p_off,
+                              void *workspace, size_t workspace_bytes, uint64_t *total_out, void *stream);
+int qrlsh_lists_replace_fill(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                             int64_t m, int32_t b, int32_t K, const void *replaced_map, const uint32_t *replaced_ids,
+                             const void *pick_map, const uint32_t *pick_ids, int64_t n_pick, int64_t n_raw,
+                             const int64_t *r_off, const int32_t *r_idx, const int32_t *r_milli, const int64_t *p_off,
+                             const int32_t *p_idx, const int32_t *p_milli, const void *workspace, size_t workspace_bytes,
+                             int64_t total, int32_t *src_out, int32_t *dst_out, int32_t *val_out, void *stream);
+
 /* ---- recommendations: top-k unrated queries per user (the consumer of N1's output) ---------------------
  * Replaces the selection of the interactive prompt, recommender.py:357-375 (just_scored of :361, the argsort of
  * :370), in batch form over the completed matrix.  ratings / pred int32 [nu][nq] (qrlsh_predict's input and output),

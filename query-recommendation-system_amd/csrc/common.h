@@ -47,6 +47,13 @@ int qr_aux_join(hipStream_t st);
 // the per-band directory of sorted index bands (index.hip); `who` names the entry point in a launch error
 int qr_index_dir(const uint64_t *keys, int64_t n, int32_t b, uint32_t *dir_out, hipStream_t st, const char *who);
 
+// row bookkeeping of top-K lists (lists.hip): [old_lo, old_hi) = the stored entries of every row (run heads and tails
+// of src; *bad != 0 when src is not ascending or an id lies outside [0, n)), [rev_lo, rev_hi) = its run among reverse
+// records id << 11 | (1000 - milli) sorted by id; rows that are absent keep what the caller put there (zeros)
+void qr_lists_old_rows(const int32_t *src, const int32_t *dst, int64_t n_edges, int64_t n, uint32_t *old_lo,
+                       uint32_t *old_hi, uint32_t *bad, hipStream_t st);
+void qr_lists_rev_rows(const uint64_t *rec, int64_t n_raw, int64_t n, uint32_t *rev_lo, uint32_t *rev_hi, hipStream_t st);
+
 // the rows of chosen users (predict.hip, compiled without FMA contraction): out[x] = the completed (eligible = false)
 // or eligible-only (true: 0 where rated) row of users[x], rows `ostride` words apart; `who` names the entry point
 int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,

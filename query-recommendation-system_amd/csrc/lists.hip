@@ -277,6 +277,17 @@ static inline unsigned lu_grid(int64_t work, int64_t per_block) {
   return (unsigned)(g < LU_GRID ? (g > 0 ? g : 1) : LU_GRID);
 }
 
+// the row bookkeeping of stored lists and of sorted reverse records, also for the replacement's lists (replace.hip)
+void qr_lists_old_rows(const int32_t *src, const int32_t *dst, int64_t n_edges, int64_t n, uint32_t *old_lo,
+                       uint32_t *old_hi, uint32_t *bad, hipStream_t st) {
+  QR_LAUNCH("lists_old_rows", lists_old_rows_kernel, dim3(lu_grid(n_edges, LU_THREADS)), dim3(LU_THREADS), 0, st, src, dst,
+            n_edges, n, old_lo, old_hi, bad);
+}
+void qr_lists_rev_rows(const uint64_t *rec, int64_t n_raw, int64_t n, uint32_t *rev_lo, uint32_t *rev_hi, hipStream_t st) {
+  QR_LAUNCH("lists_rev_rows", lists_rev_rows_kernel, dim3((unsigned)ceil_div64(n_raw, LU_THREADS)), dim3(LU_THREADS), 0, st,
+            rec, n_raw, n, rev_lo, rev_hi);
+}
+
 QRLSH_EXPORT int qrlsh_lists_update_count(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges,
                                           int64_t n, int64_t m, int32_t b, int32_t K, const uint64_t *raw,
                                           const uint64_t *select_keys, int64_t n_raw, const int64_t *new_off,
@@ -306,13 +317,9 @@ QRLSH_EXPORT int qrlsh_lists_update_count(const int32_t *src, const int32_t *dst
         return QRLSH_EHIP;
       }
     }
-    if (n > 0)
-      QR_LAUNCH("lists_rev_rows", lists_rev_rows_kernel, dim3((unsigned)ceil_div64(n_raw, LU_THREADS)), dim3(LU_THREADS), 0,
-                st, (const uint64_t *)w.rec_a, n_raw, n, w.rev_lo, w.rev_hi);
+    if (n > 0) qr_lists_rev_rows(w.rec_a, n_raw, n, w.rev_lo, w.rev_hi, st);
   }
-  if (n_edges > 0 && n > 0)
-    QR_LAUNCH("lists_old_rows", lists_old_rows_kernel, dim3(lu_grid(n_edges, LU_THREADS)), dim3(LU_THREADS), 0, st, src, dst,
-              n_edges, n, w.old_lo, w.old_hi, w.bad);
+  if (n_edges > 0 && n > 0) qr_lists_old_rows(src, dst, n_edges, n, w.old_lo, w.old_hi, w.bad, st);
   else if (n_edges > 0) {  // entries without rows to belong to
     if (hipMemsetAsync(w.bad, 0xFF, 4, st) != hipSuccess) {
       qrlsh_set_error("qrlsh_lists_update_count: hipMemsetAsync failed");

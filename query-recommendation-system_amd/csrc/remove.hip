@@ -22,52 +22,7 @@
 //             same way as the bands (tiles, a scan, ballots): a kept entry's output position is the kept entries before
 //             it plus the re-probed entries of the picked rows below its src; the head entry of a picked row leaves
 //             that row's output position for the kernel that copies the re-probed lists.  Every entry places itself.
-#include "common.h"
-
-constexpr int RM_THREADS = 256;
-constexpr int RM_PER = 8;                       // records (list entries) per lane, RM_THREADS apart
-constexpr int RM_TILE = RM_THREADS * RM_PER;    // records per workgroup: qrlsh/_lib.py REMOVE_TILE
-constexpr int RM_GRID = 2048;                   // workgroups of the grid-stride kernels (256 CUs x 8)
-constexpr int RM_MAXK = QRLSH_INDEX_MAX_K;
-
-static inline size_t rm_al16(size_t x) { return (x + 15) / 16 * 16; }
-static inline unsigned rm_grid(int64_t work, int64_t per_block) {
-  const int64_t g = ceil_div64(work, per_block);
-  return (unsigned)(g < RM_GRID ? (g > 0 ? g : 1) : RM_GRID);
-}
-
-// ---- id map ---------------------------------------------------------------------------------------------------------
-// words uint2 [nw + 1] {bits, members below the word} (entry nw: no bits, the member count) | popcounts u64 [nw + 2] |
-// scan scratch           (nw = ceil(n / 32))
-struct IdMap {
-  uint2 *w;
-  uint64_t *cnt, *sums;
-  int64_t nw;
-  size_t bytes;
-};
-static IdMap idmap_layout(void *map, int64_t n) {
-  IdMap m;
-  m.nw = (n + 31) / 32;
-  char *p = static_cast<char *>(map);
-  size_t o = 0;
-  m.w = reinterpret_cast<uint2 *>(p + o), o += rm_al16((size_t)(m.nw + 1) * 8);
-  m.cnt = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(m.nw + 2) * 8);
-  m.sums = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(ceil_div64(m.nw + 1, SCANL_CHUNK) + 2) * 8);
-  m.bytes = o;
-  return m;
-}
-
-__device__ static inline bool idmap_has(uint2 w, uint32_t id) { return (w.x >> (id & 31u)) & 1u; }
-// members below id (w = the entry of id's word)
-__device__ static inline uint32_t idmap_rank(uint2 w, uint32_t id) {
-  return w.y + (uint32_t)__popc(w.x & ((1u << (id & 31u)) - 1u));
-}
-// test before set (shard.hip, idset_mark_kernel: an atomic on a bit that is already set is the expensive way to find out)
-__device__ static inline void idmap_set(uint2 *map, uint32_t id) {
-  uint32_t *bits = reinterpret_cast<uint32_t *>(map + (id >> 5));
-  const uint32_t m = 1u << (id & 31u);
-  if (!(__hip_atomic_load(bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m)) atomicOr(bits, m);
-}
+#include "idmap.h"
 
 QRLSH_EXPORT size_t qrlsh_idmap_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
@@ -217,31 +172,6 @@ QRLSH_EXPORT int qrlsh_rows_remove(const void *rows, int64_t row_bytes, const in
   else rows_remove_launch<uint16_t>(rows, row_bytes, norm2, n, rm, rows_out, norm2_out, st);
   QR_LAUNCH_CHECK("qrlsh_rows_remove");
   return QRLSH_OK;
-}
-
-// ---- stable compaction of a tile ------------------------------------------------------------------------------------
-// element (k, thread) of the tile is its element k * RM_THREADS + thread.  wc: RM_PER * 4 words of LDS.  -> before[k] =
-// kept elements of the tile that precede element (k, thread); returns the tile's kept total.  All threads call it.
-__device__ static inline uint32_t rm_tile_prefix(const bool (&keep)[RM_PER], uint32_t *wc, uint32_t (&before)[RM_PER]) {
-  const int lane = lane_id(), wave = threadIdx.x >> 6;
-  uint32_t in_wave[RM_PER];
-#pragma unroll
-  for (int k = 0; k < RM_PER; ++k) {
-    const uint64_t bal = __ballot(keep[k]);
-    in_wave[k] = (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wc[k * 4 + wave] = (uint32_t)__popcll(bal);
-  }
-  __syncthreads();
-  uint32_t run = 0;
-#pragma unroll
-  for (int k = 0; k < RM_PER; ++k)
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-      if (v == wave) before[k] = run + in_wave[k];
-      run += wc[k * 4 + v];
-    }
-  __syncthreads();  // wc may be rewritten by the caller's next tile
-  return run;
 }
 
 // ---- index ----------------------------------------------------------------------------------------------------------

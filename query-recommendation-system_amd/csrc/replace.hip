@@ -1,0 +1,622 @@
+// replace.hip -- queries of a built index get new rows in place: ids, n, b and the directory width stay as they are.
+//
+// R is a set of m distinct ids, given ascending (rids), with the id map of remove.hip over it; batch row x goes to id
+// rids[x].  A band's order is "top 32 bits of mix64(key), then id ascending", so the band after the replacement is the
+// old band without the records of R -- the SURVIVORS, in place order -- merged with the batch records sorted by
+// (mix bits, id).  A replaced id sits in the middle of the id range: among equal mix bits a batch record goes where
+// its id puts it, not behind the old records as an appended one does.
+//
+//   rows:   one lane per 16 bytes (8 / 4 / 2 for other widths) of a batch row: row x overwrites row rids[x].
+//   index:  sort:  the batch as the build sorts it (mix bits 32..64, payload = batch index, which is the id order).
+//           count: one workgroup per (tile of RM_TILE records, band) counts its survivors (ids read, one map load
+//                  each) and writes the composite (mix bits << 32 | id) of every record that leaves to slot rank_R(id)
+//                  of the band's "left" list.  Slots ascend by id, so a stable sort on bits 32..64 orders the list by
+//                  (mix bits, id): half the passes of a 64-bit sort.  A scan over all (band, tile) counts follows.
+//           rank:  one lane per sorted batch record j: p = old records that order before (bits, id) (old directory,
+//                  then a binary search on the composite), q = records of the left list that do; s_j = p - q survivors
+//                  order before it and it is written at s_j + j.  The left list was chosen over counting the removed
+//                  records in front of p from the tile counts plus a sweep of p's tile: that sweep reads up to
+//                  RM_TILE ids per batch record, the list costs two searches of log2(m) steps.
+//           fill:  the tile ranks its survivors with ballots; survivor number s of the band goes to
+//                  s + #{j : s_j <= s}.  Two searches per tile narrow the batch range to [jlo, jhi); a tile whose range
+//                  is empty is a copy shifted by jlo.  A survivor whose id is in the pick map also leaves its key as
+//                  the probe key of that row, as the removal does.
+//           The directory is index_dir_kernel over the output.  12 B read + 12 B written per band record, plus 4 B for
+//           the ids of the count pass and 8 B for the directory's read.
+//   lists:  rows outside R keep their stored entries whose dst is outside R and gain the replaced queries that now
+//           name them; a row of exactly K entries that loses one is picked (qrlsh_lists_remove_mark over R) and probed
+//           again, rows of R are probed with their new rows.
+//           records: a kept raw word of R's probe whose id is neither in R nor picked becomes the reverse record
+//                    id << 11 | (1000 - milli), payload x, sorted as lists.hip sorts them: by (row, value descending,
+//                    x ascending = replaced id ascending).
+//           count:   kept[e] = 1 for a stored entry whose dst stays, scanned over all entries: the surviving entries
+//                    of a row before entry e are kept[e] - kept[row's first].  len = min(K, surviving + reverse) for an
+//                    unpicked row outside R, the finish's length for the others; one scan over the n rows.
+//           fill:    every element ranks itself: a surviving stored entry by its place among the row's surviving
+//                    entries plus the records of the row's run that order before it (larger value, or equal value and
+//                    smaller replaced id); a record by its place in the run plus the surviving entries that order
+//                    before it (larger value, or equal value and smaller dst).  Ties go by id both ways.
+#include "idmap.h"
+
+constexpr int RP_MAXK = QRLSH_INDEX_MAX_K;
+
+__device__ static inline uint32_t rp_top32(uint64_t k) { return (uint32_t)(qr_mix64(k) >> 32); }
+
+// ---- rows -----------------------------------------------------------------------------------------------------------
+template <typename V>
+__global__ __launch_bounds__(RM_THREADS) void rows_replace_kernel(V *__restrict__ rows, int64_t chunks,
+                                                                 int64_t *__restrict__ norm2, int64_t n,
+                                                                 const uint32_t *__restrict__ rids,
+                                                                 const V *__restrict__ new_rows,
+                                                                 const int64_t *__restrict__ new_norm2, int64_t m) {
+  const int64_t all = m * chunks;
+  for (int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; g < all; g += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t x = g / chunks, c = g - x * chunks;
+    const int64_t i = rids[x];
+    if (i >= n) continue;  // never, for ids the map build accepted
+    rows[i * chunks + c] = new_rows[g];
+    if (c == 0 && norm2) norm2[i] = new_norm2[x];
+  }
+}
+
+template <typename V>
+static void rows_replace_launch(void *rows, int64_t row_bytes, int64_t *norm2, int64_t n, const uint32_t *rids,
+                                const void *new_rows, const int64_t *new_norm2, int64_t m, hipStream_t st) {
+  const int64_t chunks = row_bytes / (int64_t)sizeof(V);
+  QR_LAUNCH("rows_replace", rows_replace_kernel<V>, dim3(rm_grid(m * chunks, RM_THREADS)), dim3(RM_THREADS), 0, st,
+            static_cast<V *>(rows), chunks, norm2, n, rids, static_cast<const V *>(new_rows), new_norm2, m);
+}
+
+QRLSH_EXPORT int qrlsh_rows_replace(void *rows, int64_t row_bytes, int64_t *norm2, int64_t n, const uint32_t *ids,
+                                    const void *new_rows, const int64_t *new_norm2, int64_t m, void *stream) {
+  QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && m >= 0 && m <= n && row_bytes > 0 && row_bytes % 2 == 0,
+               "qrlsh_rows_replace: bad sizes n=%lld m=%lld row_bytes=%lld (a multiple of 2)", (long long)n, (long long)m,
+               (long long)row_bytes);
+  if (m == 0) return QRLSH_OK;
+  QR_CHECK_ARG(rows && ids && new_rows && (!norm2 || new_norm2), "qrlsh_rows_replace: null pointer");
+  QR_CHECK_ARG(((uintptr_t)rows | (uintptr_t)new_rows) % 16 == 0, "qrlsh_rows_replace: rows must be 16-byte aligned");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (row_bytes % 16 == 0) rows_replace_launch<uint4>(rows, row_bytes, norm2, n, ids, new_rows, new_norm2, m, st);
+  else if (row_bytes % 8 == 0) rows_replace_launch<uint2>(rows, row_bytes, norm2, n, ids, new_rows, new_norm2, m, st);
+  else if (row_bytes % 4 == 0) rows_replace_launch<uint32_t>(rows, row_bytes, norm2, n, ids, new_rows, new_norm2, m, st);
+  else rows_replace_launch<uint16_t>(rows, row_bytes, norm2, n, ids, new_rows, new_norm2, m, st);
+  QR_LAUNCH_CHECK("qrlsh_rows_replace");
+  return QRLSH_OK;
+}
+
+// ---- index ----------------------------------------------------------------------------------------------------------
+// one workgroup per (tile, band): tile_cnt[band * tiles + tile] = survivors of the tile; a record that leaves writes
+// its composite to left[band][rank_R(id)]
+__global__ __launch_bounds__(RM_THREADS) void index_replace_count_kernel(const uint64_t *__restrict__ keys,
+                                                                        const uint32_t *__restrict__ ids, int64_t n,
+                                                                        int64_t m, const uint2 *__restrict__ rm,
+                                                                        uint64_t *__restrict__ tile_cnt,
+                                                                        uint64_t *__restrict__ left) {
+  __shared__ uint32_t wc[RM_PER * 4];
+  const int64_t t = blockIdx.y, tile = blockIdx.x;
+  const int64_t o = tile * RM_TILE;
+  const uint32_t *bi = ids + t * n;
+  const uint64_t *bk = keys + t * n;
+  uint32_t id[RM_PER];
+  uint2 w[RM_PER];
+  bool keep[RM_PER];
+#pragma unroll
+  for (int k = 0; k < RM_PER; ++k) {  // every load of the tile is issued before the first is used
+    const int64_t x = o + (int64_t)k * RM_THREADS + threadIdx.x;
+    id[k] = x < n ? bi[x] : 0xFFFFFFFFu;
+  }
+#pragma unroll
+  for (int k = 0; k < RM_PER; ++k) {
+    const bool ok = (int64_t)id[k] < n;  // false past the band's end (and for an id no build writes)
+    w[k] = ok ? rm[id[k] >> 5] : make_uint2(0u, 0u);
+    keep[k] = ok && !idmap_has(w[k], id[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < RM_PER; ++k) {
+    const int64_t x = o + (int64_t)k * RM_THREADS + threadIdx.x;
+    if (keep[k] || (int64_t)id[k] >= n) continue;
+    const int64_t j = idmap_rank(w[k], id[k]);
+    if (j < m) left[t * m + j] = (uint64_t)rp_top32(bk[x]) << 32 | id[k];
+  }
+  uint32_t before[RM_PER];
+  const uint32_t kept = rm_tile_prefix(keep, wc, before);
+  if (threadIdx.x == 0) tile_cnt[t * gridDim.x + tile] = kept;
+}
+
+// first position of [L, R) of a sorted band whose (mix bits, id) is not below c = bits << 32 | id
+__device__ static inline uint32_t rp_lower_band(const uint64_t *bk, const uint32_t *bi, uint32_t L, uint32_t R, uint64_t c) {
+  while (L < R) {
+    const uint32_t mid = L + (R - L) / 2;
+    if (((uint64_t)rp_top32(bk[mid]) << 32 | bi[mid]) < c) L = mid + 1;
+    else R = mid;
+  }
+  return L;
+}
+
+// one lane per (band, sorted batch record j): s[band][j] = survivors that order before it; the record goes to s + j
+__global__ __launch_bounds__(RM_THREADS) void index_replace_rank_kernel(
+    const uint64_t *__restrict__ okeys, const uint32_t *__restrict__ oids, const uint32_t *__restrict__ odir, int64_t n,
+    int d, const uint64_t *__restrict__ bkeys, const uint32_t *__restrict__ bx, const uint32_t *__restrict__ rids,
+    const uint64_t *__restrict__ left, int64_t m, uint32_t *__restrict__ s_out, uint64_t *__restrict__ keys_out,
+    uint32_t *__restrict__ ids_out) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m) return;
+  const int64_t t = blockIdx.y;
+  const uint64_t key = bkeys[t * m + j];
+  const uint32_t x = bx[t * m + j];
+  if ((int64_t)x >= m) return;  // never, for the payload the sort wrote
+  const uint32_t id = rids[x];
+  const uint64_t h = qr_mix64(key);
+  const uint64_t c = (h >> 32) << 32 | id;
+  const uint32_t *bd = odir + t * ((1ll << d) + 1);
+  const uint32_t p = rp_lower_band(okeys + t * n, oids + t * n, bd[h >> (64 - d)], bd[(h >> (64 - d)) + 1], c);
+  const uint64_t *lf = left + t * m;
+  int64_t L = 0, R = m;
+  while (L < R) {
+    const int64_t mid = L + (R - L) / 2;
+    if (lf[mid] < c) L = mid + 1;
+    else R = mid;
+  }
+  const int64_t s = (int64_t)p - L;  // >= 0: every record of the left list below c is an old record below c
+  s_out[t * m + j] = (uint32_t)s;
+  const int64_t pos = s + j;
+  if (s < 0 || pos >= n) return;  // never, for a band that holds every id once
+  keys_out[t * n + pos] = key;
+  ids_out[t * n + pos] = id;
+}
+
+// #{j in [L, R) : s[j] <= v} + L for the non-decreasing s
+__device__ static inline int64_t rp_upper(const uint32_t *s, int64_t L, int64_t R, int64_t v) {
+  while (L < R) {
+    const int64_t mid = L + (R - L) / 2;
+    if ((int64_t)s[mid] <= v) L = mid + 1;
+    else R = mid;
+  }
+  return L;
+}
+
+// one workgroup per (tile, band); tile_off = the exclusive scan of the counts over the bands back to back
+__global__ __launch_bounds__(RM_THREADS) void index_replace_fill_kernel(
+    const uint64_t *__restrict__ keys, const uint32_t *__restrict__ ids, int64_t n, int64_t m,
+    const uint2 *__restrict__ rm, const uint2 *__restrict__ pick, int64_t n_pick, const uint64_t *__restrict__ tile_off,
+    const uint32_t *__restrict__ s_all, uint64_t *__restrict__ keys_out, uint32_t *__restrict__ ids_out,
+    uint64_t *__restrict__ pick_keys_out) {
+  __shared__ uint32_t wc[RM_PER * 4];
+  const int64_t t = blockIdx.y, tile = blockIdx.x;
+  const int64_t o = tile * RM_TILE;
+  const uint32_t *bi = ids + t * n;
+  const uint64_t *bk = keys + t * n;
+  uint32_t id[RM_PER];
+  uint64_t key[RM_PER];
+  bool keep[RM_PER];
+#pragma unroll
+  for (int k = 0; k < RM_PER; ++k) {  // every load of the tile is issued before the first is used
+    const int64_t x = o + (int64_t)k * RM_THREADS + threadIdx.x;
+    id[k] = x < n ? bi[x] : 0xFFFFFFFFu;
+    key[k] = x < n ? bk[x] : 0;
+  }
+  const int64_t base = (int64_t)tile_off[t * gridDim.x + tile] - t * (n - m);  // survivors of the band before the tile
+#pragma unroll
+  for (int k = 0; k < RM_PER; ++k) {
+    const bool ok = (int64_t)id[k] < n;
+    const uint2 w = ok ? rm[id[k] >> 5] : make_uint2(0u, 0u);
+    keep[k] = ok && !idmap_has(w, id[k]);
+  }
+  uint32_t before[RM_PER];
+  const uint32_t kept = rm_tile_prefix(keep, wc, before);
+  if (kept == 0 || base < 0) return;
+  const uint32_t *s = s_all + t * m;
+  const int64_t jlo = rp_upper(s, 0, m, base);                  // batch records before the tile's first survivor
+  const int64_t jhi = rp_upper(s, jlo, m, base + kept - 1);     // ... and before its last
+#pragma unroll
+  for (int k = 0; k < RM_PER; ++k) {
+    if (!keep[k]) continue;
+    const int64_t sv = base + before[k];
+    const int64_t pos = sv + (jlo == jhi ? jlo : rp_upper(s, jlo, jhi, sv));
+    if (pos < n) {  // always, for a band that holds every id once
+      keys_out[t * n + pos] = key[k];
+      ids_out[t * n + pos] = id[k];
+    }
+    if (pick) {
+      const uint2 pw = pick[id[k] >> 5];
+      const int64_t j = idmap_rank(pw, id[k]);
+      if (idmap_has(pw, id[k]) && j < n_pick) pick_keys_out[t * n_pick + j] = key[k];
+    }
+  }
+}
+
+struct RpWs {
+  uint64_t *ktmp, *left_a, *left_b, *tile_off, *sums;
+  uint32_t *bx, *xtmp, *s;
+  void *sort_ws;
+  size_t sort_bytes, bytes;
+};
+static RpWs rp_layout(void *workspace, int64_t n, int64_t m, int32_t b) {
+  RpWs w;
+  const size_t bm = (size_t)b * (size_t)m;
+  const int64_t tiles = ceil_div64(n, RM_TILE) * b;
+  char *p = static_cast<char *>(workspace);
+  size_t o = 0;
+  w.ktmp = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(bm * 8);
+  w.left_a = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(bm * 8);
+  w.left_b = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(bm * 8);
+  w.bx = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(bm * 4);
+  w.xtmp = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(bm * 4);
+  w.s = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(bm * 4);
+  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(tiles + 1) * 8);
+  w.sums = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
+  w.sort_ws = p + o;
+  w.sort_bytes = qrlsh_sort_workspace_bytes(m, b);
+  o += rm_al16(w.sort_bytes);
+  w.bytes = o;
+  return w;
+}
+
+QRLSH_EXPORT size_t qrlsh_index_replace_workspace_bytes(int64_t n, int64_t m, int32_t b) {
+  if (n <= 0 || m <= 0 || b <= 0) return 0;
+  return rp_layout(nullptr, n, m, b).bytes;
+}
+
+QRLSH_EXPORT int qrlsh_index_replace(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
+                                     const void *replaced_map, const uint32_t *replaced_ids, uint64_t *new_keys, int64_t m,
+                                     const void *pick_map, int64_t n_pick, uint64_t *keys_out, uint32_t *ids_out,
+                                     uint32_t *dir_out, uint64_t *pick_keys_out, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+  QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && b > 0 && b <= 65535 && m >= 0 && m <= n && n_pick >= 0 && n_pick <= n - m,
+               "qrlsh_index_replace: bad sizes n=%lld b=%d m=%lld n_pick=%lld", (long long)n, b, (long long)m,
+               (long long)n_pick);
+  if (m == 0) return QRLSH_OK;  // nothing changes: the outputs are not written
+  QR_CHECK_ARG(keys && ids && dir && replaced_map && replaced_ids && new_keys && keys_out && ids_out && dir_out &&
+                   workspace && (n_pick == 0 || (pick_map && pick_keys_out)),
+               "qrlsh_index_replace: null pointer");
+  if (workspace_bytes < qrlsh_index_replace_workspace_bytes(n, m, b)) {
+    qrlsh_set_error("qrlsh_index_replace: workspace %zu < %zu bytes", workspace_bytes,
+                    qrlsh_index_replace_workspace_bytes(n, m, b));
+    return QRLSH_EWORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RpWs w = rp_layout(workspace, n, m, b);
+  const int64_t tiles = ceil_div64(n, RM_TILE), all = tiles * b;
+  const uint2 *rm = idmap_layout(const_cast<void *>(replaced_map), n).w;
+  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+  int rc = qrlsh_sort_u64(new_keys, w.ktmp, w.bx, w.xtmp, m, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0, w.sort_ws,
+                          w.sort_bytes, stream);
+  if (rc < 0) return rc;
+  const uint64_t *sk = rc == 1 ? w.ktmp : new_keys;
+  const uint32_t *sx = rc == 1 ? w.xtmp : w.bx;
+  const dim3 grid((unsigned)tiles, (unsigned)b), block(RM_THREADS);
+  QR_LAUNCH("index_replace_count", index_replace_count_kernel, grid, block, 0, st, keys, ids, n, m, rm, w.tile_off, w.left_a);
+  qr_scan_u64(w.tile_off, all, w.tile_off + all, w.sums, st);
+  rc = qrlsh_sort_u64(w.left_a, w.left_b, nullptr, nullptr, m, b, 32, 64, 0, 0, w.sort_ws, w.sort_bytes, stream);
+  if (rc < 0) return rc;
+  QR_LAUNCH("index_replace_rank", index_replace_rank_kernel, dim3((unsigned)ceil_div64(m, RM_THREADS), (unsigned)b), block,
+            0, st, keys, ids, dir, n, (int)qrlsh_index_dir_bits(n), sk, sx, replaced_ids,
+            (const uint64_t *)(rc == 1 ? w.left_b : w.left_a), m, w.s, keys_out, ids_out);
+  QR_LAUNCH("index_replace_fill", index_replace_fill_kernel, grid, block, 0, st, keys, ids, n, m, rm, pk, n_pick,
+            (const uint64_t *)w.tile_off, (const uint32_t *)w.s, keys_out, ids_out, pick_keys_out);
+  return qr_index_dir(keys_out, n, b, dir_out, st, "qrlsh_index_replace");
+}
+
+// ---- lists ----------------------------------------------------------------------------------------------------------
+constexpr int RL_PER = 4;                       // stored entries per lane of the fill, RM_THREADS apart
+constexpr int RL_TILE = RM_THREADS * RL_PER;
+
+static inline int rl_id_bits(int64_t n) {
+  int bits = 1;
+  while (bits < 32 && (1ll << bits) < n) ++bits;
+  return bits;
+}
+
+struct RlWs {
+  uint64_t *rec_a, *rec_b;                       // [n_raw] reverse records, ping-pong
+  uint32_t *pay_a, *pay_b;                       // [n_raw] their batch rows
+  uint32_t *old_lo, *old_hi, *rev_lo, *rev_hi;   // [n] each, contiguous (one memset)
+  uint64_t *kept;                                // [n_edges + 1] stored entries whose dst stays, then their scan
+  uint64_t *off;                                 // [n + 1] lengths, then output offsets; [n] = total
+  uint64_t *sums;                                // scan scratch
+  uint32_t *bad;
+  void *sort_ws;
+  size_t sort_bytes, bytes;
+};
+static RlWs rl_layout(void *workspace, int64_t n, int64_t n_edges, int64_t n_raw) {
+  RlWs w;
+  char *p = static_cast<char *>(workspace);
+  size_t o = 0;
+  const size_t nr = (size_t)n_raw, nn = (size_t)n, ne = (size_t)n_edges;
+  w.rec_a = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(nr * 8);
+  w.rec_b = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(nr * 8);
+  w.pay_a = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(nr * 4);
+  w.pay_b = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(nr * 4);
+  w.old_lo = reinterpret_cast<uint32_t *>(p + o);
+  w.old_hi = w.old_lo + nn;
+  w.rev_lo = w.old_hi + nn;
+  w.rev_hi = w.rev_lo + nn;
+  o += rm_al16(nn * 16);
+  w.kept = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((ne + 1) * 8);
+  w.off = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((nn + 1) * 8);
+  w.sums = reinterpret_cast<uint64_t *>(p + o);
+  o += rm_al16((size_t)(ceil_div64((int64_t)(ne > nn ? ne : nn), SCANL_CHUNK) + 1) * 8);
+  w.bad = reinterpret_cast<uint32_t *>(p + o), o += 16;
+  w.sort_ws = p + o;
+  w.sort_bytes = qrlsh_sort_workspace_bytes(n_raw, 1);
+  o += rm_al16(w.sort_bytes);
+  w.bytes = o;
+  return w;
+}
+
+QRLSH_EXPORT size_t qrlsh_lists_replace_workspace_bytes(int64_t n, int64_t n_edges, int64_t n_raw) {
+  if (n < 0 || n_edges < 0 || n_raw < 0) return 0;
+  return rl_layout(nullptr, n, n_edges, n_raw).bytes;
+}
+
+// one lane per raw word of R's probe: the reverse record of a kept word that names a row outside R that is not picked
+__global__ __launch_bounds__(RM_THREADS) void lists_replace_records_kernel(
+    const uint64_t *__restrict__ raw, const uint64_t *__restrict__ skeys, int64_t n_raw, int64_t n, int64_t m, int b,
+    const uint2 *__restrict__ rm, const uint2 *__restrict__ pick, uint64_t *__restrict__ rec, uint32_t *__restrict__ pay) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_raw) return;
+  const uint64_t k = skeys[i];
+  const uint64_t x = (raw[i] >> 32) / (uint32_t)b;
+  const uint64_t id = k & 0xFFFFFFFFull, inv = k >> 32;
+  bool keep = k != ~0ull && (int64_t)id < n && (int64_t)x < m && inv <= 2000;
+  if (keep) keep = !idmap_has(rm[id >> 5], (uint32_t)id) && !(pick && idmap_has(pick[id >> 5], (uint32_t)id));
+  rec[i] = keep ? (id << 11 | inv) : ~0ull;
+  pay[i] = (uint32_t)x;
+}
+
+// kept[e] = 1 for a stored entry whose dst is a query outside R
+__global__ __launch_bounds__(RM_THREADS) void lists_replace_kept_kernel(const int32_t *__restrict__ dst, int64_t n_edges,
+                                                                       int64_t n, const uint2 *__restrict__ rm,
+                                                                       uint64_t *__restrict__ kept) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t d = dst[e];
+    kept[e] = d >= 0 && d < n && !idmap_has(rm[d >> 5], (uint32_t)d) ? 1ull : 0ull;
+  }
+}
+
+// one lane per row: its length after the replacement
+__global__ __launch_bounds__(RM_THREADS) void lists_replace_len_kernel(
+    const uint32_t *__restrict__ old_lo, const uint32_t *__restrict__ old_hi, const uint32_t *__restrict__ rev_lo,
+    const uint32_t *__restrict__ rev_hi, const uint64_t *__restrict__ kept, int64_t n_edges, int64_t n,
+    const uint2 *__restrict__ rm, const int64_t *__restrict__ r_off, int64_t m, const uint2 *__restrict__ pick,
+    const int64_t *__restrict__ p_off, int64_t n_pick, int K, uint64_t *__restrict__ len) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const uint2 w = rm[i >> 5];
+    const uint2 pw = pick ? pick[i >> 5] : make_uint2(0u, 0u);
+    uint64_t l = 0;
+    if (idmap_has(w, (uint32_t)i)) {
+      const int64_t j = idmap_rank(w, (uint32_t)i);
+      if (j < m && r_off[j + 1] > r_off[j]) l = (uint64_t)(r_off[j + 1] - r_off[j]);
+    } else if (idmap_has(pw, (uint32_t)i)) {
+      const int64_t j = idmap_rank(pw, (uint32_t)i);
+      if (j < n_pick && p_off[j + 1] > p_off[j]) l = (uint64_t)(p_off[j + 1] - p_off[j]);
+    } else {
+      const int64_t lo = old_lo[i], hi = old_hi[i];
+      if (hi > lo && hi <= n_edges) l = kept[hi] - kept[lo];
+      l += rev_hi[i] - rev_lo[i];
+    }
+    len[i] = l < (uint64_t)K ? l : (uint64_t)K;
+  }
+}
+
+// *total_out = the number of entries of the new lists, or ~0 when the stored lists break the contract
+__global__ void lists_replace_total_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ bad,
+                                           uint64_t *__restrict__ total_out) {
+  if (threadIdx.x == 0) *total_out = *bad ? ~0ull : *total;
+}
+
+// stored entries, RL_PER per lane: a surviving entry of an unpicked row outside R ranks itself
+__global__ __launch_bounds__(RM_THREADS) void lists_replace_fill_old_kernel(
+    const int32_t *__restrict__ src, const int32_t *__restrict__ dst, const int32_t *__restrict__ val, int64_t n_edges,
+    int64_t n, int K, const uint2 *__restrict__ rm, const uint2 *__restrict__ pick, const uint32_t *__restrict__ rids,
+    int64_t m, const uint32_t *__restrict__ old_lo, const uint32_t *__restrict__ rev_lo,
+    const uint32_t *__restrict__ rev_hi, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ pay,
+    const uint64_t *__restrict__ kept, const uint64_t *__restrict__ out_off, int64_t total, int32_t *__restrict__ src_out,
+    int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
+  const int64_t ntiles = (n_edges + RL_TILE - 1) / RL_TILE;
+  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int64_t e0 = tile * RL_TILE + threadIdx.x;
+    int32_t s[RL_PER], d[RL_PER], v[RL_PER];
+    uint64_t kp[RL_PER];
+#pragma unroll
+    for (int k = 0; k < RL_PER; ++k) {  // every load of the step is issued before the first is used
+      const int64_t e = e0 + (int64_t)k * RM_THREADS;
+      const bool live = e < n_edges;
+      s[k] = live ? src[e] : -1;
+      d[k] = live ? dst[e] : -1;
+      v[k] = live ? val[e] : 0;
+      kp[k] = live ? kept[e] : 0;
+    }
+#pragma unroll
+    for (int k = 0; k < RL_PER; ++k) {
+      const int64_t i = s[k], dd = d[k];
+      if (i < 0 || i >= n || dd < 0 || dd >= n) continue;
+      if (idmap_has(rm[i >> 5], (uint32_t)i) || idmap_has(rm[dd >> 5], (uint32_t)dd)) continue;
+      if (pick && idmap_has(pick[i >> 5], (uint32_t)i)) continue;
+      uint32_t L = rev_lo[i], R = rev_hi[i];
+      const uint32_t first = L;
+      const uint64_t inv = (uint64_t)(int64_t)(1000 - v[k]);
+      while (L < R) {  // records of the run that order before the entry: larger value, or equal and smaller replaced id
+        const uint32_t mid = L + (R - L) / 2;
+        const uint64_t ri = rec[mid] & 2047u;
+        const uint32_t x = pay[mid];
+        const int64_t rid = (int64_t)x < m ? (int64_t)rids[x] : n;
+        if (ri < inv || (ri == inv && rid < dd)) L = mid + 1;
+        else R = mid;
+      }
+      const int64_t rank = (int64_t)(kp[k] - kept[old_lo[i]]) + (int64_t)(L - first);
+      if (rank < 0 || rank >= K) continue;
+      const int64_t o = (int64_t)out_off[i] + rank;
+      if (o >= total) continue;  // never, for offsets the count wrote
+      src_out[o] = (int32_t)i;
+      dst_out[o] = (int32_t)dd;
+      val_out[o] = v[k];
+    }
+  }
+}
+
+// sorted records, one lane each: rank = place in the run + surviving stored entries of the row that order before it
+__global__ __launch_bounds__(RM_THREADS) void lists_replace_fill_rev_kernel(
+    const uint64_t *__restrict__ rec, const uint32_t *__restrict__ pay, int64_t n_raw, int64_t n, int K,
+    const uint32_t *__restrict__ rids, int64_t m, const int32_t *__restrict__ dst, const int32_t *__restrict__ val,
+    int64_t n_edges, const uint32_t *__restrict__ old_lo, const uint32_t *__restrict__ old_hi,
+    const uint32_t *__restrict__ rev_lo, const uint64_t *__restrict__ kept, const uint64_t *__restrict__ out_off,
+    int64_t total, int32_t *__restrict__ src_out, int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n_raw) return;
+  const uint64_t r = rec[k];
+  if (r == ~0ull) return;
+  const int64_t id = (int64_t)(r >> 11);
+  const uint32_t x = pay[k];
+  if (id >= n || (int64_t)x >= m) return;  // never, for a record the records kernel wrote
+  const int32_t mi = 1000 - (int32_t)(r & 2047u);
+  const int64_t rid = rids[x];
+  uint32_t L = old_lo[id], R = old_hi[id];
+  if (R > (uint64_t)n_edges) R = (uint32_t)n_edges;
+  if (L > R) L = R;
+  const uint32_t lo = L;
+  while (L < R) {  // the stored row is ordered by value descending, dst ascending: the first entry that orders after
+    const uint32_t mid = L + (R - L) / 2;
+    const int32_t sv = val[mid];
+    if (sv > mi || (sv == mi && (int64_t)dst[mid] < rid)) L = mid + 1;
+    else R = mid;
+  }
+  const int64_t rank = (k - (int64_t)rev_lo[id]) + (int64_t)(kept[L] - kept[lo]);
+  if (rank < 0 || rank >= K) return;
+  const int64_t o = (int64_t)out_off[id] + rank;
+  if (o >= total) return;
+  src_out[o] = (int32_t)id;
+  dst_out[o] = (int32_t)rid;
+  val_out[o] = mi;
+}
+
+// the probed lists: entry k of probe row j, which is query self[j]
+__global__ __launch_bounds__(RM_THREADS) void lists_replace_fill_re_kernel(
+    const int64_t *__restrict__ re_off, const int32_t *__restrict__ re_idx, const int32_t *__restrict__ re_milli,
+    const uint32_t *__restrict__ self, int64_t count, int64_t n, int K, const uint64_t *__restrict__ out_off,
+    int64_t total, int32_t *__restrict__ src_out, int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
+  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= count * K) return;
+  const int64_t j = g / K, k = g - j * K;
+  const int64_t a = re_off[j], i = self[j];
+  if (k >= re_off[j + 1] - a || i >= n) return;
+  const int64_t at = (int64_t)out_off[i] + k;
+  if (at >= total) return;
+  src_out[at] = (int32_t)i;
+  dst_out[at] = re_idx[a + k];
+  val_out[at] = re_milli[a + k];
+}
+
+static int rl_args(const char *who, const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                   int64_t m, int32_t b, int32_t K, const void *replaced_map, const uint32_t *replaced_ids,
+                   const void *pick_map, const uint32_t *pick_ids, int64_t n_pick, int64_t n_raw, const int64_t *r_off,
+                   const int64_t *p_off, const void *workspace, size_t workspace_bytes) {
+  QR_CHECK_ARG(K >= 1 && K <= RP_MAXK, "%s: K=%d not in [1, %d]", who, K, RP_MAXK);
+  QR_CHECK_ARG(n >= 0 && n < (1ll << 31) && n_edges >= 0 && n_edges < (1ll << 31) && m >= 1 && m <= n && n_pick >= 0 &&
+                   n_pick <= n - m && n_raw >= 0 && n_raw < (1ll << 32) && b > 0 && b <= 65535 &&
+                   m * (int64_t)b < (1ll << 32),
+               "%s: bad sizes n=%lld n_edges=%lld m=%lld n_pick=%lld n_raw=%lld b=%d", who, (long long)n,
+               (long long)n_edges, (long long)m, (long long)n_pick, (long long)n_raw, b);
+  QR_CHECK_ARG(replaced_map && replaced_ids && r_off && workspace && (n_edges == 0 || (src && dst && val)) &&
+                   (n_pick == 0 || (pick_map && pick_ids && p_off)),
+               "%s: null pointer", who);
+  if (workspace_bytes < qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw)) {
+    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes,
+                    qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw));
+    return QRLSH_EWORKSPACE;
+  }
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_lists_replace_count(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges,
+                                           int64_t n, int64_t m, int32_t b, int32_t K, const void *replaced_map,
+                                           const uint32_t *replaced_ids, const void *pick_map, const uint32_t *pick_ids,
+                                           int64_t n_pick, const uint64_t *raw, const uint64_t *select_keys, int64_t n_raw,
+                                           const int64_t *r_off, const int64_t *p_off, void *workspace,
+                                           size_t workspace_bytes, uint64_t *total_out, void *stream) {
+  QR_CHECK_ARG(total_out, "qrlsh_lists_replace_count: null total_out");
+  const int rc = rl_args("qrlsh_lists_replace_count", src, dst, val, n_edges, n, m, b, K, replaced_map, replaced_ids,
+                         pick_map, pick_ids, n_pick, n_raw, r_off, p_off, workspace, workspace_bytes);
+  if (rc != QRLSH_OK) return rc;
+  QR_CHECK_ARG(n_raw == 0 || (raw && select_keys), "qrlsh_lists_replace_count: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RlWs w = rl_layout(workspace, n, n_edges, n_raw);
+  const uint2 *rm = idmap_layout(const_cast<void *>(replaced_map), n).w;
+  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+  if (hipMemsetAsync(w.bad, 0, 16, st) != hipSuccess || hipMemsetAsync(w.old_lo, 0, (size_t)n * 16, st) != hipSuccess ||
+      hipMemsetAsync(w.kept, 0, sizeof(uint64_t), st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_lists_replace_count: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  const dim3 block(RM_THREADS);
+  if (n_raw > 0) {
+    QR_LAUNCH("lists_replace_records", lists_replace_records_kernel, dim3((unsigned)ceil_div64(n_raw, RM_THREADS)), block, 0,
+              st, raw, select_keys, n_raw, n, m, (int)b, rm, pk, w.rec_a, w.pay_a);
+    const int where = qrlsh_sort_u64(w.rec_a, w.rec_b, w.pay_a, w.pay_b, n_raw, 1, 0, 11 + rl_id_bits(n), 0, 0, w.sort_ws,
+                                     w.sort_bytes, stream);
+    if (where < 0) return where;
+    if (where == 1) {  // the sorted records are always left in rec_a / pay_a
+      if (hipMemcpyAsync(w.rec_a, w.rec_b, (size_t)n_raw * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+          hipMemcpyAsync(w.pay_a, w.pay_b, (size_t)n_raw * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        qrlsh_set_error("qrlsh_lists_replace_count: hipMemcpyAsync failed");
+        return QRLSH_EHIP;
+      }
+    }
+    qr_lists_rev_rows(w.rec_a, n_raw, n, w.rev_lo, w.rev_hi, st);
+  }
+  if (n_edges > 0) {
+    qr_lists_old_rows(src, dst, n_edges, n, w.old_lo, w.old_hi, w.bad, st);
+    QR_LAUNCH("lists_replace_kept", lists_replace_kept_kernel, dim3(rm_grid(n_edges, RM_THREADS)), block, 0, st, dst,
+              n_edges, n, rm, w.kept);
+    qr_scan_u64(w.kept, n_edges, w.kept + n_edges, w.sums, st);
+  }
+  QR_LAUNCH("lists_replace_len", lists_replace_len_kernel, dim3(rm_grid(n, RM_THREADS)), block, 0, st,
+            (const uint32_t *)w.old_lo, (const uint32_t *)w.old_hi, (const uint32_t *)w.rev_lo, (const uint32_t *)w.rev_hi,
+            (const uint64_t *)w.kept, n_edges, n, rm, r_off, m, pk, p_off, n_pick, (int)K, w.off);
+  qr_scan_u64(w.off, n, w.off + n, w.sums, st);
+  QR_LAUNCH("lists_replace_total", lists_replace_total_kernel, dim3(1), dim3(64), 0, st, (const uint64_t *)(w.off + n),
+            (const uint32_t *)w.bad, total_out);
+  QR_LAUNCH_CHECK("qrlsh_lists_replace_count");
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_lists_replace_fill(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges,
+                                          int64_t n, int64_t m, int32_t b, int32_t K, const void *replaced_map,
+                                          const uint32_t *replaced_ids, const void *pick_map, const uint32_t *pick_ids,
+                                          int64_t n_pick, int64_t n_raw, const int64_t *r_off, const int32_t *r_idx,
+                                          const int32_t *r_milli, const int64_t *p_off, const int32_t *p_idx,
+                                          const int32_t *p_milli, const void *workspace, size_t workspace_bytes,
+                                          int64_t total, int32_t *src_out, int32_t *dst_out, int32_t *val_out,
+                                          void *stream) {
+  const int rc = rl_args("qrlsh_lists_replace_fill", src, dst, val, n_edges, n, m, b, K, replaced_map, replaced_ids,
+                         pick_map, pick_ids, n_pick, n_raw, r_off, p_off, workspace, workspace_bytes);
+  if (rc != QRLSH_OK) return rc;
+  QR_CHECK_ARG(total >= 0 && total <= n * (int64_t)K, "qrlsh_lists_replace_fill: bad total %lld", (long long)total);
+  if (total == 0) return QRLSH_OK;
+  QR_CHECK_ARG(src_out && dst_out && val_out, "qrlsh_lists_replace_fill: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const RlWs w = rl_layout(const_cast<void *>(workspace), n, n_edges, n_raw);
+  const uint2 *rm = idmap_layout(const_cast<void *>(replaced_map), n).w;
+  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+  const dim3 block(RM_THREADS);
+  if (n_edges > 0)
+    QR_LAUNCH("lists_replace_fill_old", lists_replace_fill_old_kernel, dim3(rm_grid(n_edges, RL_TILE)), block, 0, st, src,
+              dst, val, n_edges, n, (int)K, rm, pk, replaced_ids, m, (const uint32_t *)w.old_lo,
+              (const uint32_t *)w.rev_lo, (const uint32_t *)w.rev_hi, (const uint64_t *)w.rec_a,
+              (const uint32_t *)w.pay_a, (const uint64_t *)w.kept, (const uint64_t *)w.off, total, src_out, dst_out, val_out);
+  if (n_raw > 0)
+    QR_LAUNCH("lists_replace_fill_rev", lists_replace_fill_rev_kernel, dim3((unsigned)ceil_div64(n_raw, RM_THREADS)), block,
+              0, st, (const uint64_t *)w.rec_a, (const uint32_t *)w.pay_a, n_raw, n, (int)K, replaced_ids, m, dst, val,
+              n_edges, (const uint32_t *)w.old_lo, (const uint32_t *)w.old_hi, (const uint32_t *)w.rev_lo,
+              (const uint64_t *)w.kept, (const uint64_t *)w.off, total, src_out, dst_out, val_out);
+  if (r_idx && r_milli)  // (no probed list has an entry when the finish wrote none: its arrays may be empty)
+    QR_LAUNCH("lists_replace_fill_re", lists_replace_fill_re_kernel, dim3((unsigned)ceil_div64(m * K, RM_THREADS)), block, 0,
+              st, r_off, r_idx, r_milli, replaced_ids, m, n, (int)K, (const uint64_t *)w.off, total, src_out, dst_out,
+              val_out);
+  if (n_pick > 0 && p_idx && p_milli)
+    QR_LAUNCH("lists_replace_fill_re", lists_replace_fill_re_kernel, dim3((unsigned)ceil_div64(n_pick * K, RM_THREADS)),
+              block, 0, st, p_off, p_idx, p_milli, pick_ids, n_pick, n, (int)K, (const uint64_t *)w.off, total, src_out,
+              dst_out, val_out);
+  QR_LAUNCH_CHECK("qrlsh_lists_replace_fill");
+  return QRLSH_OK;
+}

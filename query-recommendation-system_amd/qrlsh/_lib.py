@@ -135,6 +135,15 @@ SIGNATURES = {
     "qrlsh_lists_remove_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _sz, _vp, _vp]),
     "qrlsh_lists_remove_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz,
                                                _i64, _vp, _vp, _vp, _vp]),
+    "qrlsh_rows_replace": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "qrlsh_index_replace_workspace_bytes": (_sz, [_i64, _i64, _i32]),
+    "qrlsh_index_replace": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,
+                                           _vp, _sz, _vp]),
+    "qrlsh_lists_replace_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "qrlsh_lists_replace_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64,
+                                                 _vp, _vp, _i64, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "qrlsh_lists_replace_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64,
+                                                _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i64, _vp, _vp, _vp, _vp]),
     "qrlsh_recommend_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
     "qrlsh_recommend_topk": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _sz,
                                             _vp]),

@@ -17,6 +17,8 @@ top-K lists (lists=...) keeps them current on the way (update_lists=True, csrc/l
 is probed against the grown index and every list, old and new, becomes what a run over all rows with the same K gives.
 Queries leave with remove (csrc/remove.hip): the survivors are renumbered by rank, the band arrays are compacted into
 what a fresh build of the surviving rows gives, and held lists are kept exact on the way (update_lists=True).
+Queries change with replace / set (csrc/replace.hip): chosen ids take new rows and keep their ids; the band arrays lose
+their old records and gain the new ones where (mix bits, id) puts them, and held lists are kept exact on the way.
 
 Everything runs on the device; the indexed data never leaves it."""
 import numpy as np
@@ -79,6 +81,7 @@ class QueryIndex:
         self.table = table
         self.norm2 = norm2 if norm2 is not None else ops.row_norms(ops.sig_to_int32(sig))
         self._sig_buf, self._norm2_buf = self.sig, self.norm2      # capacity buffers; .sig / .norm2 = their first n rows
+        self._own_rows = False      # the buffers are still the constructor's tensors: copied before the first write
         keys = ops.band_keys(ops.sig_to_int32(sig), b) if keys is None else keys.clone()
         self.keys, self.ids, self.dir = ops.index_build(keys)
         self.lists, self.lists_K = None, None
@@ -157,6 +160,7 @@ class QueryIndex:
         norm2_buf[:self.n].copy_(self.norm2)
         self._sig_buf, self._norm2_buf = sig_buf, norm2_buf
         self.sig, self.norm2 = sig_buf[:self.n], norm2_buf[:self.n]
+        self._own_rows = True
 
     def append(self, sig, norm2=None, keys=None, update_lists=False):
         """index m more queries: sig as in neighbours() (int32 or compact int16 rows, converted to the index's format);
@@ -273,11 +277,108 @@ class QueryIndex:
         self.n = left
         self.sig, self.norm2 = sig, norm2
         self._sig_buf, self._norm2_buf = sig, norm2
+        self._own_rows = True
         if self._default_K:
             self.K = self._K_rule(self.n)
         self.lists = lists if update_lists else None
         self.last_picked = pick.count if update_lists else None
         return new_pos
+
+    # ---- replacing queries in place -------------------------------------------------------------------------------
+    def replace(self, ids, sig, norm2=None, keys=None, update_lists=False):
+        """give indexed queries new rows: ids = their positions (array or tensor of m distinct integers in [0, n), any
+        order; ValueError for a duplicate or an id outside, the index unchanged), sig / norm2 / keys [b, m] as append()
+        takes them, row x for ids[x].  n, b and every other id stay.  Afterwards .sig, .norm2, .keys, .ids and .dir are
+        the arrays a fresh QueryIndex over the rows with those overwritten holds (with caller keys: over the key matrix
+        with those columns overwritten); a new record goes among the records of equal mix bits by its id.
+        update_lists=True (an index that holds lists; ValueError otherwise): .lists becomes the lists of a run over the
+        new rows at .lists_K.  A row outside ids drops its entries that name a replaced query and merges with the
+        replaced queries that now name it, ties by id both ways; a row of exactly K entries that loses one is probed
+        again with the keys it is indexed under (.last_picked counts them); a replaced query is probed with its new row.
+        Any split of a batch into successive replacements gives the same result.  update_lists=False: .lists becomes
+        None.  No ids: nothing happens.  The tensors given to the constructor are never written."""
+        if update_lists and self.lists is None:
+            raise ValueError("this index holds no lists to update (none were given, or a call without update_lists=True "
+                             "dropped them)")
+        dev = self.sig.device
+        if isinstance(ids, torch.Tensor):
+            if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+                raise ValueError("ids must be integers")
+            t = ids.reshape(-1).to(dev, torch.int64)
+        else:
+            a = np.asarray(ids).reshape(-1)
+            if a.size and not np.issubdtype(a.dtype, np.integer):
+                raise ValueError("ids must be integers")
+            t = torch.from_numpy(a.astype(np.int64)).to(dev)
+        sig, norm2, keys = self._probe_rows(sig, norm2, keys)     # the sort below leaves copies: consumed freely
+        n, m = self.n, sig.shape[0]
+        if t.numel() != m:
+            raise ValueError("%d ids for %d rows" % (t.numel(), m))
+        if update_lists and n >= 2**31:
+            raise ValueError("lists are kept for fewer than 2^31 queries")
+        if m == 0:
+            return
+        t, order = torch.sort(t)
+        if bool(((t[0] < 0) | (t[-1] >= n) | (t[1:] == t[:-1]).any()).item()):
+            raise ValueError("ids must be distinct and lie in [0, %d)" % n)
+        sig, norm2, keys = sig[order].contiguous(), norm2[order].contiguous(), keys[:, order].contiguous()
+        step = max(1, (2**32 - 1) // self.b)      # the probe of an update takes m * b < 2^32 words per call
+        if update_lists and m > step:             # successive replacements give the same lists
+            self._replace_check_lists(t)
+            picked = 0
+            for q0 in range(0, m, step):
+                q1 = min(m, q0 + step)
+                self.replace(t[q0:q1], sig[q0:q1], norm2[q0:q1], keys[:, q0:q1].contiguous(), update_lists=True)
+                picked += self.last_picked
+            self.last_picked = picked
+            return
+        rids = ((t + 2**31) % 2**32 - 2**31).to(torch.int32)
+        replaced = ops.idmap_build(rids, n)
+        pick = None
+        if update_lists:
+            K = self.lists_K
+            pick = ops.lists_remove_mark(self.lists[0], self.lists[1], n, K, replaced)     # raises before any write
+        nkeys, nids, ndir, pick_keys = ops.index_replace(self.keys, self.ids, self.dir, replaced, rids,
+                                                         keys.clone() if update_lists else keys, pick)
+        if not self._own_rows:      # copy on first write: the constructor's tensors stay as they were given
+            self._sig_buf, self._norm2_buf = self._sig_buf.clone(), self._norm2_buf.clone()
+            self.sig, self.norm2 = self._sig_buf[:n], self._norm2_buf[:n]
+            self._own_rows = True
+        ops.rows_replace(self.sig, self.norm2, rids, sig, norm2)
+        self.keys, self.ids, self.dir = nkeys, nids, ndir
+        if not update_lists:
+            self.lists, self.last_picked = None, None
+            return
+        raw, pws = ops.index_probe(nkeys, nids, ndir, self.r, keys)
+        r_off, r_idx, r_milli, _, skeys = ops.index_finish_rows(self.sig, self.norm2, sig, norm2, self.b, pws, raw, K, rids,
+                                                                want_keys=True)
+        pick_ids = pick.members()
+        rows = pick_ids.to(torch.int64) & 0xFFFFFFFF
+        psig, pnorm2 = self.sig[rows], self.norm2[rows]
+        offs, idxs, millis, base = [torch.zeros((1,), dtype=torch.int64, device=dev)], [], [], 0
+        for q0 in range(0, pick.count, step):
+            q1 = min(pick.count, q0 + step)
+            praw, ppws = ops.index_probe(nkeys, nids, ndir, self.r, pick_keys[:, q0:q1].contiguous())
+            off, idx, milli, _ = ops.index_finish_rows(self.sig, self.norm2, psig[q0:q1], pnorm2[q0:q1].contiguous(),
+                                                       self.b, ppws, praw, K, pick_ids[q0:q1].contiguous())
+            offs.append(off[1:] + base)
+            idxs.append(idx)
+            millis.append(milli)
+            base += idx.numel()
+        e = torch.empty((0,), dtype=torch.int32, device=dev)
+        self.lists = ops.lists_replace(*self.lists, n, self.b, K, replaced, rids, pick, pick_ids, raw, skeys, r_off, r_idx,
+                                       r_milli, torch.cat(offs), torch.cat(idxs) if idxs else e,
+                                       torch.cat(millis) if millis else e)
+        self.last_picked = pick.count
+
+    def _replace_check_lists(self, t):
+        """the stored lists' contract, checked before the first of several successive replacements writes anything"""
+        rids = ((t[:1] + 2**31) % 2**32 - 2**31).to(torch.int32)
+        ops.lists_remove_mark(self.lists[0], self.lists[1], self.n, self.lists_K, ops.idmap_build(rids, self.n))
+
+    def set(self, ids, offsets, rows, update_lists=False):
+        """signatures() of CSR answer sets, then replace(): answer set x becomes that of indexed query ids[x]"""
+        return self.replace(ids, *self.signatures(offsets, rows), update_lists=update_lists)
 
     def neighbours_of(self, first_id, m, K=None, keys=None):
         """the lists of the indexed queries first_id .. first_id + m - 1 recomputed from the index: each query's K best

@@ -1148,9 +1148,10 @@ def index_remove(keys, ids, removed, pick=None):
     return keys_out, ids_out, dir_out, pick_keys
 
 
-def index_finish_rows(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K, self_ids):
+def index_finish_rows(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K, self_ids, want_keys=False):
     """index_finish for probe rows scattered over the index: row q is indexed query self_ids[q] (int32 device tensor
-    [m]) and stays out of its own list (qrlsh_index_probe_finish_rows) -> (off, idx, milli, avail)"""
+    [m]) and stays out of its own list (qrlsh_index_probe_finish_rows) -> (off, idx, milli, avail); want_keys: and the
+    select key of every raw word, as index_finish returns them"""
     lib = _lib.load()
     n, P = sig.shape
     m = probe_sig.shape[0]
@@ -1169,6 +1170,8 @@ def index_finish_rows(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K, s
                                                  m, _ptr(self_ids), _ptr(probe_ws), _ptr(raw), n_raw, K, _ptr(off),
                                                  _ptr(idx), _ptr(milli), _ptr(avail), _ptr(ws), ws.numel(), _stream()))
     cnt = int(off[m].item()) if m else 0
+    if want_keys:
+        return off, idx[:cnt], milli[:cnt], avail, ws[:n_raw * 8].view(torch.int64)
     return off, idx[:cnt], milli[:cnt], avail
 
 
@@ -1224,6 +1227,96 @@ def lists_remove(src, dst, val, n, K, removed, pick, re_off, re_idx, re_milli, r
     _lib.check(lib.qrlsh_lists_remove_fill(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, int(K), _ptr(removed.ws),
                                            _ptr(pick.ws), _ptr(re_off), _ptr(re_idx), _ptr(re_milli), _ptr(re_self), n_pick,
                                            _ptr(ws), ws.numel(), cnt, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()))
+    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+
+
+# ---------------------------------------------------------------------------
+# replacing queries of a built index in place (csrc/replace.hip)
+# ---------------------------------------------------------------------------
+def rows_replace(sig, norm2, replaced_ids, new_sig, new_norm2):
+    """rows (and norms) replaced_ids[x] of sig / norm2 become new_sig[x] / new_norm2[x], IN PLACE (qrlsh_rows_replace);
+    replaced_ids: int32 device tensor [m] of distinct ids"""
+    lib = _lib.load()
+    n, P = sig.shape
+    m = new_sig.shape[0]
+    _need(replaced_ids, torch.int32, "replaced_ids", 1)
+    _need(new_norm2, torch.int64, "new_norm2", 1)
+    if new_sig.dtype != sig.dtype or new_sig.shape[1] != P or replaced_ids.numel() != m or new_norm2.numel() != m:
+        raise ValueError("the new rows must have the rows' format, with one id and one norm each")
+    if not (sig.is_contiguous() and norm2.is_contiguous() and new_sig.is_contiguous()):
+        raise ValueError("rows and norms must be contiguous")
+    _lib.check(lib.qrlsh_rows_replace(_ptr(sig), P * sig.element_size(), _ptr(norm2), n, _ptr(replaced_ids), _ptr(new_sig),
+                                      _ptr(new_norm2), m, _stream()))
+
+
+def index_replace(keys, ids, dirw, replaced, replaced_ids, new_keys, pick=None):
+    """a built index (keys int64 [b, n], ids int32 [b, n], directory) whose queries replaced_ids (int32 [m], ascending;
+    `replaced` = their IdMap) take the band keys new_keys int64 [b, m] (consumed) -> (keys [b, n], ids [b, n],
+    directory, pick_keys): byte for byte index_build of the key matrix with those columns overwritten.  pick: an IdMap
+    of ids outside `replaced`; pick_keys int64 [b, pick.count] = the keys those rows are indexed under (None without)."""
+    lib = _lib.load()
+    _need(keys, torch.int64, "keys", 2)
+    _need(ids, torch.int32, "ids", 2)
+    _need(dirw, torch.int32, "dirw", 1)
+    _need(new_keys, torch.int64, "new_keys", 2)
+    _need(replaced_ids, torch.int32, "replaced_ids", 1)
+    b, n = keys.shape
+    m = replaced.count
+    if tuple(ids.shape) != (b, n) or replaced.n != n or (pick is not None and pick.n != n):
+        raise ValueError("ids must be [b, n] and the id maps cover [0, n) = [0, %d)" % n)
+    if tuple(new_keys.shape) != (b, m) or replaced_ids.numel() != m or new_keys.device != keys.device:
+        raise ValueError("new_keys must be [b, m] = [%d, %d] with one distinct id per column, on the index's device" % (b, m))
+    if dirw.numel() < int(lib.qrlsh_index_dir_words(n, b)):
+        raise ValueError("the directory is shorter than qrlsh_index_dir_words(n, b)")
+    dev = keys.device
+    n_pick = pick.count if pick is not None else 0
+    pick_keys = torch.empty((b, n_pick), dtype=torch.int64, device=dev) if pick is not None else None
+    if m == 0:
+        return keys, ids, dirw, pick_keys
+    keys_out, ids_out, dir_out = torch.empty_like(keys), torch.empty_like(ids), torch.empty_like(dirw)
+    ws = _ws(lib.qrlsh_index_replace_workspace_bytes(n, m, b), dev)
+    _lib.check(lib.qrlsh_index_replace(_ptr(keys), _ptr(ids), _ptr(dirw), n, b, _ptr(replaced.ws), _ptr(replaced_ids),
+                                       _ptr(new_keys), m, _ptr(pick.ws) if n_pick else None, n_pick, _ptr(keys_out),
+                                       _ptr(ids_out), _ptr(dir_out), _ptr(pick_keys) if n_pick else None, _ptr(ws),
+                                       ws.numel(), _stream()))
+    return keys_out, ids_out, dir_out, pick_keys
+
+
+def lists_replace(src, dst, val, n, b, K, replaced, replaced_ids, pick, pick_ids, raw, select_keys, r_off, r_idx, r_milli,
+                  p_off, p_idx, p_milli):
+    """The stored top-K lists after the queries of `replaced` took new rows (csrc/replace.hip).  raw / select_keys /
+    r_off / r_idx / r_milli: the probe of the batch against the new index (index_probe, index_finish_rows with
+    self_ids = replaced_ids and want_keys); pick / pick_ids: lists_remove_mark's rows over `replaced` and their
+    members(); p_off / p_idx / p_milli: their probe.  -> (src, dst, val): new tensors, element for element the lists
+    of a run over the new rows at K."""
+    lib = _lib.load()
+    _remove_lists_args(src, dst, val, n, K)
+    dev = src.device
+    m, n_pick, n_edges, n_raw = replaced.count, pick.count, src.numel(), raw.numel()
+    for t, name in ((raw, "raw"), (select_keys, "select_keys"), (r_off, "r_off"), (p_off, "p_off")):
+        _need(t, torch.int64, name, 1)
+    for t, name in ((r_idx, "r_idx"), (r_milli, "r_milli"), (p_idx, "p_idx"), (p_milli, "p_milli"),
+                    (replaced_ids, "replaced_ids"), (pick_ids, "pick_ids")):
+        _need(t, torch.int32, name, 1)
+    if (select_keys.numel() != n_raw or r_off.numel() != m + 1 or p_off.numel() != n_pick + 1
+            or replaced_ids.numel() != m or pick_ids.numel() != n_pick or r_idx.numel() != r_milli.numel()
+            or p_idx.numel() != p_milli.numel()):
+        raise ValueError("select_keys must match raw, the offsets hold one more entry than their rows, idx match milli")
+    if m * b >= 2**32:
+        raise ValueError("a list replacement takes m * b < 2^32 per call")
+    ws = _ws(lib.qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw), dev)
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    head = (_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, int(b), int(K), _ptr(replaced.ws), _ptr(replaced_ids),
+            _ptr(pick.ws), _ptr(pick_ids), n_pick)
+    _lib.check(lib.qrlsh_lists_replace_count(*head, _ptr(raw), _ptr(select_keys), n_raw, _ptr(r_off), _ptr(p_off), _ptr(ws),
+                                             ws.numel(), _ptr(total), _stream()))
+    cnt = int(total.item())
+    if cnt < 0:
+        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
+    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
+    _lib.check(lib.qrlsh_lists_replace_fill(*head, n_raw, _ptr(r_off), _ptr(r_idx), _ptr(r_milli), _ptr(p_off), _ptr(p_idx),
+                                            _ptr(p_milli), _ptr(ws), ws.numel(), cnt, _ptr(out[0]), _ptr(out[1]),
+                                            _ptr(out[2]), _stream()))
     return out[0][:cnt], out[1][:cnt], out[2][:cnt]
 
 

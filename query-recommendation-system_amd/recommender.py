@@ -291,6 +291,43 @@ class Recommender:
         self.ratings = np.ascontiguousarray(self.ratings[:, keep])
         return new_pos
 
+    def replace_queries(self, positions, queries, ratings=None, update_lists=False):
+        """Give served queries new texts without a new run: queries (parse_queries' form, one per position) go through
+        the same answer-set and signature route as add_queries and overwrite self.queries[positions] and the rows of
+        the run's index (QueryIndex.replace: no rebuild, no renumbering).  positions: distinct integers in any order
+        (ValueError for a duplicate or one outside the set, nothing changed).  queriesIDs stay.  ratings=None keeps the
+        ratings columns -- an edited query keeps its ratings; an integer [users, m] block overwrites them.
+        update_lists=True: the index keeps the run's top-K lists exact (QueryIndex.replace(update_lists=True)), so
+        current_query_similarities(), compute_scores(reuse_lists=True) and recommend_users serve the edited set at the
+        run's K.  Without the flag the live lists are dropped, and a later update_lists=True raises ValueError.
+        last_result stays the closed-set run's output."""
+        qi, sig, norm2, keys = self._new_query_rows(queries)
+        if update_lists and qi.lists is None:
+            raise ValueError("the live lists were dropped by a call without update_lists=True; "
+                             "compute_querySimilarities starts afresh")
+        if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
+            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        q = np.asarray(_as_numpy(queries), dtype=object)
+        m = q.shape[0]
+        pos = np.asarray(_as_numpy(positions)).reshape(-1)
+        if pos.size and not np.issubdtype(pos.dtype, np.integer):
+            raise ValueError("positions must be integers")
+        pos = pos.astype(np.int64)
+        if pos.size != m or np.unique(pos).size != m or (m and (pos.min() < 0 or pos.max() >= qi.n)):
+            raise ValueError("positions must be %d distinct integers in [0, %d)" % (m, qi.n))
+        nu = self.usersIDs.size
+        block = None
+        if ratings is not None:
+            block = np.asarray(_as_numpy(ratings))
+            if block.ndim != 2 or block.shape != (nu, m) or not np.issubdtype(block.dtype, np.integer):
+                raise ValueError("ratings must be an integer [users, m] = [%d, %d] block" % (nu, m))
+        qi.replace(pos, sig, norm2, keys, update_lists=update_lists)
+        self.queries = np.array(np.asarray(self.queries, dtype=object), copy=True)
+        self.queries[pos] = q
+        if block is not None:
+            self.ratings = np.array(self.ratings, copy=True)
+            self.ratings[:, pos] = block.astype(self.ratings.dtype)
+
     def _live_lists(self):
         """(src, dst, val) that know every added query, or None: the run's own lists before any append, the index's
         while add_queries(update_lists=True) kept them current"""
