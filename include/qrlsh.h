@@ -768,6 +768,65 @@ size_t qrlsh_user_gram_workspace_bytes(int64_t nu, int64_t nq);
 int qrlsh_user_gram(const int32_t *ratings, int64_t nu, int64_t nq, double *mean_out, double *inv_scale_out,
                     double *gram_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- user lists that stay exact when users rate queries (csrc/userlists.hip) ----------------------------------------
+ * After a batch of rating edits the user lists are element for element what qrlsh/users.py's user_similarities gives on
+ * the edited matrix, with the cluster labels and K of the build held fixed.  Lists only name users of one cluster, so
+ * the rows R that were edited touch their own clusters only.  Every entry point takes device pointers, allocates
+ * nothing, works on one stream, and returns at once and writes nothing when its batch is empty (0 cells, rows, pairs).
+ *   ratings_set: m cell edits ratings[users[i]][queries[i]] = values[i] (0 = unrate) into ratings int32 [nu][nq], in
+ *     place.  The cells of one batch are distinct (the caller's duty).  *flag_out (device uint32): bit 0 = an id outside
+ *     range was seen (that cell is not written); nothing is to be used then.
+ *   rows_stats: for the m rows in `rows` (uint32 [m]; NULL = all nu rows, m == nu) mean[row] (float64: (double)sum /
+ *     (double)count over the non-zero ratings, 0 without any -- qrlsh_center_rows' expression) and norm2[row] (int64: the
+ *     squared norm of the truncated centred row), written at the row's own index.  One workgroup per row.
+ *   pairs_score: pairs uint64 [n] = a << 32 | b (a, b < nu in any order, grouped by a) -> milli_out [n], what
+ *     qrlsh_score_pairs gives on qrlsh_center_rows' output, bit for bit, computed from the raw ratings: an element is
+ *     centred on the fly (x == 0 ? 0 : (int32_t)((double)x - mean)), the dot is exact in int64, cs = (na && nb) ?
+ *     (double)dot / (sqrt((double)na) * sqrt((double)nb)) : 0, milli = (int32_t)rint(cs * 1000.0).  Grid = (column
+ *     slice, tile of 8 consecutive pairs), slices of 256 .. 4096 columns chosen so that a handful of pairs fills the
+ *     machine; a run of pairs with one first row centres that row's slice once (LDS) and streams the other rows past
+ *     it.  16-byte loads on each address's own alignment, scalar head and tail: only `ratings` itself must be 16-byte
+ *     aligned.  Partial dots go to workspace int64 [slices][n] (qrlsh_user_pairs_score_workspace_bytes(nq, n)); a
+ *     finish kernel sums them (integers: no atomics, no memset).  No centred row is written to memory.
+ *   cluster structure: label int32 [nu] dense in [0, nc); c_off int64 [nc + 1]; c_mem int32 [nu], members ascending
+ *     within a cluster; c_pos int32 [nu], a user's place in its cluster.
+ *   cluster_pairs: rows uint32 [s] ascending -> count: off_out int64 [s + 1] (exclusive scan of cluster size - 1; [s] =
+ *     the number of pairs); fill: pairs_out[off[x] + j - (j > c_pos[rows[x]])] = rows[x] << 32 | member j, for every
+ *     other member of rows[x]'s cluster in member order: the slot of a (row, member) is computable without a search.
+ *   lists: dense, idx int32 [nu][K] (-1 past the end), milli int32 [nu][K] (0 past the end), len int32 [nu]; a row is
+ *     ordered by value descending, then id ascending, and holds positive values only.
+ *     mark: changed_map = qrlsh_idmap_build over R.  A row v outside R with len[v] == K and an entry in R enters
+ *       pick_map_out (qrlsh_idmap_workspace_bytes(nu) bytes).  out3 (device uint64 [3]; the one read-back of the update)
+ *       = {picked rows, 0 -- or ~0 when the lists break the contract (an idx outside [0, nu), a len outside [0, K]);
+ *       nothing may follow then, the number of pairs of the picked rows (sum of cluster size - 1)}.
+ *     apply (in place): S = R + picked, s = |S|; off / pair_milli = cluster_pairs_count over S ascending and the scores
+ *       of cluster_pairs_fill's pairs.  A row of S becomes the first K, by (milli descending, id ascending), of its
+ *       positive scored pairs; a row outside S of a touched cluster the first K of the merge of its stored entries whose
+ *       idx is outside R with the positive (milli(r, v), r) of every r in R of its cluster (ties by id both ways); every
+ *       other row keeps its bytes.  One wave per row; any cluster size (candidates are taken 64 at a time against the
+ *       best K so far).
+ * Limits (QRLSH_EINVAL otherwise): 1 <= K <= 64, nu < 2^31, nq < 2^31, n < 2^32. */
+int qrlsh_ratings_set(int32_t *ratings, int64_t nu, int64_t nq, const uint32_t *users, const uint32_t *queries,
+                      const int32_t *values, int64_t m, uint32_t *flag_out, void *stream);
+int qrlsh_user_rows_stats(const int32_t *ratings, int64_t nu, int64_t nq, const uint32_t *rows, int64_t m, double *mean,
+                          int64_t *norm2, void *stream);
+size_t qrlsh_user_pairs_score_workspace_bytes(int64_t nq, int64_t n);
+int qrlsh_user_pairs_score(const int32_t *ratings, int64_t nu, int64_t nq, const double *mean, const int64_t *norm2,
+                           const uint64_t *pairs, int64_t n, int32_t *milli_out, void *workspace, size_t workspace_bytes,
+                           void *stream);
+int qrlsh_user_cluster_pairs_count(const uint32_t *rows, int64_t s, const int32_t *label, const int64_t *c_off, int64_t nu,
+                                   int64_t nc, int64_t *off_out, void *stream);
+int qrlsh_user_cluster_pairs_fill(const uint32_t *rows, int64_t s, const int32_t *label, const int64_t *c_off,
+                                  const int32_t *c_mem, const int32_t *c_pos, int64_t nu, int64_t nc, const int64_t *off,
+                                  uint64_t *pairs_out, void *stream);
+int qrlsh_user_lists_mark(const int32_t *idx, const int32_t *len, int64_t nu, int32_t K, const void *changed_map,
+                          const int32_t *label, const int64_t *c_off, int64_t nc, void *pick_map_out, uint64_t *out3,
+                          void *stream);
+int qrlsh_user_lists_apply(int32_t *idx, int32_t *milli, int32_t *len, int64_t nu, int32_t K, const void *changed_map,
+                           const void *pick_map, int64_t s, const int32_t *label, const int64_t *c_off, const int32_t *c_mem,
+                           const int32_t *c_pos, int64_t nc, const int64_t *off, const int32_t *pair_milli, int64_t n_pairs,
+                           void *stream);
+
 /* ---- multi-GPU, "sets" mode: answer sets of chosen queries out of the replicated per-shard CSR arrays ------------
  * Every rank holds every shard's answer sets as an all-gather delivered them: offs[world][nql + 1] (off_bytes = 4 or 8)
  * and rows[world][max_nnz] (row_bytes = 2: unsigned 16-bit row ids, tables of at most 65536 rows; or 4), shard g =

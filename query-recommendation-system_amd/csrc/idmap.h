@@ -48,6 +48,9 @@ __device__ static inline void idmap_set(uint2 *map, uint32_t id) {
   if (!(__hip_atomic_load(bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m)) atomicOr(bits, m);
 }
 
+// the bits are set: prefix counts into the entries, the member count to *count_out (may be null)  (remove.hip)
+void idmap_finish(const IdMap &m, uint64_t *count_out, hipStream_t st);
+
 // ---- stable compaction of a tile ------------------------------------------------------------------------------------
 // element (k, thread) of the tile is its element k * RM_THREADS + thread.  wc: RM_PER * 4 words of LDS.  -> before[k] =
 // kept elements of the tile that precede element (k, thread); returns the tile's kept total.  All threads call it.

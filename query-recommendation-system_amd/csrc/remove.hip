@@ -55,7 +55,7 @@ __global__ __launch_bounds__(RM_THREADS) void idmap_pack_kernel(uint2 *__restric
 }
 
 // the bits are set: prefix counts into the entries, the member count to *count_out (may be null)
-static void idmap_finish(const IdMap &m, uint64_t *count_out, hipStream_t st) {
+void idmap_finish(const IdMap &m, uint64_t *count_out, hipStream_t st) {
   const dim3 grid((unsigned)ceil_div64(m.nw + 1, RM_THREADS)), block(RM_THREADS);
   QR_LAUNCH("idmap_popc", idmap_popc_kernel, grid, block, 0, st, (const uint2 *)m.w, m.nw, m.cnt);
   qr_scan_u64(m.cnt, m.nw + 1, m.cnt + m.nw + 1, m.sums, st);

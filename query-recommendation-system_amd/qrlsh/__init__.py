@@ -39,5 +39,6 @@ from .answers import build_answer_index, encode_queries, answer_sets, AnswerInde
 from .recommend import top_k, for_users  # noqa: F401
 from .predict import predict_users, user_lists  # noqa: F401
 from .index import QueryIndex  # noqa: F401
+from .userlists import UserLists  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

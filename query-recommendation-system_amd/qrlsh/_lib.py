@@ -28,6 +28,7 @@ SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
 INDEX_MAX_K = 256
+USER_LISTS_MAX_K = 64     # the prediction kernels' ku (csrc/userlists.hip UL_MAXK)
 REMOVE_TILE = 2048      # records (list entries) per workgroup of the removal's compactions (csrc/remove.hip RM_TILE)
 
 _vp = ctypes.c_void_p
@@ -157,6 +158,15 @@ SIGNATURES = {
     "qrlsh_center_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "qrlsh_user_gram_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_user_gram": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_ratings_set": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "qrlsh_user_rows_stats": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "qrlsh_user_pairs_score_workspace_bytes": (_sz, [_i64, _i64]),
+    "qrlsh_user_pairs_score": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "qrlsh_user_cluster_pairs_count": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _vp]),
+    "qrlsh_user_cluster_pairs_fill": (ctypes.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
+    "qrlsh_user_lists_mark": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "qrlsh_user_lists_apply": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
+                                              _i64, _vp]),
     "qrlsh_gather_sets_workspace_bytes": (_sz, [_i64]),
     "qrlsh_gather_sets_count": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
     "qrlsh_gather_sets_fill": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),

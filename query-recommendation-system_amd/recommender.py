@@ -417,6 +417,36 @@ class Recommender:
         self._log("\n" + str(round(time.time() - t0, 3)) + "s for overall users_similarity scores")
         return user_sim
 
+    # ---- user lists that follow the ratings (qrlsh.UserLists) -------------------------------------------------------
+    def live_user_similarities(self, labels=None, K=None):
+        """Build self.user_index (qrlsh.UserLists) over self.ratings: the all-device user lists (value descending, then
+        id ascending; positive values only) at list length K (default round(log_1.5 users)), which rate() then keeps
+        exact without a recompute.  labels: cluster ids per user, held fixed from here on (default:
+        users.cluster_labels, on the device when cluster_on_device).  While the index exists, recommend_users and
+        predict_users called without user_sim / ratings serve from it.  -> self.user_index"""
+        from qrlsh import users
+        from qrlsh.userlists import UserLists
+        if labels is None:
+            labels = users.cluster_labels(self.ratings, device=self.device if self.cluster_on_device else None)
+        self.user_index = UserLists.build(np.asarray(self.ratings), labels, K=K, device=self.device)
+        return self.user_index
+
+    def rate(self, users, queries, values):
+        """"user u rated query q": users / queries are 0-based positions, values the new ratings (0 = unrate; repeats
+        of one cell keep the last).  Edits self.ratings and self.user_index (UserLists.rate: the lists of the touched
+        clusters are brought up to date, nothing is recomputed).  ValueError when live_user_similarities has not built
+        an index, for a position outside range or a negative value (nothing changed).  -> rows of the lists rewritten"""
+        ui = getattr(self, "user_index", None)
+        if ui is None:
+            raise ValueError("there is no user index: call live_user_similarities first")
+        if ui.nu != self.ratings.shape[0] or ui.nq != self.ratings.shape[1]:
+            raise ValueError("the user index holds a %d x %d matrix, the recommender %d x %d (queries were added or "
+                             "removed: call live_user_similarities again)" % ((ui.nu, ui.nq) + tuple(self.ratings.shape)))
+        n = ui.rate(users, queries, values)
+        u, q, v = (np.asarray(ops.to_host(a)).reshape(-1).astype(np.int64) for a in (users, queries, values))
+        self.ratings[u, q] = v.astype(self.ratings.dtype)       # numpy assigns in order: the last repeat wins here too
+        return n
+
     # ---- N1: hybrid prediction (device) ------------------------------------------------
     def compute_scores(self, reuse_lists=False):
         """(scores_to_predict, finalPredictions DataFrame, scores_missed), recommender.py:292-343.
@@ -479,6 +509,9 @@ class Recommender:
         sum_order = self.sum_order if sum_order is None else sum_order
         if sum_order not in ("pairwise", "sequential"):
             raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        ui = getattr(self, "user_index", None)
+        if ui is not None and user_sim is None and ratings is None and (ui.nu, ui.nq) == tuple(self.ratings.shape):
+            return lists, sum_order, ui.as_user_sims(), ui.ratings   # the live user lists and their device matrix
         if user_sim is None:
             user_sim = self.compute_userSimilarities()
         return lists, sum_order, user_sim, self.ratings if ratings is None else ratings
