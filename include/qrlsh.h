@@ -827,6 +827,31 @@ int qrlsh_user_lists_apply(int32_t *idx, int32_t *milli, int32_t *len, int64_t n
                            const int32_t *c_pos, int64_t nc, const int64_t *off, const int32_t *pair_milli, int64_t n_pairs,
                            void *stream);
 
+/* ---- the matrix of the user lists follows added, removed and re-rated queries (csrc/usercolumns.hip) -----------------
+ * A column operation changes a user's centred row only where the user's old and new values in the affected columns
+ * differ (the mean is over the non-zero ratings, zeros stay zero): those rows R take the place of the edited rows in
+ * the update above, over the matrix in its new column space.  Device pointers, one stream, nothing allocated; both
+ * return QRLSH_OK at once, whatever the pointers, when m == 0 or nu == 0.
+ *   columns_changed: cols int32 [m] = the affected old column, or -1 for none (an appended column); block int32
+ *     [nu][m] = the incoming values, NULL = all zero (a removal).  With old(u, k) = cols[k] >= 0 ? ratings[u][cols[k]]
+ *     : 0 and new(u, k) = block ? block[u][k] : 0, row u enters changed_map_out (an id map over the nu rows,
+ *     qrlsh_idmap_workspace_bytes(nu) bytes, ready for qrlsh_idmap_list and qrlsh_user_lists_mark) exactly when some k
+ *     has old != new.  out2 (device uint64 [2]) = {rows in the map, 1 when a column lies outside [-1, nq): nothing is
+ *     read for it}.  Repeated columns are harmless where block is NULL.  One lane per (row, k) cell.
+ *   columns_move: out[u][j] = src[j] >= 0 ? in[u][src[j]] : block[u][~src[j]] for j < nq2; in int32 [nu][nq], block
+ *     int32 [nu][m] (NULL = all zero), out a fresh contiguous int32 [nu][nq2] that overlaps neither, 16-byte aligned.
+ *     An append is src = 0 .. nq-1, ~0 .. ~(m-1); a removal the surviving old columns in ascending order (m = the
+ *     number removed, block NULL); an overwrite the identity with ~k at the positions given.  *flag_out (device
+ *     uint32) = 1 when a src value lies outside [-m, nq): nothing is written for that column.  nq2 == 0 launches
+ *     nothing.  Grid = (tile of 4096 output columns, rows 4 apart, 8 a trip): such rows split the tile into scalar
+ *     head, 16-byte vectors and scalar tail alike, so a lane reads its 17 src values once and keeps them in registers;
+ *     per row every load (4-byte gathers) is issued before the first 16-byte store.  No LDS, no scratch.
+ * Limits (QRLSH_EINVAL otherwise): 0 <= nu, nq, nq2, m < 2^31. */
+int qrlsh_ratings_columns_changed(const int32_t *ratings, int64_t nu, int64_t nq, const int32_t *cols,
+                                  const int32_t *block, int64_t m, void *changed_map_out, uint64_t *out2, void *stream);
+int qrlsh_ratings_columns_move(const int32_t *in, int64_t nu, int64_t nq, const int32_t *src, int64_t nq2,
+                               const int32_t *block, int64_t m, int32_t *out, uint32_t *flag_out, void *stream);
+
 /* ---- multi-GPU, "sets" mode: answer sets of chosen queries out of the replicated per-shard CSR arrays ------------
  * Every rank holds every shard's answer sets as an all-gather delivered them: offs[world][nql + 1] (off_bytes = 4 or 8)
  * and rows[world][max_nnz] (row_bytes = 2: unsigned 16-bit row ids, tables of at most 65536 rows; or 4), shard g =

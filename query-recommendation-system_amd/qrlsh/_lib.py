@@ -167,6 +167,8 @@ SIGNATURES = {
     "qrlsh_user_lists_mark": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "qrlsh_user_lists_apply": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp,
                                               _i64, _vp]),
+    "qrlsh_ratings_columns_changed": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "qrlsh_ratings_columns_move": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "qrlsh_gather_sets_workspace_bytes": (_sz, [_i64]),
     "qrlsh_gather_sets_count": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
     "qrlsh_gather_sets_fill": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -5,7 +5,12 @@ matrix and brings the lists of the touched clusters up to date: afterwards they 
 users.user_similarities(new_ratings, labels, K) gives, with the labels and K of the build.  The changed rows R and the
 full rows that name one of them (picked) are scored against their clusters from the raw ratings (qrlsh_user_pairs_score:
 no centred copy of the matrix); every other row of a touched cluster merges R's new scores into what it holds.  One
-read-back per batch (the number of picked rows)."""
+read-back per batch (the number of picked rows).
+
+.add_columns(), .remove_columns() and .set_columns() follow queries that are appended, removed or re-rated
+(csrc/usercolumns.hip): the rows whose values in the affected columns differ are found on the device, the matrix moves
+out of place to its new column space, and the same update runs over it with those rows as R.  Two read-backs per batch
+(R's count with its pair count, then the picked rows)."""
 import numpy as np
 import torch
 
@@ -43,7 +48,8 @@ def rows_stats(ratings, rows=None, mean=None, norm2=None):
 
 
 class UserLists:
-    """The live user lists of one utility matrix.  Fields (device tensors): ratings int32 [nu][nq] (edited in place),
+    """The live user lists of one utility matrix.  Fields (device tensors): ratings int32 [nu][nq] (edited in place by
+    rate(); a column operation binds a new tensor and leaves the old one as it was),
     idx / milli int32 [nu][K] (-1 / 0 past a row's end), len int32 [nu], mean float64 [nu], norm2 int64 [nu], label
     int32 [nu] (dense), c_off int64 [nc + 1], c_mem / c_pos int32 [nu]."""
 
@@ -84,7 +90,8 @@ class UserLists:
         pos[order] = torch.arange(nu, device=dev) - self.c_off[:-1][dense[order]]
         self.c_pos = pos.to(torch.int32).contiguous()
         self.label = dense.to(torch.int32).contiguous()
-        self._sizes = counts.cpu().numpy()                    # host copies: the pair count of R needs no read-back
+        self._counts = counts                                 # cluster sizes, int64 [nc]
+        self._sizes = counts.cpu().numpy()                    # host copies: the pair count of rate()'s R needs no read-back
         self._dense_host = dense.cpu().numpy()
         # the first lists, in the dense form
         src, dst, val = _users.user_similarities(r, lab, self.K, device=dev)
@@ -130,20 +137,30 @@ class UserLists:
         R = np.unique(u)
 
         lib, st, dev = _lib.load(), _stream(), self.ratings.device
-        nu, nq, K, nc = self.nu, self.nq, self.K, self.nc
+        nu, nq = self.nu, self.nq
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
         ud, qd, vd, Rd = up(u), up(q), up(v), up(R)
         flag = torch.zeros((1,), dtype=torch.int32, device=dev)
         _lib.check(lib.qrlsh_ratings_set(_ptr(self.ratings), nu, nq, _ptr(ud), _ptr(qd), _ptr(vd), u.size, _ptr(flag), st))
+        return self._refresh(Rd, int(R.size), int((self._sizes[self._dense_host[R]] - 1).sum()))
+
+    def _refresh(self, Rd, r, r_pairs, rmap=None):
+        """The lists after the rows R (Rd: int32 device ids ascending, r of them, r_pairs = the sum of their clusters'
+        sizes - 1) changed in self.ratings: their statistics, mark, S = R + picked scored against their clusters, apply.
+        rmap: the id map over R where the caller holds it.  -> len(S); sets .last_picked"""
+        lib, st, dev = _lib.load(), _stream(), self.ratings.device
+        nu, K, nc = self.nu, self.K, self.nc
         rows_stats(self.ratings, Rd, self.mean, self.norm2)
         map_bytes = lib.qrlsh_idmap_workspace_bytes(nu)
-        rmap, pmap = ops._ws(map_bytes, dev), ops._ws(map_bytes, dev)
-        out2 = torch.zeros((2,), dtype=torch.int64, device=dev)
+        pmap = ops._ws(map_bytes, dev)
         out3 = torch.zeros((3,), dtype=torch.int64, device=dev)
-        _lib.check(lib.qrlsh_idmap_build(_ptr(Rd), R.size, nu, _ptr(rmap), rmap.numel(), _ptr(out2), st))
+        if rmap is None:
+            rmap = ops._ws(map_bytes, dev)
+            out2 = torch.zeros((2,), dtype=torch.int64, device=dev)
+            _lib.check(lib.qrlsh_idmap_build(_ptr(Rd), r, nu, _ptr(rmap), rmap.numel(), _ptr(out2), st))
         _lib.check(lib.qrlsh_user_lists_mark(_ptr(self.idx), _ptr(self.len), nu, K, _ptr(rmap), _ptr(self.label),
                                              _ptr(self.c_off), nc, _ptr(pmap), _ptr(out3), st))
-        n_pick, broken, pick_pairs = out3.tolist()            # the one read-back of the update
+        n_pick, broken, pick_pairs = out3.tolist()            # the one read-back of the shared tail
         if broken:
             raise ValueError("the stored user lists break their contract (an index outside [0, %d) or a length outside "
                              "[0, %d])" % (nu, K))
@@ -154,7 +171,7 @@ class UserLists:
         else:
             S = Rd
         s = int(S.numel())
-        n_pairs = int((self._sizes[self._dense_host[R]] - 1).sum()) + int(pick_pairs)
+        n_pairs = int(r_pairs) + int(pick_pairs)
         off = torch.empty((s + 1,), dtype=torch.int64, device=dev)
         pairs = torch.empty((max(n_pairs, 1),), dtype=torch.int64, device=dev)
         _lib.check(lib.qrlsh_user_cluster_pairs_count(_ptr(S), s, _ptr(self.label), _ptr(self.c_off), nu, nc, _ptr(off), st))
@@ -166,6 +183,112 @@ class UserLists:
                                               _ptr(self.c_pos), nc, _ptr(off), _ptr(pm), n_pairs, st))
         self.last_picked = int(n_pick)
         return s
+
+    # ---- queries appended, removed, re-rated: the matrix moves to its new column space (csrc/usercolumns.hip) ----------
+    def _block(self, block, m=None):
+        """a batch's incoming values -> (int32 device tensor [nu][m] or None for all zero, m).  A host array is checked
+        (integers in [0, 2^31), shape [nu][m]) and uploaded; an int32 device tensor is taken as it is."""
+        if isinstance(block, torch.Tensor) and block.device.type != "cpu":
+            if block.dtype != torch.int32 or block.dim() != 2 or block.shape[0] != self.nu or (m is not None and block.shape[1] != m):
+                raise ValueError("a device block must be int32 [%d][%s], got %s %s"
+                                 % (self.nu, "m" if m is None else m, block.dtype, tuple(block.shape)))
+            if block.device != self.ratings.device:
+                raise ValueError("the block is on %s, the matrix on %s" % (block.device, self.ratings.device))
+            return block.contiguous(), int(block.shape[1])
+        b = np.asarray(block.numpy() if isinstance(block, torch.Tensor) else block)
+        if b.ndim != 2 or b.shape[0] != self.nu or (m is not None and b.shape[1] != m) or not np.issubdtype(b.dtype, np.integer):
+            raise ValueError("the block must be an integer [%d][%s] array, got %s %s"
+                             % (self.nu, "m" if m is None else m, b.dtype, b.shape))
+        if b.size and (b.min() < 0 or b.max() >= 2**31):
+            raise ValueError("values must lie in [0, 2^31)")
+        return torch.from_numpy(np.ascontiguousarray(b, dtype=np.int32)).to(self.ratings.device), int(b.shape[1])
+
+    def _columns(self, name, cols, m=None):
+        c = np.asarray(cols.cpu() if isinstance(cols, torch.Tensor) else cols).reshape(-1)
+        if c.size and not np.issubdtype(c.dtype, np.integer):
+            raise ValueError("%s: the columns must be integers" % name)
+        c = c.astype(np.int64)
+        if m is not None and c.size != m:
+            raise ValueError("%s: %d columns for a block of %d" % (name, c.size, m))
+        if c.size and (c.min() < 0 or c.max() >= self.nq):
+            raise ValueError("%s: column outside [0, %d)" % (name, self.nq))
+        return c
+
+    def _move(self, cols, block, m, src):
+        """cols: the affected old columns (host int64 [m], -1 = none), block: device int32 [nu][m] or None (zeros),
+        src: host int64 [nq2] -- what the matrix holds afterwards (usercolumns.hip).  The rows whose values differ are
+        found against the old matrix, the matrix moves out of place, then the lists follow."""
+        lib, st, dev = _lib.load(), _stream(), self.ratings.device
+        nu, nq, nq2 = self.nu, self.nq, int(src.size)
+        if nq2 >= 2**31:
+            raise ValueError("the matrix would have %d columns: fewer than 2^31 are served" % nq2)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+        rmap = ops._ws(lib.qrlsh_idmap_workspace_bytes(nu), dev)
+        head = torch.zeros((4,), dtype=torch.int64, device=dev)     # R's count, a refused column, R's pairs, a refused src
+        flag = torch.zeros((1,), dtype=torch.int32, device=dev)
+        _lib.check(lib.qrlsh_ratings_columns_changed(_ptr(self.ratings), nu, nq, _ptr(up(cols)), _ptr(block), m, _ptr(rmap),
+                                                     _ptr(head), st))
+        new = torch.empty((nu, nq2), dtype=torch.int32, device=dev)
+        _lib.check(lib.qrlsh_ratings_columns_move(_ptr(self.ratings), nu, nq, _ptr(up(src)), nq2, _ptr(block), m, _ptr(new),
+                                                  _ptr(flag), st))
+        Rbuf = torch.full((nu,), -1, dtype=torch.int32, device=dev)
+        _lib.check(lib.qrlsh_idmap_list(_ptr(rmap), nu, _ptr(Rbuf), st))
+        member = Rbuf >= 0
+        head[2] = ((self._counts[self.label.to(torch.int64)[Rbuf.clamp(min=0).to(torch.int64)]] - 1) * member).sum()
+        head[3] = flag[0]
+        r, bad_col, r_pairs, bad_src = head.tolist()          # the first read-back; the tail's mark is the second
+        if bad_col or bad_src:
+            raise RuntimeError("a column outside range reached the device (%d, %d)" % (bad_col, bad_src))
+        self.ratings, self.nq = new, nq2
+        self.last_picked = 0
+        if r == 0:
+            return 0
+        return self._refresh(Rbuf[:r].contiguous(), r, r_pairs, rmap)
+
+    def add_columns(self, block):
+        """Append columns to the matrix: block = integer [nu][m] host array (values in [0, 2^31)), int32 device tensor
+        [nu][m], or an int m = m unrated columns.  The lists follow exactly: the rows that rated one of the new columns
+        are the changed rows.  ValueError for a wrong shape or value (nothing changed).  -> the number of rows
+        rewritten; .last_picked as after rate().  The matrix is rebuilt out of place (.ratings is a new tensor)."""
+        if isinstance(block, (int, np.integer)) and not isinstance(block, bool):
+            m, bd = int(block), None
+            if m < 0:
+                raise ValueError("cannot append %d columns" % m)
+        else:
+            bd, m = self._block(block)
+        if m == 0:
+            self.last_picked = 0
+            return 0
+        src = np.concatenate((np.arange(self.nq, dtype=np.int64), -1 - np.arange(m, dtype=np.int64)))
+        return self._move(np.full(m, -1, dtype=np.int64), bd, m, src)
+
+    def remove_columns(self, cols):
+        """Take columns out of the matrix (integers in any order, duplicates allowed; ValueError for one outside
+        [0, nq), nothing changed); the columns left keep their order.  The rows that had rated one of them are the
+        changed rows.  Removing every column is legal (nq == 0: every list is empty then).  -> rows rewritten"""
+        c = np.unique(self._columns("remove_columns", cols))
+        if c.size == 0:
+            self.last_picked = 0
+            return 0
+        keep = np.ones(self.nq, dtype=bool)
+        keep[c] = False
+        return self._move(c, None, int(c.size), np.flatnonzero(keep))
+
+    def set_columns(self, cols, block):
+        """Overwrite whole columns: block[:, k] becomes column cols[k] (cols distinct; block as add_columns takes it,
+        but not an int).  The rows whose values in these columns differ from the block are the changed rows.
+        ValueError for a duplicate or a column outside [0, nq), a wrong shape or value (nothing changed).
+        -> rows rewritten"""
+        c = self._columns("set_columns", cols)
+        if np.unique(c).size != c.size:
+            raise ValueError("set_columns: the columns must be distinct")
+        bd, m = self._block(block, int(c.size))
+        if m == 0:
+            self.last_picked = 0
+            return 0
+        src = np.arange(self.nq, dtype=np.int64)
+        src[c] = -1 - np.arange(m, dtype=np.int64)
+        return self._move(c, bd, m, src)
 
     def coo(self):
         """(src, dst, milli) int32 device tensors, the form users.user_similarities returns"""

@@ -116,9 +116,11 @@ def user_similarities(ratings, labels, K=None, device="cuda"):
     nu = ratings.shape[0]
     if K is None:
         K = max_candidates(nu)
-    pairs, milli = cluster_pair_scores(ratings, labels, device)
     z = torch.empty((0,), dtype=torch.int32, device=device)
-    keep = milli > 0                                         # :276 negatives -> 0; zero weights are dropped
+    if ratings.shape[1] == 0:                                # no columns (UserLists.remove_columns of all): nobody is similar
+        return z, z.clone(), z.clone()
+    pairs, milli = cluster_pair_scores(ratings, labels, device)
+    keep = milli > 0                                        # :276 negatives -> 0; zero weights are dropped
     pairs, milli = pairs[keep].contiguous(), milli[keep].contiguous()
     if pairs.numel() == 0:
         return z, z.clone(), z.clone()

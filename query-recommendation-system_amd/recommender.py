@@ -207,6 +207,17 @@ class Recommender:
         sig, norm2, keys = qi.signatures(offsets, rows)
         return qi, sig, norm2, keys
 
+    def _user_index_in_step(self, block=None):
+        """self.user_index when it holds self.ratings' shape now (it then follows the column operation under way), else
+        None: an index that is already out of step is left alone.  A ratings block the index would refuse is refused
+        here, before the query index takes the batch."""
+        ui = getattr(self, "user_index", None)
+        if ui is None or (ui.nu, ui.nq) != tuple(self.ratings.shape):
+            return None
+        if block is not None and block.size and (block.min() < 0 or block.max() >= 2**31):
+            raise ValueError("ratings must lie in [0, 2^31) while a user index follows them")
+        return ui
+
     def add_queries(self, queries, ratings=None, ids=None, update_lists=False):
         """Take m new queries (parse_queries' form) into the served set without a new run: their answer sets and
         signatures under the last run's table are appended to the run's index (QueryIndex.append: no rebuild), and
@@ -222,7 +233,10 @@ class Recommender:
         update_lists=True: the index also keeps the run's top-K lists current (QueryIndex.append(update_lists=True)):
         current_query_similarities() then returns what compute_querySimilarities would over all queries at the run's
         K, and compute_scores(reuse_lists=True) predicts from them.  last_result is still left alone.  Without the flag
-        the live lists are dropped (they would be stale), and a later update_lists=True raises ValueError."""
+        the live lists are dropped (they would be stale), and a later update_lists=True raises ValueError.
+        A user index in step with self.ratings (live_user_similarities) follows, whatever update_lists says:
+        UserLists.add_columns takes the block (m unrated columns without one), so rate, recommend_users and
+        predict_users keep serving from it."""
         qi, sig, norm2, keys = self._new_query_rows(queries)
         if update_lists and qi.lists is None:
             raise ValueError("the live lists were dropped by an add_queries without update_lists=True; "
@@ -254,7 +268,10 @@ class Recommender:
                 labels = labels.astype(cur.dtype)
             except (TypeError, ValueError):
                 raise ValueError("ids of dtype %s do not fit queriesIDs of dtype %s" % (labels.dtype, cur.dtype))
+        ui = self._user_index_in_step(None if ratings is None else block)
         first, _ = qi.append(sig, norm2, keys, update_lists=update_lists)
+        if ui is not None:
+            ui.add_columns(m if ratings is None else block)
         self.queries = np.concatenate((np.asarray(self.queries, dtype=object), q), axis=0)
         self.queriesIDs = np.concatenate((cur, labels))
         self.ratings = np.hstack((self.ratings, block))
@@ -268,7 +285,8 @@ class Recommender:
         update_lists=True: the index keeps the run's top-K lists exact (QueryIndex.remove(update_lists=True)), so
         current_query_similarities() and compute_scores(reuse_lists=True) serve the shrunk set at the run's K.  Without
         the flag the live lists are dropped, and a later update_lists=True raises ValueError.  last_result stays the
-        closed-set run's output."""
+        closed-set run's output.  A user index in step with self.ratings follows (UserLists.remove_columns), whatever
+        update_lists says."""
         from qrlsh.index import QueryIndex
         res = getattr(self, "last_result", None)
         if res is None or getattr(self, "last_table", None) is None:
@@ -284,7 +302,10 @@ class Recommender:
         pos = np.asarray(_as_numpy(positions)).reshape(-1)
         if pos.size and not np.issubdtype(pos.dtype, np.integer):
             raise ValueError("positions must be integers")
+        ui = self._user_index_in_step()
         new_pos = ops.to_host(qi.remove(pos, update_lists=update_lists))
+        if ui is not None:
+            ui.remove_columns(pos)
         keep = new_pos >= 0
         self.queries = np.asarray(self.queries, dtype=object)[keep]
         self.queriesIDs = self.queriesIDs[keep]
@@ -300,7 +321,8 @@ class Recommender:
         update_lists=True: the index keeps the run's top-K lists exact (QueryIndex.replace(update_lists=True)), so
         current_query_similarities(), compute_scores(reuse_lists=True) and recommend_users serve the edited set at the
         run's K.  Without the flag the live lists are dropped, and a later update_lists=True raises ValueError.
-        last_result stays the closed-set run's output."""
+        last_result stays the closed-set run's output.  With a ratings block, a user index in step with self.ratings
+        follows (UserLists.set_columns), whatever update_lists says; without one it is not touched."""
         qi, sig, norm2, keys = self._new_query_rows(queries)
         if update_lists and qi.lists is None:
             raise ValueError("the live lists were dropped by a call without update_lists=True; "
@@ -321,7 +343,10 @@ class Recommender:
             block = np.asarray(_as_numpy(ratings))
             if block.ndim != 2 or block.shape != (nu, m) or not np.issubdtype(block.dtype, np.integer):
                 raise ValueError("ratings must be an integer [users, m] = [%d, %d] block" % (nu, m))
+        ui = self._user_index_in_step(block) if block is not None else None
         qi.replace(pos, sig, norm2, keys, update_lists=update_lists)
+        if ui is not None:
+            ui.set_columns(pos, block)
         self.queries = np.array(np.asarray(self.queries, dtype=object), copy=True)
         self.queries[pos] = q
         if block is not None:
@@ -421,7 +446,8 @@ class Recommender:
     def live_user_similarities(self, labels=None, K=None):
         """Build self.user_index (qrlsh.UserLists) over self.ratings: the all-device user lists (value descending, then
         id ascending; positive values only) at list length K (default round(log_1.5 users)), which rate() then keeps
-        exact without a recompute.  labels: cluster ids per user, held fixed from here on (default:
+        exact without a recompute, and add_queries / remove_queries / replace_queries keep in step with the served
+        queries (UserLists.add_columns / remove_columns / set_columns).  labels: cluster ids per user, held fixed from here on (default:
         users.cluster_labels, on the device when cluster_on_device).  While the index exists, recommend_users and
         predict_users called without user_sim / ratings serve from it.  -> self.user_index"""
         from qrlsh import users
@@ -435,7 +461,9 @@ class Recommender:
         """"user u rated query q": users / queries are 0-based positions, values the new ratings (0 = unrate; repeats
         of one cell keep the last).  Edits self.ratings and self.user_index (UserLists.rate: the lists of the touched
         clusters are brought up to date, nothing is recomputed).  ValueError when live_user_similarities has not built
-        an index, for a position outside range or a negative value (nothing changed).  -> rows of the lists rewritten"""
+        an index, for a position outside range or a negative value (nothing changed), and for an index that fell out of
+        step with self.ratings (add_queries, remove_queries and replace_queries keep an index in step that was in step
+        when they were called).  -> rows of the lists rewritten"""
         ui = getattr(self, "user_index", None)
         if ui is None:
             raise ValueError("there is no user index: call live_user_similarities first")
