@@ -852,6 +852,42 @@ int qrlsh_ratings_columns_changed(const int32_t *ratings, int64_t nu, int64_t nq
 int qrlsh_ratings_columns_move(const int32_t *in, int64_t nu, int64_t nq, const int32_t *src, int64_t nq2,
                                const int32_t *block, int64_t m, int32_t *out, uint32_t *flag_out, void *stream);
 
+/* ---- users join and leave the live user lists (csrc/userrows.hip) ------------------------------------------------------
+ * The user-row counterpart of the column operations: labels and K stay those of the build.  New rows are the changed
+ * rows R of the update above over grown arrays (no stored entry names a new id, so nothing is picked); removed rows are
+ * R with mean and norm2 set to zero (every score against them is 0 and positive-only lists drop them), after which the
+ * survivors are renumbered by rank.  Device pointers, one stream, nothing allocated.
+ *   rows_nearest: rows int32 [m][nq] (a block of its own, 16-byte aligned) with rows_mean / rows_norm2 by
+ *     qrlsh_user_rows_stats over it; ratings / mean / norm2 the nu existing users.  best_user_out[k] = the existing user
+ *     with the largest milli(k, u) -- pairs_score's expression -- ties to the lowest id, best_milli_out[k] that value;
+ *     (-1, 0) where no score is positive.  milli_out int32 [m][nu] = every score, NULL to skip.  Grid = (slice of 1024
+ *     columns, tile of 8 new rows, group of 128 existing rows that are 4 apart: such rows share their alignment): the
+ *     tile's slice is centred once into LDS (32 KB), every wave streams existing rows past it with 16-byte loads, and the
+ *     exact integer partial dots are added to workspace int64 [nu][m] (qrlsh_user_rows_nearest_workspace_bytes(nu, m),
+ *     8-byte aligned; cleared inside the call) with 64-bit integer atomics -- any order gives the same sum.  The matrix
+ *     is read once per tile of new rows.  m == 0 returns at once.
+ *   rows_move: out[u2] = src[u2] >= 0 ? in[src[u2]] : block[~src[u2]] for u2 < nu2, whole rows of nq values; in int32
+ *     [nu][nq], block int32 [m][nq] (NULL when m == 0), out a fresh contiguous int32 [nu2][nq] that overlaps neither,
+ *     16-byte aligned.  An append is src = 0 .. nu-1, ~0 .. ~(m-1); a removal the surviving rows in ascending order
+ *     (m = 0).  *flag_out (device uint32) = 1 when a src value lies outside [-m, nu): that row is not written.  16-byte
+ *     stores on the output's alignment with scalar head and tail; 16-byte loads where the source piece shares that
+ *     alignment (always when nq % 4 == 0 and block is 16-byte aligned), 4-byte loads otherwise.  nu2 == 0 returns at once.
+ *   lists_renumber: idx_out / milli_out [nu2][K], len_out [nu2] = row src[u2] of idx / milli / len [nu][K] with every
+ *     id d rewritten to new_pos[d] (int32 [nu]; negative = gone); src[u2] < 0 = an empty row (-1 / 0 / 0).  *flag_out
+ *     (device uint32) = 1 when an entry's target is gone or outside [0, nu2), an index outside [0, nu), a length outside
+ *     [0, K] or a src value >= nu was seen: nothing is to be used then.  One lane per entry of the new lists.
+ * Limits (QRLSH_EINVAL otherwise): 1 <= K <= 64; 0 <= nu, nu2, nq, m < 2^31; rows_nearest: m * nu < 2^32. */
+size_t qrlsh_user_rows_nearest_workspace_bytes(int64_t nu, int64_t m);
+int qrlsh_user_rows_nearest(const int32_t *ratings, int64_t nu, int64_t nq, const double *mean, const int64_t *norm2,
+                            const int32_t *rows, int64_t m, const double *rows_mean, const int64_t *rows_norm2,
+                            int32_t *best_user_out, int32_t *best_milli_out, int32_t *milli_out, void *workspace,
+                            size_t workspace_bytes, void *stream);
+int qrlsh_ratings_rows_move(const int32_t *in, int64_t nu, int64_t nq, const int32_t *src, int64_t nu2,
+                            const int32_t *block, int64_t m, int32_t *out, uint32_t *flag_out, void *stream);
+int qrlsh_user_lists_renumber(const int32_t *idx, const int32_t *milli, const int32_t *len, int64_t nu, int32_t K,
+                              const int32_t *src, int64_t nu2, const int32_t *new_pos, int32_t *idx_out,
+                              int32_t *milli_out, int32_t *len_out, uint32_t *flag_out, void *stream);
+
 /* ---- multi-GPU, "sets" mode: answer sets of chosen queries out of the replicated per-shard CSR arrays ------------
  * Every rank holds every shard's answer sets as an all-gather delivered them: offs[world][nql + 1] (off_bytes = 4 or 8)
  * and rows[world][max_nnz] (row_bytes = 2: unsigned 16-bit row ids, tables of at most 65536 rows; or 4), shard g =

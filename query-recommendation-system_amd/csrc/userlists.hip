@@ -23,7 +23,7 @@
 //   lists_mark     one lane per stored entry; a picked row enters the pick map once and adds its pair count.
 //   lists_apply    one wave per row of a touched cluster: the best K (K <= 64: one per lane) of any number of
 //                  candidates, taken in chunks of 64 that are ranked against the best so far.
-#include "idmap.h"
+#include "userlists.h"
 
 constexpr int US_THREADS = 256;
 constexpr int US_TP = 8;             // pairs per tile
@@ -31,10 +31,6 @@ constexpr int US_MAXCOLS = 4096;     // columns per slice at most (the first row
 constexpr int US_MINCOLS = 256;
 constexpr int US_VPT = US_MAXCOLS / 4 / US_THREADS;   // 16-byte vectors per lane and row slice (4)
 constexpr int US_WANT_WG = 2048;     // workgroups wanted before slices stop shrinking (256 CUs x 8)
-constexpr int UL_MAXK = 64;
-
-// the reference's integer centring (users.hip, center_rows_kernel): zeros stay zero, float64 -> int truncates
-__device__ static inline int32_t us_centre(int32_t x, double mean) { return x == 0 ? 0 : (int32_t)((double)x - mean); }
 
 // ---- the cell edits ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(US_THREADS) void ratings_set_kernel(int32_t *__restrict__ ratings, int64_t nu, int64_t nq,
@@ -73,7 +69,6 @@ QRLSH_EXPORT int qrlsh_ratings_set(int32_t *ratings, int64_t nu, int64_t nq, con
 // 1024 lanes walk the row twice (sum and count, then the centred squares: the row is in L2 by then) in 16-byte vectors
 // on the row's own alignment, four loads in flight per lane; the scalars before and behind go to lanes 0 .. 2, 64 .. 66
 constexpr int UST_THREADS = 1024;
-typedef int32_t us_i32x4 __attribute__((ext_vector_type(4)));
 
 template <typename F> __device__ static inline void us_walk_row(const int32_t *row, int64_t elem0, int64_t nq, F f) {
   const int t = threadIdx.x;
@@ -174,21 +169,6 @@ static UsSlices us_slices(int64_t nq, int64_t n) {
   s.count = ceil_div64(nq, s.cols);
   if (s.count < 1) s.count = 1;
   return s;
-}
-
-// the columns [0, len) of a row piece that starts at element p of the matrix: lanes below `head` and lanes 64 ..
-// 64 + tail - 1 take the scalars before and behind the aligned middle, lane t its vectors t, t + 256, ...
-struct UsPiece {
-  int head, nvec, tail0, tail;
-};
-__device__ static inline UsPiece us_piece(int64_t elem0, int len) {
-  UsPiece p;
-  const int h = (int)((4 - (elem0 & 3)) & 3);
-  p.head = h < len ? h : len;
-  p.nvec = (len - p.head) >> 2;
-  p.tail0 = p.head + 4 * p.nvec;
-  p.tail = len - p.tail0;
-  return p;
 }
 
 __global__ __launch_bounds__(US_THREADS) void user_pairs_score_kernel(const int32_t *__restrict__ ratings, int64_t nu,
@@ -472,11 +452,6 @@ QRLSH_EXPORT int qrlsh_user_lists_mark(const int32_t *idx, const int32_t *len, i
   idmap_finish(pk, out3, st);
   QR_LAUNCH_CHECK("qrlsh_user_lists_mark");
   return QRLSH_OK;
-}
-
-// list order as one unsigned word: larger = earlier (value descending, then id ascending); 0 = no entry (values are >= 1)
-__device__ static inline uint64_t ul_key(int32_t milli, int64_t id) {
-  return ((uint64_t)(uint32_t)milli << 32) | (uint32_t)(0x7FFFFFFF - (int32_t)id);
 }
 
 // the best 64 of the 64 held and 64 offered words, in order, one per lane (a one-wave workgroup calls it: the barriers

@@ -169,6 +169,10 @@ SIGNATURES = {
                                               _i64, _vp]),
     "qrlsh_ratings_columns_changed": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
     "qrlsh_ratings_columns_move": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "qrlsh_user_rows_nearest_workspace_bytes": (_sz, [_i64, _i64]),
+    "qrlsh_user_rows_nearest": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_ratings_rows_move": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "qrlsh_user_lists_renumber": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "qrlsh_gather_sets_workspace_bytes": (_sz, [_i64]),
     "qrlsh_gather_sets_count": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
     "qrlsh_gather_sets_fill": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -207,6 +207,27 @@ class Recommender:
         sig, norm2, keys = qi.signatures(offsets, rows)
         return qi, sig, norm2, keys
 
+    @staticmethod
+    def _ids_like(cur, ids, pos, what, name):
+        """the labels of new entries of an id array `cur` (queriesIDs, usersIDs), kept in its kind: ids (default: the
+        positions) as strings in a string-labelled set, integers only in an integer one, otherwise what converts to
+        cur's dtype; ValueError for a wrong count or kind"""
+        m = pos.size
+        labels = pos if ids is None else np.asarray(ids)
+        if labels.ndim != 1 or labels.size != m:
+            raise ValueError("ids must hold one label per new %s (%d)" % (what, m))
+        if cur.dtype.kind in "US":
+            labels = labels.astype(str)           # a string-labelled set stays one: default labels are str(position)
+        elif cur.dtype.kind in "iu":
+            if labels.dtype.kind not in "iu":
+                raise ValueError("ids of dtype %s do not fit %s of dtype %s" % (labels.dtype, name, cur.dtype))
+        else:                                     # object, float, ...: labels (the positions by default) in that dtype
+            try:
+                labels = labels.astype(cur.dtype)
+            except (TypeError, ValueError):
+                raise ValueError("ids of dtype %s do not fit %s of dtype %s" % (labels.dtype, name, cur.dtype))
+        return labels
+
     def _user_index_in_step(self, block=None):
         """self.user_index when it holds self.ratings' shape now (it then follows the column operation under way), else
         None: an index that is already out of step is left alone.  A ratings block the index would refuse is refused
@@ -254,20 +275,8 @@ class Recommender:
         if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
             raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
         pos = np.arange(qi.n, qi.n + m, dtype=np.int64)
-        labels = pos if ids is None else np.asarray(ids)
-        if labels.ndim != 1 or labels.size != m:
-            raise ValueError("ids must hold one label per new query (%d)" % m)
         cur = self.queriesIDs
-        if cur.dtype.kind in "US":
-            labels = labels.astype(str)           # a string-labelled set stays one: default labels are str(position)
-        elif cur.dtype.kind in "iu":
-            if labels.dtype.kind not in "iu":
-                raise ValueError("ids of dtype %s do not fit queriesIDs of dtype %s" % (labels.dtype, cur.dtype))
-        else:                                     # object, float, ...: labels (the positions by default) in that dtype
-            try:
-                labels = labels.astype(cur.dtype)
-            except (TypeError, ValueError):
-                raise ValueError("ids of dtype %s do not fit queriesIDs of dtype %s" % (labels.dtype, cur.dtype))
+        labels = self._ids_like(cur, ids, pos, "query", "queriesIDs")
         ui = self._user_index_in_step(None if ratings is None else block)
         first, _ = qi.append(sig, norm2, keys, update_lists=update_lists)
         if ui is not None:
@@ -446,8 +455,8 @@ class Recommender:
     def live_user_similarities(self, labels=None, K=None):
         """Build self.user_index (qrlsh.UserLists) over self.ratings: the all-device user lists (value descending, then
         id ascending; positive values only) at list length K (default round(log_1.5 users)), which rate() then keeps
-        exact without a recompute, and add_queries / remove_queries / replace_queries keep in step with the served
-        queries (UserLists.add_columns / remove_columns / set_columns).  labels: cluster ids per user, held fixed from here on (default:
+        exact without a recompute, add_queries / remove_queries / replace_queries keep in step with the served
+        queries (UserLists.add_columns / remove_columns / set_columns), and add_users / remove_users with the served users.  labels: cluster ids per user, held fixed from here on (default:
         users.cluster_labels, on the device when cluster_on_device).  While the index exists, recommend_users and
         predict_users called without user_sim / ratings serve from it.  -> self.user_index"""
         from qrlsh import users
@@ -456,6 +465,56 @@ class Recommender:
             labels = users.cluster_labels(self.ratings, device=self.device if self.cluster_on_device else None)
         self.user_index = UserLists.build(np.asarray(self.ratings), labels, K=K, device=self.device)
         return self.user_index
+
+    def add_users(self, ratings, ids=None, labels=None):
+        """Take m new users into the served set without a rebuild: ratings = integer [m, queries] block of their
+        ratings; ids: their entries of usersIDs, under the dtype rule add_queries applies to queriesIDs (default: their
+        positions).  self.usersIDs and self.ratings grow by the same m.  A user index in step with self.ratings
+        (live_user_similarities) follows (UserLists.add_users): labels = one cluster label per new user in the label
+        space the index was built with, or None -- each joins the cluster of the existing user it is most similar to,
+        or gets a cluster of its own where no similarity is positive.  Afterwards rate, recommend_users and
+        predict_users serve the new user set from the index.  An index that is out of step is left alone (labels then
+        go unused); the query side is not touched -- its lists do not depend on ratings.  ValueError for a wrong shape,
+        a non-integer block, a value the index refuses or a wrong id count or kind (nothing changed).
+        -> int64 [m], the positions assigned."""
+        block = np.asarray(_as_numpy(ratings))
+        nu, nq = self.ratings.shape
+        if block.ndim != 2 or block.shape[1] != nq or not np.issubdtype(block.dtype, np.integer):
+            raise ValueError("ratings must be an integer [m, queries] = [m, %d] block" % nq)
+        block = block.astype(np.int64)
+        m = block.shape[0]
+        pos = np.arange(nu, nu + m, dtype=np.int64)
+        new_ids = self._ids_like(self.usersIDs, ids, pos, "user", "usersIDs")
+        ui = self._user_index_in_step(block)
+        if ui is not None:
+            ui.add_users(block, labels=labels)
+        self.usersIDs = np.concatenate((self.usersIDs, new_ids))
+        self.ratings = np.vstack((self.ratings, block.astype(self.ratings.dtype)))
+        return pos
+
+    def remove_users(self, positions):
+        """Take users out of the served set without a rebuild, the mirror of add_users: positions (integers, any order,
+        duplicates allowed; ValueError for one outside the set or when nobody would be left, nothing changed) leave
+        self.usersIDs and self.ratings, and the users left are renumbered by rank.  A user index in step with
+        self.ratings follows (UserLists.remove_users: the lists stay exact); one out of step is left alone.
+        -> int64 host array [old count]: the new position of every old one, -1 for a removed one."""
+        pos = np.asarray(_as_numpy(positions)).reshape(-1)
+        if pos.size and not np.issubdtype(pos.dtype, np.integer):
+            raise ValueError("positions must be integers")
+        pos = np.unique(pos.astype(np.int64))
+        nu = self.usersIDs.size
+        if pos.size and (pos[0] < 0 or pos[-1] >= nu):
+            raise ValueError("position outside [0, %d)" % nu)
+        if pos.size >= nu:
+            raise ValueError("no user would be left")
+        ui = self._user_index_in_step()
+        if ui is not None:
+            ui.remove_users(pos)
+        keep = np.ones(nu, dtype=bool)
+        keep[pos] = False
+        self.usersIDs = self.usersIDs[keep]
+        self.ratings = np.ascontiguousarray(self.ratings[keep])
+        return np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
 
     def rate(self, users, queries, values):
         """"user u rated query q": users / queries are 0-based positions, values the new ratings (0 = unrate; repeats
