@@ -888,6 +888,52 @@ int qrlsh_user_lists_renumber(const int32_t *idx, const int32_t *milli, const in
                               const int32_t *src, int64_t nu2, const int32_t *new_pos, int32_t *idx_out,
                               int32_t *milli_out, int32_t *len_out, uint32_t *flag_out, void *stream);
 
+/* ---- dataset rows come and go under a built index (csrc/tablerows.hip) --------------------------------------------------
+ * A dataset row lives in a SLOT: slot s owns row s of the permutation table (perm_t[s][0..P)) and bit s of every value
+ * bitmap.  A table drawn for `capacity` rows has free slots behind the rows in use; an added row takes the lowest slot
+ * never used, a removed row's slot stays dead and is not used again.  After any sequence of row operations signatures,
+ * norms, band keys, index arrays and lists are those of qrlsh_answer_sets_* + qrlsh_minhash + a fresh index / run (at the
+ * held K) over the edited table IN SLOT NUMBERING WITH THE SAME PERMUTATION TABLE.  The rule is this library's: the
+ * reference draws permutation(drows) and never edits the dataset.
+ * qrows int32 [n][nfeat]: the served queries as bitmap rows (value ids), -1 = unconstrained; a value that no table row
+ * holds has a bitmap row of its own.  batch_cells int32 [m][nfeat]: the value id of every cell of the batch's rows;
+ * batch_slots int32 [m]: their slots, distinct, each < the rows of perm_t (the caller's duty: the table is gathered at
+ * them unchecked).  Query q matches batch row j iff for every f qrows[q][f] == -1 || qrows[q][f] == batch_cells[j][f];
+ * no bitmap is read.  perm_t / perm_dtype / P / P_stride as qrlsh_minhash takes them; sig / sig_dtype the index's rows
+ * [n][P] (compact rows need a uint16 table).
+ *   mark: one lane per served query tests the batch in tiles of 64 rows (cells staged in LDS, read wave-uniformly) and
+ *     keeps a 64-bit match mask per tile; the wave then walks its lanes with a non-zero mask, lanes as positions p in
+ *     rounds of 64.  QRLSH_ROWS_ADD: q is changed iff some matched row has perm_t[slot_j][p] < sig[q][p], compared
+ *     UNSIGNED, so the -1 / 0xFFFF of an empty answer set loses to every value.  QRLSH_ROWS_REMOVE (run BEFORE the bits
+ *     are cleared): q is changed iff some matched row has perm_t[slot_j][p] == sig[q][p]: with a table whose columns hold
+ *     distinct values exactly "the minimum was attained there"; with repeated values a query may be marked whose row then
+ *     comes back unchanged, which is harmless.  Changed queries enter changed_map (an id map over the n queries,
+ *     qrlsh_idmap_workspace_bytes(n) bytes, cleared inside the call, ready for qrlsh_idmap_list); a query that matches
+ *     but does not change is not marked.  out2 (device uint64 [2]) = {matched queries, changed queries}.  The table rows
+ *     are read where they are (64 rows are 8 - 64 KiB: L1 / L2).
+ *   fill (ADD only): changed_ids = qrlsh_idmap_list of the mark (ascending), c of them.  One wave per changed query:
+ *     lane j tests batch row j of a tile, the ballot is the mask; sig_out[x][p] = umin(sig[q][p], min over the matched j
+ *     of perm_t[slot_j][p]) in the index's row format, norm2_out[x] the exact int64 squared norm.  Rows are written once,
+ *     out of place; sig is never written (qrlsh_rows_replace does that).  An id >= n writes nothing.
+ *   bitmaps_set_rows: sets (on = 1) or clears (on = 0) bit batch_slots[j] of bitmap rows batch_cells[j][f] and of
+ *     live_row, with vector atomics on the words (bitmaps uint32 [rows][words_per_row]); a slot >= 32 * words_per_row or
+ *     a negative row is skipped, a cell >= the bitmap's rows is the caller's duty.
+ * Limits (QRLSH_EINVAL otherwise): n < 2^32 - 1, 1 <= nfeat <= 63 (the live row is the 64th column an answer-set query
+ * can carry), m <= 65536 per call, any P >= 1.  No allocation, one stream, no scratch; m == 0 gives an empty map. */
+#define QRLSH_ROWS_ADD 0
+#define QRLSH_ROWS_REMOVE 1
+int qrlsh_table_rows_mark(const int32_t *qrows, int64_t n, int32_t nfeat, const int32_t *batch_cells,
+                          const int32_t *batch_slots, int64_t m, const void *perm_t, int32_t perm_dtype, int32_t P,
+                          int32_t P_stride, const void *sig, int32_t sig_dtype, int32_t mode, void *changed_map,
+                          uint64_t *out2, void *stream);
+int qrlsh_table_rows_fill(const int32_t *qrows, int64_t n, int32_t nfeat, const int32_t *batch_cells,
+                          const int32_t *batch_slots, int64_t m, const void *perm_t, int32_t perm_dtype, int32_t P,
+                          int32_t P_stride, const void *sig, int32_t sig_dtype, const uint32_t *changed_ids, int64_t c,
+                          void *sig_out, int64_t *norm2_out, void *stream);
+int qrlsh_bitmaps_set_rows(uint32_t *bitmaps, int64_t words_per_row, const int32_t *batch_cells,
+                           const int32_t *batch_slots, int64_t m, int32_t nfeat, int64_t live_row, int32_t on,
+                           void *stream);
+
 /* ---- multi-GPU, "sets" mode: answer sets of chosen queries out of the replicated per-shard CSR arrays ------------
  * Every rank holds every shard's answer sets as an all-gather delivered them: offs[world][nql + 1] (off_bytes = 4 or 8)
  * and rows[world][max_nnz] (row_bytes = 2: unsigned 16-bit row ids, tables of at most 65536 rows; or 4), shard g =

@@ -40,5 +40,6 @@ from .recommend import top_k, for_users  # noqa: F401
 from .predict import predict_users, user_lists  # noqa: F401
 from .index import QueryIndex  # noqa: F401
 from .userlists import UserLists  # noqa: F401
+from .table import LiveTable, TableDictionary  # noqa: F401
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -29,6 +29,10 @@ SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
 INDEX_MAX_K = 256
 USER_LISTS_MAX_K = 64     # the prediction kernels' ku (csrc/userlists.hip UL_MAXK)
+ROWS_ADD = 0
+ROWS_REMOVE = 1
+TABLE_ROWS_MAX_M = 65536  # batch rows per call of qrlsh_table_rows_* (csrc/tablerows.hip TR_MAXM)
+TABLE_ROWS_MAX_FEAT = 63  # features of a live table: the live row is the 64th column of an answer-set query
 REMOVE_TILE = 2048      # records (list entries) per workgroup of the removal's compactions (csrc/remove.hip RM_TILE)
 
 _vp = ctypes.c_void_p
@@ -173,6 +177,11 @@ SIGNATURES = {
     "qrlsh_user_rows_nearest": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_ratings_rows_move": (ctypes.c_int, [_vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "qrlsh_user_lists_renumber": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "qrlsh_table_rows_mark": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp,
+                                             _vp]),
+    "qrlsh_table_rows_fill": (ctypes.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp,
+                                             _vp, _vp]),
+    "qrlsh_bitmaps_set_rows": (ctypes.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i64, _i32, _vp]),
     "qrlsh_gather_sets_workspace_bytes": (_sz, [_i64]),
     "qrlsh_gather_sets_count": (ctypes.c_int, [_vp, _i64, _vp, _i32, _i64, _i64, _vp, _vp, _sz, _vp]),
     "qrlsh_gather_sets_fill": (ctypes.c_int, [_vp, _i64, _vp, _i32, _vp, _i32, _i64, _i64, _vp, _vp, _vp]),

@@ -1338,3 +1338,84 @@ def predict_columns(ratings, off, idx, milli, query_weight, user_weight, default
     if f & 2:
         raise ValueError("a neighbour index lies outside the %d columns of the ratings" % nq)
     return out
+
+
+# ---------------------------------------------------------------------------
+# dataset rows come and go under a built index (csrc/tablerows.hip)
+# ---------------------------------------------------------------------------
+class RowBatch:
+    """a batch of dataset rows on the device: .cells int32 [m, nfeat] (the value id = bitmap row of every cell), .slots
+    int32 [m] (distinct), with the host's bounds on both -- the kernels gather at them unchecked"""
+
+    def __init__(self, cells, slots, device):
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        slots = np.ascontiguousarray(slots, dtype=np.int32).reshape(-1)
+        if cells.ndim != 2 or cells.shape[0] != slots.size or cells.shape[1] < 1:
+            raise ValueError("cells must be [m, nfeat] with one slot per row")
+        if slots.size and (cells.min() < 0 or slots.min() < 0 or np.unique(slots).size != slots.size):
+            raise ValueError("cells and slots must be non-negative, the slots distinct")
+        self.m, self.nfeat = cells.shape
+        self.cell_hi = int(cells.max()) + 1 if slots.size else 0
+        self.slot_hi = int(slots.max()) + 1 if slots.size else 0
+        self.cells = torch.from_numpy(cells).to(device)
+        self.slots = torch.from_numpy(slots).to(device)
+
+
+def _table_rows_args(qrows, batch, table, sig):
+    _need(qrows, torch.int32, "qrows", 2)
+    n, nfeat = qrows.shape
+    if sig.dtype not in (torch.int32, torch.int16):
+        raise TypeError("sig must be int32 or compact int16 rows")
+    _need(sig, sig.dtype, "sig", 2)
+    if tuple(sig.shape) != (n, table.P) or nfeat != batch.nfeat:
+        raise ValueError("qrows [%d, %d], sig %s and a batch of %d features under a table of %d values do not fit"
+                         % (n, nfeat, tuple(sig.shape), batch.nfeat, table.P))
+    if batch.slot_hi > table.D:
+        raise ValueError("slot %d lies outside the permutation table's %d rows" % (batch.slot_hi - 1, table.D))
+    if batch.m > _lib.TABLE_ROWS_MAX_M:
+        raise ValueError("at most %d rows per call" % _lib.TABLE_ROWS_MAX_M)
+    return n, nfeat, _lib.SIG_U16 if sig.dtype == torch.int16 else _lib.SIG_I32
+
+
+def table_rows_mark(qrows, batch, table, sig, remove=False):
+    """the served queries (qrows int32 [n, nfeat], -1 = unconstrained) that the RowBatch changes under `table`, against
+    the index's rows sig: -> (IdMap of the changed queries, matched queries).  remove=False: the batch is added (a
+    matched row undercuts a value); True: it leaves (a matched row holds a value) -- call before its bits are cleared.
+    One read-back."""
+    lib = _lib.load()
+    n, nfeat, code = _table_rows_args(qrows, batch, table, sig)
+    dev = qrows.device
+    ws = _ws(lib.qrlsh_idmap_workspace_bytes(n), dev)
+    out2 = torch.zeros((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_table_rows_mark(_ptr(qrows), n, nfeat, _ptr(batch.cells), _ptr(batch.slots), batch.m,
+                                         _ptr(table.tab), table.code, table.P, table.P_stride, _ptr(sig), code,
+                                         _lib.ROWS_REMOVE if remove else _lib.ROWS_ADD, _ptr(ws), _ptr(out2), _stream()))
+    matched, changed = out2.tolist()
+    return IdMap(ws, n, changed), matched
+
+
+def table_rows_fill(qrows, batch, table, sig, changed_ids):
+    """the new rows of the changed queries of an added RowBatch (changed_ids: the mark's members, int32 [c] ascending):
+    -> (sig [c, P] in sig's format, norm2 int64 [c]); sig itself is not written"""
+    lib = _lib.load()
+    n, nfeat, code = _table_rows_args(qrows, batch, table, sig)
+    _need(changed_ids, torch.int32, "changed_ids", 1)
+    c = changed_ids.numel()
+    out = torch.empty((c, table.P), dtype=sig.dtype, device=sig.device)
+    norm2 = torch.empty((c,), dtype=torch.int64, device=sig.device)
+    if c:
+        _lib.check(lib.qrlsh_table_rows_fill(_ptr(qrows), n, nfeat, _ptr(batch.cells), _ptr(batch.slots), batch.m,
+                                             _ptr(table.tab), table.code, table.P, table.P_stride, _ptr(sig), code,
+                                             _ptr(changed_ids), c, _ptr(out), _ptr(norm2), _stream()))
+    return out, norm2
+
+
+def bitmaps_set_rows(bitmaps, batch, live_row, on):
+    """set (on=True) or clear the RowBatch's bits in the value rows of bitmaps (int32 [rows, wpr]) and in row live_row"""
+    lib = _lib.load()
+    _need(bitmaps, torch.int32, "bitmaps", 2)
+    rows, wpr = bitmaps.shape
+    if batch.cell_hi > rows or not 0 <= live_row < rows or batch.slot_hi > wpr * 32:
+        raise ValueError("the batch names a bitmap row or a slot outside the %d x %d-bit bitmaps" % (rows, wpr * 32))
+    _lib.check(lib.qrlsh_bitmaps_set_rows(_ptr(bitmaps), wpr, _ptr(batch.cells), _ptr(batch.slots), batch.m, batch.nfeat,
+                                          int(live_row), 1 if on else 0, _stream()))

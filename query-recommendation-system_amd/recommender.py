@@ -59,6 +59,8 @@ class Recommender:
     verbose = True
     bands = None            # override the band rule (BASELINE shapes 128/32, 256/64 need it)
     max_candidates = None   # override K
+    row_capacity = None     # dataset rows the permutation table is drawn for (None: the dataset's own, as the reference);
+                            # a value >= the dataset's rows leaves free slots for add_rows
 
     def _log(self, *a):
         if self.verbose:
@@ -140,7 +142,12 @@ class Recommender:
         drows = self.dataset.shape[0]
         self._log("\nPermutations: {}".format(PERM))
         # PERM consecutive draws from the global legacy RNG, exactly as recommender.py:120
-        perms = ops.legacy_permutations(PERM, drows, rng=np.random)
+        cap = drows
+        if self.row_capacity is not None:
+            cap = int(self.row_capacity)
+            if cap < drows:
+                raise ValueError("row_capacity %d is below the dataset's %d rows" % (cap, drows))
+        perms = ops.legacy_permutations(PERM, cap, rng=np.random)
         table = ops.perm_table(perms, self.device)
         return offsets, rows, table
 
@@ -182,6 +189,7 @@ class Recommender:
         self.last_result = res
         self.last_table = table      # kept for serving new queries (similar_queries & co.)
         self._query_index = None
+        self._live_table, self.row_slots = None, None      # row operations start afresh with the run
         query_sim = pipeline.sims_to_dict(res.src, res.dst, res.val)
         self._log("\n" + str(round(time.time() - queryTime, 3)) + "s for overall queries_similarity scores")
         return query_sim
@@ -201,6 +209,11 @@ class Recommender:
         if getattr(self, "_query_index", None) is None:
             self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
         qi = self._query_index
+        lt = getattr(self, "_live_table", None)
+        if lt is not None:          # rows have come or gone: the table in slot numbering answers
+            offsets, rows = lt.answer_sets(lt.encode(q))
+            sig, norm2, keys = qi.signatures(offsets, rows)
+            return qi, sig, norm2, keys
         if getattr(self, "_answer_index", None) is None or getattr(self, "_answer_index_key", None) != id(self.dataset):
             self.answer_sets_device()  # (re)builds the cached AnswerIndex of this dataset
         offsets, rows = answers.answer_sets(self._answer_index, answers.encode_queries(self._answer_index, q))
@@ -279,6 +292,8 @@ class Recommender:
         labels = self._ids_like(cur, ids, pos, "query", "queriesIDs")
         ui = self._user_index_in_step(None if ratings is None else block)
         first, _ = qi.append(sig, norm2, keys, update_lists=update_lists)
+        if getattr(self, "_live_table", None) is not None:
+            self._live_table.add_queries(self._live_table.encode(q))
         if ui is not None:
             ui.add_columns(m if ratings is None else block)
         self.queries = np.concatenate((np.asarray(self.queries, dtype=object), q), axis=0)
@@ -313,6 +328,8 @@ class Recommender:
             raise ValueError("positions must be integers")
         ui = self._user_index_in_step()
         new_pos = ops.to_host(qi.remove(pos, update_lists=update_lists))
+        if getattr(self, "_live_table", None) is not None:
+            self._live_table.remove_queries(new_pos)
         if ui is not None:
             ui.remove_columns(pos)
         keep = new_pos >= 0
@@ -354,6 +371,8 @@ class Recommender:
                 raise ValueError("ratings must be an integer [users, m] = [%d, %d] block" % (nu, m))
         ui = self._user_index_in_step(block) if block is not None else None
         qi.replace(pos, sig, norm2, keys, update_lists=update_lists)
+        if getattr(self, "_live_table", None) is not None:
+            self._live_table.set_queries(pos, self._live_table.encode(q))
         if ui is not None:
             ui.set_columns(pos, block)
         self.queries = np.array(np.asarray(self.queries, dtype=object), copy=True)
@@ -361,6 +380,85 @@ class Recommender:
         if block is not None:
             self.ratings = np.array(self.ratings, copy=True)
             self.ratings[:, pos] = block.astype(self.ratings.dtype)
+
+    # ---- dataset rows come and go (qrlsh.LiveTable) ------------------------------------------------------------------
+    def _live_rows(self, update_lists):
+        """(LiveTable, QueryIndex) of the last run; the table is built on first use from self.dataset (slot = position),
+        self.queries and the run's permutation table (its rows are the capacity)"""
+        from qrlsh.index import QueryIndex
+        from qrlsh.table import LiveTable
+        res = getattr(self, "last_result", None)
+        if res is None or getattr(self, "last_table", None) is None:
+            raise ValueError("compute_querySimilarities has not run: there is no index for rows to come and go under")
+        if getattr(self, "_query_index", None) is None:
+            self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
+        qi = self._query_index
+        if qi.n != self.queriesIDs.size:
+            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        if update_lists and qi.lists is None:
+            raise ValueError("the live lists were dropped by a call without update_lists=True; "
+                             "compute_querySimilarities starts afresh")
+        if getattr(self, "_live_table", None) is None:
+            if len(self.datasetFeatures) > 63:
+                raise ValueError("rows come and go under at most 63 dataset features, got %d" % len(self.datasetFeatures))
+            cols = [self.dataset[f].to_numpy() for f in self.datasetFeatures]
+            self._live_table = LiveTable.build(cols, self.queries, capacity=self.last_table.D, device=self.device)
+            self.row_slots = np.arange(self.dataset.shape[0], dtype=np.int64)
+        return self._live_table, qi
+
+    def add_rows(self, rows, update_lists=False):
+        """Take m new tuples into the dataset without a new run: rows = a frame or array with one column per entry of
+        datasetFeatures (a frame that names all of self.dataset's columns is appended whole; otherwise the other columns
+        get "").  Each row takes a free slot of the run's permutation table (row_capacity), the served queries whose
+        signature it lowers get their new rows through qrlsh.LiveTable.add_rows / QueryIndex.replace, and self.dataset
+        grows by the m rows (index reset); self.row_slots holds the slot of every dataset position.  update_lists as
+        replace_queries treats it -- except that a batch that changes no query leaves the index and its lists alone.
+        ValueError, nothing changed: no finished run, a wrong column count, or fewer than m free slots (raise
+        row_capacity before the run).  -> int64 [m], the positions assigned in self.dataset."""
+        feats = list(self.datasetFeatures)
+        if isinstance(rows, pd.DataFrame) or hasattr(rows, "to_pandas"):
+            frame = _as_pandas(rows).astype(str)
+            if not all(f in frame.columns for f in feats):
+                if frame.shape[1] != len(feats):
+                    raise ValueError("rows must have one column per dataset feature (%d)" % len(feats))
+                frame.columns = feats
+        else:
+            a = np.asarray(rows, dtype=object)
+            if a.ndim != 2 or a.shape[1] != len(feats):
+                raise ValueError("rows must have one column per dataset feature (%d)" % len(feats))
+            frame = pd.DataFrame(a, columns=feats).astype(str)
+        lt, qi = self._live_rows(update_lists)
+        m = frame.shape[0]
+        if lt.D + m > lt.capacity:
+            raise ValueError("%d rows for %d free slots: row_capacity (%d) must be raised before the run"
+                             % (m, lt.capacity - lt.D, lt.capacity))
+        slots = lt.add_rows(frame[feats].to_numpy(), qi, update_lists=update_lists)
+        first = self.dataset.shape[0]
+        self.dataset = pd.concat((self.dataset, frame.reindex(columns=self.dataset.columns, fill_value="")),
+                                 ignore_index=True)
+        self.row_slots = np.concatenate((self.row_slots, slots))
+        return np.arange(first, first + m, dtype=np.int64)
+
+    def remove_rows(self, positions, update_lists=False):
+        """Take tuples out of the dataset without a new run, under remove_queries' contract: positions in the current
+        self.dataset (integers, any order, duplicates allowed; ValueError for one outside, nothing changed).  Their slots
+        die, the served queries whose minimum sat on one of them get their answer sets taken again
+        (qrlsh.LiveTable.remove_rows / QueryIndex.set), and self.dataset keeps the live rows only (index reset).
+        -> int64 host array [old rows]: the new position of every old one, -1 for a removed one."""
+        pos = np.asarray(_as_numpy(positions)).reshape(-1)
+        if pos.size and not np.issubdtype(pos.dtype, np.integer):
+            raise ValueError("positions must be integers")
+        lt, qi = self._live_rows(update_lists)
+        drows = self.dataset.shape[0]
+        pos = np.unique(pos.astype(np.int64))
+        if pos.size and (pos[0] < 0 or pos[-1] >= drows):
+            raise ValueError("position outside [0, %d)" % drows)
+        lt.remove_rows(self.row_slots[pos], qi, update_lists=update_lists)
+        keep = np.ones(drows, dtype=bool)
+        keep[pos] = False
+        self.dataset = self.dataset[keep].reset_index(drop=True)
+        self.row_slots = self.row_slots[keep]
+        return np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
 
     def _live_lists(self):
         """(src, dst, val) that know every added query, or None: the run's own lists before any append, the index's
