@@ -744,6 +744,52 @@ int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64_t nq, const 
                           int32_t *val_out, int32_t *avail_out, uint32_t *flags_out, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ---- evaluation: the prediction error on rated cells, hold-out and leave-one-out -----------------------------------
+ * The blend of cell (i, j) never reads ratings[i][j]: a rated cell can be predicted as if it were unrated and compared
+ * with its rating.  Predictions and ratings are integers, so every statistic is an exact integer sum, independent of the
+ * launch order.  Arguments as qrlsh_predict_users takes them (lists in CSR with milli values, similarity = milli /
+ * 1000.0; user lists u_idx / u_val [nu][ku]); same arithmetic cell for cell, both sum orders.
+ * Sample rule: `keep` is a 64-bit word in [0, 2^32]; cell (i, j) is KEPT iff
+ *     qr_mix64(seed ^ ((uint64)i << 32 | (uint32)j)) >> 32 < keep        (qrlsh_mix64_host is the host twin)
+ * keep = 2^32 keeps every cell, 0 none; membership does not depend on nq (it survives column appends).
+ * qrlsh_ratings_holdout: out int32 [nu][nq] = in with the kept non-zero cells set to 0 (out of place: in != out, `in` is
+ *   not written); *count_out (device int64) = the cells zeroed.  A streaming kernel, 16-byte accesses where both
+ *   pointers are 16-byte aligned.
+ * qrlsh_evaluate: a cell is EVALUATED iff truth[i][j] != 0 and it is kept; its prediction is the blend computed from
+ *   `ratings` exactly as if ratings[i][j] were 0 (the kernel does not read it: a list entry that names the cell's own
+ *   column or row reads as 0); err = prediction - truth.  truth == ratings: leave-one-out with the lists held fixed;
+ *   ratings = holdout(truth) under the same seed and keep: a hold-out.
+ *   per_user_out int64 [nu][16], one 128-byte line per user: words 0-3, 4-7, 8-11 = n, sum err, sum |err|, sum err^2 of
+ *   the cells predicted from the query side only, the user side only and both (the three non-zero branches of the
+ *   blend); word 12 = evaluated cells whose prediction is 0 (missed: in none of the sums); word 13 = evaluated cells;
+ *   words 14-15 = 0.  totals_out int64 [16] = its column sums.  pred_out: NULL, or int32 [nu][nq] = the prediction at
+ *   evaluated cells (0 = missed), -1 elsewhere.
+ *   One workgroup per (column slice, user): the user's row of `ratings` staged in LDS as bytes (nq <= 131072 and every
+ *   value of the row in 0 .. 255) or read from memory; `truth` read coalesced; the evaluated cells of a slice are queued
+ *   in LDS and predicted 1024 at a time, so a thin sample costs what its cells cost.  Per-slice sums go to the workspace
+ *   (qrlsh_evaluate_workspace_bytes(nu, nq), 8-byte aligned) and two small kernels add them: no atomics.
+ * qrlsh_evaluate_cells: an explicit test set of m triplets (cell_user, cell_query, cell_truth int32 [m]); every triplet
+ *   is evaluated, repeats once each, whatever `ratings` holds there.  pred_out: NULL or int32 [m] (-1 for a triplet
+ *   outside the matrix); totals_out int64 [16] as above (64-bit integer atomics).
+ * *flags_out (device uint32, required) = 0, or bit 0: a query list longer than 64, bit 1: a list index outside [0, nq),
+ *   bit 2 (cells form): a user or query id outside range.  Such lists are never walked or gathered and such cells never
+ *   read; the result is not to be used.  A user-list entry >= nu is not gathered (its rating reads as 0).
+ * Limits (QRLSH_EINVAL otherwise): ku <= 64, nq < 2^31, nu < 2^31, keep <= 2^32.  The sums are exact while |err| < 2^31
+ * and they fit int64.  nu = 0 or nq = 0: all outputs 0.  No allocation, one stream, no read-back. */
+int qrlsh_ratings_holdout(const int32_t *in, int64_t nu, int64_t nq, uint64_t seed, uint64_t keep, int32_t *out,
+                          int64_t *count_out, void *stream);
+size_t qrlsh_evaluate_workspace_bytes(int64_t nu, int64_t nq);
+int qrlsh_evaluate(const int32_t *ratings, const int32_t *truth, int64_t nu, int64_t nq, const int64_t *q_off,
+                   const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                   double query_weight, double user_weight, double default_mean, int32_t sum_order, uint64_t seed,
+                   uint64_t keep, int64_t *per_user_out, int64_t *totals_out, int32_t *pred_out, uint32_t *flags_out,
+                   void *workspace, size_t workspace_bytes, void *stream);
+int qrlsh_evaluate_cells(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off, const int32_t *q_idx,
+                         const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                         double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                         const int32_t *cell_user, const int32_t *cell_query, const int32_t *cell_truth, int64_t m,
+                         int32_t *pred_out, int64_t *totals_out, uint32_t *flags_out, void *stream);
+
 /* ---- N4: user similarity, the part after the clustering ----------------------------------------
  * Recommender.compute_userSimilarities, recommender.py:263-288: inside a cluster every user's row is centred on
  * the mean of its non-zero ratings IN AN INTEGER ARRAY (the centred values are truncated toward zero), then

@@ -737,3 +737,455 @@ QRLSH_EXPORT int qrlsh_predict_users(const int32_t *ratings, int64_t nu, int64_t
                           user_weight, default_mean, sum_order, users, m, false, out, nq, flags_out,
                           static_cast<hipStream_t>(stream));
 }
+
+// ---- evaluation: the prediction error on rated cells (qrlsh_ratings_holdout, qrlsh_evaluate, qrlsh_evaluate_cells) ----
+// The blend of cell (i, j) reads the user's ratings of j's neighbour queries and the neighbour users' ratings of j, never
+// ratings[i][j] itself.  So a RATED cell can be predicted as if it were unrated -- predict_users_kernel's computation over
+// the complement of the cells it fills -- and compared with its rating.  Predictions and ratings are integers: every
+// statistic is an exact integer sum and the result cannot depend on the launch order.
+// Sample rule (one rule, everywhere): cell (i, j) is KEPT iff the top 32 bits of mix64(seed ^ (i << 32 | j)) lie below
+// `keep` (a 64-bit word in [0, 2^32]: 2^32 keeps every cell, 0 none).  It does not depend on nq.
+__device__ static inline bool ev_kept(uint64_t seed, uint64_t keep, int64_t i, int64_t j) {
+  return (qr_mix64(seed ^ ((uint64_t)i << 32 | (uint64_t)(uint32_t)j)) >> 32) < keep;
+}
+
+// The 14 integers of one line of per_user_out, in registers (no indexed array: selects).  Words 0-3, 4-7, 8-11 = n,
+// sum err, sum |err|, sum err^2 of the cells predicted from the query side only, the user side only and both; word 12 =
+// cells whose prediction is 0 (missed: in no sum); word 13 = cells.
+constexpr int EV_WORDS = 14;
+struct EvalStats {
+  long long qn, qe, qa, qs, un, ue, ua, us, bn, be, ba, bs, missed, cells;
+  __device__ void clear() { qn = qe = qa = qs = un = ue = ua = us = bn = be = ba = bs = missed = cells = 0; }
+  // branch: 0 query side only, 1 user side only, 2 both (of a non-zero prediction)
+  __device__ void add(int32_t pred, int branch, int32_t truth) {
+    const long long e = (long long)pred - (long long)truth, a = e < 0 ? -e : e, s = e * e;
+    const bool hit = pred != 0, q = hit && branch == 0, u = hit && branch == 1, b = hit && branch == 2;
+    qn += q ? 1 : 0; qe += q ? e : 0; qa += q ? a : 0; qs += q ? s : 0;
+    un += u ? 1 : 0; ue += u ? e : 0; ua += u ? a : 0; us += u ? s : 0;
+    bn += b ? 1 : 0; be += b ? e : 0; ba += b ? a : 0; bs += b ? s : 0;
+    missed += hit ? 0 : 1;
+    cells += 1;
+  }
+  template <typename F> __device__ void each(F f) {
+    f(qn, 0); f(qe, 1); f(qa, 2); f(qs, 3); f(un, 4); f(ue, 5); f(ua, 6); f(us, 7);
+    f(bn, 8); f(be, 9); f(ba, 10); f(bs, 11); f(missed, 12); f(cells, 13);
+  }
+};
+
+// sum over the workgroup (THREADS threads, all of them call it); red: LDS [THREADS / WAVE][EV_WORDS].  Afterwards thread
+// w < EV_WORDS returns word w of the workgroup's sum (other threads: 0).
+template <int THREADS> __device__ static inline long long ev_block_sum(EvalStats &s, long long (*red)[EV_WORDS]) {
+  s.each([](long long &v, int) {
+#pragma unroll
+    for (int d = WAVE / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, WAVE);
+  });
+  const int t = threadIdx.x, w = t >> 6;
+  if ((t & (WAVE - 1)) == 0) s.each([&](long long &v, int word) { red[w][word] = v; });
+  __syncthreads();
+  long long sum = 0;
+  if (t < EV_WORDS) {
+#pragma unroll
+    for (int k = 0; k < THREADS / WAVE; ++k) sum += red[k][t];
+  }
+  return sum;
+}
+
+// The prediction of cell (i, j) as if ratings[i][j] were 0: predict_users_kernel's two weighted averages and blend.  The
+// cell's own rating is never part of either side (a list entry naming j itself, or a user list naming i, reads as 0 --
+// decided by the index, not by the rating).  rating_at(q) = ratings[i][q] (LDS bytes or the row in memory).  A list
+// longer than PRED_MAXK is not walked and an index outside the matrix is not gathered: the prediction is 0 (flagged by
+// predict_users_check_kernel).  -> the prediction; branch as EvalStats::add takes it.
+template <typename RatingAt>
+__device__ static inline int32_t ev_predict(const int32_t *__restrict__ ratings, int64_t nu, int64_t nq, int64_t i, int64_t j,
+                                            const int64_t *__restrict__ q_off, const int32_t *__restrict__ q_idx,
+                                            const int32_t *__restrict__ q_milli, const int32_t *__restrict__ ui,
+                                            const double *__restrict__ uv, int mu, double qw, double uw, double dmean,
+                                            bool sequential, RatingAt rating_at, int &branch) {
+  branch = 0;
+  const int64_t lo = q_off[j], n64 = q_off[j + 1] - lo;
+  if (n64 < 0 || n64 > PRED_MAXK) return 0;  // flagged (bit 0); never walked
+  bool outside = false;
+  const double qp = weighted_average(
+      (int)n64, sequential,
+      [&](int k) {
+        const int32_t q = q_idx[lo + k];
+        if ((uint32_t)q >= (uint32_t)nq) {  // flagged (bit 1); never gathered
+          outside = true;
+          return (int32_t)0;
+        }
+        return q == j ? (int32_t)0 : rating_at(q);
+      },
+      [&](int k) { return (double)q_milli[lo + k] / 1000.0; });
+  const double up = weighted_average(
+      mu, sequential,
+      [&](int k) {
+        const int64_t u = ui[k];
+        return (u >= nu || u == i) ? (int32_t)0 : ratings[u * nq + j];   // u >= 0 for k < mu
+      },
+      [&](int k) { return uv[k]; });
+  double r;
+  if (up == 0.0 && qp == 0.0) r = 0.0;
+  else if (up == 0.0) r = qp * (qw + (uw * 0.5)) + dmean * (uw * 0.5);
+  else if (qp == 0.0) r = up * (uw + (qw * 0.5)) + dmean * (qw * 0.5);
+  else r = qp * qw + up * uw;
+  branch = up == 0.0 ? 0 : (qp == 0.0 ? 1 : 2);
+  return outside ? 0 : (int32_t)rint(r);
+}
+
+// The sweep: one workgroup per (column slice, user), the users of a slice together, the user's row of `ratings` staged in
+// LDS as bytes where it fits (predict_users_kernel's two forms).  The workgroup reads its slice of `truth` coalesced,
+// 1024 columns at a time, and queues the evaluated cells (truth != 0 and kept) in LDS; whenever 1024 are queued every
+// thread predicts one, so the lanes stay full however thin the sample is.  Each thread keeps its 14 sums in registers;
+// the workgroup's sums go to part[user][slice][16] (summed by evaluate_finish_kernel: no atomics, no order).
+constexpr int EV_THREADS = 1024;
+constexpr int EV_QUEUE = 2 * EV_THREADS;   // fewer than EV_THREADS cells wait when up to EV_THREADS more arrive
+constexpr int EV_AUTO_GROUPS = 4096;
+
+static int64_t ev_slices(int64_t nu, int64_t nq) {
+  int64_t slices = ceil_div64(EV_AUTO_GROUPS, nu > 0 ? nu : 1);
+  const int64_t most = ceil_div64(nq, EV_THREADS);
+  if (slices > most) slices = most;
+  return slices < 1 ? 1 : slices;
+}
+
+__global__ __launch_bounds__(EV_THREADS) void evaluate_kernel(
+    const int32_t *__restrict__ ratings, const int32_t *__restrict__ truth, int64_t nu, int64_t nq,
+    const int64_t *__restrict__ q_off, const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli,
+    const int32_t *__restrict__ u_idx, const double *__restrict__ u_val, int ku, double qw, double uw, double dmean,
+    int sequential, uint64_t seed, uint64_t keep, int64_t slices, long long *__restrict__ part,
+    int32_t *__restrict__ pred_out) {
+  __shared__ uint8_t lrow[PR_MAXQ];
+  __shared__ int32_t queue_j[EV_QUEUE];
+  __shared__ int32_t queue_v[EV_QUEUE];
+  __shared__ long long red[EV_THREADS / WAVE][EV_WORDS];
+  __shared__ uint32_t wsum[EV_THREADS / WAVE];
+  __shared__ int wide;
+  const int64_t s = blockIdx.x / nu, i = blockIdx.x - s * nu;
+  const int t = threadIdx.x;
+  const int64_t per = (nq + slices - 1) / slices;
+  const int64_t j0 = s * per, j1 = min(nq, j0 + per);
+  const int32_t *row = ratings + i * nq;
+  const int32_t *trow = truth + i * nq;
+  bool in_lds = false;
+  if (nq <= PR_MAXQ) {  // uniform
+    if (t == 0) wide = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int64_t j = t; j < nq; j += EV_THREADS) {
+      const int32_t v = row[j];
+      bad |= (v < 0) | (v > 255);
+      lrow[j] = (uint8_t)v;
+    }
+    if (bad) wide = 1;
+    __syncthreads();
+    in_lds = wide == 0;
+  }
+  const int32_t *ui = u_idx + i * ku;
+  const double *uv = u_val + i * ku;
+  int mu = 0;
+  while (mu < ku && ui[mu] >= 0) ++mu;  // uniform: the user's own neighbour list
+  EvalStats st;
+  st.clear();
+  auto one = [&](uint32_t slot) {
+    const int64_t j = queue_j[slot & (EV_QUEUE - 1)];
+    const int32_t tv = queue_v[slot & (EV_QUEUE - 1)];
+    int branch;
+    const int32_t pred = ev_predict(
+        ratings, nu, nq, i, j, q_off, q_idx, q_milli, ui, uv, mu, qw, uw, dmean, sequential != 0,
+        [&](int32_t q) { return in_lds ? (int32_t)lrow[q] : row[q]; }, branch);
+    st.add(pred, branch, tv);
+    if (pred_out) pred_out[i * nq + j] = pred;
+  };
+  uint32_t head = 0, tail = 0;  // uniform
+  for (int64_t base = j0; base < j1; base += EV_THREADS) {
+    const int64_t j = base + t;
+    int32_t tv = 0;
+    if (j < j1) tv = trow[j];
+    const bool take = tv != 0 && ev_kept(seed, keep, i, j);
+    if (pred_out && j < j1 && !take) pred_out[i * nq + j] = -1;
+    uint32_t total;
+    const uint32_t pos = block_excl_scan<EV_THREADS>(take ? 1u : 0u, wsum, total);
+    if (take) {
+      queue_j[(tail + pos) & (EV_QUEUE - 1)] = (int32_t)j;
+      queue_v[(tail + pos) & (EV_QUEUE - 1)] = tv;
+    }
+    tail += total;
+    if (tail - head >= (uint32_t)EV_THREADS) {  // uniform
+      __syncthreads();
+      one(head + t);
+      head += EV_THREADS;
+    }
+    // the next scan's first barrier stands between these reads of the queue and the writes that follow it
+  }
+  __syncthreads();
+  if ((uint32_t)t < tail - head) one(head + t);
+  const long long sum = ev_block_sum<EV_THREADS>(st, red);
+  if (t < 16) part[(i * slices + s) * 16 + t] = t < EV_WORDS ? sum : 0;
+}
+
+// per_user_out[u][w] = the sum over the slices of part[u][.][w]; one workgroup per 64 users (thread = (user, word)), whose
+// column sums go to gpart[workgroup][16]
+constexpr int EVF_USERS = 64;
+__global__ __launch_bounds__(EVF_USERS * 16) void evaluate_finish_kernel(const long long *__restrict__ part, int64_t nu,
+                                                                         int64_t slices,
+                                                                         long long *__restrict__ per_user_out,
+                                                                         long long *__restrict__ gpart) {
+  __shared__ long long tile[EVF_USERS][16];
+  const int t = threadIdx.x, ul = t >> 4, w = t & 15;
+  const int64_t u = (int64_t)blockIdx.x * EVF_USERS + ul;
+  long long sum = 0;
+  if (u < nu) {
+    for (int64_t s = 0; s < slices; ++s) sum += part[(u * slices + s) * 16 + w];
+    per_user_out[u * 16 + w] = sum;
+  }
+  tile[ul][w] = sum;
+  __syncthreads();
+  if (t < 16) {
+    long long col = 0;
+#pragma unroll 8
+    for (int k = 0; k < EVF_USERS; ++k) col += tile[k][t];
+    gpart[(int64_t)blockIdx.x * 16 + t] = col;
+  }
+}
+
+// totals_out[w] = the sum of gpart[.][w] (one workgroup)
+__global__ __launch_bounds__(1024) void evaluate_totals_kernel(const long long *__restrict__ gpart, int64_t groups,
+                                                               long long *__restrict__ totals_out) {
+  __shared__ long long tile[64][16];
+  const int t = threadIdx.x, r = t >> 4, w = t & 15;
+  long long sum = 0;
+  for (int64_t g = r; g < groups; g += 64) sum += gpart[g * 16 + w];
+  tile[r][w] = sum;
+  __syncthreads();
+  if (t < 16) {
+    long long col = 0;
+#pragma unroll 8
+    for (int k = 0; k < 64; ++k) col += tile[k][t];
+    totals_out[t] = col;
+  }
+}
+
+// workspace: [part: nu x slices x 16 int64][gpart: ceil(nu / 64) x 16 int64]
+QRLSH_EXPORT size_t qrlsh_evaluate_workspace_bytes(int64_t nu, int64_t nq) {
+  if (nu <= 0 || nq <= 0) return 0;
+  return ((size_t)nu * (size_t)ev_slices(nu, nq) + (size_t)ceil_div64(nu, EVF_USERS)) * 16 * sizeof(long long);
+}
+
+static int ev_check_lists(const char *who, int64_t nu, int64_t nq, int32_t ku, int32_t sum_order, uint64_t keep) {
+  QR_CHECK_ARG(nu >= 0 && nq >= 0 && nu <= 2147483647ll && nq <= 2147483647ll && ku >= 0 && ku <= PRED_MAXK,
+               "%s: bad sizes nu=%lld nq=%lld ku=%d (<= %d)", who, (long long)nu, (long long)nq, ku, PRED_MAXK);
+  QR_CHECK_ARG(sum_order == QRLSH_SUM_PAIRWISE || sum_order == QRLSH_SUM_SEQUENTIAL, "%s: bad sum_order %d", who,
+               sum_order);
+  QR_CHECK_ARG(keep <= (1ull << 32), "%s: keep=%llu above 2^32", who, (unsigned long long)keep);
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_evaluate(const int32_t *ratings, const int32_t *truth, int64_t nu, int64_t nq, const int64_t *q_off,
+                                const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val,
+                                int32_t ku, double query_weight, double user_weight, double default_mean,
+                                int32_t sum_order, uint64_t seed, uint64_t keep, int64_t *per_user_out, int64_t *totals_out,
+                                int32_t *pred_out, uint32_t *flags_out, void *workspace, size_t workspace_bytes,
+                                void *stream) {
+  const int rc = ev_check_lists("qrlsh_evaluate", nu, nq, ku, sum_order, keep);
+  if (rc != QRLSH_OK) return rc;
+  QR_CHECK_ARG(flags_out && totals_out, "qrlsh_evaluate: flags_out and totals_out are required");
+  const bool empty = nu == 0 || nq == 0;
+  QR_CHECK_ARG(empty || (ratings && truth && q_off && per_user_out && (ku == 0 || (u_idx && u_val))),
+               "qrlsh_evaluate: null pointer");
+  const size_t need = qrlsh_evaluate_workspace_bytes(nu, nq);
+  QR_CHECK_ARG(empty || (workspace && workspace_bytes >= need && (uintptr_t)workspace % 8 == 0),
+               "qrlsh_evaluate: needs %zu workspace bytes (8-byte aligned), got %zu", need, workspace_bytes);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
+      (empty && hipMemsetAsync(totals_out, 0, 16 * sizeof(int64_t), st) != hipSuccess) ||
+      (empty && nu > 0 && hipMemsetAsync(per_user_out, 0, (size_t)nu * 16 * sizeof(int64_t), st) != hipSuccess)) {
+    qrlsh_set_error("qrlsh_evaluate: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  if (empty) return QRLSH_OK;
+  const int64_t slices = ev_slices(nu, nq), groups = ceil_div64(nu, EVF_USERS);
+  if (nu * slices > 2147483647ll) {
+    qrlsh_set_error("qrlsh_evaluate: nu=%lld x %lld slices above 2^31 - 1 workgroups", (long long)nu, (long long)slices);
+    return QRLSH_EUNSUPPORTED;
+  }
+  long long *part = static_cast<long long *>(workspace);
+  long long *gpart = part + (size_t)nu * slices * 16;
+  QR_LAUNCH("evaluate_check", predict_users_check_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, q_off,
+            q_idx, nq, (const int32_t *)nullptr, (int64_t)0, nu, flags_out);   // the lists' two flags
+  QR_LAUNCH("evaluate", evaluate_kernel, dim3((unsigned)(nu * slices)), dim3(EV_THREADS), 0, st, ratings, truth, nu, nq,
+            q_off, q_idx, q_milli, u_idx, u_val, (int)ku, query_weight, user_weight, default_mean,
+            (int)(sum_order == QRLSH_SUM_SEQUENTIAL), seed, keep, slices, part, pred_out);
+  QR_LAUNCH("evaluate_finish", evaluate_finish_kernel, dim3((unsigned)groups), dim3(EVF_USERS * 16), 0, st,
+            (const long long *)part, nu, slices, reinterpret_cast<long long *>(per_user_out), gpart);
+  QR_LAUNCH("evaluate_totals", evaluate_totals_kernel, dim3(1), dim3(1024), 0, st, (const long long *)gpart, groups,
+            reinterpret_cast<long long *>(totals_out));
+  QR_LAUNCH_CHECK("qrlsh_evaluate");
+  return QRLSH_OK;
+}
+
+// An explicit test set: one thread per triplet (user, query, truth), the row read from memory; every triplet counts
+// (repeats once each).  The workgroup's sums reach totals_out by 64-bit integer atomics: exact in any order.
+constexpr int EVC_THREADS = 256;
+__global__ __launch_bounds__(EVC_THREADS) void evaluate_cells_kernel(
+    const int32_t *__restrict__ ratings, int64_t nu, int64_t nq, const int64_t *__restrict__ q_off,
+    const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli, const int32_t *__restrict__ u_idx,
+    const double *__restrict__ u_val, int ku, double qw, double uw, double dmean, int sequential,
+    const int32_t *__restrict__ cell_user, const int32_t *__restrict__ cell_query, const int32_t *__restrict__ cell_truth,
+    int64_t m, int32_t *__restrict__ pred_out, unsigned long long *__restrict__ totals, uint32_t *__restrict__ flags) {
+  __shared__ long long red[EVC_THREADS / WAVE][EV_WORDS];
+  const int64_t c = (int64_t)blockIdx.x * EVC_THREADS + threadIdx.x;
+  EvalStats st;
+  st.clear();
+  if (c < m) {
+    const int64_t i = cell_user[c], j = cell_query[c];
+    if (i < 0 || i >= nu || j < 0 || j >= nq) {  // flagged (bit 2); nothing of the cell is read
+      atomicOr(flags, 4u);
+      if (pred_out) pred_out[c] = -1;
+    } else {
+      const int32_t *row = ratings + i * nq;
+      const int32_t *ui = u_idx + i * ku;
+      int mu = 0;
+      while (mu < ku && ui[mu] >= 0) ++mu;
+      int branch;
+      const int32_t pred = ev_predict(
+          ratings, nu, nq, i, j, q_off, q_idx, q_milli, ui, u_val + i * ku, mu, qw, uw, dmean, sequential != 0,
+          [&](int32_t q) { return row[q]; }, branch);
+      st.add(pred, branch, cell_truth[c]);
+      if (pred_out) pred_out[c] = pred;
+    }
+  }
+  const long long sum = ev_block_sum<EVC_THREADS>(st, red);
+  if (threadIdx.x < EV_WORDS && sum != 0) atomicAdd(totals + threadIdx.x, (unsigned long long)sum);
+}
+
+QRLSH_EXPORT int qrlsh_evaluate_cells(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
+                                      const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx,
+                                      const double *u_val, int32_t ku, double query_weight, double user_weight,
+                                      double default_mean, int32_t sum_order, const int32_t *cell_user,
+                                      const int32_t *cell_query, const int32_t *cell_truth, int64_t m, int32_t *pred_out,
+                                      int64_t *totals_out, uint32_t *flags_out, void *stream) {
+  const int rc = ev_check_lists("qrlsh_evaluate_cells", nu, nq, ku, sum_order, 0);
+  if (rc != QRLSH_OK) return rc;
+  QR_CHECK_ARG(m >= 0 && ceil_div64(m, EVC_THREADS) <= 2147483647ll, "qrlsh_evaluate_cells: bad m=%lld", (long long)m);
+  QR_CHECK_ARG(flags_out && totals_out, "qrlsh_evaluate_cells: flags_out and totals_out are required");
+  QR_CHECK_ARG(m == 0 || (cell_user && cell_query && cell_truth), "qrlsh_evaluate_cells: null pointer");
+  QR_CHECK_ARG(m == 0 || nu == 0 || nq == 0 || (ratings && q_off && (ku == 0 || (u_idx && u_val))),
+               "qrlsh_evaluate_cells: null pointer");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
+      hipMemsetAsync(totals_out, 0, 16 * sizeof(int64_t), st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_evaluate_cells: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  if (m == 0) return QRLSH_OK;
+  if (nq > 0)
+    QR_LAUNCH("evaluate_check", predict_users_check_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, q_off,
+              q_idx, nq, (const int32_t *)nullptr, (int64_t)0, nu, flags_out);   // the lists' two flags; ids: below
+  QR_LAUNCH("evaluate_cells", evaluate_cells_kernel, dim3((unsigned)ceil_div64(m, EVC_THREADS)), dim3(EVC_THREADS), 0, st,
+            ratings, nu, nq, q_off, q_idx, q_milli, u_idx, u_val, (int)ku, query_weight, user_weight, default_mean,
+            (int)(sum_order == QRLSH_SUM_SEQUENTIAL), cell_user, cell_query, cell_truth, m, pred_out,
+            reinterpret_cast<unsigned long long *>(totals_out), flags_out);
+  QR_LAUNCH_CHECK("qrlsh_evaluate_cells");
+  return QRLSH_OK;
+}
+
+// The hold-out copy: out = in with the kept non-zero cells set to 0, *count_out = how many.  A streaming kernel: 16-byte
+// loads and stores over the flat matrix where both pointers are 16-byte aligned (a thread finds its first row by one
+// division and steps from there), single words otherwise and for the last nu x nq % 4 cells.
+constexpr int HO_THREADS = 256;
+constexpr int HO_MAX_GROUPS = 4096;   // 16 workgroups per CU; a thread strides over the rest
+__global__ __launch_bounds__(HO_THREADS) void ratings_holdout_kernel(const int32_t *__restrict__ in, int64_t nq,
+                                                                     int64_t total, int64_t n4, int64_t step_i,
+                                                                     int64_t step_j, uint64_t seed, uint64_t keep,
+                                                                     int32_t *__restrict__ out,
+                                                                     unsigned long long *__restrict__ count) {
+  const int64_t stride = (int64_t)gridDim.x * HO_THREADS;
+  const int64_t g = (int64_t)blockIdx.x * HO_THREADS + threadIdx.x;
+  uint32_t zeroed = 0;
+  const int4 *in4 = reinterpret_cast<const int4 *>(in);
+  int4 *out4 = reinterpret_cast<int4 *>(out);
+  // (i, j) of the thread's next vector: one division at the start, then steps of one stride = step_i rows + step_j
+  // columns (the host's division)
+  int64_t ci = 0, cj = 0;
+  if (g < n4) {
+    ci = (g * 4) / nq;
+    cj = g * 4 - ci * nq;
+  }
+  auto four = [&](int4 v) {
+    int64_t i = ci, j = cj;
+    ci += step_i;
+    cj += step_j;
+    if (cj >= nq) {
+      cj -= nq;
+      ++ci;
+    }
+    int32_t e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      if (e[k] != 0 && ev_kept(seed, keep, i, j)) {
+        e[k] = 0;
+        ++zeroed;
+      }
+      if (++j == nq) {
+        j = 0;
+        ++i;
+      }
+    }
+    return make_int4(e[0], e[1], e[2], e[3]);
+  };
+  // two vectors per trip, both loads issued before either is used
+  for (int64_t c4 = g; c4 < n4; c4 += 2 * stride) {
+    const int64_t d4 = c4 + stride;
+    const bool two = d4 < n4;
+    const int4 v0 = in4[c4];
+    const int4 v1 = two ? in4[d4] : make_int4(0, 0, 0, 0);
+    out4[c4] = four(v0);
+    if (two) out4[d4] = four(v1);
+  }
+  for (int64_t c = n4 * 4 + g; c < total; c += stride) {
+    const int64_t i = c / nq, j = c - i * nq;
+    int32_t v = in[c];
+    if (v != 0 && ev_kept(seed, keep, i, j)) {
+      v = 0;
+      ++zeroed;
+    }
+    out[c] = v;
+  }
+  // one atomic per workgroup: thousands of adds to one word cost more than the copy
+  __shared__ uint32_t wz[HO_THREADS / WAVE];
+#pragma unroll
+  for (int d = WAVE / 2; d >= 1; d >>= 1) zeroed += __shfl_xor(zeroed, d, WAVE);
+  if ((threadIdx.x & (WAVE - 1)) == 0) wz[threadIdx.x >> 6] = zeroed;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long sum = 0;
+#pragma unroll
+    for (int k = 0; k < HO_THREADS / WAVE; ++k) sum += wz[k];
+    if (sum) atomicAdd(count, sum);
+  }
+}
+
+QRLSH_EXPORT int qrlsh_ratings_holdout(const int32_t *in, int64_t nu, int64_t nq, uint64_t seed, uint64_t keep, int32_t *out,
+                                       int64_t *count_out, void *stream) {
+  QR_CHECK_ARG(nu >= 0 && nq >= 0 && nu <= 2147483647ll && nq <= 2147483647ll, "qrlsh_ratings_holdout: bad sizes nu=%lld nq=%lld",
+               (long long)nu, (long long)nq);
+  QR_CHECK_ARG(keep <= (1ull << 32), "qrlsh_ratings_holdout: keep=%llu above 2^32", (unsigned long long)keep);
+  QR_CHECK_ARG(count_out, "qrlsh_ratings_holdout: count_out is required");
+  const int64_t total = nu * nq;
+  QR_CHECK_ARG(total == 0 || (in && out && in != out), "qrlsh_ratings_holdout: null pointer, or in == out");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(count_out, 0, sizeof(int64_t), st) != hipSuccess) {
+    qrlsh_set_error("qrlsh_ratings_holdout: hipMemsetAsync failed");
+    return QRLSH_EHIP;
+  }
+  if (total == 0) return QRLSH_OK;
+  const bool aligned = ((uintptr_t)in | (uintptr_t)out) % 16 == 0;
+  const int64_t n4 = aligned ? total / 4 : 0;
+  int64_t groups = ceil_div64(aligned ? ceil_div64(total, 4) : total, HO_THREADS);
+  if (groups > HO_MAX_GROUPS) groups = HO_MAX_GROUPS;   // grid-stride beyond
+  const int64_t step = groups * HO_THREADS * 4;   // cells between a thread's vectors
+  QR_LAUNCH("ratings_holdout", ratings_holdout_kernel, dim3((unsigned)groups), dim3(HO_THREADS), 0, st, in, nq, total, n4,
+            step / nq, step % nq, seed, keep, out, reinterpret_cast<unsigned long long *>(count_out));
+  QR_LAUNCH_CHECK("qrlsh_ratings_holdout");
+  return QRLSH_OK;
+}

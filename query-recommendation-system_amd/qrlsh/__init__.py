@@ -38,6 +38,7 @@ from .synth import synth_csr, poisson_cdf_u32  # noqa: F401
 from .answers import build_answer_index, encode_queries, answer_sets, AnswerIndex  # noqa: F401
 from .recommend import top_k, for_users  # noqa: F401
 from .predict import predict_users, user_lists  # noqa: F401
+from .evaluate import holdout, evaluate, evaluate_cells, Evaluation  # noqa: F401
 from .index import QueryIndex  # noqa: F401
 from .userlists import UserLists  # noqa: F401
 from .table import LiveTable, TableDictionary  # noqa: F401

@@ -159,6 +159,14 @@ SIGNATURES = {
     "qrlsh_recommend_users": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
                                              _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_ratings_holdout": (ctypes.c_int, [_vp, _i64, _i64, _u64, _u64, _vp, _vp, _vp]),
+    "qrlsh_evaluate_workspace_bytes": (_sz, [_i64, _i64]),
+    "qrlsh_evaluate": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                      ctypes.c_double, ctypes.c_double, _i32, _u64, _u64, _vp, _vp, _vp, _vp, _vp, _sz,
+                                      _vp]),
+    "qrlsh_evaluate_cells": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                                            _vp]),
     "qrlsh_center_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "qrlsh_user_gram_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_user_gram": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -534,6 +534,11 @@ class Recommender:
         (np.argsort(row)[::-1][:K], :282) on those scores, so the lists -- tie order and zero-valued entries
         included -- are the reference's.  qrlsh.users.user_similarities is the all-device variant with a
         defined tie order (value descending, id ascending) for sizes where a host loop per user is not wanted."""
+        return self._user_similarities_over(self.ratings)
+
+    def _user_similarities_over(self, ratings):
+        """compute_userSimilarities over `ratings` (host integers, one row per entry of usersIDs): self.ratings, or the
+        train matrix of evaluate(holdout=True)"""
         from qrlsh import users
         t0 = time.time()
         nu = self.usersIDs.size
@@ -543,8 +548,8 @@ class Recommender:
         self._log("\nCluster count: {}, Total users: {}".format(n_clusters, nu))
         # StandardScaler + PCA on the device (Gram matrix on the matrix cores), BIRCH by the reference's own
         # scikit-learn call; cluster_on_device = False: the whole clustering on the host, as the reference runs it
-        label = users.cluster_labels(self.ratings, device=self.device if self.cluster_on_device else None)
-        pairs, milli = users.cluster_pair_scores(self.ratings, label, self.device)
+        label = users.cluster_labels(ratings, device=self.device if self.cluster_on_device else None)
+        pairs, milli = users.cluster_pair_scores(ratings, label, self.device)
         user_sim = users.reference_cut(pairs, milli, label, top)
         self._log("\n" + str(round(time.time() - t0, 3)) + "s for overall users_similarity scores")
         return user_sim
@@ -737,6 +742,52 @@ class Recommender:
                                      DEFAULT_MEAN, self.device, sum_order=sum_order)
         ids = np.arange(self.usersIDs.size) if users is None else np.asarray(ops.to_host(users), dtype=np.int64)
         return pd.DataFrame(ops.to_host(rows), index=self.usersIDs[ids], columns=self.queriesIDs).astype(int)
+
+    # ---- how good is the served model: the prediction error on rated cells (qrlsh.evaluate) -----------------------
+    def evaluate(self, fraction=1.0, seed=0, holdout=False, cells=None, sum_order=None, user_sim=None):
+        """The prediction error of the model served now, on the device -> qrlsh.Evaluation (.mae, .rmse, .bias,
+        .coverage, .by_branch, .per_user, .totals).  The query side comes from the live lists (ValueError when there are
+        none); the sample is about `fraction` of the rated cells, chosen by `seed` (qrlsh.evaluate.is_kept).
+        holdout=False: leave-one-out -- every kept rated cell is predicted without its own rating, from the live lists
+        and the user index when it is in step (otherwise user_sim, default compute_userSimilarities): _serving_inputs'
+        choice, so the answer is current after rate, add_queries(update_lists=True), remove_rows and the rest.  THE LISTS
+        ARE HELD FIXED: the user similarities were computed with the cell present, which flatters the user side.
+        holdout=True is the protocol without that leak: the kept rated cells are zeroed in a train copy on the device,
+        the user side is built over that copy (a user index in step: UserLists.build over it with the index's labels
+        and K; otherwise user_sim, default the compute_userSimilarities route over it) and the held-out cells are
+        predicted from it and compared with self.ratings.  The query lists do not depend on ratings and are used as
+        they stand.  Neither self.ratings nor user_index is modified.
+        cells=(users, queries, values): an explicit test set instead of the sample (0-based positions; every triplet
+        counts), predicted from the ratings as they stand as if each cell were unrated.
+        ValueError for a fraction outside [0, 1], a bad sum_order, or cells together with holdout."""
+        from qrlsh.evaluate import keep_word, holdout as train_copy, evaluate as sweep, evaluate_cells
+        from qrlsh.userlists import UserLists
+        keep_word(fraction)
+        if cells is not None and holdout:
+            raise ValueError("cells name their own test set: holdout=True does not apply")
+        weights = dict(query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT, default_mean=DEFAULT_MEAN, device=self.device)
+        if not holdout:
+            lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, None)
+            if cells is not None:
+                users, queries, values = cells
+                return evaluate_cells(ratings, lists[0], lists[1], lists[2], user_sim, users, queries, values,
+                                      sum_order=sum_order, **weights)
+            return sweep(ratings, lists[0], lists[1], lists[2], user_sim, fraction=fraction, seed=seed,
+                         sum_order=sum_order, **weights)
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        sum_order = self.sum_order if sum_order is None else sum_order
+        ui = self._user_index_in_step() if user_sim is None else None
+        truth = ui.ratings if ui is not None else torch.from_numpy(
+            np.ascontiguousarray(self.ratings, dtype=np.int32)).to(self.device)
+        train, _ = train_copy(truth, fraction, seed=seed, device=self.device)
+        if ui is not None:
+            user_sim = UserLists.build(train, ui.user_labels(), K=ui.K, device=self.device).as_user_sims()
+        elif user_sim is None:
+            user_sim = self._user_similarities_over(ops.to_host(train))
+        return sweep(train, lists[0], lists[1], lists[2], user_sim, truth=truth, fraction=fraction, seed=seed,
+                     sum_order=sum_order, **weights)
 
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
         """Interactive top-k prompt of recommender.py:345-381 (`ask` is injectable for tests)."""
