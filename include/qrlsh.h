@@ -626,7 +626,7 @@ int qrlsh_lists_remove_fill(const int32_t *src, const int32_t *dst, const int32_
                             void *workspace, size_t workspace_bytes, int64_t total, int32_t *src_out, int32_t *dst_out,
                             int32_t *val_out, void *stream);
 
-/* ---- replacing queries of a built index in place (csrc/replace.hip) -----------------------------------------------------
+/* ---- replacing queries of a built index in place (csrc/replace.hip; the lists: the merge of csrc/lists.hip) -------------
  * m distinct ids R of 0 .. n-1 get new rows: batch row x goes to id replaced_ids[x] (device uint32 [m], ASCENDING;
  * replaced_map = qrlsh_idmap_build over them, whose member count must be m).  n, b, qrlsh_index_dir_bits(n) and every
  * other id stay as they are.  Afterwards the arrays are byte for byte those of qrlsh_index_build over the key matrix with

@@ -53,6 +53,11 @@ int qr_index_dir(const uint64_t *keys, int64_t n, int32_t b, uint32_t *dir_out, 
 void qr_lists_old_rows(const int32_t *src, const int32_t *dst, int64_t n_edges, int64_t n, uint32_t *old_lo,
                        uint32_t *old_hi, uint32_t *bad, hipStream_t st);
 void qr_lists_rev_rows(const uint64_t *rec, int64_t n_raw, int64_t n, uint32_t *rev_lo, uint32_t *rev_hi, hipStream_t st);
+// probed lists taken as they are (lists.hip): entry k < K of list j (off / idx / milli of a finish) goes to
+// base[at] + k with src = id, where id = ids ? ids[j] : first_id + j and at = base_by_id ? id : j (at < base_rows)
+void qr_lists_fill_probed(const int64_t *off, const int32_t *idx, const int32_t *milli, const uint32_t *ids,
+                          int64_t first_id, int64_t count, int K, const uint64_t *base, int64_t base_rows, bool base_by_id,
+                          int64_t total, int32_t *src_out, int32_t *dst_out, int32_t *val_out, hipStream_t st);
 
 // the rows of chosen users (predict.hip, compiled without FMA contraction): out[x] = the completed (eligible = false)
 // or eligible-only (true: 0 where rated) row of users[x], rows `ostride` words apart; `who` names the entry point
@@ -63,6 +68,13 @@ int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_
                      hipStream_t st);
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
+static inline size_t qr_al16(size_t x) { return (x + 15) / 16 * 16; }
+// bits that hold every id below n (at least 1, at most 32)
+static inline int qr_id_bits(int64_t n) {
+  int bits = 1;
+  while (bits < 32 && (1ll << bits) < n) ++bits;
+  return bits;
+}
 
 // 64-bit bijective mixer (splitmix64 finaliser).  Bijective => equal mixes <=> equal keys
 // on all 64 bits; the grouping sort uses only the top 32 bits and resolves the (rare)

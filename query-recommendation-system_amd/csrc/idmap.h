@@ -1,5 +1,6 @@
 // idmap.h -- what the kernels that take queries out of a built index (remove.hip) and put others in their place
-// (replace.hip) share: the tile geometry of their compactions, the id map, and the stable compaction of a tile.
+// (replace.hip) share, and the list merge (lists.hip) with them: the tile geometry of their compactions, the capped
+// grid of the grid-stride kernels, the id map, and the stable compaction of a tile.
 #pragma once
 #include "common.h"
 
@@ -9,7 +10,6 @@ constexpr int RM_TILE = RM_THREADS * RM_PER;    // records per workgroup: qrlsh/
 constexpr int RM_GRID = 2048;                   // workgroups of the grid-stride kernels (256 CUs x 8)
 constexpr int RM_MAXK = QRLSH_INDEX_MAX_K;
 
-static inline size_t rm_al16(size_t x) { return (x + 15) / 16 * 16; }
 static inline unsigned rm_grid(int64_t work, int64_t per_block) {
   const int64_t g = ceil_div64(work, per_block);
   return (unsigned)(g < RM_GRID ? (g > 0 ? g : 1) : RM_GRID);
@@ -29,9 +29,9 @@ static IdMap idmap_layout(void *map, int64_t n) {
   m.nw = (n + 31) / 32;
   char *p = static_cast<char *>(map);
   size_t o = 0;
-  m.w = reinterpret_cast<uint2 *>(p + o), o += rm_al16((size_t)(m.nw + 1) * 8);
-  m.cnt = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(m.nw + 2) * 8);
-  m.sums = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(ceil_div64(m.nw + 1, SCANL_CHUNK) + 2) * 8);
+  m.w = reinterpret_cast<uint2 *>(p + o), o += qr_al16((size_t)(m.nw + 1) * 8);
+  m.cnt = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(m.nw + 2) * 8);
+  m.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(m.nw + 1, SCANL_CHUNK) + 2) * 8);
   m.bytes = o;
   return m;
 }

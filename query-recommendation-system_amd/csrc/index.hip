@@ -420,12 +420,10 @@ __global__ __launch_bounds__(256) void index_compact_kernel(const int32_t *__res
   }
 }
 
-static inline size_t ix_al16(size_t x) { return (x + 15) / 16 * 16; }
-
 // workspace: keys u64 [n_raw] | pidx i32 [m][K] | pmilli i32 [m][K] | scan sums
 QRLSH_EXPORT size_t qrlsh_index_finish_workspace_bytes(int64_t m, int32_t K, int64_t n_raw) {
   if (m <= 0 || K <= 0 || K > IX_MAXK || n_raw < 0) return 0;
-  return ix_al16((size_t)n_raw * 8) + 2 * ix_al16((size_t)m * K * 4) + (size_t)(ceil_div64(m, SCANL_CHUNK) + 1) * 8;
+  return qr_al16((size_t)n_raw * 8) + 2 * qr_al16((size_t)m * K * 4) + (size_t)(ceil_div64(m, SCANL_CHUNK) + 1) * 8;
 }
 
 static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig, const int64_t *probe_norm2,
@@ -458,9 +456,9 @@ static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const voi
   }
   char *ws = static_cast<char *>(workspace);
   uint64_t *keys = reinterpret_cast<uint64_t *>(ws);
-  int32_t *pidx = reinterpret_cast<int32_t *>(ws + ix_al16((size_t)n_raw * 8));
-  int32_t *pmilli = reinterpret_cast<int32_t *>(ws + ix_al16((size_t)n_raw * 8) + ix_al16((size_t)m * K * 4));
-  uint64_t *sums = reinterpret_cast<uint64_t *>(ws + ix_al16((size_t)n_raw * 8) + 2 * ix_al16((size_t)m * K * 4));
+  int32_t *pidx = reinterpret_cast<int32_t *>(ws + qr_al16((size_t)n_raw * 8));
+  int32_t *pmilli = reinterpret_cast<int32_t *>(ws + qr_al16((size_t)n_raw * 8) + qr_al16((size_t)m * K * 4));
+  uint64_t *sums = reinterpret_cast<uint64_t *>(ws + qr_al16((size_t)n_raw * 8) + 2 * qr_al16((size_t)m * K * 4));
   if (n_raw > 0) {
     const dim3 grid((unsigned)ceil_div64(n_raw, 256)), block(256);
     if (sig_dtype == QRLSH_SIG_U16)
@@ -678,7 +676,7 @@ __global__ __launch_bounds__(256) void index_merge_kernel(const uint64_t *__rest
 QRLSH_EXPORT size_t qrlsh_index_append_workspace_bytes(int64_t m, int32_t b) {
   if (m <= 0 || b <= 0) return 0;
   const size_t bm = (size_t)b * (size_t)m;
-  return ix_al16(bm * 8) + 3 * ix_al16(bm * 4) + qrlsh_sort_workspace_bytes(m, b);
+  return qr_al16(bm * 8) + 3 * qr_al16(bm * 4) + qrlsh_sort_workspace_bytes(m, b);
 }
 
 QRLSH_EXPORT int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
@@ -699,10 +697,10 @@ QRLSH_EXPORT int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, c
   const size_t bm = (size_t)b * (size_t)m;
   char *ws = static_cast<char *>(workspace);
   uint64_t *ktmp = reinterpret_cast<uint64_t *>(ws);
-  uint32_t *bids = reinterpret_cast<uint32_t *>(ws + ix_al16(bm * 8));
-  uint32_t *itmp = reinterpret_cast<uint32_t *>(ws + ix_al16(bm * 8) + ix_al16(bm * 4));
-  uint32_t *q = reinterpret_cast<uint32_t *>(ws + ix_al16(bm * 8) + 2 * ix_al16(bm * 4));
-  void *sws = ws + ix_al16(bm * 8) + 3 * ix_al16(bm * 4);
+  uint32_t *bids = reinterpret_cast<uint32_t *>(ws + qr_al16(bm * 8));
+  uint32_t *itmp = reinterpret_cast<uint32_t *>(ws + qr_al16(bm * 8) + qr_al16(bm * 4));
+  uint32_t *q = reinterpret_cast<uint32_t *>(ws + qr_al16(bm * 8) + 2 * qr_al16(bm * 4));
+  void *sws = ws + qr_al16(bm * 8) + 3 * qr_al16(bm * 4);
   const int rc = qrlsh_sort_u64(new_keys, ktmp, bids, itmp, m, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0, sws,
                                 qrlsh_sort_workspace_bytes(m, b), stream);
   if (rc < 0) return rc;

@@ -21,7 +21,8 @@
 //             pick map and it is probed again against the shrunk index.  count / fill compact the stored entries the
 //             same way as the bands (tiles, a scan, ballots): a kept entry's output position is the kept entries before
 //             it plus the re-probed entries of the picked rows below its src; the head entry of a picked row leaves
-//             that row's output position for the kernel that copies the re-probed lists.  Every entry places itself.
+//             that row's output position for the copy of the re-probed lists (qr_lists_fill_probed, lists.hip).  Every
+//             entry places itself.
 #include "idmap.h"
 
 QRLSH_EXPORT size_t qrlsh_idmap_workspace_bytes(int64_t n) {
@@ -231,7 +232,7 @@ __global__ __launch_bounds__(RM_THREADS) void index_remove_kernel(
 QRLSH_EXPORT size_t qrlsh_index_remove_workspace_bytes(int64_t n, int32_t b) {
   if (n <= 0 || b <= 0) return 0;
   const int64_t tiles = ceil_div64(n, RM_TILE) * b;
-  return rm_al16((size_t)(tiles + 1) * 8) + rm_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
+  return qr_al16((size_t)(tiles + 1) * 8) + qr_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
 }
 
 QRLSH_EXPORT int qrlsh_index_remove(const uint64_t *keys, const uint32_t *ids, int64_t n, int32_t b, const void *removed_map,
@@ -254,7 +255,7 @@ QRLSH_EXPORT int qrlsh_index_remove(const uint64_t *keys, const uint32_t *ids, i
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t n_out = n - n_removed, tiles = ceil_div64(n, RM_TILE), all = tiles * b;
   uint64_t *tile_off = static_cast<uint64_t *>(workspace);
-  uint64_t *sums = reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + rm_al16((size_t)(all + 1) * 8));
+  uint64_t *sums = reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + qr_al16((size_t)(all + 1) * 8));
   const uint2 *rm = idmap_layout(const_cast<void *>(removed_map), n).w;
   const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
   const dim3 grid((unsigned)tiles, (unsigned)b), block(RM_THREADS);
@@ -326,9 +327,9 @@ static LrWs lr_layout(void *workspace, int64_t n, int64_t n_edges) {
   w.rows = n < n_edges ? n : n_edges;  // no more picked rows than rows, or than entries
   char *p = static_cast<char *>(workspace);
   size_t o = 0;
-  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(w.tiles + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(ceil_div64(w.tiles, SCANL_CHUNK) + 1) * 8);
-  w.pick_base = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)w.rows * 8);
+  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(w.tiles + 1) * 8);
+  w.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(w.tiles, SCANL_CHUNK) + 1) * 8);
+  w.pick_base = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)w.rows * 8);
   w.bad = reinterpret_cast<uint32_t *>(p + o), o += 16;
   w.bytes = o;
   return w;
@@ -408,23 +409,6 @@ __global__ void lists_remove_total_kernel(const uint64_t *__restrict__ kept, con
   if (threadIdx.x == 0) *total_out = *bad ? ~0ull : *kept + (n_pick > 0 ? (uint64_t)re_off[n_pick] : 0ull);
 }
 
-// the re-probed lists: entry k of picked row j
-__global__ __launch_bounds__(RM_THREADS) void lists_remove_fill_re_kernel(
-    const int64_t *__restrict__ re_off, const int32_t *__restrict__ re_idx, const int32_t *__restrict__ re_milli,
-    const uint32_t *__restrict__ re_self, int64_t n_pick, int K, const uint64_t *__restrict__ pick_base, int64_t total,
-    int32_t *__restrict__ src_out, int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
-  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n_pick * K) return;
-  const int64_t j = g / K, k = g - j * K;
-  const int64_t a = re_off[j];
-  if (k >= re_off[j + 1] - a) return;
-  const int64_t at = (int64_t)pick_base[j] + k;
-  if (at >= total) return;
-  src_out[at] = (int32_t)re_self[j];
-  dst_out[at] = re_idx[a + k];
-  val_out[at] = re_milli[a + k];
-}
-
 static int lr_args(const char *who, const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
                    int32_t K, const void *removed_map, const void *pick_map, const int64_t *re_off, int64_t n_pick,
                    const void *workspace, size_t workspace_bytes) {
@@ -490,10 +474,9 @@ QRLSH_EXPORT int qrlsh_lists_remove_fill(const int32_t *src, const int32_t *dst,
     QR_LAUNCH("lists_remove_fill", lists_remove_kernel<true>, dim3((unsigned)w.tiles), dim3(RM_THREADS), 0, st, src, dst, val,
               n_edges, n, rm, pk, re_off, n_pick, w.tile_off, w.bad, total, w.pick_base, src_out, dst_out, val_out);
   }
-  if (n_pick > 0 && re_idx && re_milli)  // (no re-probed list has an entry when the finish wrote none)
-    QR_LAUNCH("lists_remove_fill_re", lists_remove_fill_re_kernel, dim3((unsigned)ceil_div64(n_pick * K, RM_THREADS)),
-              dim3(RM_THREADS), 0, st, re_off, re_idx, re_milli, re_self, n_pick, (int)K, (const uint64_t *)w.pick_base,
-              total, src_out, dst_out, val_out);
+  // the re-probed lists: list j at pick_base[j], src = the row's new id
+  qr_lists_fill_probed(re_off, re_idx, re_milli, re_self, 0, n_pick, (int)K, w.pick_base, n_pick, false, total, src_out,
+                       dst_out, val_out, st);
   QR_LAUNCH_CHECK("qrlsh_lists_remove_fill");
   return QRLSH_OK;
 }

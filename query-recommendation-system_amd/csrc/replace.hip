@@ -25,20 +25,9 @@
 //           the ids of the count pass and 8 B for the directory's read.
 //   lists:  rows outside R keep their stored entries whose dst is outside R and gain the replaced queries that now
 //           name them; a row of exactly K entries that loses one is picked (qrlsh_lists_remove_mark over R) and probed
-//           again, rows of R are probed with their new rows.
-//           records: a kept raw word of R's probe whose id is neither in R nor picked becomes the reverse record
-//                    id << 11 | (1000 - milli), payload x, sorted as lists.hip sorts them: by (row, value descending,
-//                    x ascending = replaced id ascending).
-//           count:   kept[e] = 1 for a stored entry whose dst stays, scanned over all entries: the surviving entries
-//                    of a row before entry e are kept[e] - kept[row's first].  len = min(K, surviving + reverse) for an
-//                    unpicked row outside R, the finish's length for the others; one scan over the n rows.
-//           fill:    every element ranks itself: a surviving stored entry by its place among the row's surviving
-//                    entries plus the records of the row's run that order before it (larger value, or equal value and
-//                    smaller replaced id); a record by its place in the run plus the surviving entries that order
-//                    before it (larger value, or equal value and smaller dst).  Ties go by id both ways.
+//           again, rows of R are probed with their new rows.  That is the merge of lists.hip with R as the dropped
+//           ids and rids as the record ids: qrlsh_lists_replace_* live there.
 #include "idmap.h"
-
-constexpr int RP_MAXK = QRLSH_INDEX_MAX_K;
 
 __device__ static inline uint32_t rp_top32(uint64_t k) { return (uint32_t)(qr_mix64(k) >> 32); }
 
@@ -237,17 +226,17 @@ static RpWs rp_layout(void *workspace, int64_t n, int64_t m, int32_t b) {
   const int64_t tiles = ceil_div64(n, RM_TILE) * b;
   char *p = static_cast<char *>(workspace);
   size_t o = 0;
-  w.ktmp = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(bm * 8);
-  w.left_a = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(bm * 8);
-  w.left_b = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(bm * 8);
-  w.bx = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(bm * 4);
-  w.xtmp = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(bm * 4);
-  w.s = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(bm * 4);
-  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(tiles + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
+  w.ktmp = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(bm * 8);
+  w.left_a = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(bm * 8);
+  w.left_b = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(bm * 8);
+  w.bx = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(bm * 4);
+  w.xtmp = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(bm * 4);
+  w.s = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(bm * 4);
+  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(tiles + 1) * 8);
+  w.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
   w.sort_ws = p + o;
   w.sort_bytes = qrlsh_sort_workspace_bytes(m, b);
-  o += rm_al16(w.sort_bytes);
+  o += qr_al16(w.sort_bytes);
   w.bytes = o;
   return w;
 }
@@ -295,328 +284,4 @@ QRLSH_EXPORT int qrlsh_index_replace(const uint64_t *keys, const uint32_t *ids, 
   QR_LAUNCH("index_replace_fill", index_replace_fill_kernel, grid, block, 0, st, keys, ids, n, m, rm, pk, n_pick,
             (const uint64_t *)w.tile_off, (const uint32_t *)w.s, keys_out, ids_out, pick_keys_out);
   return qr_index_dir(keys_out, n, b, dir_out, st, "qrlsh_index_replace");
-}
-
-// ---- lists ----------------------------------------------------------------------------------------------------------
-constexpr int RL_PER = 4;                       // stored entries per lane of the fill, RM_THREADS apart
-constexpr int RL_TILE = RM_THREADS * RL_PER;
-
-static inline int rl_id_bits(int64_t n) {
-  int bits = 1;
-  while (bits < 32 && (1ll << bits) < n) ++bits;
-  return bits;
-}
-
-struct RlWs {
-  uint64_t *rec_a, *rec_b;                       // [n_raw] reverse records, ping-pong
-  uint32_t *pay_a, *pay_b;                       // [n_raw] their batch rows
-  uint32_t *old_lo, *old_hi, *rev_lo, *rev_hi;   // [n] each, contiguous (one memset)
-  uint64_t *kept;                                // [n_edges + 1] stored entries whose dst stays, then their scan
-  uint64_t *off;                                 // [n + 1] lengths, then output offsets; [n] = total
-  uint64_t *sums;                                // scan scratch
-  uint32_t *bad;
-  void *sort_ws;
-  size_t sort_bytes, bytes;
-};
-static RlWs rl_layout(void *workspace, int64_t n, int64_t n_edges, int64_t n_raw) {
-  RlWs w;
-  char *p = static_cast<char *>(workspace);
-  size_t o = 0;
-  const size_t nr = (size_t)n_raw, nn = (size_t)n, ne = (size_t)n_edges;
-  w.rec_a = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(nr * 8);
-  w.rec_b = reinterpret_cast<uint64_t *>(p + o), o += rm_al16(nr * 8);
-  w.pay_a = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(nr * 4);
-  w.pay_b = reinterpret_cast<uint32_t *>(p + o), o += rm_al16(nr * 4);
-  w.old_lo = reinterpret_cast<uint32_t *>(p + o);
-  w.old_hi = w.old_lo + nn;
-  w.rev_lo = w.old_hi + nn;
-  w.rev_hi = w.rev_lo + nn;
-  o += rm_al16(nn * 16);
-  w.kept = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((ne + 1) * 8);
-  w.off = reinterpret_cast<uint64_t *>(p + o), o += rm_al16((nn + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o);
-  o += rm_al16((size_t)(ceil_div64((int64_t)(ne > nn ? ne : nn), SCANL_CHUNK) + 1) * 8);
-  w.bad = reinterpret_cast<uint32_t *>(p + o), o += 16;
-  w.sort_ws = p + o;
-  w.sort_bytes = qrlsh_sort_workspace_bytes(n_raw, 1);
-  o += rm_al16(w.sort_bytes);
-  w.bytes = o;
-  return w;
-}
-
-QRLSH_EXPORT size_t qrlsh_lists_replace_workspace_bytes(int64_t n, int64_t n_edges, int64_t n_raw) {
-  if (n < 0 || n_edges < 0 || n_raw < 0) return 0;
-  return rl_layout(nullptr, n, n_edges, n_raw).bytes;
-}
-
-// one lane per raw word of R's probe: the reverse record of a kept word that names a row outside R that is not picked
-__global__ __launch_bounds__(RM_THREADS) void lists_replace_records_kernel(
-    const uint64_t *__restrict__ raw, const uint64_t *__restrict__ skeys, int64_t n_raw, int64_t n, int64_t m, int b,
-    const uint2 *__restrict__ rm, const uint2 *__restrict__ pick, uint64_t *__restrict__ rec, uint32_t *__restrict__ pay) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_raw) return;
-  const uint64_t k = skeys[i];
-  const uint64_t x = (raw[i] >> 32) / (uint32_t)b;
-  const uint64_t id = k & 0xFFFFFFFFull, inv = k >> 32;
-  bool keep = k != ~0ull && (int64_t)id < n && (int64_t)x < m && inv <= 2000;
-  if (keep) keep = !idmap_has(rm[id >> 5], (uint32_t)id) && !(pick && idmap_has(pick[id >> 5], (uint32_t)id));
-  rec[i] = keep ? (id << 11 | inv) : ~0ull;
-  pay[i] = (uint32_t)x;
-}
-
-// kept[e] = 1 for a stored entry whose dst is a query outside R
-__global__ __launch_bounds__(RM_THREADS) void lists_replace_kept_kernel(const int32_t *__restrict__ dst, int64_t n_edges,
-                                                                       int64_t n, const uint2 *__restrict__ rm,
-                                                                       uint64_t *__restrict__ kept) {
-  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n_edges; e += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t d = dst[e];
-    kept[e] = d >= 0 && d < n && !idmap_has(rm[d >> 5], (uint32_t)d) ? 1ull : 0ull;
-  }
-}
-
-// one lane per row: its length after the replacement
-__global__ __launch_bounds__(RM_THREADS) void lists_replace_len_kernel(
-    const uint32_t *__restrict__ old_lo, const uint32_t *__restrict__ old_hi, const uint32_t *__restrict__ rev_lo,
-    const uint32_t *__restrict__ rev_hi, const uint64_t *__restrict__ kept, int64_t n_edges, int64_t n,
-    const uint2 *__restrict__ rm, const int64_t *__restrict__ r_off, int64_t m, const uint2 *__restrict__ pick,
-    const int64_t *__restrict__ p_off, int64_t n_pick, int K, uint64_t *__restrict__ len) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const uint2 w = rm[i >> 5];
-    const uint2 pw = pick ? pick[i >> 5] : make_uint2(0u, 0u);
-    uint64_t l = 0;
-    if (idmap_has(w, (uint32_t)i)) {
-      const int64_t j = idmap_rank(w, (uint32_t)i);
-      if (j < m && r_off[j + 1] > r_off[j]) l = (uint64_t)(r_off[j + 1] - r_off[j]);
-    } else if (idmap_has(pw, (uint32_t)i)) {
-      const int64_t j = idmap_rank(pw, (uint32_t)i);
-      if (j < n_pick && p_off[j + 1] > p_off[j]) l = (uint64_t)(p_off[j + 1] - p_off[j]);
-    } else {
-      const int64_t lo = old_lo[i], hi = old_hi[i];
-      if (hi > lo && hi <= n_edges) l = kept[hi] - kept[lo];
-      l += rev_hi[i] - rev_lo[i];
-    }
-    len[i] = l < (uint64_t)K ? l : (uint64_t)K;
-  }
-}
-
-// *total_out = the number of entries of the new lists, or ~0 when the stored lists break the contract
-__global__ void lists_replace_total_kernel(const uint64_t *__restrict__ total, const uint32_t *__restrict__ bad,
-                                           uint64_t *__restrict__ total_out) {
-  if (threadIdx.x == 0) *total_out = *bad ? ~0ull : *total;
-}
-
-// stored entries, RL_PER per lane: a surviving entry of an unpicked row outside R ranks itself
-__global__ __launch_bounds__(RM_THREADS) void lists_replace_fill_old_kernel(
-    const int32_t *__restrict__ src, const int32_t *__restrict__ dst, const int32_t *__restrict__ val, int64_t n_edges,
-    int64_t n, int K, const uint2 *__restrict__ rm, const uint2 *__restrict__ pick, const uint32_t *__restrict__ rids,
-    int64_t m, const uint32_t *__restrict__ old_lo, const uint32_t *__restrict__ rev_lo,
-    const uint32_t *__restrict__ rev_hi, const uint64_t *__restrict__ rec, const uint32_t *__restrict__ pay,
-    const uint64_t *__restrict__ kept, const uint64_t *__restrict__ out_off, int64_t total, int32_t *__restrict__ src_out,
-    int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
-  const int64_t ntiles = (n_edges + RL_TILE - 1) / RL_TILE;
-  for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t e0 = tile * RL_TILE + threadIdx.x;
-    int32_t s[RL_PER], d[RL_PER], v[RL_PER];
-    uint64_t kp[RL_PER];
-#pragma unroll
-    for (int k = 0; k < RL_PER; ++k) {  // every load of the step is issued before the first is used
-      const int64_t e = e0 + (int64_t)k * RM_THREADS;
-      const bool live = e < n_edges;
-      s[k] = live ? src[e] : -1;
-      d[k] = live ? dst[e] : -1;
-      v[k] = live ? val[e] : 0;
-      kp[k] = live ? kept[e] : 0;
-    }
-#pragma unroll
-    for (int k = 0; k < RL_PER; ++k) {
-      const int64_t i = s[k], dd = d[k];
-      if (i < 0 || i >= n || dd < 0 || dd >= n) continue;
-      if (idmap_has(rm[i >> 5], (uint32_t)i) || idmap_has(rm[dd >> 5], (uint32_t)dd)) continue;
-      if (pick && idmap_has(pick[i >> 5], (uint32_t)i)) continue;
-      uint32_t L = rev_lo[i], R = rev_hi[i];
-      const uint32_t first = L;
-      const uint64_t inv = (uint64_t)(int64_t)(1000 - v[k]);
-      while (L < R) {  // records of the run that order before the entry: larger value, or equal and smaller replaced id
-        const uint32_t mid = L + (R - L) / 2;
-        const uint64_t ri = rec[mid] & 2047u;
-        const uint32_t x = pay[mid];
-        const int64_t rid = (int64_t)x < m ? (int64_t)rids[x] : n;
-        if (ri < inv || (ri == inv && rid < dd)) L = mid + 1;
-        else R = mid;
-      }
-      const int64_t rank = (int64_t)(kp[k] - kept[old_lo[i]]) + (int64_t)(L - first);
-      if (rank < 0 || rank >= K) continue;
-      const int64_t o = (int64_t)out_off[i] + rank;
-      if (o >= total) continue;  // never, for offsets the count wrote
-      src_out[o] = (int32_t)i;
-      dst_out[o] = (int32_t)dd;
-      val_out[o] = v[k];
-    }
-  }
-}
-
-// sorted records, one lane each: rank = place in the run + surviving stored entries of the row that order before it
-__global__ __launch_bounds__(RM_THREADS) void lists_replace_fill_rev_kernel(
-    const uint64_t *__restrict__ rec, const uint32_t *__restrict__ pay, int64_t n_raw, int64_t n, int K,
-    const uint32_t *__restrict__ rids, int64_t m, const int32_t *__restrict__ dst, const int32_t *__restrict__ val,
-    int64_t n_edges, const uint32_t *__restrict__ old_lo, const uint32_t *__restrict__ old_hi,
-    const uint32_t *__restrict__ rev_lo, const uint64_t *__restrict__ kept, const uint64_t *__restrict__ out_off,
-    int64_t total, int32_t *__restrict__ src_out, int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n_raw) return;
-  const uint64_t r = rec[k];
-  if (r == ~0ull) return;
-  const int64_t id = (int64_t)(r >> 11);
-  const uint32_t x = pay[k];
-  if (id >= n || (int64_t)x >= m) return;  // never, for a record the records kernel wrote
-  const int32_t mi = 1000 - (int32_t)(r & 2047u);
-  const int64_t rid = rids[x];
-  uint32_t L = old_lo[id], R = old_hi[id];
-  if (R > (uint64_t)n_edges) R = (uint32_t)n_edges;
-  if (L > R) L = R;
-  const uint32_t lo = L;
-  while (L < R) {  // the stored row is ordered by value descending, dst ascending: the first entry that orders after
-    const uint32_t mid = L + (R - L) / 2;
-    const int32_t sv = val[mid];
-    if (sv > mi || (sv == mi && (int64_t)dst[mid] < rid)) L = mid + 1;
-    else R = mid;
-  }
-  const int64_t rank = (k - (int64_t)rev_lo[id]) + (int64_t)(kept[L] - kept[lo]);
-  if (rank < 0 || rank >= K) return;
-  const int64_t o = (int64_t)out_off[id] + rank;
-  if (o >= total) return;
-  src_out[o] = (int32_t)id;
-  dst_out[o] = (int32_t)rid;
-  val_out[o] = mi;
-}
-
-// the probed lists: entry k of probe row j, which is query self[j]
-__global__ __launch_bounds__(RM_THREADS) void lists_replace_fill_re_kernel(
-    const int64_t *__restrict__ re_off, const int32_t *__restrict__ re_idx, const int32_t *__restrict__ re_milli,
-    const uint32_t *__restrict__ self, int64_t count, int64_t n, int K, const uint64_t *__restrict__ out_off,
-    int64_t total, int32_t *__restrict__ src_out, int32_t *__restrict__ dst_out, int32_t *__restrict__ val_out) {
-  const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= count * K) return;
-  const int64_t j = g / K, k = g - j * K;
-  const int64_t a = re_off[j], i = self[j];
-  if (k >= re_off[j + 1] - a || i >= n) return;
-  const int64_t at = (int64_t)out_off[i] + k;
-  if (at >= total) return;
-  src_out[at] = (int32_t)i;
-  dst_out[at] = re_idx[a + k];
-  val_out[at] = re_milli[a + k];
-}
-
-static int rl_args(const char *who, const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
-                   int64_t m, int32_t b, int32_t K, const void *replaced_map, const uint32_t *replaced_ids,
-                   const void *pick_map, const uint32_t *pick_ids, int64_t n_pick, int64_t n_raw, const int64_t *r_off,
-                   const int64_t *p_off, const void *workspace, size_t workspace_bytes) {
-  QR_CHECK_ARG(K >= 1 && K <= RP_MAXK, "%s: K=%d not in [1, %d]", who, K, RP_MAXK);
-  QR_CHECK_ARG(n >= 0 && n < (1ll << 31) && n_edges >= 0 && n_edges < (1ll << 31) && m >= 1 && m <= n && n_pick >= 0 &&
-                   n_pick <= n - m && n_raw >= 0 && n_raw < (1ll << 32) && b > 0 && b <= 65535 &&
-                   m * (int64_t)b < (1ll << 32),
-               "%s: bad sizes n=%lld n_edges=%lld m=%lld n_pick=%lld n_raw=%lld b=%d", who, (long long)n,
-               (long long)n_edges, (long long)m, (long long)n_pick, (long long)n_raw, b);
-  QR_CHECK_ARG(replaced_map && replaced_ids && r_off && workspace && (n_edges == 0 || (src && dst && val)) &&
-                   (n_pick == 0 || (pick_map && pick_ids && p_off)),
-               "%s: null pointer", who);
-  if (workspace_bytes < qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes,
-                    qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw));
-    return QRLSH_EWORKSPACE;
-  }
-  return QRLSH_OK;
-}
-
-QRLSH_EXPORT int qrlsh_lists_replace_count(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges,
-                                           int64_t n, int64_t m, int32_t b, int32_t K, const void *replaced_map,
-                                           const uint32_t *replaced_ids, const void *pick_map, const uint32_t *pick_ids,
-                                           int64_t n_pick, const uint64_t *raw, const uint64_t *select_keys, int64_t n_raw,
-                                           const int64_t *r_off, const int64_t *p_off, void *workspace,
-                                           size_t workspace_bytes, uint64_t *total_out, void *stream) {
-  QR_CHECK_ARG(total_out, "qrlsh_lists_replace_count: null total_out");
-  const int rc = rl_args("qrlsh_lists_replace_count", src, dst, val, n_edges, n, m, b, K, replaced_map, replaced_ids,
-                         pick_map, pick_ids, n_pick, n_raw, r_off, p_off, workspace, workspace_bytes);
-  if (rc != QRLSH_OK) return rc;
-  QR_CHECK_ARG(n_raw == 0 || (raw && select_keys), "qrlsh_lists_replace_count: null pointer");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const RlWs w = rl_layout(workspace, n, n_edges, n_raw);
-  const uint2 *rm = idmap_layout(const_cast<void *>(replaced_map), n).w;
-  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
-  if (hipMemsetAsync(w.bad, 0, 16, st) != hipSuccess || hipMemsetAsync(w.old_lo, 0, (size_t)n * 16, st) != hipSuccess ||
-      hipMemsetAsync(w.kept, 0, sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_lists_replace_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
-  const dim3 block(RM_THREADS);
-  if (n_raw > 0) {
-    QR_LAUNCH("lists_replace_records", lists_replace_records_kernel, dim3((unsigned)ceil_div64(n_raw, RM_THREADS)), block, 0,
-              st, raw, select_keys, n_raw, n, m, (int)b, rm, pk, w.rec_a, w.pay_a);
-    const int where = qrlsh_sort_u64(w.rec_a, w.rec_b, w.pay_a, w.pay_b, n_raw, 1, 0, 11 + rl_id_bits(n), 0, 0, w.sort_ws,
-                                     w.sort_bytes, stream);
-    if (where < 0) return where;
-    if (where == 1) {  // the sorted records are always left in rec_a / pay_a
-      if (hipMemcpyAsync(w.rec_a, w.rec_b, (size_t)n_raw * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(w.pay_a, w.pay_b, (size_t)n_raw * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        qrlsh_set_error("qrlsh_lists_replace_count: hipMemcpyAsync failed");
-        return QRLSH_EHIP;
-      }
-    }
-    qr_lists_rev_rows(w.rec_a, n_raw, n, w.rev_lo, w.rev_hi, st);
-  }
-  if (n_edges > 0) {
-    qr_lists_old_rows(src, dst, n_edges, n, w.old_lo, w.old_hi, w.bad, st);
-    QR_LAUNCH("lists_replace_kept", lists_replace_kept_kernel, dim3(rm_grid(n_edges, RM_THREADS)), block, 0, st, dst,
-              n_edges, n, rm, w.kept);
-    qr_scan_u64(w.kept, n_edges, w.kept + n_edges, w.sums, st);
-  }
-  QR_LAUNCH("lists_replace_len", lists_replace_len_kernel, dim3(rm_grid(n, RM_THREADS)), block, 0, st,
-            (const uint32_t *)w.old_lo, (const uint32_t *)w.old_hi, (const uint32_t *)w.rev_lo, (const uint32_t *)w.rev_hi,
-            (const uint64_t *)w.kept, n_edges, n, rm, r_off, m, pk, p_off, n_pick, (int)K, w.off);
-  qr_scan_u64(w.off, n, w.off + n, w.sums, st);
-  QR_LAUNCH("lists_replace_total", lists_replace_total_kernel, dim3(1), dim3(64), 0, st, (const uint64_t *)(w.off + n),
-            (const uint32_t *)w.bad, total_out);
-  QR_LAUNCH_CHECK("qrlsh_lists_replace_count");
-  return QRLSH_OK;
-}
-
-QRLSH_EXPORT int qrlsh_lists_replace_fill(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges,
-                                          int64_t n, int64_t m, int32_t b, int32_t K, const void *replaced_map,
-                                          const uint32_t *replaced_ids, const void *pick_map, const uint32_t *pick_ids,
-                                          int64_t n_pick, int64_t n_raw, const int64_t *r_off, const int32_t *r_idx,
-                                          const int32_t *r_milli, const int64_t *p_off, const int32_t *p_idx,
-                                          const int32_t *p_milli, const void *workspace, size_t workspace_bytes,
-                                          int64_t total, int32_t *src_out, int32_t *dst_out, int32_t *val_out,
-                                          void *stream) {
-  const int rc = rl_args("qrlsh_lists_replace_fill", src, dst, val, n_edges, n, m, b, K, replaced_map, replaced_ids,
-                         pick_map, pick_ids, n_pick, n_raw, r_off, p_off, workspace, workspace_bytes);
-  if (rc != QRLSH_OK) return rc;
-  QR_CHECK_ARG(total >= 0 && total <= n * (int64_t)K, "qrlsh_lists_replace_fill: bad total %lld", (long long)total);
-  if (total == 0) return QRLSH_OK;
-  QR_CHECK_ARG(src_out && dst_out && val_out, "qrlsh_lists_replace_fill: null pointer");
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  const RlWs w = rl_layout(const_cast<void *>(workspace), n, n_edges, n_raw);
-  const uint2 *rm = idmap_layout(const_cast<void *>(replaced_map), n).w;
-  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
-  const dim3 block(RM_THREADS);
-  if (n_edges > 0)
-    QR_LAUNCH("lists_replace_fill_old", lists_replace_fill_old_kernel, dim3(rm_grid(n_edges, RL_TILE)), block, 0, st, src,
-              dst, val, n_edges, n, (int)K, rm, pk, replaced_ids, m, (const uint32_t *)w.old_lo,
-              (const uint32_t *)w.rev_lo, (const uint32_t *)w.rev_hi, (const uint64_t *)w.rec_a,
-              (const uint32_t *)w.pay_a, (const uint64_t *)w.kept, (const uint64_t *)w.off, total, src_out, dst_out, val_out);
-  if (n_raw > 0)
-    QR_LAUNCH("lists_replace_fill_rev", lists_replace_fill_rev_kernel, dim3((unsigned)ceil_div64(n_raw, RM_THREADS)), block,
-              0, st, (const uint64_t *)w.rec_a, (const uint32_t *)w.pay_a, n_raw, n, (int)K, replaced_ids, m, dst, val,
-              n_edges, (const uint32_t *)w.old_lo, (const uint32_t *)w.old_hi, (const uint32_t *)w.rev_lo,
-              (const uint64_t *)w.kept, (const uint64_t *)w.off, total, src_out, dst_out, val_out);
-  if (r_idx && r_milli)  // (no probed list has an entry when the finish wrote none: its arrays may be empty)
-    QR_LAUNCH("lists_replace_fill_re", lists_replace_fill_re_kernel, dim3((unsigned)ceil_div64(m * K, RM_THREADS)), block, 0,
-              st, r_off, r_idx, r_milli, replaced_ids, m, n, (int)K, (const uint64_t *)w.off, total, src_out, dst_out,
-              val_out);
-  if (n_pick > 0 && p_idx && p_milli)
-    QR_LAUNCH("lists_replace_fill_re", lists_replace_fill_re_kernel, dim3((unsigned)ceil_div64(n_pick * K, RM_THREADS)),
-              block, 0, st, p_off, p_idx, p_milli, pick_ids, n_pick, n, (int)K, (const uint64_t *)w.off, total, src_out,
-              dst_out, val_out);
-  QR_LAUNCH_CHECK("qrlsh_lists_replace_fill");
-  return QRLSH_OK;
 }

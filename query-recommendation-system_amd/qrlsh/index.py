@@ -38,6 +38,24 @@ def _int_arg(v, name, lo, hi):
     return int(v)
 
 
+def _ids_arg(ids, dev):
+    """the ids of remove() / replace(): a tensor or array of integers (floats and bools: ValueError) -> flat int64
+    tensor on dev"""
+    if isinstance(ids, torch.Tensor):
+        if ids.dtype.is_floating_point or ids.dtype == torch.bool:
+            raise ValueError("ids must be integers")
+        return ids.reshape(-1).to(dev, torch.int64)
+    a = np.asarray(ids).reshape(-1)
+    if a.size and not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("ids must be integers")
+    return torch.from_numpy(a.astype(np.int64)).to(dev)
+
+
+def _u32_bits(t):
+    """int64 values in [0, 2^32) -> int32 tensor of their uint32 bit patterns, as the library takes ids"""
+    return ((t + 2**31) % 2**32 - 2**31).to(torch.int32)
+
+
 class QueryIndex:
     """sig: the indexed signature rows (int32 [n, P], or compact uint16 rows carried as torch.int16) on the device;
     norm2: int64 [n] (None: computed); b: bands (P % b == 0); table: the ops.PermTable the rows were drawn with
@@ -230,15 +248,7 @@ class QueryIndex:
             raise ValueError("this index holds no lists to update (none were given, or an append or remove without "
                              "update_lists=True dropped them)")
         dev = self.sig.device
-        if isinstance(ids, torch.Tensor):
-            if ids.dtype.is_floating_point or ids.dtype == torch.bool:
-                raise ValueError("ids must be integers")
-            t = ids.reshape(-1).to(dev, torch.int64)
-        else:
-            a = np.asarray(ids).reshape(-1)
-            if a.size and not np.issubdtype(a.dtype, np.integer):
-                raise ValueError("ids must be integers")
-            t = torch.from_numpy(a.astype(np.int64)).to(dev)
+        t = _ids_arg(ids, dev)
         n = self.n
         if update_lists and n >= 2**31:
             raise ValueError("lists are kept for fewer than 2^31 queries")
@@ -246,7 +256,7 @@ class QueryIndex:
             return torch.arange(n, dtype=torch.int64, device=dev)
         # ids beyond uint32 all become 2^32 - 1, which no index holds (n < 2^32 - 1): the map build flags them
         t = torch.where((t < 0) | (t > 0xFFFFFFFF), torch.full_like(t, 0xFFFFFFFF), t)
-        removed = ops.idmap_build(((t + 2**31) % 2**32 - 2**31).to(torch.int32), n)
+        removed = ops.idmap_build(_u32_bits(t), n)
         new_pos = removed.positions()
         left = n - removed.count
         pick = None
@@ -257,22 +267,8 @@ class QueryIndex:
         sig, norm2 = ops.rows_remove(self.sig, self.norm2, removed)
         if update_lists:
             self_ids = new_pos[pick.members().to(torch.int64) & 0xFFFFFFFF].to(torch.int32)
-            rows = self_ids.to(torch.int64)
-            psig, pnorm2 = sig[rows], norm2[rows]
-            step = max(1, (2**32 - 1) // self.b)      # the probe takes n_pick * b < 2^32 words per call
-            offs, idxs, millis, base = [torch.zeros((1,), dtype=torch.int64, device=dev)], [], [], 0
-            for q0 in range(0, pick.count, step):
-                q1 = min(pick.count, q0 + step)
-                raw, pws = ops.index_probe(keys, ids_, dirw, self.r, pick_keys[:, q0:q1].contiguous())
-                off, idx, milli, _ = ops.index_finish_rows(sig, norm2, psig[q0:q1], pnorm2[q0:q1].contiguous(), self.b,
-                                                           pws, raw, K, self_ids[q0:q1].contiguous())
-                offs.append(off[1:] + base)
-                idxs.append(idx)
-                millis.append(milli)
-                base += idx.numel()
-            e = torch.empty((0,), dtype=torch.int32, device=dev)
-            lists = ops.lists_remove(*self.lists, n, K, removed, pick, torch.cat(offs), torch.cat(idxs) if idxs else e,
-                                     torch.cat(millis) if millis else e, self_ids)
+            lists = ops.lists_remove(*self.lists, n, K, removed, pick,
+                                     *self._probe_indexed((keys, ids_, dirw), sig, norm2, self_ids, pick_keys, K), self_ids)
         self.keys, self.ids, self.dir = keys, ids_, dirw
         self.n = left
         self.sig, self.norm2 = sig, norm2
@@ -300,16 +296,7 @@ class QueryIndex:
         if update_lists and self.lists is None:
             raise ValueError("this index holds no lists to update (none were given, or a call without update_lists=True "
                              "dropped them)")
-        dev = self.sig.device
-        if isinstance(ids, torch.Tensor):
-            if ids.dtype.is_floating_point or ids.dtype == torch.bool:
-                raise ValueError("ids must be integers")
-            t = ids.reshape(-1).to(dev, torch.int64)
-        else:
-            a = np.asarray(ids).reshape(-1)
-            if a.size and not np.issubdtype(a.dtype, np.integer):
-                raise ValueError("ids must be integers")
-            t = torch.from_numpy(a.astype(np.int64)).to(dev)
+        t = _ids_arg(ids, self.sig.device)
         sig, norm2, keys = self._probe_rows(sig, norm2, keys)     # the sort below leaves copies: consumed freely
         n, m = self.n, sig.shape[0]
         if t.numel() != m:
@@ -332,7 +319,7 @@ class QueryIndex:
                 picked += self.last_picked
             self.last_picked = picked
             return
-        rids = ((t + 2**31) % 2**32 - 2**31).to(torch.int32)
+        rids = _u32_bits(t)
         replaced = ops.idmap_build(rids, n)
         pick = None
         if update_lists:
@@ -353,28 +340,46 @@ class QueryIndex:
         r_off, r_idx, r_milli, _, skeys = ops.index_finish_rows(self.sig, self.norm2, sig, norm2, self.b, pws, raw, K, rids,
                                                                 want_keys=True)
         pick_ids = pick.members()
-        rows = pick_ids.to(torch.int64) & 0xFFFFFFFF
-        psig, pnorm2 = self.sig[rows], self.norm2[rows]
-        offs, idxs, millis, base = [torch.zeros((1,), dtype=torch.int64, device=dev)], [], [], 0
-        for q0 in range(0, pick.count, step):
-            q1 = min(pick.count, q0 + step)
-            praw, ppws = ops.index_probe(nkeys, nids, ndir, self.r, pick_keys[:, q0:q1].contiguous())
-            off, idx, milli, _ = ops.index_finish_rows(self.sig, self.norm2, psig[q0:q1], pnorm2[q0:q1].contiguous(),
-                                                       self.b, ppws, praw, K, pick_ids[q0:q1].contiguous())
-            offs.append(off[1:] + base)
-            idxs.append(idx)
-            millis.append(milli)
-            base += idx.numel()
-        e = torch.empty((0,), dtype=torch.int32, device=dev)
         self.lists = ops.lists_replace(*self.lists, n, self.b, K, replaced, rids, pick, pick_ids, raw, skeys, r_off, r_idx,
-                                       r_milli, torch.cat(offs), torch.cat(idxs) if idxs else e,
-                                       torch.cat(millis) if millis else e)
+                                       r_milli, *self._probe_indexed((nkeys, nids, ndir), self.sig, self.norm2, pick_ids,
+                                                                     pick_keys, K))
         self.last_picked = pick.count
 
     def _replace_check_lists(self, t):
         """the stored lists' contract, checked before the first of several successive replacements writes anything"""
-        rids = ((t[:1] + 2**31) % 2**32 - 2**31).to(torch.int32)
-        ops.lists_remove_mark(self.lists[0], self.lists[1], self.n, self.lists_K, ops.idmap_build(rids, self.n))
+        ops.lists_remove_mark(self.lists[0], self.lists[1], self.n, self.lists_K,
+                              ops.idmap_build(_u32_bits(t[:1]), self.n))
+
+    def _chunked(self, m, probe):
+        """probe(q0, q1) -> (off, idx, milli, ...) of probe rows q0 .. q1-1, called for chunks of m * b < 2^32 words (what
+        the library takes per call; the results do not depend on the split) -> the same for all m rows, offsets stitched.
+        m = 0 gives the empty (off, idx, milli) of _probe_indexed; neighbours() answers m = 0 itself"""
+        step = max(1, (2**32 - 1) // self.b)
+        parts = [probe(q0, min(m, q0 + step)) for q0 in range(0, m, step)]
+        if len(parts) == 1:
+            return parts[0]
+        dev = self.sig.device
+        if not parts:
+            e = torch.empty((0,), dtype=torch.int32, device=dev)
+            return torch.zeros((1,), dtype=torch.int64, device=dev), e, e
+        offs, base = [torch.zeros((1,), dtype=torch.int64, device=dev)], 0
+        for p in parts:
+            offs.append(p[0][1:] + base)
+            base += p[1].numel()
+        return (torch.cat(offs),) + tuple(torch.cat([p[k] for p in parts]) for k in range(1, len(parts[0])))
+
+    def _probe_indexed(self, index, sig, norm2, self_ids, keys, K):
+        """the lists of chosen indexed rows: self_ids int32 [count] (uint32 bit patterns) = their ids in sig / norm2, keys
+        [b, count] = the keys they are indexed under, index = (keys, ids, dir) to probe -> (off, idx, milli), every row
+        kept out of its own list"""
+        rows = self_ids.to(torch.int64) & 0xFFFFFFFF
+        psig, pnorm2 = sig[rows], norm2[rows]
+
+        def probe(q0, q1):
+            raw, pws = ops.index_probe(*index, self.r, keys[:, q0:q1].contiguous())
+            return ops.index_finish_rows(sig, norm2, psig[q0:q1], pnorm2[q0:q1].contiguous(), self.b, pws, raw, K,
+                                         self_ids[q0:q1].contiguous())[:3]
+        return self._chunked(self_ids.numel(), probe)
 
     def set(self, ids, offsets, rows, update_lists=False):
         """signatures() of CSR answer sets, then replace(): answer set x becomes that of indexed query ids[x]"""
@@ -419,21 +424,7 @@ class QueryIndex:
             z = torch.zeros((1,), dtype=torch.int64, device=dev)
             e = torch.empty((0,), dtype=torch.int32, device=dev)
             return z, e, e.clone(), e.clone()
-        step = max(1, (2**32 - 1) // self.b)      # m * b < 2^32 per library call; results do not depend on the batch
-        parts = []
-        for q0 in range(0, m, step):
-            q1 = min(m, q0 + step)
-            (off, idx, milli, avail, _), _ = self._run(sig[q0:q1], norm2[q0:q1], keys[:, q0:q1].contiguous(), K)
-            parts.append((off, idx, milli, avail))
-        if len(parts) == 1:
-            return parts[0]
-        base = 0
-        offs = [torch.zeros((1,), dtype=torch.int64, device=dev)]
-        for off, idx, _, _ in parts:
-            offs.append(off[1:] + base)
-            base += idx.numel()
-        return (torch.cat(offs), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]),
-                torch.cat([p[3] for p in parts]))
+        return self._chunked(m, lambda q0, q1: self._run(sig[q0:q1], norm2[q0:q1], keys[:, q0:q1].contiguous(), K)[0][:4])
 
     def candidates(self, sig, norm2=None, keys=None):
         """every candidate of every new query, uncut: -> (query int64, id int64) device tensors, ordered by query,

@@ -1018,6 +1018,19 @@ def index_finish(sig, norm2, probe_sig, probe_norm2, b, probe_ws, raw, K, first_
     return off, idx[:cnt], milli[:cnt], avail, ws[:n_raw * 8].view(torch.int64)
 
 
+def _lists_count_fill(n, dev, count, fill):
+    """the tail the list updates share: count(total pointer) leaves the number of entries on the device (~0: the stored
+    lists break the contract), fill(cnt, src, dst, val pointers) writes them -> (src, dst, val) new int32 tensors"""
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(count(_ptr(total)))
+    cnt = int(total.item())
+    if cnt < 0:     # ~0: the count saw stored lists that break the contract
+        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
+    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
+    _lib.check(fill(cnt, *(_ptr(t) for t in out)))
+    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+
+
 def lists_update(src, dst, val, n, m, b, K, raw, select_keys, new_off, new_idx, new_milli):
     """The top-K lists (src, dst, val int32 COO: by src, value descending, dst ascending, at most K per src) of a run
     over queries 0 .. n-1, brought up to date with m appended queries n .. n+m-1 (csrc/lists.hip).  raw: index_probe's
@@ -1050,18 +1063,13 @@ def lists_update(src, dst, val, n, m, b, K, raw, select_keys, new_off, new_idx, 
     if m == 0:
         return src, dst, val
     ws = _ws(lib.qrlsh_lists_update_workspace_bytes(n, m, n_edges, n_raw), dev)
-    total = torch.zeros((1,), dtype=torch.int64, device=dev)
-    _lib.check(lib.qrlsh_lists_update_count(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, b, K, _ptr(raw),
-                                            _ptr(select_keys), n_raw, _ptr(new_off), _ptr(ws), ws.numel(), _ptr(total),
-                                            _stream()))
-    cnt = int(total.item())
-    if cnt < 0:     # ~0: the count saw stored lists that break the contract
-        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
-    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
-    _lib.check(lib.qrlsh_lists_update_fill(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, b, K, n_raw, _ptr(new_off),
-                                           _ptr(new_idx), _ptr(new_milli), _ptr(ws), ws.numel(), cnt, _ptr(out[0]),
-                                           _ptr(out[1]), _ptr(out[2]), _stream()))
-    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+    head = (_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, b, K)
+    return _lists_count_fill(
+        n, dev,
+        lambda total: lib.qrlsh_lists_update_count(*head, _ptr(raw), _ptr(select_keys), n_raw, _ptr(new_off), _ptr(ws),
+                                                   ws.numel(), total, _stream()),
+        lambda cnt, *out: lib.qrlsh_lists_update_fill(*head, n_raw, _ptr(new_off), _ptr(new_idx), _ptr(new_milli), _ptr(ws),
+                                                      ws.numel(), cnt, *out, _stream()))
 
 
 # ---------------------------------------------------------------------------
@@ -1216,18 +1224,12 @@ def lists_remove(src, dst, val, n, K, removed, pick, re_off, re_idx, re_milli, r
     if re_off.numel() != n_pick + 1 or re_self.numel() != n_pick or re_idx.numel() != re_milli.numel():
         raise ValueError("re_off must hold count + 1 offsets, re_self count ids, re_idx match re_milli")
     ws = _ws(lib.qrlsh_lists_remove_workspace_bytes(n, n_edges), dev)
-    total = torch.zeros((1,), dtype=torch.int64, device=dev)
-    _lib.check(lib.qrlsh_lists_remove_count(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, int(K), _ptr(removed.ws),
-                                            _ptr(pick.ws), _ptr(re_off), n_pick, _ptr(ws), ws.numel(), _ptr(total),
-                                            _stream()))
-    cnt = int(total.item())
-    if cnt < 0:
-        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
-    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
-    _lib.check(lib.qrlsh_lists_remove_fill(_ptr(src), _ptr(dst), _ptr(val), n_edges, n, int(K), _ptr(removed.ws),
-                                           _ptr(pick.ws), _ptr(re_off), _ptr(re_idx), _ptr(re_milli), _ptr(re_self), n_pick,
-                                           _ptr(ws), ws.numel(), cnt, _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _stream()))
-    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+    head = (_ptr(src), _ptr(dst), _ptr(val), n_edges, n, int(K), _ptr(removed.ws), _ptr(pick.ws), _ptr(re_off))
+    return _lists_count_fill(
+        n, dev,
+        lambda total: lib.qrlsh_lists_remove_count(*head, n_pick, _ptr(ws), ws.numel(), total, _stream()),
+        lambda cnt, *out: lib.qrlsh_lists_remove_fill(*head, _ptr(re_idx), _ptr(re_milli), _ptr(re_self), n_pick, _ptr(ws),
+                                                      ws.numel(), cnt, *out, _stream()))
 
 
 # ---------------------------------------------------------------------------
@@ -1284,7 +1286,7 @@ def index_replace(keys, ids, dirw, replaced, replaced_ids, new_keys, pick=None):
 
 def lists_replace(src, dst, val, n, b, K, replaced, replaced_ids, pick, pick_ids, raw, select_keys, r_off, r_idx, r_milli,
                   p_off, p_idx, p_milli):
-    """The stored top-K lists after the queries of `replaced` took new rows (csrc/replace.hip).  raw / select_keys /
+    """The stored top-K lists after the queries of `replaced` took new rows (csrc/lists.hip).  raw / select_keys /
     r_off / r_idx / r_milli: the probe of the batch against the new index (index_probe, index_finish_rows with
     self_ids = replaced_ids and want_keys); pick / pick_ids: lists_remove_mark's rows over `replaced` and their
     members(); p_off / p_idx / p_milli: their probe.  -> (src, dst, val): new tensors, element for element the lists
@@ -1305,19 +1307,15 @@ def lists_replace(src, dst, val, n, b, K, replaced, replaced_ids, pick, pick_ids
     if m * b >= 2**32:
         raise ValueError("a list replacement takes m * b < 2^32 per call")
     ws = _ws(lib.qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw), dev)
-    total = torch.zeros((1,), dtype=torch.int64, device=dev)
     head = (_ptr(src), _ptr(dst), _ptr(val), n_edges, n, m, int(b), int(K), _ptr(replaced.ws), _ptr(replaced_ids),
             _ptr(pick.ws), _ptr(pick_ids), n_pick)
-    _lib.check(lib.qrlsh_lists_replace_count(*head, _ptr(raw), _ptr(select_keys), n_raw, _ptr(r_off), _ptr(p_off), _ptr(ws),
-                                             ws.numel(), _ptr(total), _stream()))
-    cnt = int(total.item())
-    if cnt < 0:
-        raise ValueError("the stored lists are not ordered by src, or hold ids outside [0, %d)" % n)
-    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
-    _lib.check(lib.qrlsh_lists_replace_fill(*head, n_raw, _ptr(r_off), _ptr(r_idx), _ptr(r_milli), _ptr(p_off), _ptr(p_idx),
-                                            _ptr(p_milli), _ptr(ws), ws.numel(), cnt, _ptr(out[0]), _ptr(out[1]),
-                                            _ptr(out[2]), _stream()))
-    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+    return _lists_count_fill(
+        n, dev,
+        lambda total: lib.qrlsh_lists_replace_count(*head, _ptr(raw), _ptr(select_keys), n_raw, _ptr(r_off), _ptr(p_off),
+                                                    _ptr(ws), ws.numel(), total, _stream()),
+        lambda cnt, *out: lib.qrlsh_lists_replace_fill(*head, n_raw, _ptr(r_off), _ptr(r_idx), _ptr(r_milli), _ptr(p_off),
+                                                       _ptr(p_idx), _ptr(p_milli), _ptr(ws), ws.numel(), cnt, *out,
+                                                       _stream()))
 
 
 def predict_columns(ratings, off, idx, milli, query_weight, user_weight, default_mean, sum_order):

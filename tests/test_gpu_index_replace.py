@@ -67,6 +67,27 @@ def test_index_byte_for_byte_and_lists_element_for_element(crowded_refs, hi, com
     _assert_snapshot(qi, snap, "no ids")
 
 
+@pytest.mark.parametrize("compact", FORMATS)
+def test_stored_lists_that_end_on_a_tile_boundary(crowded_refs, compact):
+    """the merge's fill works the stored entries in steps of 1024 (4 per lane, 256 lanes), with dropped ids as without:
+    lists trimmed to 255, 256, 257 entries (the sparse shape) and to 1023, 1024, 1025 (the crowded one); a trimmed list
+    is still a list, its last row shorter and the rows behind it empty.  Rows are picked at every size"""
+    c = LC.CROWDED
+    N, b, K = c["N"], c["b"], c["K"]
+    case = PC.replacement_sets(N)["random40"]
+    for hi, sizes in ((40, (255, 256, 257)), (3, (1023, 1024, 1025))):
+        sig, stored = crowded_refs[hi]
+        assert len(stored[0]) > max(sizes)
+        ids, rows_new = case[0], PC.new_rows(sig, case)
+        for E in sizes:
+            cutl = tuple(a[:E] for a in stored)
+            want, picked = PC.restate_replace_lists(cutl, sig, ids, rows_new, b, K)
+            qi = _index(sig, b, K, compact, lists=cutl)
+            _replace(qi, ids, rows_new, compact, update_lists=True)
+            _assert_lists(qi.lists, want, (hi, E, compact))
+            assert qi.last_picked == len(picked) > 0, (hi, E, compact)
+
+
 # ------------------------------------------------------------------------------------------------ 2. band tiles
 def test_band_records_on_tile_boundaries():
     """the band kernels work tiles of REMOVE_TILE records; few distinct values, so runs of equal mix bits straddle the

@@ -39,7 +39,7 @@ from query_index_probe import HBM_PEAK, timed  # noqa: E402
 COPY_RATE = 6.29e12      # streaming copy, DESIGN section 4
 BANDS = ("index_remove_count", "index_remove_fill", "index_dir")
 ROWS = ("rows_remove",)
-LISTS = ("lists_remove_mark", "lists_remove_count", "lists_remove_fill", "lists_remove_fill_re", "lists_remove_total")
+LISTS = ("lists_remove_mark", "lists_remove_count", "lists_remove_fill", "lists_fill_probed", "lists_remove_total")
 REPROBE = ("index_probe_count", "index_probe_fill", "index_score", "index_select", "index_compact")
 
 

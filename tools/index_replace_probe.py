@@ -42,8 +42,8 @@ from query_index_probe import HBM_PEAK, timed  # noqa: E402
 COPY_RATE = 6.29e12      # streaming copy, DESIGN section 4
 BANDS = ("index_replace_count", "index_replace_rank", "index_replace_fill", "index_dir")
 ROWS = ("rows_replace",)
-LISTS = ("lists_remove_mark", "lists_replace_records", "lists_replace_kept", "lists_replace_len", "lists_old_rows",
-         "lists_rev_rows", "lists_replace_fill_old", "lists_replace_fill_rev", "lists_replace_fill_re", "lists_replace_total")
+LISTS = ("lists_remove_mark", "lists_records", "lists_kept", "lists_len", "lists_old_rows", "lists_rev_rows",
+         "lists_fill_old", "lists_fill_rev", "lists_fill_probed", "lists_total")
 PROBES = ("index_probe_count", "index_probe_fill", "index_score", "index_select", "index_compact")
 
 

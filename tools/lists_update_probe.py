@@ -34,7 +34,7 @@ import torch  # noqa: E402
 from query_index_probe import HBM_PEAK, timed  # noqa: E402
 
 COPY_RATE = 6.29e12      # streaming copy, DESIGN section 4
-FILL = ("lists_fill_old", "lists_fill_rev", "lists_fill_new")
+FILL = ("lists_fill_old", "lists_fill_rev", "lists_fill_probed")
 BOOK = ("lists_records", "lists_rev_rows", "lists_old_rows", "lists_len", "lists_total")
 
 
