@@ -53,7 +53,9 @@ def encode_queries(index, queries):
     out = np.full((nq, index.nfeat), -1, dtype=np.int32)
     for f in range(index.nfeat):
         vals, base = index.value_rows[f]
-        col = queries[:, f].astype(vals.dtype if vals.dtype.kind in "US" else object)
+        # the kind of the table's values at the width the QUERY values need: casting to the column's own fixed width
+        # would cut a longer (hence absent) value down to a prefix that may be present
+        col = queries[:, f].astype(vals.dtype.kind if vals.dtype.kind in "US" else object)
         want = col != ""
         if not want.any():
             continue

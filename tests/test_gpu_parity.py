@@ -1864,6 +1864,6 @@ def test_answer_sets_one_sweep_equals_count_then_fill():
         b_off, b_rows = answers.answer_sets(idx, qr, one_sweep=False)
         assert torch.equal(a_off, b_off) and torch.equal(a_rows, b_rows)
         sizes = np.diff(a_off.cpu().numpy())
-        assert (sizes.max() <= 64) == two or not two     # first case exercises the compact path, the others the refill
+        assert (sizes.max() <= 64) == two                # first case exercises the compact path, the others the refill
         roff, rrows = O.answer_sets(cols, q[:300])
         assert np.array_equal(a_off.cpu().numpy()[:301], roff) and np.array_equal(a_rows.cpu().numpy()[:roff[-1]], rrows)
