@@ -790,6 +790,47 @@ int qrlsh_evaluate_cells(const int32_t *ratings, int64_t nu, int64_t nq, const i
                          const int32_t *cell_user, const int32_t *cell_query, const int32_t *cell_truth, int64_t m,
                          int32_t *pred_out, int64_t *totals_out, uint32_t *flags_out, void *stream);
 
+/* ---- ranking evaluation: precision, recall and NDCG at k of the served lists against held-out cells ---------------
+ * Hold-out only (a rated cell is not ranked while it is rated).  `train` int32 [nu][nq] = the matrix with the test cells
+ * zeroed, `truth` = the full matrix, same shape.  A TEST cell of user u: train[u][j] == 0 && truth[u][j] != 0; it is
+ * RELEVANT when truth[u][j] >= relevant (int32 >= 1).  The list of request x is qrlsh_recommend_users(train, ...)'s: the
+ * eligible cells (train == 0 and a non-zero prediction), value descending then column ascending, cut at k; a test cell
+ * is 0 in `train`, so the serving arithmetic over `train` is its hold-out prediction.  Lists, weights, sum_order, users,
+ * m, k, lo and slices as qrlsh_recommend_users takes them (slices > 0 also sets the sweep's column slices).
+ * candidates: QRLSH_RANK_ALL -- every unrated cell of `train` is a candidate (the list the user would be shown; cells
+ *   the truth does not rate count as not relevant, and `known` tells how many listed cells the truth rates);
+ *   QRLSH_RANK_HELDOUT -- only the test cells are (a cell of `train` that `truth` does not rate is no candidate).
+ * gain int64 [k], gain_prefix int64 [k + 1] (device; gain_prefix[n] = gain[0] + .. + gain[n - 1]): the caller's DCG
+ *   gains per list position.  The library computes no logarithm; DCG is an exact integer.  Gains must be >= 0 (flag bit
+ *   3 otherwise) and m x gain_prefix[k] must fit int64 (the caller's to ensure).
+ * idx_out / val_out int32 [m][k], avail_out int32 [m]: the served lists, as qrlsh_recommend_users writes them.
+ * per_user_out int64 [m][8], one 64-byte line per request: word 0 listed = min(k, avail); 1 hits = listed cells that
+ *   are relevant; 2 known = listed cells the truth rates; 3 the 1-based rank of the first hit (0 = none); 4 dcg = the sum
+ *   of gain[p] over the hit positions p; 5 relevant test cells of the user; 6 test cells of the user (both include cells
+ *   whose prediction is 0: the model cannot reach them, recall must not forget them); 7 avail.  A request with a user id
+ *   outside [0, nu): words 0-6 = 0, word 7 = avail = -1, nothing added to the totals, flag bit 2.
+ * totals_out int64 [16]: words 0-7 = the column sums of the lines of the requests served; 8 = requests served; 9 =
+ *   requests with >= 1 relevant test cell; 10 = requests with >= 1 hit; 11 = the sum of the ideal DCG
+ *   gain_prefix[min(k, relevant test cells)]; 12-15 = 0.  64-bit integer atomics: exact in any order.
+ * *flags_out (device uint32, required) = 0, or bits 0-2 as qrlsh_recommend_users raises them, bit 3: a negative gain.
+ * workspace: qrlsh_evaluate_ranking_workspace_bytes(m, nq, k, slices) bytes, 16-byte aligned (0 for arguments outside
+ *   the limits).  One sweep workgroup per (column slice, request) in qrlsh_predict_users' two row forms; with
+ *   QRLSH_RANK_HELDOUT the test cells of a slice are queued in LDS and predicted 1024 at a time, so the work follows the
+ *   test cells, not nq.
+ * Limits: those of qrlsh_recommend_users (ku <= 64, lists <= 64, 1 <= k <= 1024, nq < 2^31, m <= 2^24), relevant >= 1,
+ * candidates one of the two (QRLSH_EINVAL / QRLSH_EUNSUPPORTED / QRLSH_EWORKSPACE as there, all before any device work).
+ * m = 0: totals and flags 0.  No allocation, one stream, no read-back. */
+#define QRLSH_RANK_ALL 0
+#define QRLSH_RANK_HELDOUT 1
+size_t qrlsh_evaluate_ranking_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices);
+int qrlsh_evaluate_ranking(const int32_t *train, const int32_t *truth, int64_t nu, int64_t nq, const int64_t *q_off,
+                           const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val,
+                           int32_t ku, double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                           const int32_t *users, int64_t m, int32_t k, int32_t relevant, int32_t candidates, int32_t lo,
+                           int32_t slices, const int64_t *gain, const int64_t *gain_prefix, int32_t *idx_out,
+                           int32_t *val_out, int32_t *avail_out, int64_t *per_user_out, int64_t *totals_out,
+                           uint32_t *flags_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- N4: user similarity, the part after the clustering ----------------------------------------
  * Recommender.compute_userSimilarities, recommender.py:263-288: inside a cluster every user's row is centred on
  * the mean of its non-zero ratings IN AN INTEGER ARRAY (the centred values are truncated toward zero), then

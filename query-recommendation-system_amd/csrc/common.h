@@ -67,6 +67,17 @@ int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_
                      const int32_t *users, int64_t m, bool eligible, int32_t *out, int64_t ostride, uint32_t *flags_out,
                      hipStream_t st);
 
+// the top-k selection over compact eligible-mode rows (recommend.hip): row x of `rows` (qr_select_compact_stride(nq)
+// words apart, 16-byte aligned) is request x, a cell is eligible when it is not 0.  _plan makes the checks of k, m, nq and
+// slices that qrlsh_recommend_users makes (no device work) and gives the bytes of the rows and of the selection's own
+// workspace (0 in the rows form); qr_select_compact then ranks the rows over `select_ws` of that size.
+int64_t qr_select_compact_stride(int64_t nq);
+int qr_select_compact_plan(const char *who, int64_t m, int64_t nq, int32_t k, int32_t slices, size_t *rows_bytes,
+                           size_t *select_bytes);
+int qr_select_compact(const char *who, const int32_t *rows, int64_t nu, int64_t nq, const int32_t *users, int64_t m,
+                      int32_t k, int32_t lo, int32_t slices, int32_t *idx_out, int32_t *val_out, int32_t *avail_out,
+                      void *select_ws, hipStream_t st);
+
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t qr_al16(size_t x) { return (x + 15) / 16 * 16; }
 // bits that hold every id below n (at least 1, at most 32)

@@ -528,6 +528,33 @@ QRLSH_EXPORT int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pre
                           avail_out, static_cast<uint8_t *>(workspace), static_cast<hipStream_t>(stream));
 }
 
+// ---- the selection over compact rows for other files (common.h): qrlsh_evaluate_ranking's sweep in predict.hip writes
+// the rows, rc_select<true> ranks them -- the path qrlsh_recommend_users takes after qr_predict_users
+int64_t qr_select_compact_stride(int64_t nq) { return rc_compact_stride(nq); }
+
+int qr_select_compact_plan(const char *who, int64_t m, int64_t nq, int32_t k, int32_t slices, size_t *rows_bytes,
+                           size_t *select_bytes) {
+  QR_CHECK_ARG(k >= 1 && k <= QRLSH_RECOMMEND_MAX_K, "%s: k=%d outside 1..%d", who, k, QRLSH_RECOMMEND_MAX_K);
+  QR_CHECK_ARG(m >= 0 && nq >= 0 && nq <= 2147483647ll, "%s: bad sizes m=%lld nq=%lld", who, (long long)m, (long long)nq);
+  QR_CHECK_ARG(slices >= 0 && slices <= RC_MAXS, "%s: slices=%d outside 0..%d", who, slices, RC_MAXS);
+  const int64_t S = rc_slices(m, nq, slices);
+  if (m > RC_MAX_GROUPS || m * (S > 0 ? S : 1) > RC_MAX_GROUPS) {
+    qrlsh_set_error("%s: m=%lld x slices=%lld above the %lld workgroups served", who, (long long)m, (long long)S,
+                    (long long)RC_MAX_GROUPS);
+    return QRLSH_EUNSUPPORTED;
+  }
+  *rows_bytes = rc_round((size_t)m * (size_t)rc_compact_stride(nq) * sizeof(int32_t));
+  *select_bytes = S > 0 && m > 0 && nq > 0 ? rc_layout(m, k, S).total : 0;
+  return QRLSH_OK;
+}
+
+int qr_select_compact(const char *who, const int32_t *rows, int64_t nu, int64_t nq, const int32_t *users, int64_t m,
+                      int32_t k, int32_t lo, int32_t slices, int32_t *idx_out, int32_t *val_out, int32_t *avail_out,
+                      void *select_ws, hipStream_t st) {
+  return rc_select<true>(who, nullptr, rows, rc_compact_stride(nq), nu, nq, users, m, k, lo, rc_slices(m, nq, slices),
+                         idx_out, val_out, avail_out, static_cast<uint8_t *>(select_ws), st);
+}
+
 // workspace: [compact eligible-mode rows: m x round_up(nq, 4) int32][the selection's workspace (slice form)]
 QRLSH_EXPORT size_t qrlsh_recommend_users_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices) {
   if (m <= 0 || nq <= 0 || k < 1 || k > QRLSH_RECOMMEND_MAX_K || slices < 0 || slices > RC_MAXS) return 0;

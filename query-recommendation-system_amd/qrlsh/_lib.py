@@ -27,6 +27,8 @@ SORT_HOST = 16
 SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
+RANK_ALL = 0
+RANK_HELDOUT = 1
 INDEX_MAX_K = 256
 USER_LISTS_MAX_K = 64     # the prediction kernels' ku (csrc/userlists.hip UL_MAXK)
 ROWS_ADD = 0
@@ -167,6 +169,10 @@ SIGNATURES = {
     "qrlsh_evaluate_cells": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_double, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
                                             _vp]),
+    "qrlsh_evaluate_ranking_workspace_bytes": (_sz, [_i64, _i64, _i32, _i32]),
+    "qrlsh_evaluate_ranking": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                              ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _i32, _i32, _i32, _i32,
+                                              _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_center_rows": (ctypes.c_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "qrlsh_user_gram_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_user_gram": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -789,6 +789,44 @@ class Recommender:
         return sweep(train, lists[0], lists[1], lists[2], user_sim, truth=truth, fraction=fraction, seed=seed,
                      sum_order=sum_order, **weights)
 
+    # ---- and are the lists it serves any good: precision / recall / NDCG at k on held-out cells (qrlsh.ranking) -----
+    def evaluate_ranking(self, k, relevant, fraction=0.1, seed=0, candidates="all", users=None, sum_order=None,
+                         user_sim=None):
+        """Score the top-k lists of the model served now against held-out ratings, on the device ->
+        qrlsh.RankingEvaluation (.precision, .recall, .ndcg, .hit_rate, .known_share, .macro(), .per_user, .totals,
+        .idx / .val / .avail).  The split and the user side are those of evaluate(holdout=True): about `fraction` of
+        the rated cells, chosen by `seed`, are zeroed in a train copy on the device; the user side is built over that
+        copy (a user index in step: UserLists.build over it with the index's labels and K; otherwise user_sim, default
+        the compute_userSimilarities route over it); the query side comes from the live lists as they stand
+        (ValueError when there are none).  Each requested user (default: all) is served its list from the train copy,
+        and the list is held to self.ratings: a held-out cell rated >= relevant is a hit.  candidates: "all" ranks
+        every unrated cell of the train copy, "heldout" the held-out cells only.  Neither self.ratings nor user_index
+        is modified.  ValueError for a bad k, relevant, candidates, fraction, sum_order or user id."""
+        from qrlsh.evaluate import keep_word, holdout as train_copy
+        from qrlsh.ranking import check_arguments, evaluate_ranking as score
+        from qrlsh.userlists import UserLists
+        keep_word(fraction)
+        check_arguments(k, relevant, candidates)
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        sum_order = self.sum_order if sum_order is None else sum_order
+        if sum_order not in ("pairwise", "sequential"):
+            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        ui = self._user_index_in_step() if user_sim is None else None
+        truth = ui.ratings if ui is not None else torch.from_numpy(
+            np.ascontiguousarray(self.ratings, dtype=np.int32)).to(self.device)
+        train, _ = train_copy(truth, fraction, seed=seed, device=self.device)
+        if ui is not None:
+            user_sim = UserLists.build(train, ui.user_labels(), K=ui.K, device=self.device).as_user_sims()
+        elif user_sim is None:
+            user_sim = self._user_similarities_over(ops.to_host(train))
+        return score(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, users=users,
+                     candidates=candidates, sum_order=sum_order, query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT,
+                     default_mean=DEFAULT_MEAN, device=self.device)
+
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
         """Interactive top-k prompt of recommender.py:345-381 (`ask` is injectable for tests)."""
         pred = predictions.to_numpy()
