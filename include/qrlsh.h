@@ -790,6 +790,46 @@ int qrlsh_evaluate_cells(const int32_t *ratings, int64_t nu, int64_t nq, const i
                          const int32_t *cell_user, const int32_t *cell_query, const int32_t *cell_truth, int64_t m,
                          int32_t *pred_out, int64_t *totals_out, uint32_t *flags_out, void *stream);
 
+/* ---- tuning: qrlsh_evaluate's cells under a grid of list cuts and blend weights, in one sweep -----------------------
+ * qrlsh_evaluate_grid evaluates the cells qrlsh_evaluate evaluates (truth != 0 and kept by the sample rule) under
+ *     S = ncq x ncu x nw settings,    setting s = (cq * ncu + cu) * nw + w:
+ * query lists cut at q_cuts[cq], user lists cut at u_cuts[cu], blended with weights[w] = (query_weight, user_weight,
+ * default_mean).  Arguments up to `ku` and sum_order / seed / keep are qrlsh_evaluate's; q_cuts (device int32 [ncq]),
+ * u_cuts (device int32 [ncu]) and weights (device double [nw][3]) are read on the device.
+ * A cut c >= 0 means "the first min(len, c) entries of the list as stored": 0 switches that side off (the ablation
+ *   "user side only" / "query side only"), c >= len is the whole list.  Every stored list is ordered score descending,
+ *   ties by id ascending, so that prefix is the list a run with K = c would have stored: the figures under a cut are the
+ *   figures of that run.  The two sides of a cell do not depend on the weights: a cell costs one query side per query cut
+ *   and one user side per user cut (each with its own accumulation: the pairwise order depends on the length), and per
+ *   setting only the blend, the rounding and the error.  The arithmetic is qrlsh_evaluate's, one copy of it; a list
+ *   entry naming the cell's own column or row reads 0; both sum orders.
+ * Output: 8 exact int64 words per setting.  totals_out int64 [S][8]; per_user_out NULL or int64 [nu][S][8]:
+ *     word 0 = n, the cells with a non-zero prediction        word 4 = missed (prediction 0; in none of the sums)
+ *     word 1 = sum err   (err = prediction - truth)           word 5 = cells evaluated (the same for every setting)
+ *     word 2 = sum |err|                                      word 6 = n predicted from the query side only
+ *     word 3 = sum err^2                                      word 7 = n predicted from the user side only
+ *   In qrlsh_evaluate's 16 words e[]: word k = e[k] + e[4 + k] + e[8 + k] (k = 0 .. 3), word 4 = e[12], word 5 = e[13],
+ *   word 6 = e[0], word 7 = e[4].  One setting with the whole lists gives qrlsh_evaluate's result through that mapping.
+ * *flags_out (device uint32, required) = 0, or bit 0 / bit 1 exactly as qrlsh_evaluate raises them (a stored list longer
+ *   than 64, a list index outside [0, nq) -- whatever the cuts), bit 3: a negative cut (it reads as 0).  A flagged result
+ *   is not to be used; nothing is read out of bounds.
+ * One workgroup per (column slice, user) as qrlsh_evaluate; the sums of a workgroup are kept in an LDS table [S][8] and
+ * go to the workspace (qrlsh_evaluate_grid_workspace_bytes(nu, nq, S), 8-byte aligned), two small kernels add them: no
+ * global atomics, the result does not depend on the launch order.
+ * Limits (QRLSH_EINVAL otherwise, before any device work): 1 <= ncq, ncu <= QRLSH_GRID_MAX_CUTS, nw >= 1,
+ * S <= QRLSH_GRID_MAX_SETTINGS, and qrlsh_evaluate's: ku <= 64, nq < 2^31, nu < 2^31, keep <= 2^32.  QRLSH_EWORKSPACE for
+ * a workspace that is missing or short.  Exact under qrlsh_evaluate's conditions.  nu = 0 or nq = 0: all outputs 0 (the
+ * cuts are still checked).  No allocation, one stream, no read-back. */
+#define QRLSH_GRID_MAX_CUTS 4
+#define QRLSH_GRID_MAX_SETTINGS 128
+size_t qrlsh_evaluate_grid_workspace_bytes(int64_t nu, int64_t nq, int32_t settings);
+int qrlsh_evaluate_grid(const int32_t *ratings, const int32_t *truth, int64_t nu, int64_t nq, const int64_t *q_off,
+                        const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val,
+                        int32_t ku, const int32_t *q_cuts, int32_t ncq, const int32_t *u_cuts, int32_t ncu,
+                        const double *weights, int32_t nw, int32_t sum_order, uint64_t seed, uint64_t keep,
+                        int64_t *per_user_out, int64_t *totals_out, uint32_t *flags_out, void *workspace,
+                        size_t workspace_bytes, void *stream);
+
 /* ---- ranking evaluation: precision, recall and NDCG at k of the served lists against held-out cells ---------------
  * Hold-out only (a rated cell is not ranked while it is rated).  `train` int32 [nu][nq] = the matrix with the test cells
  * zeroed, `truth` = the full matrix, same shape.  A TEST cell of user u: train[u][j] == 0 && truth[u][j] != 0; it is

@@ -805,6 +805,50 @@ template <int THREADS> __device__ static inline long long ev_block_sum(EvalStats
 // decided by the index, not by the rating).  rating_at(q) = ratings[i][q] (LDS bytes or the row in memory).  A list
 // longer than PRED_MAXK is not walked and an index outside the matrix is not gathered: the prediction is 0 (flagged by
 // predict_users_check_kernel).  -> the prediction; branch as EvalStats::add takes it.
+// The two sides and the blend are separate so that the grid sweep (evaluate_grid_kernel) computes a side once per list
+// cut and the blend once per setting, with the arithmetic of this one copy.
+// ev_query_side: the query side over the first n entries of the list that starts at q_idx[lo] (n <= PRED_MAXK).
+template <typename RatingAt>
+__device__ static inline double ev_query_side(int64_t nq, int64_t j, int64_t lo, int n,
+                                              const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli,
+                                              bool sequential, RatingAt rating_at, bool &outside) {
+  return weighted_average(
+      n, sequential,
+      [&](int k) {
+        const int32_t q = q_idx[lo + k];
+        if ((uint32_t)q >= (uint32_t)nq) {  // flagged (bit 1); never gathered
+          outside = true;
+          return (int32_t)0;
+        }
+        return q == j ? (int32_t)0 : rating_at(q);
+      },
+      [&](int k) { return (double)q_milli[lo + k] / 1000.0; });
+}
+
+// ev_user_side: the user side over the first mu entries of user i's list (ui / uv)
+__device__ static inline double ev_user_side(const int32_t *__restrict__ ratings, int64_t nu, int64_t nq, int64_t i,
+                                             int64_t j, const int32_t *__restrict__ ui, const double *__restrict__ uv,
+                                             int mu, bool sequential) {
+  return weighted_average(
+      mu, sequential,
+      [&](int k) {
+        const int64_t u = ui[k];
+        return (u >= nu || u == i) ? (int32_t)0 : ratings[u * nq + j];   // u >= 0 for k < mu
+      },
+      [&](int k) { return uv[k]; });
+}
+
+// ev_blend: recommender.py:324-331 in the reference's operand order, before rounding; branch as EvalStats::add takes it
+__device__ static inline double ev_blend(double qp, double up, double qw, double uw, double dmean, int &branch) {
+  double r;
+  if (up == 0.0 && qp == 0.0) r = 0.0;
+  else if (up == 0.0) r = qp * (qw + (uw * 0.5)) + dmean * (uw * 0.5);
+  else if (qp == 0.0) r = up * (uw + (qw * 0.5)) + dmean * (qw * 0.5);
+  else r = qp * qw + up * uw;
+  branch = up == 0.0 ? 0 : (qp == 0.0 ? 1 : 2);
+  return r;
+}
+
 template <typename RatingAt>
 __device__ static inline int32_t ev_predict(const int32_t *__restrict__ ratings, int64_t nu, int64_t nq, int64_t i, int64_t j,
                                             const int64_t *__restrict__ q_off, const int32_t *__restrict__ q_idx,
@@ -815,30 +859,9 @@ __device__ static inline int32_t ev_predict(const int32_t *__restrict__ ratings,
   const int64_t lo = q_off[j], n64 = q_off[j + 1] - lo;
   if (n64 < 0 || n64 > PRED_MAXK) return 0;  // flagged (bit 0); never walked
   bool outside = false;
-  const double qp = weighted_average(
-      (int)n64, sequential,
-      [&](int k) {
-        const int32_t q = q_idx[lo + k];
-        if ((uint32_t)q >= (uint32_t)nq) {  // flagged (bit 1); never gathered
-          outside = true;
-          return (int32_t)0;
-        }
-        return q == j ? (int32_t)0 : rating_at(q);
-      },
-      [&](int k) { return (double)q_milli[lo + k] / 1000.0; });
-  const double up = weighted_average(
-      mu, sequential,
-      [&](int k) {
-        const int64_t u = ui[k];
-        return (u >= nu || u == i) ? (int32_t)0 : ratings[u * nq + j];   // u >= 0 for k < mu
-      },
-      [&](int k) { return uv[k]; });
-  double r;
-  if (up == 0.0 && qp == 0.0) r = 0.0;
-  else if (up == 0.0) r = qp * (qw + (uw * 0.5)) + dmean * (uw * 0.5);
-  else if (qp == 0.0) r = up * (uw + (qw * 0.5)) + dmean * (qw * 0.5);
-  else r = qp * qw + up * uw;
-  branch = up == 0.0 ? 0 : (qp == 0.0 ? 1 : 2);
+  const double qp = ev_query_side(nq, j, lo, (int)n64, q_idx, q_milli, sequential, rating_at, outside);
+  const double up = ev_user_side(ratings, nu, nq, i, j, ui, uv, mu, sequential);
+  const double r = ev_blend(qp, up, qw, uw, dmean, branch);
   return outside ? 0 : (int32_t)rint(r);
 }
 
@@ -1030,6 +1053,292 @@ QRLSH_EXPORT int qrlsh_evaluate(const int32_t *ratings, const int32_t *truth, in
   QR_LAUNCH("evaluate_totals", evaluate_totals_kernel, dim3(1), dim3(1024), 0, st, (const long long *)gpart, groups,
             reinterpret_cast<long long *>(totals_out));
   QR_LAUNCH_CHECK("qrlsh_evaluate");
+  return QRLSH_OK;
+}
+
+// ---- the grid: qrlsh_evaluate's cells under S = ncq x ncu x nw settings in one sweep (qrlsh_evaluate_grid) ----
+// qp and up of a cell do not depend on the weights, and a stored list is ordered (score descending, id ascending), so its
+// first c entries are the list a run with K = c would have stored.  evaluate_kernel's sweep therefore serves a whole
+// grid: per cell one query side per query cut and one user side per user cut (the pairwise order depends on the length,
+// so each cut has its own accumulation -- at most 4 + 4, never one per setting), then a uniform loop over the settings
+// that blends, rounds, wave-reduces the error sums and adds them to an LDS table [S][8] of int64.  The table of a
+// workgroup goes to part[user][slice][S][8]; evaluate_grid_finish_kernel / evaluate_grid_totals_kernel add the slices and
+// the users (no global atomics, no order).
+// Table words while the sweep runs: 0-3 = n, sum err, sum |err|, sum err^2 over the non-zero predictions, 6 / 7 = n of
+// the query-only / user-only branch; words 4 (missed = cells - n) and 5 (cells, the same for every setting) are filled
+// in when the table is written out.
+constexpr int EG_WORDS = 8;
+constexpr int EGF_USERS = 16;   // users per workgroup of the finish kernel
+
+__device__ static inline double eg_pick(const double (&a)[QRLSH_GRID_MAX_CUTS], int c) {   // c uniform; no indexed array
+  return c == 0 ? a[0] : (c == 1 ? a[1] : (c == 2 ? a[2] : a[3]));
+}
+
+__device__ static inline long long eg_wave_sum(long long v) {
+#pragma unroll
+  for (int d = WAVE / 2; d >= 1; d >>= 1) v += __shfl_xor(v, d, WAVE);
+  return v;
+}
+
+// flag bit 3: a negative cut (threads 0 .. 7 of one workgroup look at one cut each)
+__device__ static inline void eg_check_cuts(int t, const int32_t *__restrict__ q_cuts, int ncq,
+                                            const int32_t *__restrict__ u_cuts, int ncu, uint32_t *__restrict__ flags) {
+  bool bad = false;
+  if (t < QRLSH_GRID_MAX_CUTS) bad = t < ncq && q_cuts[t] < 0;
+  else if (t < 2 * QRLSH_GRID_MAX_CUTS) bad = t - QRLSH_GRID_MAX_CUTS < ncu && u_cuts[t - QRLSH_GRID_MAX_CUTS] < 0;
+  if (bad) atomicOr(flags, 8u);
+}
+
+__global__ __launch_bounds__(64) void evaluate_grid_cuts_kernel(const int32_t *__restrict__ q_cuts, int ncq,
+                                                                const int32_t *__restrict__ u_cuts, int ncu,
+                                                                uint32_t *__restrict__ flags) {
+  eg_check_cuts(threadIdx.x, q_cuts, ncq, u_cuts, ncu, flags);
+}
+
+__global__ __launch_bounds__(EV_THREADS) void evaluate_grid_kernel(
+    const int32_t *__restrict__ ratings, const int32_t *__restrict__ truth, int64_t nu, int64_t nq,
+    const int64_t *__restrict__ q_off, const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli,
+    const int32_t *__restrict__ u_idx, const double *__restrict__ u_val, int ku, const int32_t *__restrict__ q_cuts,
+    int ncq, const int32_t *__restrict__ u_cuts, int ncu, const double *__restrict__ weights, int nw, int sequential,
+    uint64_t seed, uint64_t keep, int64_t slices, long long *__restrict__ part, uint32_t *__restrict__ flags) {
+  __shared__ uint8_t lrow[PR_MAXQ];
+  __shared__ int32_t queue_j[EV_QUEUE];
+  __shared__ int32_t queue_v[EV_QUEUE];
+  __shared__ unsigned long long table[QRLSH_GRID_MAX_SETTINGS * EG_WORDS];
+  __shared__ unsigned long long cells_all;
+  __shared__ uint32_t wsum[EV_THREADS / WAVE];
+  __shared__ int wide;
+  const int64_t s = blockIdx.x / nu, i = blockIdx.x - s * nu;
+  const int t = threadIdx.x;
+  const int words = ncq * ncu * nw * EG_WORDS;   // <= 1024
+  const int64_t per = (nq + slices - 1) / slices;
+  const int64_t j0 = s * per, j1 = min(nq, j0 + per);
+  const int32_t *row = ratings + i * nq;
+  const int32_t *trow = truth + i * nq;
+  if (blockIdx.x == 0) eg_check_cuts(t, q_cuts, ncq, u_cuts, ncu, flags);
+  if (t < words) table[t] = 0;
+  if (t == 0) {
+    cells_all = 0;
+    wide = 0;
+  }
+  __syncthreads();
+  bool in_lds = false;
+  if (nq <= PR_MAXQ) {  // uniform
+    bool bad = false;
+    for (int64_t j = t; j < nq; j += EV_THREADS) {
+      const int32_t v = row[j];
+      bad |= (v < 0) | (v > 255);
+      lrow[j] = (uint8_t)v;
+    }
+    if (bad) wide = 1;
+    __syncthreads();
+    in_lds = wide == 0;
+  }
+  const int32_t *ui = u_idx + i * ku;
+  const double *uv = u_val + i * ku;
+  int mu = 0;
+  while (mu < ku && ui[mu] >= 0) ++mu;  // uniform: the user's own neighbour list
+  // the cuts (uniform; a negative one is flagged and reads as 0) and the user list's length under each
+  int qc[QRLSH_GRID_MAX_CUTS], um[QRLSH_GRID_MAX_CUTS];
+#pragma unroll
+  for (int c = 0; c < QRLSH_GRID_MAX_CUTS; ++c) {
+    qc[c] = c < ncq ? max(q_cuts[c], 0) : 0;
+    um[c] = c < ncu ? min(mu, max(u_cuts[c], 0)) : 0;
+  }
+  const bool seq = sequential != 0;
+  unsigned long long cells = 0;  // of this wave (uniform)
+  // one cell per active lane: its sides under every cut, then every setting; all lanes of a wave arrive together
+  auto one = [&](uint32_t slot, bool active) {
+    const unsigned long long act = __ballot(active);
+    if (act == 0) return;  // wave-uniform
+    cells += (unsigned long long)__popcll(act);
+    double qp[QRLSH_GRID_MAX_CUTS] = {0.0, 0.0, 0.0, 0.0}, up[QRLSH_GRID_MAX_CUTS] = {0.0, 0.0, 0.0, 0.0};
+    int32_t tv = 0;
+    if (active) {
+      const int64_t j = queue_j[slot & (EV_QUEUE - 1)];
+      tv = queue_v[slot & (EV_QUEUE - 1)];
+      const int64_t lo = q_off[j], n64 = q_off[j + 1] - lo;
+      if (n64 >= 0 && n64 <= PRED_MAXK) {  // else flagged (bit 0), never walked: every setting misses the cell
+        bool outside = false;
+        int last = -1;
+#pragma unroll
+        for (int c = 0; c < QRLSH_GRID_MAX_CUTS; ++c) {
+          if (c < ncq) {
+            const int n = min((int)n64, qc[c]);
+            if (c > 0 && n == last) qp[c] = qp[c - 1];  // the list is no longer than either cut: the same prefix
+            else
+              qp[c] = ev_query_side(
+                  nq, j, lo, n, q_idx, q_milli, seq, [&](int32_t q) { return in_lds ? (int32_t)lrow[q] : row[q]; },
+                  outside);
+            last = n;
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < QRLSH_GRID_MAX_CUTS; ++c) {
+          if (c < ncu) {
+            if (c > 0 && um[c] == um[c - 1]) up[c] = up[c - 1];  // uniform
+            else up[c] = ev_user_side(ratings, nu, nq, i, j, ui, uv, um[c], seq);
+          }
+        }
+        if (outside) {  // flagged (bit 1): every setting misses the cell
+#pragma unroll
+          for (int c = 0; c < QRLSH_GRID_MAX_CUTS; ++c) qp[c] = up[c] = 0.0;
+        }
+      }
+    }
+    const int lane = t & (WAVE - 1);
+    int sidx = 0;
+    for (int cq = 0; cq < ncq; ++cq) {
+      const double qpc = eg_pick(qp, cq);
+      for (int cu = 0; cu < ncu; ++cu) {
+        const double upc = eg_pick(up, cu);
+        for (int w = 0; w < nw; ++w, ++sidx) {
+          int branch;
+          const double r = ev_blend(qpc, upc, weights[3 * w], weights[3 * w + 1], weights[3 * w + 2], branch);
+          const int32_t pred = (int32_t)rint(r);   // 0 on the lanes without a cell: both sides are 0 there
+          const bool hit = pred != 0;
+          const unsigned long long hits = __ballot(hit);
+          if (hits == 0) continue;  // wave-uniform: nothing to add
+          const long long e = hit ? (long long)pred - (long long)tv : 0;
+          const long long se = eg_wave_sum(e), sa = eg_wave_sum(e < 0 ? -e : e), ss = eg_wave_sum(e * e);
+          const long long qn = __popcll(__ballot(hit && branch == 0)), un = __popcll(__ballot(hit && branch == 1));
+          // lanes 0 .. 5 add one word each: a single LDS atomic instruction per setting and wave
+          const long long v = lane == 0 ? (long long)__popcll(hits)
+                                        : (lane == 1 ? se : (lane == 2 ? sa : (lane == 3 ? ss : (lane == 4 ? qn : un))));
+          if (lane < 6 && v != 0)
+            atomicAdd(&table[sidx * EG_WORDS + (lane < 4 ? lane : lane + 2)], (unsigned long long)v);
+        }
+      }
+    }
+  };
+  uint32_t head = 0, tail = 0;  // uniform
+  for (int64_t base = j0; base < j1; base += EV_THREADS) {
+    const int64_t j = base + t;
+    int32_t tv = 0;
+    if (j < j1) tv = trow[j];
+    const bool take = tv != 0 && ev_kept(seed, keep, i, j);
+    uint32_t total;
+    const uint32_t pos = block_excl_scan<EV_THREADS>(take ? 1u : 0u, wsum, total);
+    if (take) {
+      queue_j[(tail + pos) & (EV_QUEUE - 1)] = (int32_t)j;
+      queue_v[(tail + pos) & (EV_QUEUE - 1)] = tv;
+    }
+    tail += total;
+    if (tail - head >= (uint32_t)EV_THREADS) {  // uniform
+      __syncthreads();
+      one(head + t, true);
+      head += EV_THREADS;
+    }
+    // the next scan's first barrier stands between these reads of the queue and the writes that follow it
+  }
+  __syncthreads();
+  one(head + t, (uint32_t)t < tail - head);
+  if ((t & (WAVE - 1)) == 0 && cells != 0) atomicAdd(&cells_all, cells);
+  __syncthreads();
+  if (t < words) {
+    const int word = t & (EG_WORDS - 1);
+    unsigned long long v = table[t];
+    if (word == 4) v = cells_all - table[t - 4];
+    if (word == 5) v = cells_all;
+    part[(i * slices + s) * words + t] = (long long)v;
+  }
+}
+
+// per_user_out[u][.] (when wanted) = the sum over the slices of part[u][.][.]; one workgroup per EGF_USERS users, one
+// thread per word of the table, whose sums over its users go to gpart[workgroup][words]
+__global__ __launch_bounds__(1024) void evaluate_grid_finish_kernel(const long long *__restrict__ part, int64_t nu,
+                                                                    int64_t slices, int words,
+                                                                    long long *__restrict__ per_user_out,
+                                                                    long long *__restrict__ gpart) {
+  const int t = threadIdx.x;
+  if (t >= words) return;
+  const int64_t u0 = (int64_t)blockIdx.x * EGF_USERS, u1 = min(nu, u0 + EGF_USERS);
+  long long col = 0;
+  for (int64_t u = u0; u < u1; ++u) {
+    long long sum = 0;
+    for (int64_t s = 0; s < slices; ++s) sum += part[(u * slices + s) * words + t];
+    if (per_user_out) per_user_out[u * words + t] = sum;
+    col += sum;
+  }
+  gpart[(int64_t)blockIdx.x * words + t] = col;
+}
+
+// totals_out[.] = the sum of gpart[.][.] (one workgroup)
+__global__ __launch_bounds__(1024) void evaluate_grid_totals_kernel(const long long *__restrict__ gpart, int64_t groups,
+                                                                    int words, long long *__restrict__ totals_out) {
+  const int t = threadIdx.x;
+  if (t >= words) return;
+  long long sum = 0;
+  for (int64_t g = 0; g < groups; ++g) sum += gpart[g * words + t];
+  totals_out[t] = sum;
+}
+
+// workspace: [part: nu x slices x S x 8 int64][gpart: ceil(nu / 16) x S x 8 int64]
+QRLSH_EXPORT size_t qrlsh_evaluate_grid_workspace_bytes(int64_t nu, int64_t nq, int32_t settings) {
+  if (nu <= 0 || nq <= 0 || settings <= 0 || settings > QRLSH_GRID_MAX_SETTINGS) return 0;
+  return ((size_t)nu * (size_t)ev_slices(nu, nq) + (size_t)ceil_div64(nu, EGF_USERS)) * (size_t)settings * EG_WORDS *
+         sizeof(long long);
+}
+
+QRLSH_EXPORT int qrlsh_evaluate_grid(const int32_t *ratings, const int32_t *truth, int64_t nu, int64_t nq,
+                                     const int64_t *q_off, const int32_t *q_idx, const int32_t *q_milli,
+                                     const int32_t *u_idx, const double *u_val, int32_t ku, const int32_t *q_cuts,
+                                     int32_t ncq, const int32_t *u_cuts, int32_t ncu, const double *weights, int32_t nw,
+                                     int32_t sum_order, uint64_t seed, uint64_t keep, int64_t *per_user_out,
+                                     int64_t *totals_out, uint32_t *flags_out, void *workspace, size_t workspace_bytes,
+                                     void *stream) {
+  const char *who = "qrlsh_evaluate_grid";
+  const int rc = ev_check_lists(who, nu, nq, ku, sum_order, keep);
+  if (rc != QRLSH_OK) return rc;
+  QR_CHECK_ARG(ncq >= 1 && ncq <= QRLSH_GRID_MAX_CUTS && ncu >= 1 && ncu <= QRLSH_GRID_MAX_CUTS && nw >= 1 &&
+                   (int64_t)ncq * ncu * nw <= QRLSH_GRID_MAX_SETTINGS,
+               "%s: bad grid ncq=%d ncu=%d (1 .. %d each) nw=%d (settings 1 .. %d)", who, ncq, ncu, QRLSH_GRID_MAX_CUTS, nw,
+               QRLSH_GRID_MAX_SETTINGS);
+  QR_CHECK_ARG(flags_out && totals_out && q_cuts && u_cuts && weights,
+               "%s: flags_out, totals_out, q_cuts, u_cuts and weights are required", who);
+  const bool empty = nu == 0 || nq == 0;
+  QR_CHECK_ARG(empty || (ratings && truth && q_off && (ku == 0 || (u_idx && u_val))), "%s: null pointer", who);
+  const int settings = ncq * ncu * nw, words = settings * EG_WORDS;
+  const size_t need = qrlsh_evaluate_grid_workspace_bytes(nu, nq, settings);
+  if (!empty) {
+    QR_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: the workspace must be 8-byte aligned", who);
+    if (!workspace || workspace_bytes < need) {
+      qrlsh_set_error("%s: needs %zu workspace bytes, got %zu", who, need, workspace ? workspace_bytes : 0);
+      return QRLSH_EWORKSPACE;
+    }
+  }
+  const int64_t slices = ev_slices(nu, nq), groups = ceil_div64(nu, EGF_USERS);
+  if (!empty && nu * slices > 2147483647ll) {
+    qrlsh_set_error("%s: nu=%lld x %lld slices above 2^31 - 1 workgroups", who, (long long)nu, (long long)slices);
+    return QRLSH_EUNSUPPORTED;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
+      (empty && hipMemsetAsync(totals_out, 0, (size_t)words * sizeof(int64_t), st) != hipSuccess) ||
+      (empty && nu > 0 && per_user_out &&
+       hipMemsetAsync(per_user_out, 0, (size_t)nu * words * sizeof(int64_t), st) != hipSuccess)) {
+    qrlsh_set_error("%s: hipMemsetAsync failed", who);
+    return QRLSH_EHIP;
+  }
+  if (empty) {
+    QR_LAUNCH("evaluate_grid_cuts", evaluate_grid_cuts_kernel, dim3(1), dim3(64), 0, st, q_cuts, (int)ncq, u_cuts,
+              (int)ncu, flags_out);
+    QR_LAUNCH_CHECK(who);
+    return QRLSH_OK;
+  }
+  long long *part = static_cast<long long *>(workspace);
+  long long *gpart = part + (size_t)nu * slices * words;
+  const unsigned fin_threads = (unsigned)((words + WAVE - 1) / WAVE * WAVE);
+  QR_LAUNCH("evaluate_check", predict_users_check_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, q_off,
+            q_idx, nq, (const int32_t *)nullptr, (int64_t)0, nu, flags_out);   // the lists' two flags
+  QR_LAUNCH("evaluate_grid", evaluate_grid_kernel, dim3((unsigned)(nu * slices)), dim3(EV_THREADS), 0, st, ratings, truth,
+            nu, nq, q_off, q_idx, q_milli, u_idx, u_val, (int)ku, q_cuts, (int)ncq, u_cuts, (int)ncu, weights, (int)nw,
+            (int)(sum_order == QRLSH_SUM_SEQUENTIAL), seed, keep, slices, part, flags_out);
+  QR_LAUNCH("evaluate_grid_finish", evaluate_grid_finish_kernel, dim3((unsigned)groups), dim3(fin_threads), 0, st,
+            (const long long *)part, nu, slices, words, reinterpret_cast<long long *>(per_user_out), gpart);
+  QR_LAUNCH("evaluate_grid_totals", evaluate_grid_totals_kernel, dim3(1), dim3(fin_threads), 0, st,
+            (const long long *)gpart, groups, words, reinterpret_cast<long long *>(totals_out));
+  QR_LAUNCH_CHECK(who);
   return QRLSH_OK;
 }
 

@@ -68,6 +68,9 @@ class Recommender:
 
     cluster_on_device = True   # StandardScaler + PCA of compute_userSimilarities on the device (False: scikit-learn on the host)
     sum_order = "sequential"   # order of weighted_average's two np.sum calls, see compute_scores
+    query_weight = QUERY_WEIGHT   # the blend every serving call uses (recommender.py:32-34 of the reference); tune(apply=True)
+    user_weight = USER_WEIGHT     # sets the three on the instance
+    default_mean = DEFAULT_MEAN
 
     def init(self, users, queries, queriesIDs, dataset, ratings):
         """recommender.py:51-64.  Takes what main.py:23-85 passes -- `datatable` Frames (anything Frame-like:
@@ -499,7 +502,8 @@ class Recommender:
             raise ValueError("sum_order must be 'pairwise' or 'sequential'")
         qi, sig, norm2, keys = self._new_query_rows(queries)
         off, idx, milli, _ = qi.neighbours(sig, norm2, keys)
-        return qi.predict_columns(self.ratings, off, idx, milli, sum_order, QUERY_WEIGHT, USER_WEIGHT, DEFAULT_MEAN)
+        return qi.predict_columns(self.ratings, off, idx, milli, sum_order, self.query_weight, self.user_weight,
+                                  self.default_mean)
 
     def predict_new_queries(self, queries, sum_order=None):
         """DataFrame usersIDs x new queries (0 .. m-1): the prediction compute_scores would give each user's cell of a
@@ -660,8 +664,8 @@ class Recommender:
         # "pairwise" is numpy's own np.sum order, what the reference does with @jit removed -- the run the committed
         # fixtures were captured from (numba is not installable here), on which both orders give the same matrices;
         # parity with the numba build itself stays unpinned.
-        final = predict.fill_predictions(self.ratings, lists[0], lists[1], lists[2], user_sim, QUERY_WEIGHT, USER_WEIGHT,
-                                         DEFAULT_MEAN, self.device, sum_order=self.sum_order)
+        final = predict.fill_predictions(self.ratings, lists[0], lists[1], lists[2], user_sim, self.query_weight,
+                                         self.user_weight, self.default_mean, self.device, sum_order=self.sum_order)
         final = ops.to_host(final)
         self._log(str(round(time.time() - t0, 3)) + "s for weighted averages")
         finalPredictions = pd.DataFrame(final, columns=self.queriesIDs, index=self.usersIDs).astype(int)
@@ -720,8 +724,9 @@ class Recommender:
             users = np.asarray(users)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
         idx, val, avail = rec.for_users(ratings, lists[0], lists[1], lists[2], user_sim, users, int(k),
-                                        sum_order=sum_order, query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT,
-                                        default_mean=DEFAULT_MEAN, device=self.device)
+                                        sum_order=sum_order, query_weight=self.query_weight,
+                                        user_weight=self.user_weight, default_mean=self.default_mean,
+                                        device=self.device)
         idx, val, avail = ops.to_host(idx), ops.to_host(val), ops.to_host(avail)
         ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
         out = {}
@@ -738,8 +743,8 @@ class Recommender:
         if users is not None and not isinstance(users, torch.Tensor):
             users = np.asarray(users)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
-        rows = predict.predict_users(ratings, lists[0], lists[1], lists[2], user_sim, users, QUERY_WEIGHT, USER_WEIGHT,
-                                     DEFAULT_MEAN, self.device, sum_order=sum_order)
+        rows = predict.predict_users(ratings, lists[0], lists[1], lists[2], user_sim, users, self.query_weight,
+                                     self.user_weight, self.default_mean, self.device, sum_order=sum_order)
         ids = np.arange(self.usersIDs.size) if users is None else np.asarray(ops.to_host(users), dtype=np.int64)
         return pd.DataFrame(ops.to_host(rows), index=self.usersIDs[ids], columns=self.queriesIDs).astype(int)
 
@@ -760,12 +765,12 @@ class Recommender:
         cells=(users, queries, values): an explicit test set instead of the sample (0-based positions; every triplet
         counts), predicted from the ratings as they stand as if each cell were unrated.
         ValueError for a fraction outside [0, 1], a bad sum_order, or cells together with holdout."""
-        from qrlsh.evaluate import keep_word, holdout as train_copy, evaluate as sweep, evaluate_cells
-        from qrlsh.userlists import UserLists
+        from qrlsh.evaluate import keep_word, evaluate as sweep, evaluate_cells
         keep_word(fraction)
         if cells is not None and holdout:
             raise ValueError("cells name their own test set: holdout=True does not apply")
-        weights = dict(query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT, default_mean=DEFAULT_MEAN, device=self.device)
+        weights = dict(query_weight=self.query_weight, user_weight=self.user_weight, default_mean=self.default_mean,
+                       device=self.device)
         if not holdout:
             lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, None)
             if cells is not None:
@@ -774,10 +779,24 @@ class Recommender:
                                       sum_order=sum_order, **weights)
             return sweep(ratings, lists[0], lists[1], lists[2], user_sim, fraction=fraction, seed=seed,
                          sum_order=sum_order, **weights)
+        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
+        return sweep(train, lists[0], lists[1], lists[2], user_sim, truth=truth, fraction=fraction, seed=seed,
+                     sum_order=sum_order, **weights)
+
+    def _holdout_inputs(self, fraction, seed, sum_order, user_sim):
+        """The hold-out split evaluate(holdout=True), evaluate_ranking and tune share: the live lists (ValueError when
+        there are none), the checked sum_order, a train copy on the device with the kept rated cells zeroed, the full
+        matrix, and the user side over the train copy (a user index in step: UserLists.build over it with the index's
+        labels and K; otherwise user_sim, default the compute_userSimilarities route over it).  Nothing of self is
+        modified.  -> (lists, sum_order, train, truth, user_sim)"""
+        from qrlsh.evaluate import holdout as train_copy
+        from qrlsh.userlists import UserLists
         lists = self._live_lists()
         if lists is None:
             raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
         sum_order = self.sum_order if sum_order is None else sum_order
+        if sum_order not in ("pairwise", "sequential"):
+            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
         ui = self._user_index_in_step() if user_sim is None else None
         truth = ui.ratings if ui is not None else torch.from_numpy(
             np.ascontiguousarray(self.ratings, dtype=np.int32)).to(self.device)
@@ -786,8 +805,37 @@ class Recommender:
             user_sim = UserLists.build(train, ui.user_labels(), K=ui.K, device=self.device).as_user_sims()
         elif user_sim is None:
             user_sim = self._user_similarities_over(ops.to_host(train))
-        return sweep(train, lists[0], lists[1], lists[2], user_sim, truth=truth, fraction=fraction, seed=seed,
-                     sum_order=sum_order, **weights)
+        return lists, sum_order, train, truth, user_sim
+
+    # ---- which blend serves best: evaluate()'s figures over a grid of settings in one sweep (qrlsh.tune) -----------
+    def tune(self, weights, q_cuts=None, u_cuts=None, fraction=0.1, seed=0, holdout=True, sum_order=None, user_sim=None,
+             metric="rmse", min_coverage=0.0, apply=False):
+        """evaluate()'s error for every setting of a grid, from one sweep of the device -> qrlsh.GridEvaluation
+        (.totals, .n, .mae, .rmse, .bias, .coverage, .best()).  weights: (W, 3) rows (query_weight, user_weight,
+        default_mean); q_cuts / u_cuts: up to 4 list lengths each (default: the whole lists; 0 switches a side off) --
+        the first `cut` entries of a stored list are the list a run with that K would have stored.
+        The split and the user side are those of evaluate(holdout=...): holdout=True builds the user lists once over
+        the train copy (they do not depend on the weights); holdout=False is leave-one-out with the lists held fixed.
+        apply=True sets query_weight, user_weight and default_mean to the best triple by `metric` among the settings
+        with coverage >= min_coverage (GridEvaluation.best), so every serving call uses it from then on.  CUTS ARE
+        REPORTED, NEVER APPLIED: the K of the live lists is fixed by the run.  Neither self.ratings, the lists nor
+        user_index is modified.  ValueError as qrlsh.evaluate_grid raises it, and from best() when apply=True."""
+        from qrlsh.evaluate import keep_word
+        from qrlsh.tune import evaluate_grid, METRICS
+        keep_word(fraction)
+        if metric not in METRICS:
+            raise ValueError("metric must be one of %s" % (METRICS,))
+        if holdout:
+            lists, sum_order, ratings, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
+        else:
+            lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, None)
+            truth = None
+        grid = evaluate_grid(ratings, lists[0], lists[1], lists[2], user_sim, weights, q_cuts=q_cuts, u_cuts=u_cuts,
+                             truth=truth, fraction=fraction, seed=seed, sum_order=sum_order, device=self.device)
+        if apply:
+            _, _, (qw, uw, dm), _ = grid.best(metric, min_coverage)
+            self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
+        return grid
 
     # ---- and are the lists it serves any good: precision / recall / NDCG at k on held-out cells (qrlsh.ranking) -----
     def evaluate_ranking(self, k, relevant, fraction=0.1, seed=0, candidates="all", users=None, sum_order=None,
@@ -802,30 +850,16 @@ class Recommender:
         and the list is held to self.ratings: a held-out cell rated >= relevant is a hit.  candidates: "all" ranks
         every unrated cell of the train copy, "heldout" the held-out cells only.  Neither self.ratings nor user_index
         is modified.  ValueError for a bad k, relevant, candidates, fraction, sum_order or user id."""
-        from qrlsh.evaluate import keep_word, holdout as train_copy
+        from qrlsh.evaluate import keep_word
         from qrlsh.ranking import check_arguments, evaluate_ranking as score
-        from qrlsh.userlists import UserLists
         keep_word(fraction)
         check_arguments(k, relevant, candidates)
-        lists = self._live_lists()
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
-        sum_order = self.sum_order if sum_order is None else sum_order
-        if sum_order not in ("pairwise", "sequential"):
-            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
         if users is not None and not isinstance(users, torch.Tensor):
             users = np.asarray(users)
-        ui = self._user_index_in_step() if user_sim is None else None
-        truth = ui.ratings if ui is not None else torch.from_numpy(
-            np.ascontiguousarray(self.ratings, dtype=np.int32)).to(self.device)
-        train, _ = train_copy(truth, fraction, seed=seed, device=self.device)
-        if ui is not None:
-            user_sim = UserLists.build(train, ui.user_labels(), K=ui.K, device=self.device).as_user_sims()
-        elif user_sim is None:
-            user_sim = self._user_similarities_over(ops.to_host(train))
+        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
         return score(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, users=users,
-                     candidates=candidates, sum_order=sum_order, query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT,
-                     default_mean=DEFAULT_MEAN, device=self.device)
+                     candidates=candidates, sum_order=sum_order, query_weight=self.query_weight,
+                     user_weight=self.user_weight, default_mean=self.default_mean, device=self.device)
 
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
         """Interactive top-k prompt of recommender.py:345-381 (`ask` is injectable for tests)."""
