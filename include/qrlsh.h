@@ -871,6 +871,49 @@ int qrlsh_evaluate_ranking(const int32_t *train, const int32_t *truth, int64_t n
                            int32_t *val_out, int32_t *avail_out, int64_t *per_user_out, int64_t *totals_out,
                            uint32_t *flags_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- tuning for the order of the list: qrlsh_evaluate_ranking's words under a grid of settings, in one sweep ---------
+ * qrlsh_evaluate_ranking_grid computes, for every setting s = (cq * ncu + cu) * nw + w of qrlsh_evaluate_grid's grid
+ * (query lists cut at q_cuts[cq], user lists cut at u_cuts[cu], blended with weights[w]; device arrays, read on the
+ * device), the eight per-request words and the sixteen totals that qrlsh_evaluate_ranking(..., candidates =
+ * QRLSH_RANK_HELDOUT) returns for that setting over lists cut on the host -- word for word.  train, truth, the lists,
+ * ku, sum_order, users, m, k, relevant, gain and gain_prefix as qrlsh_evaluate_ranking takes them; the cuts and the
+ * weights as qrlsh_evaluate_grid takes them.
+ *   The list of (request x, setting s): the test cells of x whose prediction under s is not 0, prediction descending,
+ *   then column ascending, cut at k.  Both sides of a test cell are computed once per cut (identical prefixes share one
+ *   accumulation), never once per setting; per setting there is the blend, the rounding, an exact selection of the k-th
+ *   largest prediction over the whole int32 range (weights may be negative or large: there is no value window) with ties
+ *   resolved toward the lowest column, and the exact position of every listed relevant cell.  No list and no (nu, nq)
+ *   matrix is written per setting.
+ * per_request_out NULL or int64 [m][S][8]: listed = min(k, avail), hits, known (= listed in this mode), the 1-based rank
+ *   of the first hit (0 = none), dcg, relevant test cells, test cells, avail.  A request with a user id outside [0, nu):
+ *   zeros and avail -1, nothing added to the totals, flag bit 2.
+ * totals_out int64 [S][16]: qrlsh_evaluate_ranking's totals per setting (12-15 = 0).  Added through the workspace by two
+ *   small kernels: no global atomics, exact in any launch order.
+ * cells: the capacity of the record arrays = an upper bound of the test cells of the m requests (a request named twice
+ *   counts twice).  The library counts them first (one pass over the rows) and places every column slice's records by a
+ *   scan of the counts, so the workspace follows the number of test cells, never nq x S.  *cells_out (device int64, may
+ *   be NULL) = the count.  More test cells than `cells`: flag bit 4, nothing is written out of bounds, the result reads
+ *   as if no request had a test cell and is not to be used.
+ * *flags_out (device uint32, required) = 0, or bit 0 a stored list longer than 64, bit 1 a neighbour index outside
+ *   [0, nq), bit 2 a user id outside [0, nu), bit 3 a negative gain or a negative cut (the cut reads as 0), bit 4 above.
+ * workspace: qrlsh_evaluate_ranking_grid_workspace_bytes(m, nq, ncq, ncu, S, cells) bytes, 16-byte aligned (0 for
+ *   arguments outside the limits): 8 + 8 (ncq + ncu) bytes per test cell, 64 bytes per (request, setting), and the
+ *   slices' offsets.
+ * Limits (QRLSH_EINVAL / QRLSH_EUNSUPPORTED / QRLSH_EWORKSPACE, all before any device work): 1 <= k <= 1024, ku <= 64,
+ * lists <= 64 (flag), 1 <= ncq, ncu <= QRLSH_GRID_MAX_CUTS, nw >= 1, S <= QRLSH_GRID_MAX_SETTINGS, nq < 2^31,
+ * m <= 2^24 and m x S < 2^31, relevant >= 1, m x gain_prefix[k] < 2^63 (the caller's to ensure); exact while every
+ * |prediction| < 2^31.  m = 0: totals, *cells_out and flags 0.  Not here: QRLSH_RANK_ALL, the lists themselves, graded
+ * relevance.  No allocation, one stream, no read-back. */
+size_t qrlsh_evaluate_ranking_grid_workspace_bytes(int64_t m, int64_t nq, int32_t ncq, int32_t ncu, int32_t settings,
+                                                   int64_t cells);
+int qrlsh_evaluate_ranking_grid(const int32_t *train, const int32_t *truth, int64_t nu, int64_t nq, const int64_t *q_off,
+                                const int32_t *q_idx, const int32_t *q_milli, const int32_t *u_idx, const double *u_val,
+                                int32_t ku, const int32_t *q_cuts, int32_t ncq, const int32_t *u_cuts, int32_t ncu,
+                                const double *weights, int32_t nw, int32_t sum_order, const int32_t *users, int64_t m,
+                                int32_t k, int32_t relevant, const int64_t *gain, const int64_t *gain_prefix,
+                                int64_t cells, int64_t *per_request_out, int64_t *totals_out, int64_t *cells_out,
+                                uint32_t *flags_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- N4: user similarity, the part after the clustering ----------------------------------------
  * Recommender.compute_userSimilarities, recommender.py:263-288: inside a cluster every user's row is centred on
  * the mean of its non-zero ratings IN AN INTEGER ARRAY (the centred values are truncated toward zero), then

@@ -41,6 +41,7 @@ from .predict import predict_users, user_lists  # noqa: F401
 from .evaluate import holdout, evaluate, evaluate_cells, Evaluation  # noqa: F401
 from .ranking import dcg_gains, evaluate_ranking, RankingEvaluation  # noqa: F401
 from .tune import evaluate_grid, GridEvaluation  # noqa: F401
+from .rankgrid import evaluate_ranking_grid, RankingGridEvaluation  # noqa: F401
 from .index import QueryIndex  # noqa: F401
 from .userlists import UserLists  # noqa: F401
 from .table import LiveTable, TableDictionary  # noqa: F401

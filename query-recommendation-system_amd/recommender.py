@@ -861,6 +861,36 @@ class Recommender:
                      candidates=candidates, sum_order=sum_order, query_weight=self.query_weight,
                      user_weight=self.user_weight, default_mean=self.default_mean, device=self.device)
 
+    # ---- which blend serves the best lists: evaluate_ranking's figures over a grid in one sweep (qrlsh.rankgrid) -----
+    def tune_ranking(self, k, relevant, weights, q_cuts=None, u_cuts=None, fraction=0.1, seed=0, users=None,
+                     sum_order=None, user_sim=None, metric="ndcg", min_recall=0.0, apply=False):
+        """evaluate_ranking(candidates="heldout")'s figures for every setting of a grid, from one sweep of the device ->
+        qrlsh.RankingGridEvaluation (.totals, .precision, .recall, .ndcg, .hit_rate, .best()).  RMSE (tune) moves with
+        the default-mean term of the blend, not with the order of the list; these are the figures for the order.
+        weights, q_cuts, u_cuts: as tune takes them; k, relevant, users: as evaluate_ranking takes them.  The split and
+        the user side are those of evaluate_ranking: _holdout_inputs, built once (they do not depend on the setting).
+        apply=True sets query_weight, user_weight and default_mean to the best triple by `metric` ('ndcg', 'precision',
+        'recall', 'hit_rate') among the settings with recall >= min_recall (RankingGridEvaluation.best), so every
+        serving call uses it from then on.  CUTS ARE REPORTED, NEVER APPLIED.  Neither self.ratings, the lists nor
+        user_index is modified.  ValueError as qrlsh.evaluate_ranking_grid raises it, and from best() when apply=True."""
+        from qrlsh.evaluate import keep_word
+        from qrlsh.ranking import check_arguments
+        from qrlsh.rankgrid import evaluate_ranking_grid, METRICS
+        keep_word(fraction)
+        check_arguments(k, relevant, "heldout")
+        if metric not in METRICS:
+            raise ValueError("metric must be one of %s" % (METRICS,))
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
+        grid = evaluate_ranking_grid(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, weights,
+                                     q_cuts=q_cuts, u_cuts=u_cuts, users=users, sum_order=sum_order,
+                                     device=self.device)
+        if apply:
+            _, _, (qw, uw, dm), _ = grid.best(metric, min_recall)
+            self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
+        return grid
+
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
         """Interactive top-k prompt of recommender.py:345-381 (`ask` is injectable for tests)."""
         pred = predictions.to_numpy()
