@@ -533,8 +533,9 @@ int qrlsh_index_probe_finish_indexed(const void *sig, const int64_t *norm2, int6
  *     neighbours (milli, n + x) for every kept raw word of probe query x that names i; a new id is larger than every
  *     old id and loses ties; a row that did not exist may appear;
  *   new row n + x:  the finish's list of x.
- * K is held fixed: a stored row was cut at K and cannot be regrown, so the result is that of a run with the SAME K over
- * the n + m queries, not with the K a fresh run would default to.  Splitting a batch into successive appends-with-update
+ * K is held fixed: a stored row was cut at K, so the result is that of a run with the SAME K over the n + m queries, not
+ * with the K a fresh run would default to.  (The list length is changed on purpose with qrlsh_lists_cut_* and
+ * qrlsh_lists_regrow_mark below: a cut row is regrown by probing it again against the index.)  Splitting a batch into successive appends-with-update
  * gives the same lists; n = 0 (from empty lists), m > n and m = 0 (the stored lists, unchanged) are served.
  * count: the reverse records (one per kept raw word with id < n: id << 11 | (1000 - milli), payload x) are sorted with
  *   qrlsh_sort_u64 over bits [0, 11 + bits(n)), rows get their stored and reverse extents, a scan their output offsets;
@@ -625,6 +626,43 @@ int qrlsh_lists_remove_fill(const int32_t *src, const int32_t *dst, const int32_
                             const int32_t *re_idx, const int32_t *re_milli, const uint32_t *re_self, int64_t n_pick,
                             void *workspace, size_t workspace_bytes, int64_t total, int32_t *src_out, int32_t *dst_out,
                             int32_t *val_out, void *stream);
+
+/* ---- changing the list length of stored lists (csrc/listcut.hip) -------------------------------------------------
+ * Stored lists at list length K_old become, element for element, the lists of a run over the same rows at K_new.
+ *   cut (K_new < K_old): the first K_new entries of a stored row are the row a run with K_new would have stored, so
+ *     entry i survives exactly when i < K_new or src[i - K_new] != src[i]: a stream compaction with a predicate on src
+ *     alone.  count: one workgroup per tile of 2048 entries reads src (16-byte loads; the predicate looks back across
+ *     the tile's start through a halo in LDS), one scan follows; *total_out (device uint64; the one read-back) = the
+ *     surviving entries -- or ~0 when the stored lists break the contract (src not ascending or outside [0, n), a row
+ *     longer than K_old); nothing may be filled then.  K_new >= K_old keeps every entry (the total is n_edges).
+ *     fill follows a count on the same workspace and arguments: src again, dst / val (16-byte loads) of the vectors that
+ *     hold a survivor, every output written once; exactly `total` entries.  No atomic on a shared cursor, no serial walk
+ *     of a row, no scratch.  src / dst / val must be 16-byte aligned.  A null or short workspace is QRLSH_EINVAL.
+ *     workspace: qrlsh_lists_cut_workspace_bytes(n_edges).
+ *   regrow (K_new > K_old): a stored row with fewer than K_old entries was never cut and is already its list at K_new;
+ *     a row of exactly K_old entries may be missing candidates and is probed again against the unchanged index.
+ *     mark: entry i is the head of such a row iff it is a run head and src[i + K_old - 1] == src[i]; the rows enter
+ *       pick_map_out (qrlsh_idmap_workspace_bytes(n) bytes); out2 (device uint64 [2]) = {picked rows, 0 -- or ~0 on a
+ *       contract break as above; nothing may follow then}.
+ *     pick keys: the key of every record of keys / ids [b][n] whose id is in pick_map goes to
+ *       pick_keys_out[band][rank_pick(id)] -- the probe keys of the picked rows in qrlsh_idmap_list order, from the
+ *       index itself (an index built on caller keys behaves the same); what qrlsh_index_remove writes on its way,
+ *       without a removal.  n_pick == 0 returns at once.
+ *     The caller probes the picked rows (qrlsh_index_probe_*, qrlsh_index_probe_finish_rows with K_new) and puts the
+ *     probed lists in their place with qrlsh_lists_remove_count / _fill over an EMPTY removed map (a zeroed
+ *     qrlsh_idmap_workspace_bytes(n) buffer) and K = K_new: unpicked rows are copied as stored, picked rows take their
+ *     probed lists.
+ * Limits: 1 <= K_old, K_new <= QRLSH_INDEX_MAX_K, n < 2^31, n_edges < 2^31.  No allocation, one stream. */
+size_t qrlsh_lists_cut_workspace_bytes(int64_t n_edges);
+int qrlsh_lists_cut_count(const int32_t *src, int64_t n_edges, int64_t n, int32_t K_old, int32_t K_new, void *workspace,
+                          size_t workspace_bytes, uint64_t *total_out, void *stream);
+int qrlsh_lists_cut_fill(const int32_t *src, const int32_t *dst, const int32_t *val, int64_t n_edges, int64_t n,
+                         int32_t K_old, int32_t K_new, const void *workspace, size_t workspace_bytes, int64_t total,
+                         int32_t *src_out, int32_t *dst_out, int32_t *val_out, void *stream);
+int qrlsh_lists_regrow_mark(const int32_t *src, int64_t n_edges, int64_t n, int32_t K_old, void *pick_map_out,
+                            uint64_t *out2, void *stream);
+int qrlsh_index_pick_keys(const uint64_t *keys, const uint32_t *ids, int64_t n, int32_t b, const void *pick_map,
+                          int64_t n_pick, uint64_t *pick_keys_out, void *stream);
 
 /* ---- replacing queries of a built index in place (csrc/replace.hip; the lists: the merge of csrc/lists.hip) -------------
  * m distinct ids R of 0 .. n-1 get new rows: batch row x goes to id replaced_ids[x] (device uint32 [m], ASCENDING;

@@ -142,6 +142,11 @@ SIGNATURES = {
     "qrlsh_lists_remove_count": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _sz, _vp, _vp]),
     "qrlsh_lists_remove_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz,
                                                _i64, _vp, _vp, _vp, _vp]),
+    "qrlsh_lists_cut_workspace_bytes": (_sz, [_i64]),
+    "qrlsh_lists_cut_count": (ctypes.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "qrlsh_lists_cut_fill": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _sz, _i64, _vp, _vp, _vp, _vp]),
+    "qrlsh_lists_regrow_mark": (ctypes.c_int, [_vp, _i64, _i64, _i32, _vp, _vp, _vp]),
+    "qrlsh_index_pick_keys": (ctypes.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp]),
     "qrlsh_rows_replace": (ctypes.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "qrlsh_index_replace_workspace_bytes": (_sz, [_i64, _i64, _i32]),
     "qrlsh_index_replace": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp,

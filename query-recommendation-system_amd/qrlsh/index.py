@@ -63,9 +63,11 @@ class QueryIndex:
     filter -- every candidate is checked against the rows); K: default list length (round(log_1.5 n); a defaulted K
     follows n when queries are appended, a given K stays); lists: the run's top-K lists (src, dst, val) int32 COO as
     pipeline.query_similarities returns them (by src, value descending, dst ascending), held in .lists by reference --
-    never written: an update puts new tensors there.  Their list length is the K of the constructor and stays that:
-    stored rows were cut at it and cannot be regrown, so appends with update_lists=True keep .lists equal to a run over
-    all rows WITH THAT K, not with the K a fresh run of the grown set would default to.
+    never written: an update puts new tensors there.  Their list length (.lists_K) starts as the K of the constructor and
+    does not follow n: stored rows were cut at it, so appends with update_lists=True keep .lists equal to a run over
+    all rows WITH THAT K, not with the K a fresh run of the grown set would default to.  set_list_length(K2) changes it
+    on purpose: a smaller K2 cuts every row to its first K2 entries, a larger one probes the rows of exactly lists_K
+    entries again against the index (the only rows the cut can have shortened) and keeps the rest as stored.
 
     .sig and .norm2 are contiguous views of the first n rows of capacity buffers: append copies the m new rows behind
     them and the buffers grow geometrically (reserve pre-sizes them).  The tensors given to the constructor are never
@@ -380,6 +382,47 @@ class QueryIndex:
             return ops.index_finish_rows(sig, norm2, psig[q0:q1], pnorm2[q0:q1].contiguous(), self.b, pws, raw, K,
                                          self_ids[q0:q1].contiguous())[:3]
         return self._chunked(self_ids.numel(), probe)
+
+    # ---- changing the list length of the held lists ---------------------------------------------------------------
+    def set_list_length(self, K2):
+        """give the held lists the list length K2 (1..MAX_K) without a run: afterwards .lists is element for element
+        the lists of a full run over the indexed rows with K = K2, .lists_K = K2, and every later update_lists=True keeps
+        them exact at K2.  .K (the default probe length), the index arrays and the rows are not touched; .lists gets new
+        tensors, the old ones are never written.
+        K2 < lists_K: a cut (csrc/listcut.hip) -- the first K2 entries of every stored row are the row a run with K2
+        would have stored; one read-back.  K2 > lists_K: a regrow -- a stored row with fewer than lists_K entries was
+        never cut and stays; the rows of exactly lists_K entries are probed again against the index with K2, under the
+        keys they are indexed under (so caller keys behave the same); two read-backs beside the probe's own (the picked
+        rows, the new total).
+        K2 == lists_K: nothing happens (.lists stays the same object).
+        -> the number of rows probed again (0 for a cut), also in .last_picked.  ValueError, nothing changed: K2 outside
+        1..MAX_K, an index without lists, n >= 2^31, or stored lists that break their contract (src not ascending, an id
+        outside [0, n), a row longer than lists_K)."""
+        K2 = _int_arg(K2, "K2", 1, MAX_K)
+        if self.lists is None:
+            raise ValueError("this index holds no lists (none were given, or a call without update_lists=True dropped them)")
+        if self.n >= 2**31:
+            raise ValueError("lists are kept for fewer than 2^31 queries")
+        K1 = self.lists_K
+        src, dst, val = self.lists
+        if K2 == K1:
+            self.last_picked = 0
+            return 0
+        if K2 < K1:
+            lists = ops.lists_cut(src, dst, val, self.n, K1, K2)        # raises before anything is bound
+            self.lists, self.lists_K, self.last_picked = lists, K2, 0
+            return 0
+        pick = ops.lists_regrow_mark(src, self.n, K1)                   # raises before anything is bound
+        if pick.count:
+            pick_ids = pick.members()
+            pick_keys = ops.index_pick_keys(self.keys, self.ids, pick)
+            probed = self._probe_indexed((self.keys, self.ids, self.dir), self.sig, self.norm2, pick_ids, pick_keys, K2)
+            lists = ops.lists_remove(src, dst, val, self.n, K2, ops.idmap_empty(self.n, src.device), pick, *probed,
+                                     pick_ids)
+        else:
+            lists = (src, dst, val)       # no row was cut: the lists at K2 are the lists held
+        self.lists, self.lists_K, self.last_picked = lists, K2, pick.count
+        return pick.count
 
     def set(self, ids, offsets, rows, update_lists=False):
         """signatures() of CSR answer sets, then replace(): answer set x becomes that of indexed query ids[x]"""

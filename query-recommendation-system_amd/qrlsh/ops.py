@@ -1233,6 +1233,77 @@ def lists_remove(src, dst, val, n, K, removed, pick, re_off, re_idx, re_milli, r
 
 
 # ---------------------------------------------------------------------------
+# changing the list length of stored lists (csrc/listcut.hip)
+# ---------------------------------------------------------------------------
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def lists_cut(src, dst, val, n, K_old, K_new):
+    """The stored top-K lists (src, dst, val: by src, value descending, dst ascending, at most K_old per src) cut to
+    K_new <= K_old entries per src (csrc/listcut.hip): entry i survives when i < K_new or src[i - K_new] != src[i].
+    -> (src, dst, val): new tensors, element for element the lists of a run over the same rows at K_new; the arguments
+    are not written.  One read-back (the surviving entries).  ValueError for a K outside 1..256, K_new > K_old, and for
+    stored lists whose src is not ascending or outside [0, n) or that hold a row longer than K_old."""
+    lib = _lib.load()
+    _remove_lists_args(src, dst, val, n, K_old)
+    if isinstance(K_new, bool) or not isinstance(K_new, (int, np.integer)) or not 1 <= K_new <= K_old:
+        raise ValueError("K_new must lie in 1..K_old = 1..%d, got %r" % (K_old, K_new))
+    dev = src.device
+    src, dst, val = _aligned16(src), _aligned16(dst), _aligned16(val)
+    n_edges = src.numel()
+    ws = _ws(lib.qrlsh_lists_cut_workspace_bytes(n_edges), dev)
+    total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_lists_cut_count(_ptr(src), n_edges, int(n), int(K_old), int(K_new), _ptr(ws), ws.numel(),
+                                         _ptr(total), _stream()))
+    cnt = int(total.item())
+    if cnt < 0:     # ~0: the count saw stored lists that break the contract
+        raise ValueError("the stored lists are not ordered by src, hold ids outside [0, %d) or a row longer than %d"
+                         % (n, K_old))
+    out = [torch.empty((max(cnt, 1),), dtype=torch.int32, device=dev) for _ in range(3)]
+    _lib.check(lib.qrlsh_lists_cut_fill(_ptr(src), _ptr(dst), _ptr(val), n_edges, int(n), int(K_old), int(K_new), _ptr(ws),
+                                        ws.numel(), cnt, *(_ptr(t) for t in out), _stream()))
+    return out[0][:cnt], out[1][:cnt], out[2][:cnt]
+
+
+def lists_regrow_mark(src, n, K_old):
+    """the rows of the stored lists that a larger list length has to probe again: those of exactly K_old entries (a
+    shorter row was never cut) -> IdMap over [0, n).  One read-back.  ValueError for stored lists that break the
+    contract (src not ascending or outside [0, n), a row longer than K_old)."""
+    lib = _lib.load()
+    _remove_lists_args(src, src, src, n, K_old)
+    dev = src.device
+    ws = _ws(lib.qrlsh_idmap_workspace_bytes(n), dev)
+    out2 = torch.zeros((2,), dtype=torch.int64, device=dev)
+    _lib.check(lib.qrlsh_lists_regrow_mark(_ptr(src), src.numel(), int(n), int(K_old), _ptr(ws), _ptr(out2), _stream()))
+    count, bad = out2.tolist()
+    if bad:
+        raise ValueError("the stored lists are not ordered by src, hold ids outside [0, %d) or a row longer than %d"
+                         % (n, K_old))
+    return IdMap(ws, n, count)
+
+
+def idmap_empty(n, device):
+    """the IdMap over [0, n) without members: zeroed memory is one (no bits, every prefix count 0); no read-back"""
+    lib = _lib.load()
+    return IdMap(torch.zeros((max(int(lib.qrlsh_idmap_workspace_bytes(n)), 16),), dtype=torch.uint8, device=device), n, 0)
+
+
+def index_pick_keys(keys, ids, pick):
+    """int64 [b, pick.count]: the keys the rows of the IdMap `pick` are indexed under in a built index (keys int64
+    [b, n], ids int32 [b, n]), in pick.members() order -- index_remove's pick_keys without a removal"""
+    lib = _lib.load()
+    _need(keys, torch.int64, "keys", 2)
+    _need(ids, torch.int32, "ids", 2)
+    b, n = keys.shape
+    if tuple(ids.shape) != (b, n) or pick.n != n:
+        raise ValueError("ids must be [b, n] and the id map cover [0, n) = [0, %d)" % n)
+    out = torch.empty((b, pick.count), dtype=torch.int64, device=keys.device)
+    _lib.check(lib.qrlsh_index_pick_keys(_ptr(keys), _ptr(ids), n, b, _ptr(pick.ws), pick.count, _ptr(out), _stream()))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # replacing queries of a built index in place (csrc/replace.hip)
 # ---------------------------------------------------------------------------
 def rows_replace(sig, norm2, replaced_ids, new_sig, new_norm2):

@@ -9,7 +9,7 @@ column) and scores them.  Every figure is an integer: the result is the one eval
 over lists cut on the host, word for word.
 
 evaluate_ranking_grid() returns a RankingGridEvaluation: the totals per setting, the figures derived from them on the
-host, and best().  Cuts are reported, never applied."""
+host, and best().  Cuts are reported here, never applied (Recommender.tune_ranking(apply_cuts=True) applies them)."""
 import numpy as np
 import torch
 

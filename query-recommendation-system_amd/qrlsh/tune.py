@@ -6,8 +6,8 @@ descending with ties by id ascending, so its first c entries are the list a run 
 switches a side off (the ablation), a cut at or past the length is the whole list.
 
 evaluate_grid() takes evaluate()'s arguments and the grid, and returns a GridEvaluation: the exact integer sums per
-setting, the figures derived from them on the host after one read-back, and best().  Cuts are reported, never applied:
-the K of stored lists is fixed by the run that made them."""
+setting, the figures derived from them on the host after one read-back, and best().  Cuts are reported here, never applied:
+applying one is QueryIndex.set_list_length / UserLists.set_list_length (Recommender.tune(apply_cuts=True))."""
 import numpy as np
 import torch
 

@@ -15,8 +15,9 @@ out of place to its new column space, and the same update runs over it with thos
 .add_users(), .remove_users() and .nearest() let users join and leave (csrc/userrows.hip): new rows are R of the same
 update over grown arrays (nothing is picked: no stored entry names a new id); removed rows are R with mean and norm2
 zeroed, so every score against them is 0 and the positive-only lists drop them, after which the survivors are renumbered
-by rank.  Labels and K stay those of the build; the original label values are kept beside the dense ones
-(.user_labels()).  One read-back per batch of new users (add_users(labels=None) adds one, for the assignment), two per
+by rank.  Labels stay those of the build, and so does K unless .set_list_length() changes it (a prefix for a smaller K;
+for a larger one the full rows are rescored as the changed rows of the same update); the original label values are
+kept beside the dense ones (.user_labels()).  One read-back per batch of new users (add_users(labels=None) adds one, for the assignment), two per
 removal (the picked rows, then the renumbering's flags)."""
 import numpy as np
 import torch
@@ -499,6 +500,49 @@ class UserLists:
             self._set_clusters(self._labels_host[keep])
         self._rebound(work)
         return new_pos
+
+    # ---- changing the list length ------------------------------------------------------------------------------------
+    def set_list_length(self, K2):
+        """give the lists the list length K2 (1..64) without a rebuild: afterwards idx / milli / len are element for
+        element what build() over the same matrix and labels gives with K = K2, .K = K2, and every later operation keeps
+        them exact at K2.  New tensors are bound throughout; the old ones are not written.
+        K2 < K: the first K2 columns (lists are ordered value descending, id ascending: a prefix is the shorter list).
+        K2 > K: the arrays are restrided to [nu][K2]; a row with fewer than K entries was never cut and stays; the rows
+        of exactly K entries are the changed rows of the ordinary update (_refresh): each is scored against its whole
+        cluster and takes its K2 best positive scores.  Every other row of a touched cluster merges scores that did not
+        change and ends as it was, and nothing else is picked -- no row is full at the new stride.  One read-back (the
+        full rows) beside the update's own.
+        -> the number of rows rescored (0 for a cut), also in .last_picked.  ValueError for K2 outside 1..64 (nothing
+        changed)."""
+        if isinstance(K2, bool) or not isinstance(K2, (int, np.integer)) or not 1 <= int(K2) <= MAX_K:
+            raise ValueError("K2 must be an integer in 1..%d, got %r" % (MAX_K, K2))
+        K1, K2 = self.K, int(K2)
+        if K2 == K1:
+            self.last_picked = 0
+            return 0
+        if K2 < K1:
+            idx, milli = self.idx[:, :K2].contiguous(), self.milli[:, :K2].contiguous()
+            self.idx, self.milli, self.len, self.K = idx, milli, self.len.clamp(max=K2), K2
+            self.last_picked = 0
+            return 0
+        dev, nu = self.ratings.device, self.nu
+        Rd = torch.nonzero(self.len == K1).reshape(-1).to(torch.int32).contiguous()
+        R = Rd.cpu().numpy().astype(np.int64)                 # the read-back: the rows the cut can have shortened
+        idx = torch.full((nu, K2), -1, dtype=torch.int32, device=dev)
+        milli = torch.zeros((nu, K2), dtype=torch.int32, device=dev)
+        idx[:, :K1], milli[:, :K1] = self.idx, self.milli
+
+        def work():
+            self.idx, self.milli, self.len, self.K = idx, milli, self.len.clone(), K2
+            if R.size:
+                self._refresh(Rd, int(R.size), int((self._sizes[self._dense_host[R]] - 1).sum()), stats=False)
+            self.last_picked = int(R.size)
+        try:
+            self._rebound(work)
+        except BaseException:
+            self.K = K1
+            raise
+        return int(R.size)
 
     def coo(self):
         """(src, dst, milli) int32 device tensors, the form users.user_similarities returns"""

@@ -641,6 +641,74 @@ class Recommender:
         self.ratings[u, q] = v.astype(self.ratings.dtype)       # numpy assigns in order: the last repeat wins here too
         return n
 
+    # ---- the list lengths of the live lists, changed in place ------------------------------------------------------
+    def _cut_plan(self, q_cut, u_cut):
+        """What tune(apply_cuts=True) does with the best setting's cuts (None: that side's cuts were not given):
+        -> (query_K, user_K) for set_list_lengths, None for a side left alone -- one whose best cut is >= its current
+        length (tune never regrows).  ValueError before anything changes: a best cut of 0 (a side switched off is not a
+        list length), or a user cut without a user index in step."""
+        from qrlsh.index import QueryIndex
+        query_K = user_K = None
+        if q_cut is not None:
+            if q_cut < 1:
+                raise ValueError("the best setting switches the query side off (cut 0): a list length is >= 1, nothing applied")
+            qi = getattr(self, "_query_index", None)
+            if qi is None:
+                qi = self._query_index = QueryIndex.from_result(self.last_result, self.last_table, lists=True)
+            if qi.lists is not None and q_cut < qi.lists_K:
+                query_K = int(q_cut)
+        if u_cut is not None:
+            if u_cut < 1:
+                raise ValueError("the best setting switches the user side off (cut 0): a list length is >= 1, nothing applied")
+            ui = self._user_index_in_step()
+            if ui is None:
+                raise ValueError("a user cut needs a user index in step with self.ratings (live_user_similarities)")
+            if u_cut < ui.K:
+                user_K = int(u_cut)
+        return query_K, user_K
+
+    def set_list_lengths(self, query_K=None, user_K=None):
+        """Change the list length of the live lists in place, without a run: query_K (1..256) goes to the run's index
+        (QueryIndex.set_list_length; the index is made from the last run's result if absent, as add_queries does),
+        user_K (1..64) to the user index (UserLists.set_list_length), which must be in step with self.ratings.  None
+        leaves a side alone.  Afterwards the lists are element for element those of a full run / build at the new
+        lengths, and everything that serves or measures from them does so at those lengths: current_query_similarities,
+        compute_scores(reuse_lists=True), recommend_users, predict_users, evaluate*, tune*, add_queries / remove_queries
+        / replace_queries(update_lists=True), rate, add_users, remove_users and the row operations.  A smaller length
+        cuts; a larger one probes (rescores) the rows the old length had filled.  last_result is left alone.
+        ValueError before anything changes: a length outside range, no finished run, no live lists, an index that does
+        not hold the served queries, or user_K without a user index in step.
+        -> (query rows probed again, user rows rescored), None for a side left alone."""
+        from qrlsh.index import QueryIndex, MAX_K, _int_arg
+        from qrlsh.userlists import MAX_K as USER_MAX_K
+        qi = ui = None
+        if query_K is not None:
+            query_K = _int_arg(query_K, "query_K", 1, MAX_K)
+            res = getattr(self, "last_result", None)
+            if res is None or getattr(self, "last_table", None) is None:
+                raise ValueError("compute_querySimilarities has not run: there are no lists to change")
+            qi = getattr(self, "_query_index", None)
+            made = qi is None
+            if made:
+                qi = QueryIndex.from_result(res, self.last_table, lists=True)
+            if qi.lists is None:
+                raise ValueError("the live lists were dropped by a call without update_lists=True; "
+                                 "compute_querySimilarities starts afresh")
+            if qi.n != self.queriesIDs.size:
+                raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        if user_K is not None:
+            user_K = _int_arg(user_K, "user_K", 1, USER_MAX_K)
+            ui = self._user_index_in_step()
+            if ui is None:
+                raise ValueError("user_K needs a user index in step with self.ratings (live_user_similarities)")
+        picked_q = picked_u = None
+        if qi is not None:
+            picked_q = qi.set_list_length(query_K)      # raises before it binds anything
+            self._query_index = qi
+        if ui is not None:
+            picked_u = ui.set_list_length(user_K)
+        return picked_q, picked_u
+
     # ---- N1: hybrid prediction (device) ------------------------------------------------
     def compute_scores(self, reuse_lists=False):
         """(scores_to_predict, finalPredictions DataFrame, scores_missed), recommender.py:292-343.
@@ -809,7 +877,7 @@ class Recommender:
 
     # ---- which blend serves best: evaluate()'s figures over a grid of settings in one sweep (qrlsh.tune) -----------
     def tune(self, weights, q_cuts=None, u_cuts=None, fraction=0.1, seed=0, holdout=True, sum_order=None, user_sim=None,
-             metric="rmse", min_coverage=0.0, apply=False):
+             metric="rmse", min_coverage=0.0, apply=False, apply_cuts=False):
         """evaluate()'s error for every setting of a grid, from one sweep of the device -> qrlsh.GridEvaluation
         (.totals, .n, .mae, .rmse, .bias, .coverage, .best()).  weights: (W, 3) rows (query_weight, user_weight,
         default_mean); q_cuts / u_cuts: up to 4 list lengths each (default: the whole lists; 0 switches a side off) --
@@ -817,9 +885,13 @@ class Recommender:
         The split and the user side are those of evaluate(holdout=...): holdout=True builds the user lists once over
         the train copy (they do not depend on the weights); holdout=False is leave-one-out with the lists held fixed.
         apply=True sets query_weight, user_weight and default_mean to the best triple by `metric` among the settings
-        with coverage >= min_coverage (GridEvaluation.best), so every serving call uses it from then on.  CUTS ARE
-        REPORTED, NEVER APPLIED: the K of the live lists is fixed by the run.  Neither self.ratings, the lists nor
-        user_index is modified.  ValueError as qrlsh.evaluate_grid raises it, and from best() when apply=True."""
+        with coverage >= min_coverage (GridEvaluation.best), so every serving call uses it from then on.
+        apply_cuts=True applies the cuts of that best setting to the live lists through set_list_lengths: a side whose
+        cuts were not given, or whose best cut is >= its current length, is left alone -- TUNE NEVER REGROWS.  A best cut
+        of 0 (side switched off) and a user cut without a user index in step raise ValueError; all of it is decided
+        before weights or lists change, so a refusal leaves the recommender as it was.  By default (apply_cuts=False)
+        cuts are only reported, and neither self.ratings, the lists nor user_index is modified.  ValueError as
+        qrlsh.evaluate_grid raises it, and from best() when apply or apply_cuts is set."""
         from qrlsh.evaluate import keep_word
         from qrlsh.tune import evaluate_grid, METRICS
         keep_word(fraction)
@@ -832,9 +904,12 @@ class Recommender:
             truth = None
         grid = evaluate_grid(ratings, lists[0], lists[1], lists[2], user_sim, weights, q_cuts=q_cuts, u_cuts=u_cuts,
                              truth=truth, fraction=fraction, seed=seed, sum_order=sum_order, device=self.device)
-        if apply:
-            _, _, (qw, uw, dm), _ = grid.best(metric, min_coverage)
-            self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
+        if apply or apply_cuts:
+            qc, uc, (qw, uw, dm), _ = grid.best(metric, min_coverage)
+            if apply_cuts:
+                self.set_list_lengths(*self._cut_plan(qc if q_cuts is not None else None, uc if u_cuts is not None else None))
+            if apply:
+                self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
         return grid
 
     # ---- and are the lists it serves any good: precision / recall / NDCG at k on held-out cells (qrlsh.ranking) -----
@@ -863,7 +938,7 @@ class Recommender:
 
     # ---- which blend serves the best lists: evaluate_ranking's figures over a grid in one sweep (qrlsh.rankgrid) -----
     def tune_ranking(self, k, relevant, weights, q_cuts=None, u_cuts=None, fraction=0.1, seed=0, users=None,
-                     sum_order=None, user_sim=None, metric="ndcg", min_recall=0.0, apply=False):
+                     sum_order=None, user_sim=None, metric="ndcg", min_recall=0.0, apply=False, apply_cuts=False):
         """evaluate_ranking(candidates="heldout")'s figures for every setting of a grid, from one sweep of the device ->
         qrlsh.RankingGridEvaluation (.totals, .precision, .recall, .ndcg, .hit_rate, .best()).  RMSE (tune) moves with
         the default-mean term of the blend, not with the order of the list; these are the figures for the order.
@@ -871,8 +946,11 @@ class Recommender:
         the user side are those of evaluate_ranking: _holdout_inputs, built once (they do not depend on the setting).
         apply=True sets query_weight, user_weight and default_mean to the best triple by `metric` ('ndcg', 'precision',
         'recall', 'hit_rate') among the settings with recall >= min_recall (RankingGridEvaluation.best), so every
-        serving call uses it from then on.  CUTS ARE REPORTED, NEVER APPLIED.  Neither self.ratings, the lists nor
-        user_index is modified.  ValueError as qrlsh.evaluate_ranking_grid raises it, and from best() when apply=True."""
+        serving call uses it from then on.  apply_cuts=True applies the best setting's cuts through set_list_lengths
+        under tune's rules (only cuts that shorten, never a regrow; a best cut of 0 or a user cut without a user index in
+        step raises ValueError before anything changes).  By default cuts are only reported, and neither self.ratings,
+        the lists nor user_index is modified.  ValueError as qrlsh.evaluate_ranking_grid raises it, and from best() when
+        apply or apply_cuts is set."""
         from qrlsh.evaluate import keep_word
         from qrlsh.ranking import check_arguments
         from qrlsh.rankgrid import evaluate_ranking_grid, METRICS
@@ -886,9 +964,12 @@ class Recommender:
         grid = evaluate_ranking_grid(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, weights,
                                      q_cuts=q_cuts, u_cuts=u_cuts, users=users, sum_order=sum_order,
                                      device=self.device)
-        if apply:
-            _, _, (qw, uw, dm), _ = grid.best(metric, min_recall)
-            self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
+        if apply or apply_cuts:
+            qc, uc, (qw, uw, dm), _ = grid.best(metric, min_recall)
+            if apply_cuts:
+                self.set_list_lengths(*self._cut_plan(qc if q_cuts is not None else None, uc if u_cuts is not None else None))
+            if apply:
+                self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
         return grid
 
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
