@@ -97,6 +97,8 @@ def answer_sets(index, qrows, one_sweep=True):
     else:
         nnz, biggest = 0, 0
     rows = torch.empty((nnz,), dtype=torch.int32, device=dev)
+    if nnz == 0:        # every answer set is empty: nothing to write (the library refuses the null pointer of an empty tensor)
+        return offsets, rows
     if slots is not None and biggest <= SLOT:
         _lib.check(lib.qrlsh_answer_sets_compact(_ptr(slots), _ptr(offsets), nq, _ptr(rows), _stream()))
     elif nq:

@@ -244,6 +244,14 @@ class Recommender:
                 raise ValueError("ids of dtype %s do not fit %s of dtype %s" % (labels.dtype, name, cur.dtype))
         return labels
 
+    def _refuse_dropped_lists(self, update_lists):
+        """ValueError for update_lists=True after a call without it dropped the live lists -- raised before the call
+        touches anything (an index that does not exist yet is made with the run's lists and has nothing dropped)"""
+        qi = getattr(self, "_query_index", None)
+        if update_lists and qi is not None and qi.lists is None:
+            raise ValueError("the live lists were dropped by a call without update_lists=True; "
+                             "compute_querySimilarities starts afresh")
+
     def _user_index_in_step(self, block=None):
         """self.user_index when it holds self.ratings' shape now (it then follows the column operation under way), else
         None: an index that is already out of step is left alone.  A ratings block the index would refuse is refused
@@ -270,14 +278,13 @@ class Recommender:
         update_lists=True: the index also keeps the run's top-K lists current (QueryIndex.append(update_lists=True)):
         current_query_similarities() then returns what compute_querySimilarities would over all queries at the run's
         K, and compute_scores(reuse_lists=True) predicts from them.  last_result is still left alone.  Without the flag
-        the live lists are dropped (they would be stale), and a later update_lists=True raises ValueError.
+        the live lists are dropped (they would be stale), and a later update_lists=True raises ValueError before anything
+        changes (the live table's dictionary included).
         A user index in step with self.ratings (live_user_similarities) follows, whatever update_lists says:
         UserLists.add_columns takes the block (m unrated columns without one), so rate, recommend_users and
         predict_users keep serving from it."""
+        self._refuse_dropped_lists(update_lists)        # before the new texts reach the live table's dictionary
         qi, sig, norm2, keys = self._new_query_rows(queries)
-        if update_lists and qi.lists is None:
-            raise ValueError("the live lists were dropped by an add_queries without update_lists=True; "
-                             "compute_querySimilarities starts afresh")
         q = np.asarray(_as_numpy(queries), dtype=object)
         m = q.shape[0]
         nu = self.usersIDs.size
@@ -349,13 +356,11 @@ class Recommender:
         ratings columns -- an edited query keeps its ratings; an integer [users, m] block overwrites them.
         update_lists=True: the index keeps the run's top-K lists exact (QueryIndex.replace(update_lists=True)), so
         current_query_similarities(), compute_scores(reuse_lists=True) and recommend_users serve the edited set at the
-        run's K.  Without the flag the live lists are dropped, and a later update_lists=True raises ValueError.
-        last_result stays the closed-set run's output.  With a ratings block, a user index in step with self.ratings
+        run's K.  Without the flag the live lists are dropped, and a later update_lists=True raises ValueError
+        before anything changes.  last_result stays the closed-set run's output.  With a ratings block, a user index in step with self.ratings
         follows (UserLists.set_columns), whatever update_lists says; without one it is not touched."""
+        self._refuse_dropped_lists(update_lists)        # before the new texts reach the live table's dictionary
         qi, sig, norm2, keys = self._new_query_rows(queries)
-        if update_lists and qi.lists is None:
-            raise ValueError("the live lists were dropped by a call without update_lists=True; "
-                             "compute_querySimilarities starts afresh")
         if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
             raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
         q = np.asarray(_as_numpy(queries), dtype=object)

@@ -156,6 +156,19 @@ def test_absent_value_gives_an_empty_set_between_undisturbed_neighbours():
     check_both_forms(idx, answers.encode_queries(idx, q2), ref2, "absent compact")
 
 
+def test_a_batch_of_nothing_but_empty_sets():
+    """every query of the batch names an absent value: offsets all zero, no rows, on both routes (this raised "null
+    pointer" from the compact and the fill pass: the rows tensor is empty; found through Recommender.add_queries of one
+    query that no row answers, by the random schedules of test_gpu_live_sequence.py)"""
+    cols, idx, pool, qr, ref = case(2049, 2)
+    absent = np.array([A.ABSENT[1], ""], dtype=object)
+    for nq in (1, 3, 65):
+        q = np.stack([absent] * nq)
+        r_off, r_rows = A.ref_answer_sets(cols, q)
+        assert r_off.tolist() == [0] * (nq + 1) and len(r_rows) == 0
+        check_both_forms(idx, answers.encode_queries(idx, q), (r_off, r_rows), ("nothing but empty sets", nq))
+
+
 @pytest.mark.parametrize("D,nfeat,kind,P,b", [(2049, 2, "u16", 100, 20), (8193, 64, "i32", 33, 11)])
 def test_device_answer_sets_feed_minhash(D, nfeat, kind, P, b):
     """the producer -> consumer contract: ascending ids in range, offsets[-1] == len(rows) -- checked by

@@ -313,6 +313,33 @@ def test_recommender_rows_come_and_go(sub):
     assert rec._live_table is None and rec.row_slots is None
 
 
+def test_a_refused_query_call_after_dropped_lists_leaves_the_table_alone():
+    """Found by the random schedules of test_gpu_live_sequence.py, cut down to its shortest form: under a live table, one
+    call without update_lists drops the lists; add_queries / replace_queries(update_lists=True) is then refused -- and
+    must be refused before its texts reach the table's dictionary (a value new to it used to get a dictionary entry and a
+    bitmap row from the refused call)."""
+    from test_gpu_recommend import _recommender_on
+    rec, _ = _recommender_on("cfg2")
+    rec.row_capacity = rec.dataset.shape[0] + 2
+    rec.compute_querySimilarities()
+    rec.remove_rows([3], update_lists=True)              # the live table exists from here on
+    rec.remove_queries([1])                              # the lists are dropped
+    lt, qi = rec._live_table, rec._query_index
+    assert qi.lists is None
+    held = (lt.bitmaps, lt.bitmaps.clone(), lt.dictionary.nrows, [dict(m) for m in lt.dictionary.maps], lt.qrows, lt.qrows.clone())
+    n = rec.queriesIDs.size
+    q = np.asarray(rec.queries, dtype=object)[:1].copy()
+    q[0, 0] = "a value no row and no query holds"
+    for call in (lambda: rec.add_queries(q, update_lists=True), lambda: rec.replace_queries([0], q, update_lists=True)):
+        with pytest.raises(ValueError, match="dropped"):
+            call()
+        assert lt.bitmaps is held[0] and torch.equal(lt.bitmaps, held[1])
+        assert lt.dictionary.nrows == held[2] and [dict(m) for m in lt.dictionary.maps] == held[3]
+        assert lt.qrows is held[4] and torch.equal(lt.qrows, held[5]) and (qi.n, rec.queriesIDs.size) == (n, n)
+    rec.add_queries(q)                                   # without the flag the call goes through, new value and all
+    assert lt.dictionary.nrows == held[2] + 1 and rec.queriesIDs.size == n + 1 == qi.n
+
+
 # ------------------------------------------------------------------------------------------------ 5. errors
 def test_errors_leave_everything_as_it_was():
     from qrlsh import _lib, ops
