@@ -782,6 +782,46 @@ int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64_t nq, const 
                           int32_t *val_out, int32_t *avail_out, uint32_t *flags_out, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ---- diversified lists: rerank a served pool by the stored neighbour lists; the redundancy of a served list ----------
+ * The project's own rule (the reference has no counterpart); integer arithmetic only.  Query lists in CSR with milli
+ * values (0 .. 1000) as qrlsh_recommend_users takes them, rows of any length.
+ *   sim(a, b) = the largest stored milli among the entries a -> b and b -> a; 0 when neither is stored.
+ * qrlsh_diversify: cand_idx / cand_val int32 [m][N] and avail int32 [m] are rows of qrlsh_recommend_topk /
+ * qrlsh_recommend_users output at k = N: request x has the pool of its first n = min(N, max(avail[x], 0)) candidates
+ * in served order.  For t = 0 .. k - 1, over the unpicked candidates c: r_c = max over the picked s of sim(c, s) (0 while
+ * nothing is picked); c is eligible when r_c < max_sim; score_c = 1000 * val_c - penalty * r_c (int64); the eligible c
+ * with the largest score is picked, ties to the smaller pool position; the request ends early when nobody is eligible.
+ * idx_out / val_out / red_out int32 [m][k]: the picks' columns, values and the r_c each had when taken, -1 / 0 / 0 past
+ * the picks; count_out int32 [m]: the picks.  penalty = 0, max_sim = 1001 gives the first min(k, n) of the pool.
+ * qrlsh_list_redundancy: idx int32 [m][k], entries of -1 are padding.  words_out int64 [m][4] per list: the entries
+ * listed, the unordered in-list pairs with sim > 0, the sum of sim over them, the largest sim.  totals_out int64 [4]
+ * (zeroed by the caller) gets the sums of the first three over the lists and the max of the last.
+ * One 256-thread workgroup per request.  The pool's columns go into an LDS hash, the candidates' list rows are walked
+ * and the pool-internal edges become, in both directions, a CSR over pool positions in the workspace (a half-edge is one
+ * word: 10 bits of position, 10 of milli); the selection then keeps r and the picked bits in LDS and per step takes an
+ * argmax over the workgroup and walks the pick's half-edges alone.  The workspace is divided evenly among the m
+ * requests; qrlsh_diversify_workspace_bytes(m, N, max_row) holds every pool of N whose list rows are at most max_row
+ * long and name no query twice (2 N min(max_row, N - 1) half-edges per request), for qrlsh_list_redundancy with N = k.
+ * *flag_out (device uint32, zeroed by the caller, required) gets bit 0: a neighbour index outside [0, nq), bit 1: a
+ * candidate column outside [0, nq) before avail (for a list: other than -1), bit 2: a column twice in one pool, bit 3:
+ * a pool whose half-edges do not fit its share of the workspace (none of them is written).  A flagged result is not to
+ * be used; nothing outside the arguments is read or written.
+ * Limits: 1 <= k <= N <= QRLSH_DIVERSIFY_MAX_POOL, 0 <= penalty <= QRLSH_DIVERSIFY_MAX_PENALTY, 0 <= max_sim <= 1001
+ * (1001: nothing is excluded), nq < 2^31 (QRLSH_EINVAL otherwise); m <= 2^24 (QRLSH_EUNSUPPORTED above); a workspace
+ * below the offsets' m (N + 4) words gives QRLSH_EWORKSPACE.  m = 0 returns at once.  No allocation, one stream, no
+ * read-back.
+ */
+#define QRLSH_DIVERSIFY_MAX_POOL 1024
+#define QRLSH_DIVERSIFY_MAX_PENALTY (1 << 20)
+size_t qrlsh_diversify_workspace_bytes(int64_t m, int32_t N, int64_t max_row);
+int qrlsh_diversify(const int32_t *cand_idx, const int32_t *cand_val, const int32_t *avail, int64_t m, int32_t N,
+                    int64_t nq, const int64_t *q_off, const int32_t *q_idx, const int32_t *q_milli, int32_t k,
+                    int64_t penalty, int32_t max_sim, int32_t *idx_out, int32_t *val_out, int32_t *red_out,
+                    int32_t *count_out, uint32_t *flag_out, void *workspace, size_t workspace_bytes, void *stream);
+int qrlsh_list_redundancy(const int32_t *idx, int64_t m, int32_t k, int64_t nq, const int64_t *q_off,
+                          const int32_t *q_idx, const int32_t *q_milli, int64_t *words_out, int64_t *totals_out,
+                          uint32_t *flag_out, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- evaluation: the prediction error on rated cells, hold-out and leave-one-out -----------------------------------
  * The blend of cell (i, j) never reads ratings[i][j]: a rated cell can be predicted as if it were unrated and compared
  * with its rating.  Predictions and ratings are integers, so every statistic is an exact integer sum, independent of the

@@ -1,0 +1,437 @@
+// diversify.hip -- rerank served lists by the stored neighbour lists, and the redundancy of any served list
+// (qrlsh_diversify, qrlsh_list_redundancy in include/qrlsh.h).  The project's own rule; integer arithmetic only.
+//
+// sim(a, b) = the largest stored milli among the list entries a -> b and b -> a, 0 when neither is stored.
+// Per request a pool of n candidates (col, val) in served order; greedily, for t = 0 .. k - 1: among the unpicked
+// candidates c with r_c = max over picked s of sim(c, s) below max_sim, take the one with the largest
+// 1000 * val_c - penalty * r_c (int64), ties to the smaller pool position; stop when none is eligible.
+//
+// One 256-thread workgroup per request, two launches:
+//   adjacency -- the pool's columns go into an LDS hash (2048 slots, <= 1024 keys); groups of 16 lanes walk the
+//                candidates' list rows and look every neighbour up; the pool-internal edges, in both directions, become
+//                a CSR in pool space in the workspace: a count per position in LDS, a scan, then the fill.  A half-edge
+//                is one word: the other end's pool position (bits 0-9) and the milli value (bits 10-19);
+//   select    -- r_c and the picked bit of every candidate in LDS, four candidates per thread; per step an argmax of
+//                (score, -position) by wave shuffles then across the waves in LDS, and a walk of the pick's half-edges
+//                alone that raises r with LDS max: a step costs the pick's pool degree;
+//   reduce    -- (redundancy) the adjacency of the list itself, then per position the pairs towards later positions:
+//                a wave folds the half-edges of a pair (one per stored direction) through a per-wave LDS row.
+// Edges past the workspace's capacity raise a flag and none is written; nothing is read or written outside the
+// request's pool, list rows and workspace slice.
+#include "common.h"
+
+namespace {
+constexpr int DV_THREADS = 256;
+constexpr int DV_WAVES = DV_THREADS / WAVE;
+constexpr int DV_MAXN = QRLSH_DIVERSIFY_MAX_POOL;   // 1024 candidates: 10 bits of pool position
+constexpr int DV_PER = DV_MAXN / DV_THREADS;        // candidates per thread
+constexpr int DV_SLOTS = 2 * DV_MAXN;               // hash slots
+constexpr int DV_GROUP = 16;                        // lanes that walk one list row together
+constexpr int DV_MAX_MILLI = 1000;
+constexpr int64_t DV_MAX_M = 1ll << 24;
+
+constexpr uint32_t DV_BAD_NEIGHBOUR = 1, DV_BAD_CANDIDATE = 2, DV_DUPLICATE = 4, DV_OVERFLOW = 8;
+
+static_assert(DV_MAXN == 1024 && DV_PER == 4, "a half-edge holds 10 bits of position; the select keeps 4 per thread");
+
+struct DvAdjLds {
+  int32_t key[DV_SLOTS];        // -1 = empty
+  uint16_t key_pos[DV_SLOTS];   // pool position of the slot's key
+  int64_t beg[DV_MAXN];         // list row of the candidate: first entry ...
+  uint32_t len[DV_MAXN];        // ... and length (0: no row is walked)
+  uint32_t cnt[DV_MAXN];        // half-edges per position, then the fill cursors
+  uint32_t wsum[DV_WAVES];
+};
+
+__device__ __forceinline__ uint32_t dv_hash(int32_t col) { return ((uint32_t)col * 2654435761u) >> 21; }
+
+// pool position of column d, -1 when it is not in the pool
+__device__ __forceinline__ int dv_lookup(const DvAdjLds &s, int32_t d) {
+  uint32_t slot = dv_hash(d);
+  for (;;) {
+    const int32_t key = s.key[slot];
+    if (key == d) return s.key_pos[slot];
+    if (key == -1) return -1;
+    slot = (slot + 1) & (DV_SLOTS - 1);
+  }
+}
+
+// f(c, q, milli) for every stored entry c -> q with both ends in the pool, c != q (positions); groups of DV_GROUP
+// lanes take the candidates in turn.  Returns the flag bits met.
+template <typename F>
+__device__ __forceinline__ uint32_t dv_walk(const DvAdjLds &s, int n, int64_t nq, const int32_t *__restrict__ q_idx,
+                                            const int32_t *__restrict__ q_milli, bool with_milli, F &&f) {
+  uint32_t fl = 0;
+  const int g = threadIdx.x / DV_GROUP, l = threadIdx.x % DV_GROUP;
+  for (int c = g; c < n; c += DV_THREADS / DV_GROUP) {
+    const uint32_t len = s.len[c];
+    const int64_t beg = s.beg[c];
+    for (uint32_t e = l; e < len; e += DV_GROUP) {
+      const int32_t d = q_idx[beg + e];
+      if (d < 0 || d >= nq) {
+        fl |= DV_BAD_NEIGHBOUR;
+        continue;
+      }
+      const int q = dv_lookup(s, d);
+      if (q < 0 || q == c) continue;
+      int32_t mi = with_milli ? q_milli[beg + e] : 0;
+      mi = mi < 0 ? 0 : mi > DV_MAX_MILLI ? DV_MAX_MILLI : mi;
+      f(c, q, (uint32_t)mi);
+    }
+  }
+  return fl;
+}
+
+// The adjacency of one pool: cols[0 .. n) (n <= n_off <= DV_MAXN) -> offs[0 .. n_off] and at most `cap` half-edges.
+// pad_ok: a column of -1 is an empty position (a padded list), not a bad candidate.  Every thread of the block calls it.
+__device__ void dv_adjacency(DvAdjLds &s, const int32_t *__restrict__ cols, int n, int n_off, bool pad_ok, int64_t nq,
+                             const int64_t *__restrict__ q_off, const int32_t *__restrict__ q_idx,
+                             const int32_t *__restrict__ q_milli, uint32_t cap, uint32_t *__restrict__ offs,
+                             uint32_t *__restrict__ edges, uint32_t *__restrict__ flag) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < DV_SLOTS; i += DV_THREADS) s.key[i] = -1;
+  __syncthreads();
+  uint32_t fl = 0;
+  for (int c = tid; c < DV_MAXN; c += DV_THREADS) {
+    int64_t beg = 0;
+    uint32_t len = 0;
+    if (c < n) {
+      const int32_t col = cols[c];
+      if (col >= 0 && col < nq) {
+        uint32_t slot = dv_hash(col);
+        bool mine = false;
+        for (;;) {
+          const int32_t old = atomicCAS(&s.key[slot], -1, col);
+          if (old == -1) {
+            s.key_pos[slot] = (uint16_t)c;
+            mine = true;
+            break;
+          }
+          if (old == col) {
+            fl |= DV_DUPLICATE;
+            break;
+          }
+          slot = (slot + 1) & (DV_SLOTS - 1);
+        }
+        if (mine) {
+          beg = q_off[col];
+          const int64_t L = q_off[col + 1] - beg;
+          if (L < 0 || L > 0x7FFFFFFFll) fl |= DV_OVERFLOW;
+          else len = (uint32_t)L;
+        }
+      } else if (!(pad_ok && col == -1)) {
+        fl |= DV_BAD_CANDIDATE;
+      }
+    }
+    s.beg[c] = beg;
+    s.len[c] = len;
+    s.cnt[c] = 0;
+  }
+  __syncthreads();
+  fl |= dv_walk(s, n, nq, q_idx, q_milli, false, [&](int c, int q, uint32_t) {
+    atomicAdd(&s.cnt[c], 1u);
+    atomicAdd(&s.cnt[q], 1u);
+  });
+  __syncthreads();
+  // thread t scans positions 4 t .. 4 t + 3; counts saturate far above any capacity
+  uint32_t own[DV_PER], sum = 0;
+#pragma unroll
+  for (int j = 0; j < DV_PER; ++j) {
+    own[j] = min(s.cnt[DV_PER * tid + j], 1u << 21);
+    sum += own[j];
+  }
+  uint32_t total;
+  uint32_t run = block_excl_scan<DV_THREADS>(sum, s.wsum, total);
+  const bool fits = total <= cap;
+  if (!fits) fl |= DV_OVERFLOW;
+#pragma unroll
+  for (int j = 0; j < DV_PER; ++j) {
+    const int p = DV_PER * tid + j;
+    if (p <= n_off) offs[p] = fits ? run : 0u;
+    s.cnt[p] = run;
+    run += own[j];
+  }
+  if (tid == DV_THREADS - 1 && n_off == DV_MAXN) offs[DV_MAXN] = fits ? total : 0u;
+  __syncthreads();
+  if (fits && total > 0) {
+    dv_walk(s, n, nq, q_idx, q_milli, true, [&](int c, int q, uint32_t mi) {
+      const uint32_t a = atomicAdd(&s.cnt[c], 1u), b = atomicAdd(&s.cnt[q], 1u);
+      if (a < cap) edges[a] = (uint32_t)q | mi << 10;
+      if (b < cap) edges[b] = (uint32_t)c | mi << 10;
+    });
+  }
+  if (fl) atomicOr(flag, fl);
+}
+
+// workspace of one request: [offs: n_off + 1 words, rounded to 4][half-edges: cap words]
+__host__ __device__ inline size_t dv_offs_words(int n_off) { return ((size_t)n_off + 1 + 3) & ~(size_t)3; }
+
+__global__ __launch_bounds__(DV_THREADS) void diversify_adjacency_kernel(
+    const int32_t *__restrict__ cand_idx, const int32_t *__restrict__ avail, int N, int64_t nq,
+    const int64_t *__restrict__ q_off, const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli,
+    uint32_t cap, uint32_t *__restrict__ ws, uint32_t *__restrict__ flag) {
+  __shared__ DvAdjLds s;
+  const int64_t x = blockIdx.x;
+  const int32_t av = avail[x];
+  const int n = av < 0 ? 0 : av > N ? N : av;
+  uint32_t *offs = ws + (size_t)x * (dv_offs_words(N) + cap);
+  dv_adjacency(s, cand_idx + x * N, n, N, false, nq, q_off, q_idx, q_milli, cap, offs, offs + dv_offs_words(N), flag);
+}
+
+__global__ __launch_bounds__(DV_THREADS) void list_adjacency_kernel(
+    const int32_t *__restrict__ idx, int k, int64_t nq, const int64_t *__restrict__ q_off,
+    const int32_t *__restrict__ q_idx, const int32_t *__restrict__ q_milli, uint32_t cap, uint32_t *__restrict__ ws,
+    uint32_t *__restrict__ flag) {
+  __shared__ DvAdjLds s;
+  const int64_t x = blockIdx.x;
+  uint32_t *offs = ws + (size_t)x * (dv_offs_words(k) + cap);
+  dv_adjacency(s, idx + x * k, k, k, true, nq, q_off, q_idx, q_milli, cap, offs, offs + dv_offs_words(k), flag);
+}
+
+__device__ __forceinline__ uint64_t dv_wave_max(uint64_t v) {
+#pragma unroll
+  for (int d = WAVE / 2; d > 0; d >>= 1) {
+    const uint64_t o = __shfl_xor(v, d, WAVE);
+    v = o > v ? o : v;
+  }
+  return v;
+}
+
+// the greedy selection over the adjacency of diversify_adjacency_kernel
+__global__ __launch_bounds__(DV_THREADS) void diversify_select_kernel(
+    const int32_t *__restrict__ cand_idx, const int32_t *__restrict__ cand_val, const int32_t *__restrict__ avail, int N,
+    int k, int64_t penalty, uint32_t max_sim, uint32_t cap, const uint32_t *__restrict__ ws,
+    int32_t *__restrict__ idx_out, int32_t *__restrict__ val_out, int32_t *__restrict__ red_out,
+    int32_t *__restrict__ count_out) {
+  __shared__ uint32_t r[DV_MAXN];          // r_c, bit 31 = picked
+  __shared__ uint32_t offs_s[DV_MAXN + 1];
+  __shared__ uint32_t picks[DV_MAXN];      // position | r << 10 of every pick
+  __shared__ uint64_t wmax[2][DV_WAVES];
+  const int tid = threadIdx.x;
+  const int64_t x = blockIdx.x;
+  const int32_t av = avail[x];
+  const int n = av < 0 ? 0 : av > N ? N : av;
+  const uint32_t *offs = ws + (size_t)x * (dv_offs_words(N) + cap);
+  const uint32_t *edges = offs + dv_offs_words(N);
+  int64_t base[DV_PER];   // 1000 * val of positions tid + 256 j
+#pragma unroll
+  for (int j = 0; j < DV_PER; ++j) {
+    const int p = tid + DV_THREADS * j;
+    base[j] = p < n ? 1000ll * (int64_t)cand_val[x * N + p] : 0;
+    r[p] = 0;
+    if (p <= N) offs_s[p] = offs[p];
+  }
+  if (tid == 0 && N == DV_MAXN) offs_s[DV_MAXN] = offs[DV_MAXN];
+  __syncthreads();
+  int t = 0;
+  for (; t < k; ++t) {
+    // key = (score + 2^43) << 10 | (1023 - position) > 0; |score| < 2^42 + 2^30
+    uint64_t best = 0;
+#pragma unroll
+    for (int j = 0; j < DV_PER; ++j) {
+      const int p = tid + DV_THREADS * j;
+      const uint32_t rc = r[p];
+      if (p < n && rc < max_sim) {   // a picked candidate has bit 31 set
+        const int64_t score = base[j] - penalty * (int64_t)rc;
+        const uint64_t key = (uint64_t)(score + (1ll << 43)) << 10 | (uint64_t)(DV_MAXN - 1 - p);
+        best = key > best ? key : best;
+      }
+    }
+    best = dv_wave_max(best);
+    if (lane_id() == 0) wmax[t & 1][tid >> 6] = best;
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < DV_WAVES; ++w) {
+      const uint64_t o = wmax[t & 1][w];
+      best = o > best ? o : best;
+    }
+    if (best == 0) break;   // nobody is eligible: the same word in every thread
+    const int p = DV_MAXN - 1 - (int)(best & (DV_MAXN - 1));
+    if (tid == 0) {   // the keys were read before the barrier, and no half-edge of p points at p
+      const uint32_t rp = r[p];
+      picks[t] = (uint32_t)p | rp << 10;
+      r[p] = rp | 0x80000000u;
+    }
+    for (uint32_t e = offs_s[p] + tid, end = offs_s[p + 1]; e < end; e += DV_THREADS) {
+      const uint32_t he = edges[e];
+      atomicMax(&r[he & (DV_MAXN - 1)], he >> 10);
+    }
+    __syncthreads();
+  }
+  // t picks (the same in every thread); `picks` was written by thread 0 before the last barrier passed
+  __syncthreads();
+  for (int j = tid; j < k; j += DV_THREADS) {
+    const bool in = j < t;
+    const uint32_t w = in ? picks[j] : 0;
+    const int p = (int)(w & (DV_MAXN - 1));
+    idx_out[x * k + j] = in ? cand_idx[x * N + p] : -1;
+    val_out[x * k + j] = in ? cand_val[x * N + p] : 0;
+    red_out[x * k + j] = in ? (int32_t)(w >> 10) : 0;
+  }
+  if (tid == 0) count_out[x] = t;
+}
+
+// words[x] = {entries listed, pairs with sim > 0, sum of sim over them, largest sim}; totals += / max
+__global__ __launch_bounds__(DV_THREADS) void list_redundancy_reduce_kernel(
+    const int32_t *__restrict__ idx, int k, uint32_t cap, const uint32_t *__restrict__ ws, int64_t *__restrict__ words,
+    unsigned long long *__restrict__ totals) {
+  __shared__ uint32_t fold[DV_WAVES][DV_MAXN];   // per wave: the largest milli towards each later position; 0 between rows
+  __shared__ uint32_t offs_s[DV_MAXN + 1];
+  __shared__ unsigned long long acc[3];
+  __shared__ uint32_t acc_max;
+  const int tid = threadIdx.x, w = tid >> 6, lane = lane_id();
+  const int64_t x = blockIdx.x;
+  const uint32_t *offs = ws + (size_t)x * (dv_offs_words(k) + cap);
+  const uint32_t *edges = offs + dv_offs_words(k);
+  uint32_t listed = 0;
+  for (int p = tid; p < DV_MAXN + 1; p += DV_THREADS) {
+    if (p <= k) offs_s[p] = offs[p];
+    if (p < k && idx[x * k + p] != -1) ++listed;
+  }
+  for (int i = tid; i < DV_WAVES * DV_MAXN; i += DV_THREADS) (&fold[0][0])[i] = 0;
+  if (tid == 0) {
+    acc[0] = acc[1] = acc[2] = 0;
+    acc_max = 0;
+  }
+  __syncthreads();
+  uint32_t pairs = 0, largest = 0;
+  unsigned long long sum = 0;
+  for (int p = w; p < k; p += DV_WAVES) {
+    const uint32_t beg = offs_s[p], end = offs_s[p + 1];
+    if (beg == end) continue;
+    for (uint32_t e = beg + lane; e < end; e += WAVE) {
+      const uint32_t he = edges[e], q = he & (DV_MAXN - 1);
+      if ((int)q > p) atomicMax(&fold[w][q], he >> 10);
+    }
+    // one wave: its LDS operations complete in program order; the fence keeps the compiler from moving them
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    for (uint32_t e = beg + lane; e < end; e += WAVE) {
+      const uint32_t he = edges[e], q = he & (DV_MAXN - 1);
+      if ((int)q > p) {
+        const uint32_t sim = atomicExch(&fold[w][q], 0u);   // the first half-edge of a pair takes it and clears the slot
+        if (sim > 0) {
+          ++pairs;
+          sum += sim;
+          largest = max(largest, sim);
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (listed) atomicAdd(&acc[0], (unsigned long long)listed);
+  if (pairs) {
+    atomicAdd(&acc[1], (unsigned long long)pairs);
+    atomicAdd(&acc[2], sum);
+    atomicMax(&acc_max, largest);
+  }
+  __syncthreads();
+  if (tid == 0) {
+    words[4 * x + 0] = (int64_t)acc[0];
+    words[4 * x + 1] = (int64_t)acc[1];
+    words[4 * x + 2] = (int64_t)acc[2];
+    words[4 * x + 3] = (int64_t)acc_max;
+    if (acc[0]) atomicAdd(&totals[0], acc[0]);
+    if (acc[1]) {
+      atomicAdd(&totals[1], acc[1]);
+      atomicAdd(&totals[2], acc[2]);
+      atomicMax(&totals[3], (unsigned long long)acc_max);
+    }
+  }
+}
+
+// half-edges per request that every well-formed pool of N with rows up to max_row needs at most
+uint32_t dv_cap_for(int64_t N, int64_t max_row) {
+  const int64_t per = max_row < N - 1 ? max_row : N - 1;
+  const int64_t cap = 2 * N * (per > 0 ? per : 0);
+  return (uint32_t)((cap + 3) & ~3ll);
+}
+
+// the capacity a workspace of `bytes` gives each of m requests (never above what any pool of N can hold); false when
+// not even the offsets fit
+bool dv_cap_from(size_t bytes, int64_t m, int N, uint32_t *cap) {
+  const size_t words = bytes / sizeof(uint32_t) / (size_t)m, offs = dv_offs_words(N);
+  if (words < offs) return false;
+  const size_t most = dv_cap_for(N, N), got = (words - offs) & ~(size_t)3;
+  *cap = (uint32_t)(got < most ? got : most);
+  return true;
+}
+}  // namespace
+
+QRLSH_EXPORT size_t qrlsh_diversify_workspace_bytes(int64_t m, int32_t N, int64_t max_row) {
+  if (m <= 0 || m > DV_MAX_M || N < 1 || N > DV_MAXN || max_row < 0) return 0;
+  return (size_t)m * (dv_offs_words(N) + dv_cap_for(N, max_row)) * sizeof(uint32_t);
+}
+
+QRLSH_EXPORT int qrlsh_diversify(const int32_t *cand_idx, const int32_t *cand_val, const int32_t *avail, int64_t m,
+                                 int32_t N, int64_t nq, const int64_t *q_off, const int32_t *q_idx,
+                                 const int32_t *q_milli, int32_t k, int64_t penalty, int32_t max_sim, int32_t *idx_out,
+                                 int32_t *val_out, int32_t *red_out, int32_t *count_out, uint32_t *flag_out,
+                                 void *workspace, size_t workspace_bytes, void *stream) {
+  QR_CHECK_ARG(N >= 1 && N <= DV_MAXN, "qrlsh_diversify: N=%d outside 1..%d", N, DV_MAXN);
+  QR_CHECK_ARG(k >= 1 && k <= N, "qrlsh_diversify: k=%d outside 1..N=%d", k, N);
+  QR_CHECK_ARG(penalty >= 0 && penalty <= QRLSH_DIVERSIFY_MAX_PENALTY, "qrlsh_diversify: penalty=%lld outside 0..%d",
+               (long long)penalty, QRLSH_DIVERSIFY_MAX_PENALTY);
+  QR_CHECK_ARG(max_sim >= 0 && max_sim <= 1001, "qrlsh_diversify: max_sim=%d outside 0..1001", max_sim);
+  QR_CHECK_ARG(m >= 0 && nq >= 0 && nq <= 2147483647ll, "qrlsh_diversify: bad sizes m=%lld nq=%lld", (long long)m,
+               (long long)nq);
+  QR_CHECK_ARG(flag_out, "qrlsh_diversify: flag_out is required");
+  if (m == 0) return QRLSH_OK;
+  QR_CHECK_ARG(cand_idx && cand_val && avail && idx_out && val_out && red_out && count_out,
+               "qrlsh_diversify: null pointer");
+  QR_CHECK_ARG(q_off && (nq == 0 || (q_idx && q_milli)), "qrlsh_diversify: null pointer among the lists");
+  if (m > DV_MAX_M) {
+    qrlsh_set_error("qrlsh_diversify: m=%lld above the %lld workgroups served", (long long)m, (long long)DV_MAX_M);
+    return QRLSH_EUNSUPPORTED;
+  }
+  QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_diversify: the workspace must be 16-byte aligned");
+  uint32_t cap = 0;
+  if (!workspace || !dv_cap_from(workspace_bytes, m, N, &cap)) {
+    qrlsh_set_error("qrlsh_diversify: needs at least %zu workspace bytes, got %zu",
+                    (size_t)m * dv_offs_words(N) * sizeof(uint32_t), workspace ? workspace_bytes : 0);
+    return QRLSH_EWORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uint32_t *ws = static_cast<uint32_t *>(workspace);
+  QR_LAUNCH("diversify_adjacency", diversify_adjacency_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, cand_idx,
+            avail, (int)N, nq, q_off, q_idx, q_milli, cap, ws, flag_out);
+  QR_LAUNCH("diversify_select", diversify_select_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, cand_idx, cand_val,
+            avail, (int)N, (int)k, penalty, (uint32_t)max_sim, cap, (const uint32_t *)ws, idx_out, val_out, red_out,
+            count_out);
+  QR_LAUNCH_CHECK("qrlsh_diversify");
+  return QRLSH_OK;
+}
+
+QRLSH_EXPORT int qrlsh_list_redundancy(const int32_t *idx, int64_t m, int32_t k, int64_t nq, const int64_t *q_off,
+                                       const int32_t *q_idx, const int32_t *q_milli, int64_t *words_out,
+                                       int64_t *totals_out, uint32_t *flag_out, void *workspace, size_t workspace_bytes,
+                                       void *stream) {
+  QR_CHECK_ARG(k >= 1 && k <= DV_MAXN, "qrlsh_list_redundancy: k=%d outside 1..%d", k, DV_MAXN);
+  QR_CHECK_ARG(m >= 0 && nq >= 0 && nq <= 2147483647ll, "qrlsh_list_redundancy: bad sizes m=%lld nq=%lld",
+               (long long)m, (long long)nq);
+  QR_CHECK_ARG(flag_out && totals_out, "qrlsh_list_redundancy: flag_out and totals_out are required");
+  if (m == 0) return QRLSH_OK;
+  QR_CHECK_ARG(idx && words_out, "qrlsh_list_redundancy: null pointer");
+  QR_CHECK_ARG(q_off && (nq == 0 || (q_idx && q_milli)), "qrlsh_list_redundancy: null pointer among the lists");
+  if (m > DV_MAX_M) {
+    qrlsh_set_error("qrlsh_list_redundancy: m=%lld above the %lld workgroups served", (long long)m,
+                    (long long)DV_MAX_M);
+    return QRLSH_EUNSUPPORTED;
+  }
+  QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_list_redundancy: the workspace must be 16-byte aligned");
+  uint32_t cap = 0;
+  if (!workspace || !dv_cap_from(workspace_bytes, m, k, &cap)) {
+    qrlsh_set_error("qrlsh_list_redundancy: needs at least %zu workspace bytes, got %zu",
+                    (size_t)m * dv_offs_words(k) * sizeof(uint32_t), workspace ? workspace_bytes : 0);
+    return QRLSH_EWORKSPACE;
+  }
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  uint32_t *ws = static_cast<uint32_t *>(workspace);
+  QR_LAUNCH("list_adjacency", list_adjacency_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, idx, (int)k, nq, q_off,
+            q_idx, q_milli, cap, ws, flag_out);
+  QR_LAUNCH("list_redundancy_reduce", list_redundancy_reduce_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, idx,
+            (int)k, cap, (const uint32_t *)ws, words_out, reinterpret_cast<unsigned long long *>(totals_out));
+  QR_LAUNCH_CHECK("qrlsh_list_redundancy");
+  return QRLSH_OK;
+}

@@ -27,6 +27,8 @@ SORT_HOST = 16
 SUM_PAIRWISE = 0
 SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
+DIVERSIFY_MAX_POOL = 1024
+DIVERSIFY_MAX_PENALTY = 1 << 20
 RANK_ALL = 0
 RANK_HELDOUT = 1
 INDEX_MAX_K = 256
@@ -166,6 +168,10 @@ SIGNATURES = {
     "qrlsh_recommend_users": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
                                              _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_diversify_workspace_bytes": (_sz, [_i64, _i32, _i64]),
+    "qrlsh_diversify": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp,
+                                       _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_list_redundancy": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_ratings_holdout": (ctypes.c_int, [_vp, _i64, _i64, _u64, _u64, _vp, _vp, _vp]),
     "qrlsh_evaluate_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_evaluate": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,

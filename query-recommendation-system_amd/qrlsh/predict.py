@@ -86,6 +86,22 @@ def fill_predictions(ratings, q_src, q_dst, q_milli, user_sims, query_weight=QUE
     return out
 
 
+def lists_csr(coo, nq, device):
+    """coo: (q_src, q_dst, q_milli) 1-D integer tensors sorted by source -> the device CSR the serving kernels take:
+    (q_off int64 (nq + 1,), q_idx int32, q_milli int32).  ValueError for a source outside [0, nq)."""
+    src = coo[0].to(device=device, dtype=torch.int64)
+    try:
+        counts = torch.bincount(src, minlength=nq)
+    except RuntimeError:   # a negative id
+        counts = None
+    if counts is None or counts.numel() != nq:
+        raise ValueError("a list's source query is outside [0, %d)" % nq)
+    q_off = torch.zeros((nq + 1,), dtype=torch.int64, device=device)
+    torch.cumsum(counts, dim=0, out=q_off[1:])
+    return (q_off, coo[1].to(device=device, dtype=torch.int32).contiguous(),
+            coo[2].to(device=device, dtype=torch.int32).contiguous())
+
+
 class ServeInputs:
     """The checked arguments of predict_users / recommend.for_users, and (after upload()) their device form.
     Every check that needs no device runs in the constructor, before anything is uploaded or the library loaded."""
@@ -140,18 +156,7 @@ class ServeInputs:
     def upload(self, device):
         from .recommend import _on_device
         self.r = _on_device(self.ratings, device)
-        nq = self.nq
-        src = self.coo[0].to(device=device, dtype=torch.int64)
-        try:
-            counts = torch.bincount(src, minlength=nq)
-        except RuntimeError:   # a negative id
-            counts = None
-        if counts is None or counts.numel() != nq:
-            raise ValueError("a list's source query is outside [0, %d)" % nq)
-        self.q_off = torch.zeros((nq + 1,), dtype=torch.int64, device=device)
-        torch.cumsum(counts, dim=0, out=self.q_off[1:])
-        self.q_idx = self.coo[1].to(device=device, dtype=torch.int32).contiguous()
-        self.q_milli = self.coo[2].to(device=device, dtype=torch.int32).contiguous()
+        self.q_off, self.q_idx, self.q_milli = lists_csr(self.coo, self.nq, device)
         us = self.user_sims
         u_idx, u_val, ku = us if isinstance(us, tuple) else user_lists(us, self.nu, device)
         self.u_idx, self.u_val = u_idx.to(device).contiguous(), u_val.to(device).contiguous()

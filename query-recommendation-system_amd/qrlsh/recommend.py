@@ -115,6 +115,18 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
     return idx, val, avail
 
 
+def _check_select_args(k, lo, slices):
+    """for_users' checks of k, lo and slices (top_k's own are the same) -> k as an int"""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
+        raise ValueError("k must be an integer in 1..%d, got %r" % (MAX_K, k))
+    k = int(k)
+    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= MAX_SLICES:
+        raise ValueError("slices must be an integer in 0..%d, got %r" % (MAX_SLICES, slices))
+    if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
+        raise ValueError("lo must be an int32, got %r" % (lo,))
+    return k
+
+
 def for_users(ratings, q_src, q_dst, q_milli, user_sims, users, k, lo=0, slices=0, sum_order="pairwise",
               query_weight=None, user_weight=None, default_mean=None, device="cuda"):
     """Top-k unrated queries of chosen users from the live lists, without a prediction matrix
@@ -126,17 +138,18 @@ def for_users(ratings, q_src, q_dst, q_milli, user_sims, users, k, lo=0, slices=
     [0, nq) and a user id outside [0, nu) (host ids before anything is uploaded; device ids and the lists through
     the library's flags)."""
     from . import predict
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
-        raise ValueError("k must be an integer in 1..%d, got %r" % (MAX_K, k))
-    k = int(k)
-    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= MAX_SLICES:
-        raise ValueError("slices must be an integer in 0..%d, got %r" % (MAX_SLICES, slices))
-    if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
-        raise ValueError("lo must be an int32, got %r" % (lo,))
+    k = _check_select_args(k, lo, slices)
     a = predict.ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, users, sum_order)
+    _lib.load()
+    a.upload(device)
+    return _serve(a, k, int(lo), int(slices), query_weight, user_weight, default_mean, device)
+
+
+def _serve(a, k, lo, slices, query_weight, user_weight, default_mean, device):
+    """for_users over checked and uploaded ServeInputs (for_users_diverse shares them with its rerank)"""
+    from . import predict
     m, nq = a.m, a.nq
     lib = _lib.load()
-    a.upload(device)
     idx = torch.empty((m, k), dtype=torch.int32, device=device)
     val = torch.empty((m, k), dtype=torch.int32, device=device)
     avail = torch.empty((m,), dtype=torch.int32, device=device)

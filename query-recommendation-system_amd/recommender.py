@@ -809,6 +809,51 @@ class Recommender:
                       "available": int(avail[i])}
         return out
 
+    def recommend_users_diverse(self, users, k, penalty, max_sim=1001, pool=None, sum_order=None, user_sim=None,
+                                ratings=None):
+        """recommend_users with the lists reranked on the device by the live neighbour lists (qrlsh.for_users_diverse):
+        from each user's `pool` best candidates (default min(1024, max(4 k, 64))) the k are picked greedily by
+        1000 * value - penalty * r, r = the largest stored similarity (milli) to a query already picked; candidates
+        with r >= max_sim are left out (1001: none is).  The remaining arguments as recommend_users takes them.
+        -> recommend_users' dict with 'redundancy' added: int64, the r each listed query had when it was picked (the
+        lists can be shorter than min(k, available) when max_sim excludes).  Raises ValueError for a bad k, pool,
+        penalty, max_sim, sum_order or user id."""
+        import importlib
+        dv = importlib.import_module("qrlsh.diversify")   # qrlsh.diversify itself is the function
+        k, penalty, max_sim = dv._check_rule(k, penalty, max_sim)
+        pool = dv._check_pool(k, pool)
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        out = dv.for_users_diverse(ratings, lists[0], lists[1], lists[2], user_sim, users, k, pool=pool,
+                                   penalty=penalty, max_sim=max_sim, sum_order=sum_order,
+                                   query_weight=self.query_weight, user_weight=self.user_weight,
+                                   default_mean=self.default_mean, device=self.device)
+        idx, val, red, count, avail = (ops.to_host(t) for t in out)
+        ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
+        recs = {}
+        for i, u in enumerate(ids):
+            n = int(count[i])
+            recs[u] = {"indexes": idx[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
+                       "available": int(avail[i]), "redundancy": red[i, :n].astype(np.int64)}
+        return recs
+
+    def list_redundancy(self, recs):
+        """How redundant served lists are, by the live neighbour lists: recs is a dict recommend / recommend_users /
+        recommend_users_diverse returned.  -> qrlsh.Redundancy: .words[i] = (entries, in-list pairs of stored
+        neighbours, the sum of their similarities in milli, the largest) for the i-th user of the dict, .totals,
+        .pairs_per_list, .mean_sim."""
+        import importlib
+        dv = importlib.import_module("qrlsh.diversify")
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        rows = [np.asarray(r["indexes"], dtype=np.int64) for r in recs.values()]
+        idx = np.full((len(rows), max([len(r) for r in rows] + [1])), -1, dtype=np.int64)
+        for i, r in enumerate(rows):
+            idx[i, :len(r)] = r
+        return dv.list_redundancy(idx, lists[0], lists[1], lists[2], int(self.queriesIDs.size), device=self.device)
+
     def predict_users(self, users, sum_order=None, user_sim=None, ratings=None):
         """DataFrame requested users x queriesIDs: their rows of compute_scores(reuse_lists=True)'s finalPredictions,
         from the live lists (arguments as recommend_users takes them)."""
