@@ -6,7 +6,7 @@ standardized ratings on the matrix cores (qrlsh_user_gram), its eigen-decomposit
 only BIRCH (2000 points of 200 dimensions) left to the reference's scikit-learn call.
 user_similarities(): everything after it (:263-288) on the device, with the hot path's own kernels: rows
 centred with the reference's integer truncation (qrlsh_center_rows), the pairs of every cluster from the
-bucket machinery (labels = a one-band key), cosine by qrlsh_score_pairs on the integer rows, negatives
+bucket machinery (the labels' dense ranks = a one-band key), cosine by qrlsh_score_pairs on the integer rows, negatives
 dropped, per-user top-K by qrlsh_topk_select_*.
 """
 import math
@@ -91,12 +91,15 @@ def center_rows(ratings):
 def cluster_pair_scores(ratings, labels, device="cuda"):
     """(pairs int64 [n] = u << 32 | v with u < v and labels[u] == labels[v], sorted; milli int32 [n] =
     rint(1000 * cosine of the two truncated centred rows)) on the device -- the O(sum of cluster_size^2 * nq)
-    part of recommender.py:263-276, every entry of every cluster's similarity matrix above its diagonal"""
+    part of recommender.py:263-276, every entry of every cluster's similarity matrix above its diagonal.
+    labels: any int64 values, -1 (scikit-learn's noise label) and the two ends of the range included: the bucket
+    machinery sees their dense ranks, never the values (the all-ones key is its mark of an empty answer set)"""
     r = ratings if isinstance(ratings, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(ratings), dtype=np.int32))
     r = r.to(device=device, dtype=torch.int32).contiguous()
     nu = r.shape[0]
     lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels), dtype=np.int64))
-    keys = lab.to(device=device, dtype=torch.int64).reshape(1, nu).contiguous()
+    lab = lab.to(device=device, dtype=torch.int64).reshape(-1)
+    keys = torch.unique(lab, return_inverse=True)[1].reshape(1, nu).contiguous()   # ranks in [0, nu): no read-back
     rows = center_rows(r)
     norms = ops.row_norms(rows)
     pairs = ops.candidate_pairs(keys, 4)                    # users sharing a label, u < v, sorted
@@ -106,7 +109,7 @@ def cluster_pair_scores(ratings, labels, device="cuda"):
 
 
 def user_similarities(ratings, labels, K=None, device="cuda"):
-    """ratings (nu, nq) integers (0 = missing), labels (nu,) cluster ids ->
+    """ratings (nu, nq) integers (0 = missing), labels (nu,) cluster ids, any int64 values (negative ones too) ->
     (src, dst, milli) int32 device tensors: for every user its at most K most similar users of the same cluster
     with POSITIVE rounded similarity, sorted by (user, value descending, neighbour id ascending).
     The reference's lists can also hold zero-valued entries (the user itself, negative cosines set to 0) when a
