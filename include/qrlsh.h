@@ -822,6 +822,46 @@ int qrlsh_list_redundancy(const int32_t *idx, int64_t m, int32_t k, int64_t nq, 
                           const int32_t *q_idx, const int32_t *q_milli, int64_t *words_out, int64_t *totals_out,
                           uint32_t *flag_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- tuning the rerank: qrlsh_diversify under S settings over one adjacency, each list scored on the device ---------
+ * qrlsh_diversify_grid applies qrlsh_diversify's rule, unchanged, to the same pools (cand_idx, cand_val, avail, m, N, k,
+ * the lists in CSR) under S settings: penalties int64 [S] and max_sims int32 [S], device arrays read on the device.
+ * Neither enters the adjacency, which is built ONCE per request (qrlsh_diversify's kernel and workspace:
+ * qrlsh_diversify_workspace_bytes(m, N, max_row)); one 256-thread workgroup per (request, setting) then runs the greedy
+ * loop (one copy of it serves both entry points), gathers the truth at the picks and folds the picks' half-edges of the
+ * POOL's adjacency towards later-ranked picks -- a served list is a subset of its pool, so no second adjacency is built.
+ * Scoring against held-out truth (truth == NULL switches it off): truth int32 [nu][nq]; users int32 [m] or NULL (request
+ *   x is user x); a pick is a hit when truth[user][col] >= relevant (>= 1); gain int64 [k], gain_prefix int64 [k + 1] as
+ *   qrlsh_evaluate_ranking takes them (a negative gain: flag bit 6); request_counts int64 [m][2] or NULL (zeros): the
+ *   relevant test cells and the test cells of each request, words 5 and 6 of a qrlsh_evaluate_ranking line.
+ * idx_out / val_out / red_out int32 [S][m][k], count_out int32 [S][m]: each NULL or, per setting, word for word what
+ *   qrlsh_diversify writes for that setting.
+ * per_request_out NULL or int64 [S][m][12]: 0 listed (the picks); 1 hits; 2 known (picks with truth != 0); 3 the 1-based
+ *   rank of the first hit (0 = none); 4 dcg = the sum of gain[p] over the hit positions; 5 relevant test cells and 6 test
+ *   cells (request_counts); 7 avail[x]; 8 the unordered in-list pairs with sim > 0; 9 the sum of sim over them; 10 the
+ *   largest sim (8-10 = qrlsh_list_redundancy's words 1-3 over the setting's list; a pair stored in both directions counts
+ *   once, at the larger milli); 11 the sum of red over the picks.  A request is not served when avail[x] < 0 or, with a
+ *   truth, when its user is outside [0, nu) (flag bit 5): words 0-6 and 8-11 = 0, word 7 = avail[x], nothing added to the
+ *   totals.
+ * totals_out int64 [S][24], required, ADDED to (the caller zeroes it; request blocks accumulate on the device): words
+ *   0-7 the column sums of words 0-7 over the requests served; 8 requests served; 9 requests with >= 1 relevant test
+ *   cell; 10 requests with >= 1 hit; 11 the sum of gain_prefix[min(k, relevant test cells)] (0-11 = qrlsh_evaluate_ranking's
+ *   totals over the diversified lists); 12 the sum of word 8; 13 of word 9; 14 the maximum of word 10; 15 the sum of word
+ *   11; 16 requests whose list differs from the plain prefix of their pool (a pick at step t that is not pool position
+ *   t, or fewer picks than min(k, n)); 17 requests that ended early (picks < min(k, n)); 18-23 = 0.  64-bit integer
+ *   atomic adds and one atomic max: exact in any launch order.  Without a truth words 1-6, 9, 10 and 11 stay 0.
+ * *flag_out as qrlsh_diversify (bits 0-3), and bit 4: a penalty outside 0 .. QRLSH_DIVERSIFY_MAX_PENALTY or a max_sim
+ *   outside 0 .. 1001 (that setting's lines are all zero, its lists empty, nothing added to its totals), bit 5, bit 6.
+ * Limits: qrlsh_diversify's (N, k, nq, m <= 2^24, the workspace), 1 <= S <= QRLSH_GRID_MAX_SETTINGS, and with a truth
+ * nu < 2^31 and relevant >= 1; QRLSH_EINVAL / QRLSH_EUNSUPPORTED / QRLSH_EWORKSPACE before any device work.  m = 0
+ * returns at once, the totals untouched.  No allocation, one stream, no read-back. */
+int qrlsh_diversify_grid(const int32_t *cand_idx, const int32_t *cand_val, const int32_t *avail, int64_t m, int32_t N,
+                         int64_t nq, const int64_t *q_off, const int32_t *q_idx, const int32_t *q_milli, int32_t k,
+                         const int64_t *penalties, const int32_t *max_sims, int32_t S, const int32_t *truth, int64_t nu,
+                         const int32_t *users, int32_t relevant, const int64_t *gain, const int64_t *gain_prefix,
+                         const int64_t *request_counts, int32_t *idx_out, int32_t *val_out, int32_t *red_out,
+                         int32_t *count_out, int64_t *per_request_out, int64_t *totals_out, uint32_t *flag_out,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- evaluation: the prediction error on rated cells, hold-out and leave-one-out -----------------------------------
  * The blend of cell (i, j) never reads ratings[i][j]: a rated cell can be predicted as if it were unrated and compared
  * with its rating.  Predictions and ratings are integers, so every statistic is an exact integer sum, independent of the

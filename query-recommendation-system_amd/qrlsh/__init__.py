@@ -39,6 +39,7 @@ from .answers import build_answer_index, encode_queries, answer_sets, AnswerInde
 from .recommend import top_k, for_users  # noqa: F401
 from .predict import predict_users, user_lists  # noqa: F401
 from .diversify import diversify, for_users_diverse, list_redundancy, Redundancy  # noqa: F401
+from .diversify import diversify_grid, evaluate_diversity, DiversityGrid  # noqa: F401
 from .evaluate import holdout, evaluate, evaluate_cells, Evaluation  # noqa: F401
 from .ranking import dcg_gains, evaluate_ranking, RankingEvaluation  # noqa: F401
 from .tune import evaluate_grid, GridEvaluation  # noqa: F401

@@ -171,6 +171,8 @@ SIGNATURES = {
     "qrlsh_diversify_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "qrlsh_diversify": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_diversify_grid": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64,
+                                            _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_list_redundancy": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_ratings_holdout": (ctypes.c_int, [_vp, _i64, _i64, _u64, _u64, _vp, _vp, _vp]),
     "qrlsh_evaluate_workspace_bytes": (_sz, [_i64, _i64]),

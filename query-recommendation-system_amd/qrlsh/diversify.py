@@ -6,7 +6,11 @@ lists are top-K cuts: one direction is often missing, both count).  A pool is a 
 k = N <= 1024: candidates (col, val) in served order.  Greedily, for t = 0 .. k - 1, over the unpicked candidates c:
 r_c = max over the picked s of sim(c, s); c is eligible when r_c < max_sim; the eligible c with the largest
 1000 * val_c - penalty * r_c (int64) is picked, ties to the smaller pool position; a request ends early when nobody is
-eligible.  penalty is rating points x 1000 per unit of similarity, max_sim is in milli (1001: nothing is excluded)."""
+eligible.  penalty is rating points x 1000 per unit of similarity, max_sim is in milli (1001: nothing is excluded).
+
+Which penalty, which max_sim?  diversify_grid / evaluate_diversity (qrlsh_diversify_grid) run the rule under a list of
+settings over one adjacency per request and score every setting's lists on the device: evaluate_ranking's words against
+a held-out truth and list_redundancy's words, 24 exact integer totals per setting -> DiversityGrid."""
 import numpy as np
 import torch
 
@@ -20,7 +24,13 @@ WORKSPACE_BUDGET = 1 << 30   # bytes of workspace per library call; more request
 _FLAG_TEXT = ((1, "a query's neighbour index is outside [0, %(nq)d)"),
               (2, "a candidate column is outside [0, %(nq)d)"),
               (4, "a candidate appears twice in one pool"),
-              (8, "a pool's edges do not fit the workspace (a list row names a query twice?)"))
+              (8, "a pool's edges do not fit the workspace (a list row names a query twice?)"),
+              (16, "a setting's penalty or max_sim is outside its range"),
+              (32, "a user id is outside the truth's rows"),
+              (64, "gains must not be negative"))
+MAX_SETTINGS = 128    # QRLSH_GRID_MAX_SETTINGS: settings per library call
+GRID_LINE, GRID_TOTALS = 12, 24
+GRID_METRICS = ("ndcg", "precision", "recall", "hit_rate")
 
 
 def _int_in(x, lo, hi, name):
@@ -204,3 +214,258 @@ def list_redundancy(idx, q_src, q_dst, q_milli, nq, device="cuda"):
     host = out.cpu().numpy()
     _raise_flags(int(host[4 * m + 4]), nq)
     return Redundancy(host[:4 * m].reshape(m, 4).copy(), host[4 * m:4 * m + 4].copy())
+
+
+# ------------------------------------------------------------------- the rerank under a grid of settings, scored
+def _check_settings(settings):
+    try:
+        rows = [tuple(x) for x in settings]
+    except TypeError:
+        rows = []
+    if not rows or any(len(r) != 2 for r in rows):
+        raise ValueError("settings must be a non-empty sequence of (penalty, max_sim) pairs")
+    return [(_int_in(p, 0, MAX_PENALTY, "penalty"), _int_in(ms, 0, 1001, "max_sim")) for p, ms in rows]
+
+
+def _ratios(a, b):
+    return [int(x) / int(y) if int(y) else float("nan") for x, y in zip(a, b)]
+
+
+class DiversityGrid:
+    """The result of diversify_grid() / evaluate_diversity() / Recommender.tune_diversity().
+    settings: the S (penalty, max_sim) pairs.  totals: host int64 (S, 24) per setting -- words 0-7 the column sums of the
+      per-request words 0-7 (listed, hits, known, first_hit, dcg, relevant test cells, test cells, avail), 8 requests
+      served, 9 requests with >= 1 relevant test cell, 10 requests with >= 1 hit, 11 the sum of the ideal DCG (0-11 are
+      RankingEvaluation.totals over the diversified lists), 12 in-list pairs of stored neighbours, 13 the sum of their
+      similarities (milli), 14 the largest, 15 the sum of the picks' red, 16 requests whose list differs from the plain
+      prefix of their pool, 17 requests that ended before min(k, pool).
+    per_request: device int64 (S, m, 12) (want_per_request) -- the eight words above, then the list's pairs, their
+      similarity sum, the largest similarity and the sum of red.  idx, val, red (S, m, k), count (S, m): device int32,
+      diversify()'s output per setting (want_lists).
+    Per setting, lists of Python floats: precision, recall, ndcg, hit_rate with RankingEvaluation's divisions (nan on a
+    zero denominator, as without a truth); pairs_per_list and mean_sim as Redundancy computes them (over the requests
+    served); changed_share = word 16 / requests served; ended_early = word 17 (a count)."""
+
+    def __init__(self, settings, totals, per_request=None, idx=None, val=None, red=None, count=None):
+        self.settings = [(int(p), int(ms)) for p, ms in settings]
+        self.totals = np.asarray(totals, dtype=np.int64).reshape(len(self.settings), GRID_TOTALS)
+        self.per_request, self.idx, self.val, self.red, self.count = per_request, idx, val, red, count
+        t = self.totals
+        self.precision = _ratios(t[:, 1], t[:, 0])
+        self.recall = _ratios(t[:, 1], t[:, 5])
+        self.hit_rate = _ratios(t[:, 10], t[:, 9])
+        self.ndcg = _ratios(t[:, 4], t[:, 11])
+        self.pairs_per_list = [int(x) / int(y) if int(y) else 0.0 for x, y in zip(t[:, 12], t[:, 8])]
+        self.mean_sim = [int(x) / int(y) / 1000.0 if int(y) else 0.0 for x, y in zip(t[:, 13], t[:, 12])]
+        self.changed_share = [int(x) / int(y) if int(y) else 0.0 for x, y in zip(t[:, 16], t[:, 8])]
+        self.ended_early = [int(x) for x in t[:, 17]]
+
+    def setting(self, index):
+        """(penalty, max_sim) of setting `index`"""
+        return self.settings[int(index)]
+
+    def _metric(self, metric):
+        if metric not in GRID_METRICS:
+            raise ValueError("metric must be one of %s" % (GRID_METRICS,))
+        return getattr(self, metric)
+
+    def best(self, metric="ndcg", max_pairs_per_list=None):
+        """The setting with the highest `metric` ('ndcg', 'precision', 'recall' or 'hit_rate') among those with
+        pairs_per_list <= max_pairs_per_list (None: all of them); ties go to the lowest index; a setting without a figure
+        (nan) never wins.  -> (penalty, max_sim, index).  ValueError when no setting is within the bound."""
+        value = self._metric(metric)
+        ok = [v == v and (max_pairs_per_list is None or p <= float(max_pairs_per_list))
+              for v, p in zip(value, self.pairs_per_list)]
+        if not any(ok):
+            raise ValueError("no setting has a %s at pairs_per_list <= %r" % (metric, max_pairs_per_list))
+        index = max((i for i in range(len(value)) if ok[i]), key=lambda i: (value[i], -i))
+        return self.settings[index] + (index,)
+
+    def least_redundant(self, metric="ndcg", keep=0.98):
+        """Among the settings whose `metric` is at least `keep` times the grid's largest: the one with the fewest pairs
+        per list, then the smallest similarity sum, then the lowest index.  -> (penalty, max_sim, index).  ValueError
+        when no setting has a figure."""
+        value = self._metric(metric)
+        known = [v for v in value if v == v]
+        if not known:
+            raise ValueError("no setting has a %s" % metric)
+        bar = float(keep) * max(known)
+        index = min((i for i in range(len(value)) if value[i] == value[i] and value[i] >= bar),
+                    key=lambda i: (self.pairs_per_list[i], int(self.totals[i, 13]), i))
+        return self.settings[index] + (index,)
+
+    def __repr__(self):
+        return "DiversityGrid(%d settings, %d requests)" % (len(self.settings), int(self.totals[0, 8]))
+
+
+def _grid(ci, cv, av, csr, nq, k, settings, max_row, device, scoring=None, want_per_request=False, want_lists=False):
+    """diversify_grid() over device int32 pools and the device CSR of the lists.  scoring: None or (truth int32 (nu, nq),
+    users int32 (m,) or None, relevant, gain int64 (k,), gain_prefix int64 (k + 1,), request_counts int64 (m, 2) or
+    None), device tensors."""
+    lib = _lib.load()
+    m, n = (int(d) for d in ci.shape)
+    S = len(settings)
+    pen = torch.tensor([p for p, _ in settings], dtype=torch.int64, device=device)
+    cut = torch.tensor([ms for _, ms in settings], dtype=torch.int32, device=device)
+    per = torch.zeros((S, m, GRID_LINE), dtype=torch.int64, device=device) if want_per_request else None
+    lists = None
+    if want_lists:
+        lists = [torch.empty((S, m, k), dtype=torch.int32, device=device) for _ in range(3)]
+        lists.append(torch.empty((S, m), dtype=torch.int32, device=device))
+    back = torch.zeros((S * GRID_TOTALS + 1,), dtype=torch.int64, device=device)   # [totals S x 24][flag: low half]
+    if m:
+        blk, ws = _block(lib, m, n, max_row, device)
+        widest = min(S, MAX_SETTINGS)
+        whole = blk >= m
+        tmp = None
+        if not whole:   # a row block's [settings][rows] outputs, copied into place after each call
+            tmp = [torch.empty((widest * blk * w,), dtype=dt, device=device) if on else None
+                   for w, dt, on in ((k, torch.int32, want_lists), (k, torch.int32, want_lists),
+                                     (k, torch.int32, want_lists), (1, torch.int32, want_lists),
+                                     (GRID_LINE, torch.int64, want_per_request))]
+        if scoring is None:
+            truth, users, relevant, gain, prefix, counts, nu = None, None, 1, None, None, None, 0
+        else:
+            truth, users, relevant, gain, prefix, counts = scoring
+            nu = int(truth.shape[0])
+            if users is None and not whole:   # request x of a later block is still row i0 + x
+                users = torch.arange(m, dtype=torch.int32, device=device)
+        st = _stream()
+        for c0 in range(0, S, MAX_SETTINGS):
+            c1 = min(S, c0 + MAX_SETTINGS)
+            for i0 in range(0, m, blk):
+                i1 = min(m, i0 + blk)
+                if whole:
+                    outs = [t[c0:c1] for t in lists] if want_lists else [None] * 4
+                    outs.append(per[c0:c1] if want_per_request else None)
+                else:
+                    outs = tmp
+                _lib.check(lib.qrlsh_diversify_grid(
+                    _ptr(ci[i0:i1]), _ptr(cv[i0:i1]), _ptr(av[i0:i1]), i1 - i0, n, nq, _ptr(csr[0]), _ptr(csr[1]),
+                    _ptr(csr[2]), k, _ptr(pen[c0:c1]), _ptr(cut[c0:c1]), c1 - c0,
+                    None if truth is None else _ptr(truth), nu, None if users is None else _ptr(users[i0:i1]),
+                    int(relevant), None if gain is None else _ptr(gain), None if prefix is None else _ptr(prefix),
+                    None if counts is None else _ptr(counts[i0:i1]), *(None if t is None else _ptr(t) for t in outs),
+                    _ptr(back[c0 * GRID_TOTALS:]), _ptr(back[S * GRID_TOTALS:]), _ptr(ws), ws.numel(), st))
+                if not whole:
+                    full = (lists if want_lists else [None] * 4) + [per]
+                    for dst, src in zip(full, tmp):
+                        if dst is not None:
+                            shape = (c1 - c0, i1 - i0) + tuple(dst.shape[2:])
+                            dst[c0:c1, i0:i1] = src[:int(np.prod(shape))].view(shape)
+    host = back.cpu().numpy()   # the flags together with the totals
+    _raise_flags(int(host[S * GRID_TOTALS]), nq)
+    return DiversityGrid(settings, host[:S * GRID_TOTALS].copy(), per, *(lists or [None] * 4))
+
+
+def _scoring_checks(k, m, relevant, gains):
+    """the scoring arguments that need no device -> (relevant, gain, gain_prefix) host values"""
+    from . import ranking
+    if isinstance(relevant, bool) or not isinstance(relevant, (int, np.integer)) or not 1 <= int(relevant) < 2**31:
+        raise ValueError("relevant must be an int32 >= 1, got %r" % (relevant,))
+    gain, prefix = ranking._gain_tables(gains, k, m)
+    return int(relevant), gain, prefix
+
+
+def diversify_grid(cand_idx, cand_val, avail, q_src, q_dst, q_milli, nq, k, settings, truth=None, users=None,
+                   relevant=None, gains=None, request_counts=None, want_per_request=False, want_lists=False,
+                   device="cuda"):
+    """diversify() under every (penalty, max_sim) of `settings` at once, each setting's lists scored on the device
+    (qrlsh_diversify_grid): the adjacency of a pool does not depend on the setting and is built once per request; per
+    setting there is the greedy selection, the truth at the picks and the redundancy of the list, folded out of the
+    pool's adjacency.  Pools, lists, nq and k as diversify takes them.
+    truth: None, or (nu, nq) integers -- the held-out matrix the picks are held to; then users: (m,) row ids (None:
+    request x is row x, m <= nu), relevant: a pick with truth >= relevant is a hit (an int32 >= 1, required), gains: k
+    non-negative integers (default dcg_gains(k)), request_counts: None or (m, 2) integers, the relevant test cells and
+    the test cells of each request (words 5 and 6 of evaluate_ranking's per_user lines; None: zeros, so recall, hit_rate
+    and ndcg have no denominator).
+    More than 128 settings run as successive library calls over the same pools and are stitched together; requests run
+    in row blocks under WORKSPACE_BUDGET and the blocks' totals are added on the device.
+    -> DiversityGrid (two read-backs: the longest list row, then the flags together with the totals).
+    Raises ValueError before anything is uploaded for a bad k, setting, nq, shape, relevant, gains or host user id, and
+    through the library's flags as diversify does, and for a device user id outside the truth's rows."""
+    k = _check_rule(k, 0, 1001)[0]
+    settings = _check_settings(settings)
+    nq = _int_in(nq, 0, 2**31 - 1, "nq")
+    ci, cv, av = _int_array(cand_idx, 2, "cand_idx"), _int_array(cand_val, 2, "cand_val"), _int_array(avail, 1, "avail")
+    if tuple(ci.shape) != tuple(cv.shape) or av.shape[0] != ci.shape[0]:
+        raise ValueError("cand_idx %s, cand_val %s and avail %s do not belong together"
+                         % (tuple(ci.shape), tuple(cv.shape), tuple(av.shape)))
+    m, n = (int(d) for d in ci.shape)
+    if not k <= n <= MAX_POOL:
+        raise ValueError("k <= N <= %d is required, got k=%d N=%d" % (MAX_POOL, k, n))
+    coo = _coo(q_src, q_dst, q_milli)
+    scoring = None
+    if truth is None:
+        if users is not None or request_counts is not None or gains is not None or relevant is not None:
+            raise ValueError("users, relevant, gains and request_counts need a truth")
+    else:
+        tt = _int_array(truth, 2, "truth")
+        nu = int(tt.shape[0])
+        if int(tt.shape[1]) != nq:
+            raise ValueError("truth has %d columns, nq = %d" % (int(tt.shape[1]), nq))
+        relevant, gain, prefix = _scoring_checks(k, m, relevant, gains)
+        if users is None:
+            if m > nu:
+                raise ValueError("%d requests but %d rows of truth: pass users" % (m, nu))
+            ut = None
+        else:
+            ut = _int_array(users, 1, "users")
+            if ut.numel() != m:
+                raise ValueError("users must name one row per request (%d), got %d" % (m, ut.numel()))
+            if not ut.is_cuda and m and (int(ut.min()) < 0 or int(ut.max()) >= nu):
+                raise ValueError("user id outside [0, %d)" % nu)
+        rc = None
+        if request_counts is not None:
+            rc = _int_array(request_counts, 2, "request_counts")
+            if tuple(rc.shape) != (m, 2):
+                raise ValueError("request_counts must have shape (%d, 2), got %s" % (m, tuple(rc.shape)))
+        scoring = (tt, ut, relevant, gain, prefix, rc)
+    from . import predict
+    _lib.load()
+    csr = predict.lists_csr(coo, nq, device)
+    if scoring is not None:
+        tt, ut, relevant, gain, prefix, rc = scoring
+        if ut is not None:   # ids past int32 must stay out of range, not wrap into it
+            ut = ut.to(device=device, dtype=torch.int64).clamp(-1, nu).to(torch.int32).contiguous()
+        scoring = (_i32(tt, device), ut, relevant, torch.from_numpy(gain).to(device), torch.from_numpy(prefix).to(device),
+                   None if rc is None else rc.to(device=device, dtype=torch.int64).contiguous())
+    return _grid(_i32(ci, device), _i32(cv, device), _i32(av, device), csr, nq, k, settings, _max_row(csr[0]), device,
+                 scoring, want_per_request, want_lists)
+
+
+def evaluate_diversity(train, truth, q_src, q_dst, q_milli, user_sims, k, relevant, settings, pool=None, users=None,
+                       gains=None, lo=0, slices=0, sum_order="pairwise", want_per_request=False, want_lists=False,
+                       query_weight=None, user_weight=None, default_mean=None, device="cuda"):
+    """What does each (penalty, max_sim) cost in NDCG, and what redundancy does it remove?  evaluate_ranking(train, ...,
+    candidates="all") at k = pool serves every request its pool and counts its test cells; diversify_grid then reranks
+    those pools to k under every setting and holds each list to `truth`.  The pools never leave the device.
+    train / truth, the lists, user_sims, users, relevant, lo, slices, sum_order and the weights: as evaluate_ranking
+    takes them; pool: candidates per request, default min(1024, max(4 k, 64)); gains: k integers, default dcg_gains(k);
+    settings, want_per_request, want_lists: as diversify_grid takes them.  Setting (0, 1001) gives evaluate_ranking(...,
+    k)'s figures.  -> DiversityGrid.  Raises what evaluate_ranking and diversify_grid raise; every check that needs no
+    device precedes any upload."""
+    from . import predict, ranking
+    from .recommend import _matrix, _on_device
+    k = _check_rule(k, 0, 1001)[0]
+    pool = _check_pool(k, pool)
+    settings = _check_settings(settings)
+    ranking.check_arguments(pool, relevant, "all", lo, slices)
+    a = predict.ServeInputs(train, q_src, q_dst, q_milli, user_sims, users, sum_order)
+    truth = _matrix(truth, "truth")
+    if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
+        raise ValueError("truth has shape %s, train %s" % (tuple(truth.shape), (a.nu, a.nq)))
+    relevant, gain, prefix = _scoring_checks(k, a.m, relevant, gains)
+    pool_gains = ranking._gain_tables(None, pool, a.m)
+    weights = tuple(d if w is None else w for w, d in ((query_weight, predict.QUERY_WEIGHT),
+                                                       (user_weight, predict.USER_WEIGHT),
+                                                       (default_mean, predict.DEFAULT_MEAN)))
+    _lib.load()
+    a.upload(device)
+    t = _on_device(truth, device)
+    ev = ranking._score(a, t, pool, relevant, "all", pool_gains[0], pool_gains[1], lo, slices, weights)
+    dev = a.r.device
+    scoring = (t, a.ut, relevant, torch.from_numpy(gain).to(dev), torch.from_numpy(prefix).to(dev),
+               ev.per_user[:, 5:7].contiguous())
+    return _grid(ev.idx, ev.val, ev.avail, (a.q_off, a.q_idx, a.q_milli), a.nq, k, settings, _max_row(a.q_off), dev,
+                 scoring, want_per_request, want_lists)

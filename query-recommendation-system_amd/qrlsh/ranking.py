@@ -132,20 +132,26 @@ def evaluate_ranking(train, truth, q_src, q_dst, q_milli, user_sims, k, relevant
     negative, or m x their sum >= 2^63), lo, slices or sum_order, a truth of another shape and a user id outside the
     matrix; through the library's flags for a list longer than 64, a neighbour index outside [0, nq) and a device user
     id outside [0, nu)."""
-    from . import recommend
     from .recommend import _matrix, _on_device
     k = check_arguments(k, relevant, candidates, lo, slices)
     a = ServeInputs(train, q_src, q_dst, q_milli, user_sims, users, sum_order)
     truth = _matrix(truth, "truth")
     if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
         raise ValueError("truth has shape %s, train %s" % (tuple(truth.shape), (a.nu, a.nq)))
-    m, nq = a.m, a.nq
-    gain, prefix = _gain_tables(gains, k, m)
-
-    lib = _lib.load()
+    gain, prefix = _gain_tables(gains, k, a.m)
+    _lib.load()
     a.upload(device)
+    return _score(a, _on_device(truth, device), k, relevant, candidates, gain, prefix, lo, slices,
+                  (query_weight, user_weight, default_mean))
+
+
+def _score(a, t, k, relevant, candidates, gain, prefix, lo, slices, weights):
+    """evaluate_ranking over uploaded ServeInputs `a`, the device truth `t` and checked gain tables (host arrays);
+    weights = (query_weight, user_weight, default_mean)"""
+    from . import recommend
+    lib = _lib.load()
+    m, nq = a.m, a.nq
     dev = a.r.device
-    t = _on_device(truth, device)
     gain_d, prefix_d = torch.from_numpy(gain).to(dev), torch.from_numpy(prefix).to(dev)
     idx = torch.empty((m, k), dtype=torch.int32, device=dev)
     val = torch.empty((m, k), dtype=torch.int32, device=dev)
@@ -163,7 +169,7 @@ def evaluate_ranking(train, truth, q_src, q_dst, q_milli, user_sims, k, relevant
     ws = torch.empty((max(int(size(blk, nq, k, int(slices))), 16),), dtype=torch.uint8, device=dev)
     starts = range(0, m, blk)
     back = torch.zeros((len(starts), 17), dtype=torch.int64, device=dev)   # per block [totals: 16][flags: low half]
-    args = a.lists_args(query_weight, user_weight, default_mean)
+    args = a.lists_args(*weights)
     st = _stream()
     for b, i0 in enumerate(starts):
         i1 = min(m, i0 + blk)

@@ -71,6 +71,8 @@ class Recommender:
     query_weight = QUERY_WEIGHT   # the blend every serving call uses (recommender.py:32-34 of the reference); tune(apply=True)
     user_weight = USER_WEIGHT     # sets the three on the instance
     default_mean = DEFAULT_MEAN
+    diversity_penalty = 0      # the rerank recommend_users_diverse applies when called without one: the plain list;
+    diversity_max_sim = 1001   # tune_diversity(apply=True) sets the two on the instance
 
     def init(self, users, queries, queriesIDs, dataset, ratings):
         """recommender.py:51-64.  Takes what main.py:23-85 passes -- `datatable` Frames (anything Frame-like:
@@ -809,17 +811,21 @@ class Recommender:
                       "available": int(avail[i])}
         return out
 
-    def recommend_users_diverse(self, users, k, penalty, max_sim=1001, pool=None, sum_order=None, user_sim=None,
+    def recommend_users_diverse(self, users, k, penalty=None, max_sim=None, pool=None, sum_order=None, user_sim=None,
                                 ratings=None):
         """recommend_users with the lists reranked on the device by the live neighbour lists (qrlsh.for_users_diverse):
         from each user's `pool` best candidates (default min(1024, max(4 k, 64))) the k are picked greedily by
         1000 * value - penalty * r, r = the largest stored similarity (milli) to a query already picked; candidates
-        with r >= max_sim are left out (1001: none is).  The remaining arguments as recommend_users takes them.
+        with r >= max_sim are left out (1001: none is).  penalty / max_sim = None: self.diversity_penalty /
+        self.diversity_max_sim (0 and 1001, the plain list, until tune_diversity(apply=True) sets them).  The remaining
+        arguments as recommend_users takes them.
         -> recommend_users' dict with 'redundancy' added: int64, the r each listed query had when it was picked (the
         lists can be shorter than min(k, available) when max_sim excludes).  Raises ValueError for a bad k, pool,
         penalty, max_sim, sum_order or user id."""
         import importlib
         dv = importlib.import_module("qrlsh.diversify")   # qrlsh.diversify itself is the function
+        penalty = self.diversity_penalty if penalty is None else penalty
+        max_sim = self.diversity_max_sim if max_sim is None else max_sim
         k, penalty, max_sim = dv._check_rule(k, penalty, max_sim)
         pool = dv._check_pool(k, pool)
         if users is not None and not isinstance(users, torch.Tensor):
@@ -1020,6 +1026,40 @@ class Recommender:
                 self.set_list_lengths(*self._cut_plan(qc if q_cuts is not None else None, uc if u_cuts is not None else None))
             if apply:
                 self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
+        return grid
+
+    # ---- and which rerank: accuracy and redundancy of the diversified lists per (penalty, max_sim) (qrlsh.diversify) ---
+    def tune_diversity(self, k, relevant, settings, pool=None, fraction=0.1, seed=0, users=None, sum_order=None,
+                       user_sim=None, metric="ndcg", max_pairs_per_list=None, apply=False):
+        """What each (penalty, max_sim) of `settings` costs in precision / recall / NDCG at k on held-out cells and what
+        redundancy it removes, from one sweep and one adjacency per request -> qrlsh.DiversityGrid (.totals, .precision,
+        .recall, .ndcg, .hit_rate, .pairs_per_list, .mean_sim, .changed_share, .ended_early, .best(),
+        .least_redundant()).  The split and the user side are those of evaluate_ranking: _holdout_inputs; every
+        requested user (default: all) is served a pool of `pool` candidates (default min(1024, max(4 k, 64))) from the
+        train copy with the blend served now, the pool is reranked to k under every setting by the live neighbour
+        lists as they stand, and each list is held to self.ratings.  Setting (0, 1001) is the plain list:
+        evaluate_ranking(k, relevant)'s figures.
+        apply=True sets diversity_penalty and diversity_max_sim to the best pair by `metric` among the settings with
+        pairs_per_list <= max_pairs_per_list (DiversityGrid.best), so recommend_users_diverse called without a penalty
+        uses it from then on.  Nothing else of self is modified.  ValueError as qrlsh.evaluate_diversity raises it, and
+        from best() when apply is set."""
+        import importlib
+        from qrlsh.evaluate import keep_word
+        dv = importlib.import_module("qrlsh.diversify")
+        keep_word(fraction)
+        k = dv._check_rule(k, 0, 1001)[0]
+        pool = dv._check_pool(k, pool)
+        settings = dv._check_settings(settings)
+        if metric not in dv.GRID_METRICS:
+            raise ValueError("metric must be one of %s" % (dv.GRID_METRICS,))
+        if users is not None and not isinstance(users, torch.Tensor):
+            users = np.asarray(users)
+        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
+        grid = dv.evaluate_diversity(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, settings,
+                                     pool=pool, users=users, sum_order=sum_order, query_weight=self.query_weight,
+                                     user_weight=self.user_weight, default_mean=self.default_mean, device=self.device)
+        if apply:
+            self.diversity_penalty, self.diversity_max_sim, _ = grid.best(metric, max_pairs_per_list)
         return grid
 
     def top_k_queries(self, to_predict, predictions, missed, ask=input):
