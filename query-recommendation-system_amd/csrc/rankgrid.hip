@@ -8,8 +8,8 @@
 //   rank_grid_count_kernel  counts the test cells of every (request, column slice); an exclusive scan of the counts gives
 //                           each slice its place in the record arrays, so a request's records lie together in column
 //                           order and the arrays follow the number of test cells, never nq x settings;
-//   rank_grid_sweep_kernel  rank_sweep_kernel<true>'s geometry (the user's row as bytes in LDS, the test cells of a slice
-//                           queued in LDS and served 1024 at a time) writes the records;
+//   rank_grid_sweep_kernel  rank_sweep_kernel<true>'s geometry (rankeval.hip: the user's row as bytes in LDS, the test
+//                           cells of a slice queued in LDS and served 1024 at a time) writes the records;
 //   rank_grid_rank_kernel   one workgroup per (request, setting): blends every record (ev_blend, rint), finds the list's
 //                           boundary by a radix select over the whole int32 range (no value window, so no fallback),
 //                           collects the <= k listed (prediction, column, relevant) keys in LDS in column order (a stable
@@ -22,7 +22,6 @@
 #include "evalsides.h"
 
 constexpr int RG_THREADS = 1024;           // sweep
-constexpr int RG_QUEUE = 2 * RG_THREADS;   // fewer than RG_THREADS cells wait when up to RG_THREADS more arrive
 constexpr int RG_AUTO_GROUPS = 4096;       // column slices: about this many sweep workgroups
 constexpr int RGC_THREADS = 256;           // count
 constexpr int RGK_THREADS = 256;           // rank
@@ -79,12 +78,11 @@ __global__ __launch_bounds__(RG_THREADS) void rank_grid_sweep_kernel(
     int64_t slices, const uint64_t *__restrict__ off, int64_t cap, int32_t *__restrict__ col, int32_t *__restrict__ tru,
     double *__restrict__ sides) {
   __shared__ uint8_t lrow[PR_MAXQ];
-  __shared__ int32_t queue_j[RG_QUEUE];
-  __shared__ int32_t queue_v[RG_QUEUE];
+  __shared__ int32_t queue_j[EV_QUEUE_SLOTS<RG_THREADS>];
+  __shared__ int32_t queue_v[EV_QUEUE_SLOTS<RG_THREADS>];
   __shared__ uint32_t wsum[RG_THREADS / WAVE];
   __shared__ int wide;
   const int64_t s = blockIdx.x / m, x = blockIdx.x - s * m;
-  const int t = threadIdx.x;
   const int64_t per = (nq + slices - 1) / slices;
   const int64_t j0 = s * per, j1 = min(nq, j0 + per);
   const int64_t i = users ? (int64_t)users[x] : x;
@@ -99,7 +97,7 @@ __global__ __launch_bounds__(RG_THREADS) void rank_grid_sweep_kernel(
   const int32_t *ui = u_idx + i * ku;
   const double *uv = u_val + i * ku;
   int mu = 0;
-  while (mu < ku && ui[mu] >= 0) ++mu;  // uniform: the user's own neighbour list
+  while (mu < ku && ui[mu] >= 0) ++mu;  // uniform: the user's own neighbour list (written out: see the queue below)
   // the cuts (uniform; a negative one is flagged and reads as 0) and the user list's length under each
   int qc[QRLSH_GRID_MAX_CUTS], um[QRLSH_GRID_MAX_CUTS];
 #pragma unroll
@@ -109,6 +107,12 @@ __global__ __launch_bounds__(RG_THREADS) void rank_grid_sweep_kernel(
   }
   const bool seq = sequential != 0;
   // one test cell: its sides under every cut -> record base + slot (slot = its rank among the slice's test cells)
+  // The queue is ev_cell_queue's (evalsides.h), written out with its ring and barriers, and so is the list-length loop
+  // above: through both helpers this kernel measured up to 1.7 % slower than before with 16 requests, through the queue
+  // helper alone still 1.1 to 1.3 % on thin samples.  As written it compiles to the instructions it had before
+  // (profiles/predict_split_parent_vs_branch.json: rank_grid_probe and diagnostic_rank_grid_sweep).
+  constexpr int RG_QUEUE = EV_QUEUE_SLOTS<RG_THREADS>;
+  const int t = threadIdx.x;
   auto one = [&](uint32_t slot) {
     const int64_t j = queue_j[slot & (RG_QUEUE - 1)];
     const int32_t tv = queue_v[slot & (RG_QUEUE - 1)];
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(RG_THREADS) void rank_grid_sweep_kernel(
           const int n = min((int)n64, qc[c]);
           if (c > 0 && n == last) qp[c] = qp[c - 1];  // the list is no longer than either cut: the same prefix
           else
-            qp[c] = ev_query_side(
+            qp[c] = ev_query_side<true>(
                 nq, j, lo, n, q_idx, q_milli, seq, [&](int32_t q) { return in_lds ? (int32_t)lrow[q] : row[q]; }, outside);
           last = n;
         }
@@ -132,7 +136,7 @@ __global__ __launch_bounds__(RG_THREADS) void rank_grid_sweep_kernel(
       for (int c = 0; c < QRLSH_GRID_MAX_CUTS; ++c) {
         if (c < ncu) {
           if (c > 0 && um[c] == um[c - 1]) up[c] = up[c - 1];  // uniform
-          else up[c] = ev_user_side(train, nu, nq, i, j, ui, uv, um[c], seq);
+          else up[c] = ev_user_side<true>(train, nu, nq, i, j, ui, uv, um[c], seq);
         }
       }
       if (outside) {  // flagged (bit 1): every setting predicts 0

@@ -528,7 +528,7 @@ QRLSH_EXPORT int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pre
                           avail_out, static_cast<uint8_t *>(workspace), static_cast<hipStream_t>(stream));
 }
 
-// ---- the selection over compact rows for other files (common.h): qrlsh_evaluate_ranking's sweep in predict.hip writes
+// ---- the selection over compact rows for other files (common.h): qrlsh_evaluate_ranking's sweep in rankeval.hip writes
 // the rows, rc_select<true> ranks them -- the path qrlsh_recommend_users takes after qr_predict_users
 int64_t qr_select_compact_stride(int64_t nq) { return rc_compact_stride(nq); }
 

@@ -152,6 +152,22 @@ def random_case(seed, nu, nq, longest_q, ku, fill=0.5):
     return ratings, tuple(x.astype(np.int32) for x in (src, dst, mil)), qs, us
 
 
+QUEUE_EDGES = (1, 1023, 1024, 1025, 2047, 2048)   # rated cells of a row: around one drain of the sweeps' queue and its ring
+
+
+def rows_with_exact_counts(truth, rows, counts, seed):
+    """truth[row] = values 1..100 in exactly `count` columns (a seeded permutation's first ones), 0 elsewhere, for every
+    (row, count); the rows' counts are asserted, so a case cannot stop covering them"""
+    rng = np.random.default_rng(seed)
+    nq = truth.shape[1]
+    for row, count in zip(rows, counts):
+        truth[row] = 0
+        cols = rng.permutation(nq)[:count]
+        truth[row, cols] = rng.integers(1, 101, size=count)
+    assert [int((truth[r] != 0).sum()) for r in rows] == list(counts)
+    return truth
+
+
 def coo_of(qs):
     """(src, dst, milli) int32 arrays sorted by source of a {j: {'indexes', 'values'}} dict"""
     src, dst, mil = [], [], []

@@ -133,6 +133,26 @@ def test_a_wide_value_beside_rows_that_stage_in_lds():
     assert 1500 < n < 3500
 
 
+def test_the_queue_drains_inside_the_loop():
+    """4096 users -> one slice of 2500 columns per user, so a workgroup queues a whole row of truth.  Rows with exactly
+    1, 1023, 1024, 1025, 2047 and 2048 rated cells stand on both sides of one drain inside the loop (1024 waiting) and
+    of the ring's wrap (2048 slots); one row is 90 % rated (two drains inside the loop and the rest after it).  They sit
+    at the first user, in the middle and at the last user; every other workgroup evaluates nothing."""
+    nu, nq = 4096, 2500
+    ratings, coo, qs, us = EC.random_case(71, nu, nq, 10, 5, fill=0.3)
+    rng = np.random.default_rng(72)
+    truth = np.zeros_like(ratings)
+    rows = [0, 513, 1777, 2048, 3000, nu - 1]
+    EC.rows_with_exact_counts(truth, rows, [1024, 1, 2047, 1023, 1025, 2048], seed=73)
+    dense = 1024
+    truth[dense] = (rng.integers(1, 101, size=nq) * (rng.random(nq) < 0.9)).astype(np.int32)
+    counts = {r: int((truth[r] != 0).sum()) for r in rows + [dense]}
+    assert sorted(counts[r] for r in rows) == list(EC.QUEUE_EDGES) and counts[0] == 1024 and counts[nu - 1] == 2048
+    assert counts[dense] > 2048 and int((truth != 0).sum()) == sum(counts.values())
+    n = check_against_restatement(ratings, truth, coo, qs, us, "drain in the loop")
+    assert n == sum(counts.values())
+
+
 @pytest.mark.parametrize("nq", [1, 1025])
 def test_one_column_and_a_partly_filled_last_slice(nq):
     ratings, coo, qs, us = EC.random_case(nq + 40, 5, nq, 6, 3, fill=0.6)

@@ -168,15 +168,19 @@ def test_a_thin_sample_runs_the_tail_drain_only(main):
 
 def test_the_queue_drains_inside_the_loop():
     """4096 users -> one slice of 2500 columns; three users' rows of truth are 90 % rated, so their workgroups predict
-    1024 cells twice inside the loop and the rest after it; every other workgroup evaluates nothing"""
+    1024 cells twice inside the loop and the rest after it; six more rows hold exactly 1, 1023, 1024, 1025, 2047 and 2048
+    rated cells (both sides of one drain inside the loop and of the ring's wrap); every other workgroup evaluates nothing"""
     nu, nq = 4096, 2500
     ratings, coo, qs, us = EC.random_case(61, nu, nq, 10, 5, fill=0.3)
     rng = np.random.default_rng(62)
     truth = np.zeros_like(ratings)
     rows = [0, 1777, nu - 1]
     truth[rows] = (rng.integers(1, 101, size=(3, nq)) * (rng.random((3, nq)) < 0.9)).astype(np.int32)
+    edges = [1, 513, 2048, 3000, 4000, nu - 2]
+    EC.rows_with_exact_counts(truth, edges, [1024, 1, 2047, 1023, 1025, 2048], seed=63)
     cells, values = EC.evaluated_cells(truth, 0, EC.ALL)
     assert all(int((truth[r] != 0).sum()) > 2048 for r in rows)
+    assert sorted(int((truth[r] != 0).sum()) for r in edges) == list(EC.QUEUE_EDGES)
     weights = TC.weight_grid(4, seed=5)
     want = TC.grid_ref(ratings, qs, us, cells, values, [3, 64], [2, 5], weights)
     assert_grid(Abi(ratings, truth, coo, us, 5)([3, 64], [2, 5], weights), want, "drain in the loop")

@@ -136,7 +136,7 @@ def main():
     out.append(rec)
     print(json.dumps(rec), flush=True)
 
-    slices = max(1, min(-(-4096 // nu), -(-nq // 1024)))     # ev_slices of csrc/predict.hip
+    slices = max(1, min(-(-4096 // nu), -(-nq // 1024)))     # ev_slices of csrc/evaluate.hip
     for fraction in (1.0, 0.1, 0.01):
         train, count = qrlsh.holdout(rt, fraction, seed=SEED, device=dev)
         mask = (train == 0) & (rt != 0)

@@ -110,7 +110,7 @@ def main():
                     before_ms = timed(before, max(2, a.reps // 2))
                     sweep_label = "rank_sweep_heldout" if candidates == "heldout" else "rank_sweep"
                     sweep = kern.get(sweep_label, 0.0)
-                    slices = max(1, min(-(-4096 // m), -(-nq // 1024)))          # rk_sweep_slices of csrc/predict.hip
+                    slices = max(1, min(-(-4096 // m), -(-nq // 1024)))          # rk_sweep_slices of csrc/rankeval.hip
                     share = m / nu
                     predicted = (count if candidates == "heldout" else unrated) * share
                     by = m * nq * 4 * (slices + 2) + predicted * ((mean_deg + Ku) * 4 + mean_deg * 8 + 16)
