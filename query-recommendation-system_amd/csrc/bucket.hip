@@ -880,7 +880,6 @@ static int n_slabs(int64_t nq, int T) { return T > 8 ? (int)((nq + (1ll << slab_
 //            [big parts: one counter per band group][pool cursor, run count: 2 u64][runs: POOL_RUNS x 16 B]
 //            [the big parts' lists: b << T u64 in all][desc: 2 x FIN_BIG_LIST x 16 B]
 // Every area starts on a multiple of 16 bytes.
-static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 constexpr int EMIT_MAX_GROUPS = 2;  // band groups of one qrlsh_bucket_pairs_emit call
 struct BucketWs {
   uint32_t *fill;
@@ -889,36 +888,25 @@ struct BucketWs {
   uint4 *runs;
   uint64_t *biglist;
   BigDesc *desc;
-  size_t bytes;
 };
-static BucketWs bucket_ws(void *workspace, int64_t nq, int32_t b, int32_t T) {
+static BucketWs bucket_layout(QrCarve &c, int64_t nq, int32_t b, int32_t T) {
   BucketWs w;
   const size_t slots = (size_t)b << T;
-  char *p = static_cast<char *>(workspace);
-  size_t off = 0;
-  w.fill = reinterpret_cast<uint32_t *>(p + off);
-  off += align16(slots * sizeof(uint32_t));
-  w.cur1 = reinterpret_cast<uint32_t *>(p + off);
-  if (T > 8) off += align16((((size_t)b * n_slabs(nq, T)) << coarse_bits(T)) * sizeof(uint32_t));
-  w.counts = reinterpret_cast<uint32_t *>(p + off);
-  off += align16(slots * sizeof(uint32_t));
-  w.nbig = reinterpret_cast<unsigned long long *>(p + off);
-  off += align16(EMIT_MAX_GROUPS * sizeof(unsigned long long));
-  w.poolctl = reinterpret_cast<unsigned long long *>(p + off);
-  off += 16;
-  w.runs = reinterpret_cast<uint4 *>(p + off);
-  off += (size_t)POOL_RUNS * sizeof(uint4);
-  w.biglist = reinterpret_cast<uint64_t *>(p + off);
-  off += align16(slots * sizeof(uint64_t));
-  w.desc = reinterpret_cast<BigDesc *>(p + off);
-  off += (size_t)EMIT_MAX_GROUPS * FIN_BIG_LIST * sizeof(BigDesc);
-  w.bytes = off;
+  w.fill = c.take<uint32_t>(slots);
+  w.cur1 = c.take<uint32_t>(T > 8 ? ((size_t)b * n_slabs(nq, T)) << coarse_bits(T) : 0);
+  w.counts = c.take<uint32_t>(slots);
+  w.nbig = c.take<unsigned long long>(EMIT_MAX_GROUPS);
+  w.poolctl = c.take<unsigned long long>(2);
+  w.runs = c.take<uint4>((size_t)POOL_RUNS);
+  w.biglist = c.take<uint64_t>(slots);
+  w.desc = c.take<BigDesc>((size_t)EMIT_MAX_GROUPS * FIN_BIG_LIST);
   return w;
 }
+static_assert(sizeof(BigDesc) == 16, "the descriptors end the workspace on a multiple of 16 bytes");
 
 QRLSH_EXPORT size_t qrlsh_bucket_workspace_bytes(int64_t nq, int32_t b, int32_t part_bits) {
   if (nq <= 0 || b <= 0 || part_bits < 8 || part_bits > 16) return 64;
-  return bucket_ws(nullptr, nq, b, part_bits).bytes;
+  return QR_LAYOUT_BYTES(bucket_layout, nq, b, part_bits);
 }
 
 static int bucket_check(const char *name, const uint64_t *keys, uint64_t *part_keys, uint32_t *part_ids,
@@ -928,18 +916,11 @@ static int bucket_check(const char *name, const uint64_t *keys, uint64_t *part_k
   QR_CHECK_ARG(part_bits >= 8 && part_bits <= 16, "%s: part_bits=%d not in [8,16]", name, part_bits);
   QR_CHECK_ARG(nq < (1ll << 32), "%s: nq too large", name);
   QR_CHECK_ARG(total_overflow_out && workspace, "%s: null pointer", name);
-  if (hipMemsetAsync(total_overflow_out, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", name);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(name, total_overflow_out, 0, 2 * sizeof(uint64_t), st);
   if (nq == 0) return QRLSH_OK;
   QR_CHECK_ARG(keys && part_keys && part_ids, "%s: null pointer", name);
   QR_CHECK_ARG(part_bits == 8 || (tmp_keys && tmp_ids), "%s: part_bits > 8 needs tmp buffers", name);
-  if (workspace_bytes < qrlsh_bucket_workspace_bytes(nq, b, part_bits)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes,
-                    qrlsh_bucket_workspace_bytes(nq, b, part_bits));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE(name, workspace, workspace_bytes, qrlsh_bucket_workspace_bytes(nq, b, part_bits));
   return QRLSH_OK;
 }
 
@@ -1036,14 +1017,12 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
                (unsigned long long)capacity);
   uint32_t *ovf = reinterpret_cast<uint32_t *>(total_overflow_out + 1);
   if (nq > (1ll << (16 + part_bits))) {  // ids beyond what a record of the last step carries: the general path
-    if (hipMemsetAsync(ovf, 1, 1, st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_bucket_pairs_emit", ovf, 1, 1, st);
     return QRLSH_OK;
   }
   const int nparts = 1 << part_bits;
-  const BucketWs w = bucket_ws(workspace, nq, b, part_bits);
+  QrCarve c(workspace);
+  const BucketWs w = bucket_layout(c, nq, b, part_bits);
 #define QR_PART_SCATTER(LEVEL2_, ...) QR_LAUNCH("part_scatter", (part_scatter_atomic_kernel<LEVEL2_>), __VA_ARGS__)
   // Partition(s) into fixed regions + the LDS finish.  The bands are independent of each other all the way to the
   // pair cursor, so they are worked in GROUPS that alternate between the caller's stream and an auxiliary one
@@ -1103,15 +1082,12 @@ QRLSH_EXPORT int qrlsh_bucket_pairs_emit_chunked(const uint64_t *keys, int64_t k
   // and one that names a part of this group would be counted twice (the overflow flag, and the step on the general
   // path).  Cleared, such a slot reads {0, 0 records}: it matches at most slot 0 and adds nothing.
   // (One kernel that clears all of it in a single launch measured slower than these calls: DESIGN section 6, round 6.)
-  if (hipMemsetAsync(cur1, 0, (((size_t)b * nslabs) << c1) * sizeof(uint32_t), st) != hipSuccess ||
-      (two && hipMemsetAsync(cur2, 0, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess) ||
-      hipMemsetAsync(w.fill, 0xFF, ((size_t)b << T) * sizeof(uint32_t), st) != hipSuccess ||
-      hipMemsetAsync(w.poolctl, 0, 16, st) != hipSuccess ||
-      hipMemsetAsync(nbig0, 0, MAX_GROUPS * sizeof(unsigned long long), st) != hipSuccess ||
-      (ngroups > 1 && hipMemsetAsync(w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st) != hipSuccess)) {
-    qrlsh_set_error("qrlsh_bucket_pairs_emit: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_bucket_pairs_emit", cur1, 0, (((size_t)b * nslabs) << c1) * sizeof(uint32_t), st);
+  if (two) QR_MEMSET("qrlsh_bucket_pairs_emit", cur2, 0, ((size_t)b << T) * sizeof(uint32_t), st);
+  QR_MEMSET("qrlsh_bucket_pairs_emit", w.fill, 0xFF, ((size_t)b << T) * sizeof(uint32_t), st);
+  QR_MEMSET("qrlsh_bucket_pairs_emit", w.poolctl, 0, 16, st);
+  QR_MEMSET("qrlsh_bucket_pairs_emit", nbig0, 0, MAX_GROUPS * sizeof(unsigned long long), st);
+  if (ngroups > 1) QR_MEMSET("qrlsh_bucket_pairs_emit", w.runs, 0, (size_t)POOL_RUNS * sizeof(uint4), st);
   hipStream_t aux = nullptr;
   int gi = 0;
   for (int g0 = 0; g0 < b; g0 += per, ++gi) {

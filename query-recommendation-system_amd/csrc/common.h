@@ -20,6 +20,8 @@ void qrlsh_set_error(const char *fmt, ...);
     }                                  \
   } while (0)
 
+#include "workspace.h"  // QrCarve, QR_CHECK_WORKSPACE, QR_CHECK_ALIGNED, QR_MEMSET, QR_MEMCPY
+
 #define QR_LAUNCH_CHECK(name)                                                        \
   do {                                                                               \
     hipError_t e__ = hipGetLastError();                                              \

@@ -317,9 +317,22 @@ __global__ __launch_bounds__(RD_THREADS) void row_unique_gather_kernel(const uin
 }
 
 // workspace: counts[2 nblk + 1] | starts[2 nblk] | longlist[nblk] | nlong | chunk totals of the scan
+struct RowUniqueWs {
+  int64_t nblk;
+  uint64_t *counts, *starts, *longlist, *nlong, *sums;
+};
+static RowUniqueWs row_unique_layout(QrCarve &c, int64_t n) {
+  RowUniqueWs w;
+  w.nblk = n > 0 ? ceil_div64(n, RD_C) : 0;
+  w.counts = c.take<uint64_t>((size_t)(2 * w.nblk + 1), 8);
+  w.starts = c.take<uint64_t>((size_t)(2 * w.nblk), 8);
+  w.longlist = c.take<uint64_t>((size_t)w.nblk, 8);
+  w.nlong = c.take<uint64_t>(1, 8);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(2 * w.nblk + 1, SCANL_CHUNK) + 1), 8);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_row_unique_workspace_bytes(int64_t n) {
-  const int64_t nblk = n > 0 ? ceil_div64(n, RD_C) : 0;
-  return (size_t)(5 * nblk + 2 + ceil_div64(2 * nblk + 1, SCANL_CHUNK) + 1) * sizeof(uint64_t);
+  return QR_LAYOUT_BYTES(row_unique_layout, n);
 }
 
 QRLSH_EXPORT int qrlsh_row_unique_count(const uint64_t *grouped, int64_t n, int32_t group_bits, int32_t id_bits,
@@ -331,31 +344,22 @@ QRLSH_EXPORT int qrlsh_row_unique_count(const uint64_t *grouped, int64_t n, int3
                "qrlsh_row_unique_count: group_bits=%d / id_bits=%d (need group_bits + id_bits <= 32)", group_bits,
                id_bits);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(total_overflow_out, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_row_unique_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_row_unique_count", total_overflow_out, 0, 2 * sizeof(uint64_t), st);
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(grouped && tmp && workspace, "qrlsh_row_unique_count: null pointer");
-  if (workspace_bytes < qrlsh_row_unique_workspace_bytes(n)) {
-    qrlsh_set_error("qrlsh_row_unique_count: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_row_unique_workspace_bytes(n));
-    return QRLSH_EWORKSPACE;
-  }
-  const int64_t nblk = ceil_div64(n, RD_C);
-  uint64_t *counts = static_cast<uint64_t *>(workspace), *starts = counts + (2 * nblk + 1);
-  uint64_t *longlist = starts + 2 * nblk, *nlong = longlist + nblk;
-  if (hipMemsetAsync(counts + 2 * nblk, 0, sizeof(uint64_t), st) != hipSuccess ||
-      hipMemsetAsync(nlong, 0, sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_row_unique_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_row_unique_count", workspace, workspace_bytes, qrlsh_row_unique_workspace_bytes(n));
+  QrCarve c(workspace);
+  const RowUniqueWs w = row_unique_layout(c, n);
+  const int64_t nblk = w.nblk;
+  uint64_t *counts = w.counts, *starts = w.starts, *longlist = w.longlist, *nlong = w.nlong;
+  QR_MEMSET("qrlsh_row_unique_count", counts + 2 * nblk, 0, sizeof(uint64_t), st);
+  QR_MEMSET("qrlsh_row_unique_count", nlong, 0, sizeof(uint64_t), st);
   QR_LAUNCH("row_unique", row_unique_kernel, dim3((unsigned)nblk), dim3(RD_THREADS), 0, st, grouped, n, tmp, counts,
             starts, longlist, reinterpret_cast<unsigned long long *>(nlong), group_bits, id_bits);
   QR_LAUNCH("row_unique_long", row_unique_long_kernel, dim3((unsigned)(nblk < RL_GRID ? nblk : RL_GRID)),
             dim3(RL_THREADS), 0, st, grouped, n, tmp, counts, (const uint64_t *)starts, (const uint64_t *)longlist,
             (const unsigned long long *)nlong, total_overflow_out + 1, group_bits, id_bits);
-  qr_scan_u64(counts, 2 * nblk + 1, total_overflow_out, nlong + 1, st);
+  qr_scan_u64(counts, 2 * nblk + 1, total_overflow_out, w.sums, st);
   QR_LAUNCH_CHECK("qrlsh_row_unique_count");
   return QRLSH_OK;
 }
@@ -365,9 +369,10 @@ QRLSH_EXPORT int qrlsh_row_unique_fill(const uint64_t *tmp, int64_t n, const voi
   QR_CHECK_ARG(n >= 0, "qrlsh_row_unique_fill: bad n");
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(tmp && workspace && out, "qrlsh_row_unique_fill: null pointer");
-  const int64_t nblk = ceil_div64(n, RD_C);
-  const uint64_t *offs = static_cast<const uint64_t *>(workspace), *starts = offs + (2 * nblk + 1);
-  QR_LAUNCH("row_unique_gather", row_unique_gather_kernel, dim3((unsigned)nblk), dim3(RD_THREADS), 0,
+  QrCarve c(workspace);
+  const RowUniqueWs w = row_unique_layout(c, n);
+  const uint64_t *offs = w.counts, *starts = w.starts;   // (the counts, scanned)
+  QR_LAUNCH("row_unique_gather", row_unique_gather_kernel, dim3((unsigned)w.nblk), dim3(RD_THREADS), 0,
             static_cast<hipStream_t>(stream), tmp, offs, starts, out);
   QR_LAUNCH_CHECK("qrlsh_row_unique_fill");
   return QRLSH_OK;
@@ -634,10 +639,25 @@ __global__ __launch_bounds__(256) void region_gather_kernel(const uint64_t *__re
 //            ends[nregions + 1] (fixed-region form only)
 static int64_t region_count(int64_t nids, int gbits) { return (nids + (1ll << gbits) - 1) >> gbits; }
 
+struct RegionWs {
+  int64_t nr;
+  uint64_t *starts, *counts, *biglist, *nbig, *sums, *ends;
+};
+static RegionWs region_layout(QrCarve &c, int64_t nids, int32_t group_bits) {
+  RegionWs w;
+  const int64_t nr = w.nr = region_count(nids, group_bits);
+  w.starts = c.take<uint64_t>((size_t)(2 * (nr + 1)), 8);   // starts | counts: adjacent
+  w.counts = qr_within(w.starts, (size_t)(nr + 1));
+  w.biglist = c.take<uint64_t>((size_t)nr, 8);
+  w.nbig = c.take<uint64_t>(1, 8);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(nr + 1, SCANL_CHUNK) + 1), 8);
+  w.ends = c.take<uint64_t>((size_t)(nr + 1), 8);
+  c.take<uint64_t>(1, 8);   // (a spare word the size has always counted)
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_region_unique_workspace_bytes(int64_t nids, int32_t group_bits) {
   if (nids <= 0 || group_bits < 0 || group_bits > 8) return 64;
-  const int64_t nr = region_count(nids, group_bits);
-  return (size_t)(4 * (nr + 1) + ceil_div64(nr + 1, SCANL_CHUNK) + 2) * sizeof(uint64_t);
+  return QR_LAYOUT_BYTES(region_layout, nids, group_bits);
 }
 
 // spans of the fixed regions qrlsh_pair_regions_scatter32 fills: region r = words [r * cap, r * cap + counts[r])
@@ -655,11 +675,6 @@ __global__ __launch_bounds__(256) void region_spans_kernel(const uint32_t *__res
 // The two count entry points -- words sorted by region (bounds by binary search, a two-word result) and the fixed regions
 // of values qrlsh_pair_regions_scatter32 filled (region r at r * cap, counts[r] values; a three-word result whose last word
 // is the scatter's capacity flag) -- share their checks and workspace layout (region_ws) and the launches of the finish.
-struct RegionWs {
-  int64_t nr;
-  uint64_t *starts, *counts, *biglist, *nbig, *sums, *ends;
-};
-
 // checks, clears the out_words result words and (n > 0) lays out the workspace
 static int region_ws(const char *name, bool pointers, int64_t n, int32_t group_bits, int32_t id_bits, int64_t nids,
                      void *workspace, size_t workspace_bytes, uint64_t *out, int out_words, hipStream_t st, RegionWs *w) {
@@ -671,27 +686,15 @@ static int region_ws(const char *name, bool pointers, int64_t n, int32_t group_b
                    (group_bits + id_bits < 32 || (group_bits + id_bits == 32 && nids < (1ll << id_bits))),
                "%s: group_bits=%d / id_bits=%d (need group_bits <= 8, id_bits <= 31, group_bits + id_bits <= 32)", name,
                group_bits, id_bits);
-  if (hipMemsetAsync(out, 0, out_words * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", name);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(name, out, 0, out_words * sizeof(uint64_t), st);
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(pointers && workspace, "%s: null pointer", name);
-  if (workspace_bytes < qrlsh_region_unique_workspace_bytes(nids, group_bits)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes,
-                    qrlsh_region_unique_workspace_bytes(nids, group_bits));
-    return QRLSH_EWORKSPACE;
-  }
-  const int64_t nr = w->nr = region_count(nids, group_bits);
-  QR_CHECK_ARG(nr <= 2147483647ll, "%s: too many regions", name);
-  w->starts = static_cast<uint64_t *>(workspace), w->counts = w->starts + (nr + 1), w->biglist = w->counts + (nr + 1);
-  w->nbig = w->biglist + nr, w->sums = w->nbig + 1;
-  w->ends = w->sums + ceil_div64(nr + 1, SCANL_CHUNK) + 1;
-  if (hipMemsetAsync(w->counts + nr, 0, sizeof(uint64_t), st) != hipSuccess ||
-      hipMemsetAsync(w->nbig, 0, sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", name);
-    return QRLSH_EHIP;
-  }
+  QR_CHECK_WORKSPACE(name, workspace, workspace_bytes, qrlsh_region_unique_workspace_bytes(nids, group_bits));
+  QR_CHECK_ARG(region_count(nids, group_bits) <= 2147483647ll, "%s: too many regions", name);
+  QrCarve c(workspace);
+  *w = region_layout(c, nids, group_bits);
+  QR_MEMSET(name, w->counts + w->nr, 0, sizeof(uint64_t), st);
+  QR_MEMSET(name, w->nbig, 0, sizeof(uint64_t), st);
   return QRLSH_OK;
 }
 
@@ -749,9 +752,10 @@ QRLSH_EXPORT int qrlsh_region_unique_fill(const uint64_t *tmp, int64_t n, int32_
   QR_CHECK_ARG(n >= 0 && nids > 0 && group_bits >= 0 && group_bits <= 8, "qrlsh_region_unique_fill: bad arguments");
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(tmp && workspace && out, "qrlsh_region_unique_fill: null pointer");
-  const int64_t nr = region_count(nids, group_bits);
-  const uint64_t *starts = static_cast<const uint64_t *>(workspace), *offs = starts + (nr + 1);
-  QR_LAUNCH("region_gather", region_gather_kernel, dim3((unsigned)nr), dim3(256), 0, static_cast<hipStream_t>(stream), tmp,
+  QrCarve c(workspace);
+  const RegionWs w = region_layout(c, nids, group_bits);
+  const uint64_t *starts = w.starts, *offs = w.counts;   // (the counts, scanned)
+  QR_LAUNCH("region_gather", region_gather_kernel, dim3((unsigned)w.nr), dim3(256), 0, static_cast<hipStream_t>(stream), tmp,
             offs, starts, out);
   QR_LAUNCH_CHECK("qrlsh_region_unique_fill");
   return QRLSH_OK;
@@ -1007,11 +1011,8 @@ QRLSH_EXPORT int qrlsh_pair_regions_scatter32(const uint64_t *words, int64_t n, 
   QR_CHECK_ARG(pair_regions_fit_u32(r),
                "qrlsh_pair_regions_scatter32: regions reach 2^32 words (na * cap_a = %llu, 2^rb * cap_b = %llu; need both < 2^32)",
                (unsigned long long)r.na * r.cap_a, (unsigned long long)r.cap_b << r.rb);
-  if (hipMemsetAsync(counts, 0, ((size_t)r.nregions + RADIX) * sizeof(uint32_t), st) != hipSuccess ||
-      hipMemsetAsync(overflow_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_pair_regions_scatter32: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_pair_regions_scatter32", counts, 0, ((size_t)r.nregions + RADIX) * sizeof(uint32_t), st);
+  QR_MEMSET("qrlsh_pair_regions_scatter32", overflow_out, 0, sizeof(uint32_t), st);
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(words && regions && (r.ra == 0 || tmp_regions), "qrlsh_pair_regions_scatter32: null pointer");
   const int sh = 32 + group_bits;
@@ -1023,7 +1024,7 @@ QRLSH_EXPORT int qrlsh_pair_regions_scatter32(const uint64_t *words, int64_t n, 
               (1u << r.rb) - 1u, counts, r.cap_b, overflow_out, none, 0u, (int)group_bits, (int)id_bits, 0u);
   } else {
     // two levels: tmp holds na * cap_a values, then as many tail bytes (5 of the 8 bytes per entry it was given)
-    QR_CHECK_ARG((reinterpret_cast<uintptr_t>(tmp_regions) & 15u) == 0, "qrlsh_pair_regions_scatter32: tmp_regions not 16-byte aligned");
+    QR_CHECK_ALIGNED("qrlsh_pair_regions_scatter32", "tmp_regions", qr_addr(tmp_regions), 16);
     uint32_t *cur_a = counts + r.nregions;
     uint32_t *tvals = reinterpret_cast<uint32_t *>(tmp_regions);
     uint8_t *ttails = reinterpret_cast<uint8_t *>(tvals + (size_t)r.na * r.cap_a);

@@ -532,20 +532,29 @@ uint32_t dv_cap_for(int64_t N, int64_t max_row) {
   return (uint32_t)((cap + 3) & ~3ll);
 }
 
-// the capacity a workspace of `bytes` gives each of m requests (never above what any pool of N can hold); false when
-// not even the offsets fit
-bool dv_cap_from(size_t bytes, int64_t m, int N, uint32_t *cap) {
-  const size_t words = bytes / sizeof(uint32_t) / (size_t)m, offs = dv_offs_words(N);
-  if (words < offs) return false;
-  const size_t most = dv_cap_for(N, N), got = (words - offs) & ~(size_t)3;
+// workspace: a slice per request, [offs: dv_offs_words(N)][half-edges: cap] (the kernels find theirs by the same rule)
+uint32_t *dv_layout(QrCarve &c, int64_t m, int N, uint32_t cap) {
+  return c.take<uint32_t>((size_t)m * (dv_offs_words(N) + cap), 4);
+}
+
+// the checks of a workspace of `bytes` for m > 0 requests; *cap = the half-edges it gives each of them (never above
+// what any pool of N can hold; QRLSH_EWORKSPACE when not even the offsets fit)
+int dv_workspace(const char *who, void *workspace, size_t bytes, int64_t m, int N, uint32_t *cap, uint32_t **ws) {
+  QR_CHECK_ALIGNED(who, "the workspace", qr_addr(workspace), 16);
+  QrCarve least(nullptr);
+  dv_layout(least, m, N, 0);
+  QR_CHECK_WORKSPACE(who, workspace, bytes, least.bytes());
+  const size_t most = dv_cap_for(N, N), got = (bytes / sizeof(uint32_t) / (size_t)m - dv_offs_words(N)) & ~(size_t)3;
   *cap = (uint32_t)(got < most ? got : most);
-  return true;
+  QrCarve c(workspace);
+  *ws = dv_layout(c, m, N, *cap);
+  return QRLSH_OK;
 }
 }  // namespace
 
 QRLSH_EXPORT size_t qrlsh_diversify_workspace_bytes(int64_t m, int32_t N, int64_t max_row) {
   if (m <= 0 || m > DV_MAX_M || N < 1 || N > DV_MAXN || max_row < 0) return 0;
-  return (size_t)m * (dv_offs_words(N) + dv_cap_for(N, max_row)) * sizeof(uint32_t);
+  return QR_LAYOUT_BYTES(dv_layout, m, N, dv_cap_for(N, max_row));
 }
 
 QRLSH_EXPORT int qrlsh_diversify(const int32_t *cand_idx, const int32_t *cand_val, const int32_t *avail, int64_t m,
@@ -569,15 +578,10 @@ QRLSH_EXPORT int qrlsh_diversify(const int32_t *cand_idx, const int32_t *cand_va
     qrlsh_set_error("qrlsh_diversify: m=%lld above the %lld workgroups served", (long long)m, (long long)DV_MAX_M);
     return QRLSH_EUNSUPPORTED;
   }
-  QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_diversify: the workspace must be 16-byte aligned");
-  uint32_t cap = 0;
-  if (!workspace || !dv_cap_from(workspace_bytes, m, N, &cap)) {
-    qrlsh_set_error("qrlsh_diversify: needs at least %zu workspace bytes, got %zu",
-                    (size_t)m * dv_offs_words(N) * sizeof(uint32_t), workspace ? workspace_bytes : 0);
-    return QRLSH_EWORKSPACE;
-  }
+  uint32_t cap = 0, *ws = nullptr;
+  const int wrc = dv_workspace("qrlsh_diversify", workspace, workspace_bytes, m, N, &cap, &ws);
+  if (wrc != QRLSH_OK) return wrc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  uint32_t *ws = static_cast<uint32_t *>(workspace);
   QR_LAUNCH("diversify_adjacency", diversify_adjacency_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, cand_idx,
             avail, (int)N, nq, q_off, q_idx, q_milli, cap, ws, flag_out);
   QR_LAUNCH("diversify_select", diversify_select_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, cand_idx, cand_val,
@@ -616,15 +620,10 @@ QRLSH_EXPORT int qrlsh_diversify_grid(const int32_t *cand_idx, const int32_t *ca
     qrlsh_set_error("qrlsh_diversify_grid: m=%lld above the %lld requests served", (long long)m, (long long)DV_MAX_M);
     return QRLSH_EUNSUPPORTED;
   }
-  QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_diversify_grid: the workspace must be 16-byte aligned");
-  uint32_t cap = 0;
-  if (!workspace || !dv_cap_from(workspace_bytes, m, N, &cap)) {
-    qrlsh_set_error("qrlsh_diversify_grid: needs at least %zu workspace bytes, got %zu",
-                    (size_t)m * dv_offs_words(N) * sizeof(uint32_t), workspace ? workspace_bytes : 0);
-    return QRLSH_EWORKSPACE;
-  }
+  uint32_t cap = 0, *ws = nullptr;
+  const int wrc = dv_workspace("qrlsh_diversify_grid", workspace, workspace_bytes, m, N, &cap, &ws);
+  if (wrc != QRLSH_OK) return wrc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  uint32_t *ws = static_cast<uint32_t *>(workspace);
   QR_LAUNCH("diversify_adjacency", diversify_adjacency_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, cand_idx,
             avail, (int)N, nq, q_off, q_idx, q_milli, cap, ws, flag_out);
   QR_LAUNCH("diversify_grid_select", diversify_grid_select_kernel, dim3((unsigned)m, (unsigned)S), dim3(DV_THREADS), 0,
@@ -651,15 +650,10 @@ QRLSH_EXPORT int qrlsh_list_redundancy(const int32_t *idx, int64_t m, int32_t k,
                     (long long)DV_MAX_M);
     return QRLSH_EUNSUPPORTED;
   }
-  QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_list_redundancy: the workspace must be 16-byte aligned");
-  uint32_t cap = 0;
-  if (!workspace || !dv_cap_from(workspace_bytes, m, k, &cap)) {
-    qrlsh_set_error("qrlsh_list_redundancy: needs at least %zu workspace bytes, got %zu",
-                    (size_t)m * dv_offs_words(k) * sizeof(uint32_t), workspace ? workspace_bytes : 0);
-    return QRLSH_EWORKSPACE;
-  }
+  uint32_t cap = 0, *ws = nullptr;
+  const int wrc = dv_workspace("qrlsh_list_redundancy", workspace, workspace_bytes, m, k, &cap, &ws);
+  if (wrc != QRLSH_OK) return wrc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  uint32_t *ws = static_cast<uint32_t *>(workspace);
   QR_LAUNCH("list_adjacency", list_adjacency_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, idx, (int)k, nq, q_off,
             q_idx, q_milli, cap, ws, flag_out);
   QR_LAUNCH("list_redundancy_reduce", list_redundancy_reduce_kernel, dim3((unsigned)m), dim3(DV_THREADS), 0, st, idx,

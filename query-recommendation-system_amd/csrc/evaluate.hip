@@ -163,9 +163,19 @@ __global__ __launch_bounds__(1024) void evaluate_totals_kernel(const long long *
 }
 
 // workspace: [part: nu x slices x 16 int64][gpart: ceil(nu / 64) x 16 int64]
+struct EvWs {
+  long long *part, *gpart;
+};
+// `words` sums per (user, slice) and per group of `group_users` users
+static EvWs ev_layout(QrCarve &c, int64_t nu, int64_t nq, size_t words, int group_users) {
+  EvWs w;
+  w.part = c.take<long long>((size_t)nu * (size_t)ev_slices(nu, nq) * words, 8);
+  w.gpart = c.take<long long>((size_t)ceil_div64(nu, group_users) * words, 8);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_evaluate_workspace_bytes(int64_t nu, int64_t nq) {
   if (nu <= 0 || nq <= 0) return 0;
-  return ((size_t)nu * (size_t)ev_slices(nu, nq) + (size_t)ceil_div64(nu, EVF_USERS)) * 16 * sizeof(long long);
+  return QR_LAYOUT_BYTES(ev_layout, nu, nq, 16, EVF_USERS);
 }
 
 static int ev_check_lists(const char *who, int64_t nu, int64_t nq, int32_t ku, int32_t sum_order, uint64_t keep) {
@@ -193,20 +203,18 @@ QRLSH_EXPORT int qrlsh_evaluate(const int32_t *ratings, const int32_t *truth, in
   QR_CHECK_ARG(empty || (workspace && workspace_bytes >= need && (uintptr_t)workspace % 8 == 0),
                "qrlsh_evaluate: needs %zu workspace bytes (8-byte aligned), got %zu", need, workspace_bytes);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
-      (empty && hipMemsetAsync(totals_out, 0, 16 * sizeof(int64_t), st) != hipSuccess) ||
-      (empty && nu > 0 && hipMemsetAsync(per_user_out, 0, (size_t)nu * 16 * sizeof(int64_t), st) != hipSuccess)) {
-    qrlsh_set_error("qrlsh_evaluate: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_evaluate", flags_out, 0, sizeof(uint32_t), st);
+  if (empty) QR_MEMSET("qrlsh_evaluate", totals_out, 0, 16 * sizeof(int64_t), st);
+  if (empty && nu > 0) QR_MEMSET("qrlsh_evaluate", per_user_out, 0, (size_t)nu * 16 * sizeof(int64_t), st);
   if (empty) return QRLSH_OK;
   const int64_t slices = ev_slices(nu, nq), groups = ceil_div64(nu, EVF_USERS);
   if (nu * slices > 2147483647ll) {
     qrlsh_set_error("qrlsh_evaluate: nu=%lld x %lld slices above 2^31 - 1 workgroups", (long long)nu, (long long)slices);
     return QRLSH_EUNSUPPORTED;
   }
-  long long *part = static_cast<long long *>(workspace);
-  long long *gpart = part + (size_t)nu * slices * 16;
+  QrCarve c(workspace);
+  const EvWs w = ev_layout(c, nu, nq, 16, EVF_USERS);
+  long long *part = w.part, *gpart = w.gpart;
   qr_lists_check("evaluate_check", q_off, q_idx, nq, nullptr, 0, nu, flags_out, st);   // the lists' two flags
   QR_LAUNCH("evaluate", evaluate_kernel, dim3((unsigned)(nu * slices)), dim3(EV_THREADS), 0, st, ratings, truth, nu, nq,
             q_off, q_idx, q_milli, u_idx, u_val, (int)ku, query_weight, user_weight, default_mean,
@@ -409,8 +417,7 @@ __global__ __launch_bounds__(1024) void evaluate_grid_totals_kernel(const long l
 // workspace: [part: nu x slices x S x 8 int64][gpart: ceil(nu / 16) x S x 8 int64]
 QRLSH_EXPORT size_t qrlsh_evaluate_grid_workspace_bytes(int64_t nu, int64_t nq, int32_t settings) {
   if (nu <= 0 || nq <= 0 || settings <= 0 || settings > QRLSH_GRID_MAX_SETTINGS) return 0;
-  return ((size_t)nu * (size_t)ev_slices(nu, nq) + (size_t)ceil_div64(nu, EGF_USERS)) * (size_t)settings * EG_WORDS *
-         sizeof(long long);
+  return QR_LAYOUT_BYTES(ev_layout, nu, nq, (size_t)settings * EG_WORDS, EGF_USERS);
 }
 
 QRLSH_EXPORT int qrlsh_evaluate_grid(const int32_t *ratings, const int32_t *truth, int64_t nu, int64_t nq,
@@ -434,11 +441,8 @@ QRLSH_EXPORT int qrlsh_evaluate_grid(const int32_t *ratings, const int32_t *trut
   const int settings = ncq * ncu * nw, words = settings * EG_WORDS;
   const size_t need = qrlsh_evaluate_grid_workspace_bytes(nu, nq, settings);
   if (!empty) {
-    QR_CHECK_ARG((uintptr_t)workspace % 8 == 0, "%s: the workspace must be 8-byte aligned", who);
-    if (!workspace || workspace_bytes < need) {
-      qrlsh_set_error("%s: needs %zu workspace bytes, got %zu", who, need, workspace ? workspace_bytes : 0);
-      return QRLSH_EWORKSPACE;
-    }
+    QR_CHECK_ALIGNED(who, "the workspace", qr_addr(workspace), 8);
+    QR_CHECK_WORKSPACE(who, workspace, workspace_bytes, need);
   }
   const int64_t slices = ev_slices(nu, nq), groups = ceil_div64(nu, EGF_USERS);
   if (!empty && nu * slices > 2147483647ll) {
@@ -446,21 +450,18 @@ QRLSH_EXPORT int qrlsh_evaluate_grid(const int32_t *ratings, const int32_t *trut
     return QRLSH_EUNSUPPORTED;
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
-      (empty && hipMemsetAsync(totals_out, 0, (size_t)words * sizeof(int64_t), st) != hipSuccess) ||
-      (empty && nu > 0 && per_user_out &&
-       hipMemsetAsync(per_user_out, 0, (size_t)nu * words * sizeof(int64_t), st) != hipSuccess)) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", who);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(who, flags_out, 0, sizeof(uint32_t), st);
+  if (empty) QR_MEMSET(who, totals_out, 0, (size_t)words * sizeof(int64_t), st);
+  if (empty && nu > 0 && per_user_out) QR_MEMSET(who, per_user_out, 0, (size_t)nu * words * sizeof(int64_t), st);
   if (empty) {
     QR_LAUNCH("evaluate_grid_cuts", evaluate_grid_cuts_kernel, dim3(1), dim3(64), 0, st, q_cuts, (int)ncq, u_cuts,
               (int)ncu, flags_out);
     QR_LAUNCH_CHECK(who);
     return QRLSH_OK;
   }
-  long long *part = static_cast<long long *>(workspace);
-  long long *gpart = part + (size_t)nu * slices * words;
+  QrCarve c(workspace);
+  const EvWs w = ev_layout(c, nu, nq, (size_t)words, EGF_USERS);
+  long long *part = w.part, *gpart = w.gpart;
   const unsigned fin_threads = (unsigned)((words + WAVE - 1) / WAVE * WAVE);
   qr_lists_check("evaluate_check", q_off, q_idx, nq, nullptr, 0, nu, flags_out, st);   // the lists' two flags
   QR_LAUNCH("evaluate_grid", evaluate_grid_kernel, dim3((unsigned)(nu * slices)), dim3(EV_THREADS), 0, st, ratings, truth,
@@ -522,11 +523,8 @@ QRLSH_EXPORT int qrlsh_evaluate_cells(const int32_t *ratings, int64_t nu, int64_
   QR_CHECK_ARG(m == 0 || nu == 0 || nq == 0 || (ratings && q_off && (ku == 0 || (u_idx && u_val))),
                "qrlsh_evaluate_cells: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
-      hipMemsetAsync(totals_out, 0, 16 * sizeof(int64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_evaluate_cells: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_evaluate_cells", flags_out, 0, sizeof(uint32_t), st);
+  QR_MEMSET("qrlsh_evaluate_cells", totals_out, 0, 16 * sizeof(int64_t), st);
   if (m == 0) return QRLSH_OK;
   qr_lists_check("evaluate_check", q_off, q_idx, nq, nullptr, 0, nu, flags_out, st);   // the lists' two flags; ids: below
   QR_LAUNCH("evaluate_cells", evaluate_cells_kernel, dim3((unsigned)ceil_div64(m, EVC_THREADS)), dim3(EVC_THREADS), 0, st,
@@ -622,10 +620,7 @@ QRLSH_EXPORT int qrlsh_ratings_holdout(const int32_t *in, int64_t nu, int64_t nq
   const int64_t total = nu * nq;
   QR_CHECK_ARG(total == 0 || (in && out && in != out), "qrlsh_ratings_holdout: null pointer, or in == out");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(count_out, 0, sizeof(int64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_ratings_holdout: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_ratings_holdout", count_out, 0, sizeof(int64_t), st);
   if (total == 0) return QRLSH_OK;
   const bool aligned = ((uintptr_t)in | (uintptr_t)out) % 16 == 0;
   const int64_t n4 = aligned ? total / 4 : 0;

@@ -22,18 +22,18 @@ struct IdMap {
   uint2 *w;
   uint64_t *cnt, *sums;
   int64_t nw;
-  size_t bytes;
 };
-static IdMap idmap_layout(void *map, int64_t n) {
+static IdMap idmap_layout(QrCarve &c, int64_t n) {
   IdMap m;
   m.nw = (n + 31) / 32;
-  char *p = static_cast<char *>(map);
-  size_t o = 0;
-  m.w = reinterpret_cast<uint2 *>(p + o), o += qr_al16((size_t)(m.nw + 1) * 8);
-  m.cnt = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(m.nw + 2) * 8);
-  m.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(m.nw + 1, SCANL_CHUNK) + 2) * 8);
-  m.bytes = o;
+  m.w = c.take<uint2>((size_t)(m.nw + 1));
+  m.cnt = c.take<uint64_t>((size_t)(m.nw + 2));
+  m.sums = c.take<uint64_t>((size_t)(ceil_div64(m.nw + 1, SCANL_CHUNK) + 2));
   return m;
+}
+static IdMap idmap_layout(const void *map, int64_t n) {
+  QrCarve c(map);
+  return idmap_layout(c, n);
 }
 
 __device__ static inline bool idmap_has(uint2 w, uint32_t id) { return (w.x >> (id & 31u)) & 1u; }

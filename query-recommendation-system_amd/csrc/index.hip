@@ -75,10 +75,7 @@ QRLSH_EXPORT int qrlsh_index_build(uint64_t *keys, uint64_t *keys_tmp, uint32_t 
   QR_CHECK_ARG(dir_out, "qrlsh_index_build: null directory");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
-    if (hipMemsetAsync(dir_out, 0, qrlsh_index_dir_words(n, b) * sizeof(uint32_t), st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_index_build: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_index_build", dir_out, 0, qrlsh_index_dir_words(n, b) * sizeof(uint32_t), st);
     return QRLSH_OK;
   }
   QR_CHECK_ARG(keys && keys_tmp && ids && ids_tmp, "qrlsh_index_build: null pointer");
@@ -86,11 +83,8 @@ QRLSH_EXPORT int qrlsh_index_build(uint64_t *keys, uint64_t *keys_tmp, uint32_t 
                                 workspace, workspace_bytes, stream);
   if (rc < 0) return rc;
   if (rc == 1) {  // the result is always left in keys / ids
-    if (hipMemcpyAsync(keys, keys_tmp, (size_t)b * n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(ids, ids_tmp, (size_t)b * n * sizeof(uint32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_index_build: hipMemcpyAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMCPY("qrlsh_index_build", keys, keys_tmp, (size_t)b * n * sizeof(uint64_t), st);
+    QR_MEMCPY("qrlsh_index_build", ids, ids_tmp, (size_t)b * n * sizeof(uint32_t), st);
   }
   return qr_index_dir(keys, n, b, dir_out, st, "qrlsh_index_build");
 }
@@ -177,10 +171,19 @@ __global__ __launch_bounds__(256) void index_probe_kernel(const uint64_t *__rest
 }
 
 // workspace: cnt / offsets u64 [m * b + 1] | scan sums
+struct ProbeWs {
+  uint64_t *cnt, *sums;
+};
+static ProbeWs probe_layout(QrCarve &c, int64_t m, int32_t b) {
+  const int64_t mb = m * b;
+  ProbeWs w;
+  w.cnt = c.take<uint64_t>((size_t)(mb + 1), 8);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(mb, SCANL_CHUNK) + 1), 8);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_index_probe_workspace_bytes(int64_t m, int32_t b) {
   if (m <= 0 || b <= 0) return 0;
-  const int64_t mb = m * b;
-  return (size_t)(mb + 1) * sizeof(uint64_t) + (size_t)(ceil_div64(mb, SCANL_CHUNK) + 1) * sizeof(uint64_t);
+  return QR_LAYOUT_BYTES(probe_layout, m, b);
 }
 
 static int probe_args(const char *who, const uint64_t *skeys, const uint32_t *dir, int64_t n, int32_t b, int32_t r,
@@ -190,10 +193,7 @@ static int probe_args(const char *who, const uint64_t *skeys, const uint32_t *di
   QR_CHECK_ARG(m * (int64_t)b < (1ll << 32), "%s: m * b = %lld must stay below 2^32", who, (long long)(m * (int64_t)b));
   if (m == 0) return QRLSH_OK;
   QR_CHECK_ARG(pkeys && workspace && (n == 0 || (skeys && dir)), "%s: null pointer", who);
-  if (workspace_bytes < qrlsh_index_probe_workspace_bytes(m, b)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, qrlsh_index_probe_workspace_bytes(m, b));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE(who, workspace, workspace_bytes, qrlsh_index_probe_workspace_bytes(m, b));
   return QRLSH_OK;
 }
 
@@ -205,29 +205,21 @@ QRLSH_EXPORT int qrlsh_index_probe_count(const uint64_t *sorted_keys, const uint
   if (rc != QRLSH_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (m == 0) {
-    if (hipMemsetAsync(total_out, 0, sizeof(uint64_t), st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_index_probe_count: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_index_probe_count", total_out, 0, sizeof(uint64_t), st);
     return QRLSH_OK;
   }
   const int64_t mb = m * b;
-  uint64_t *cnt = static_cast<uint64_t *>(workspace);
-  uint64_t *sums = cnt + mb + 1;
+  QrCarve c(workspace);
+  const ProbeWs w = probe_layout(c, m, b);
+  uint64_t *cnt = w.cnt, *sums = w.sums;
   if (n == 0) {
-    if (hipMemsetAsync(cnt, 0, (size_t)(mb + 1) * sizeof(uint64_t), st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_index_probe_count: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_index_probe_count", cnt, 0, (size_t)(mb + 1) * sizeof(uint64_t), st);
   } else {
     QR_LAUNCH("index_probe_count", index_probe_kernel<false>, dim3((unsigned)ceil_div64(mb, 256)), dim3(256), 0, st,
               sorted_keys, nullptr, n, b, r, qrlsh_index_dir_bits(n), dir, probe_keys, m, cnt, nullptr);
     qr_scan_u64(cnt, mb, cnt + mb, sums, st);
   }
-  if (hipMemcpyAsync(total_out, cnt + mb, sizeof(uint64_t), hipMemcpyDeviceToDevice, st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_index_probe_count: hipMemcpyAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMCPY("qrlsh_index_probe_count", total_out, cnt + mb, sizeof(uint64_t), st);
   QR_LAUNCH_CHECK("qrlsh_index_probe_count");
   return QRLSH_OK;
 }
@@ -241,9 +233,10 @@ QRLSH_EXPORT int qrlsh_index_probe_fill(const uint64_t *sorted_keys, const uint3
   QR_CHECK_ARG(sorted_ids && raw_out, "qrlsh_index_probe_fill: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t mb = m * b;
+  QrCarve c(workspace);
   QR_LAUNCH("index_probe_fill", index_probe_kernel<true>, dim3((unsigned)ceil_div64(mb, 256)), dim3(256), 0, st,
             sorted_keys, sorted_ids, n, b, r, qrlsh_index_dir_bits(n), dir, probe_keys, m,
-            static_cast<uint64_t *>(const_cast<void *>(workspace)), raw_out);
+            probe_layout(c, m, b).cnt, raw_out);
   QR_LAUNCH_CHECK("qrlsh_index_probe_fill");
   return QRLSH_OK;
 }
@@ -421,9 +414,21 @@ __global__ __launch_bounds__(256) void index_compact_kernel(const int32_t *__res
 }
 
 // workspace: keys u64 [n_raw] | pidx i32 [m][K] | pmilli i32 [m][K] | scan sums
+struct FinishWs {
+  uint64_t *keys, *sums;
+  int32_t *pidx, *pmilli;
+};
+static FinishWs finish_layout(QrCarve &c, int64_t m, int32_t K, int64_t n_raw) {
+  FinishWs w;
+  w.keys = c.take<uint64_t>((size_t)n_raw);
+  w.pidx = c.take<int32_t>((size_t)m * K);
+  w.pmilli = c.take<int32_t>((size_t)m * K);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(m, SCANL_CHUNK) + 1), 8);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_index_finish_workspace_bytes(int64_t m, int32_t K, int64_t n_raw) {
   if (m <= 0 || K <= 0 || K > IX_MAXK || n_raw < 0) return 0;
-  return qr_al16((size_t)n_raw * 8) + 2 * qr_al16((size_t)m * K * 4) + (size_t)(ceil_div64(m, SCANL_CHUNK) + 1) * 8;
+  return QR_LAYOUT_BYTES(finish_layout, m, K, n_raw);
 }
 
 static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const void *probe_sig, const int64_t *probe_norm2,
@@ -441,24 +446,16 @@ static int ix_finish(const void *sig, const int64_t *norm2, int64_t n, const voi
   QR_CHECK_ARG(off_out, "qrlsh_index_probe_finish: null off_out");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (m == 0) {
-    if (hipMemsetAsync(off_out, 0, sizeof(int64_t), st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_index_probe_finish: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_index_probe_finish", off_out, 0, sizeof(int64_t), st);
     return QRLSH_OK;
   }
   QR_CHECK_ARG(probe_workspace && idx_out && milli_out && avail_out && workspace && (n_raw == 0 || (sig && probe_sig && raw)),
                "qrlsh_index_probe_finish: null pointer");
-  if (workspace_bytes < qrlsh_index_finish_workspace_bytes(m, K, n_raw)) {
-    qrlsh_set_error("qrlsh_index_probe_finish: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_index_finish_workspace_bytes(m, K, n_raw));
-    return QRLSH_EWORKSPACE;
-  }
-  char *ws = static_cast<char *>(workspace);
-  uint64_t *keys = reinterpret_cast<uint64_t *>(ws);
-  int32_t *pidx = reinterpret_cast<int32_t *>(ws + qr_al16((size_t)n_raw * 8));
-  int32_t *pmilli = reinterpret_cast<int32_t *>(ws + qr_al16((size_t)n_raw * 8) + qr_al16((size_t)m * K * 4));
-  uint64_t *sums = reinterpret_cast<uint64_t *>(ws + qr_al16((size_t)n_raw * 8) + 2 * qr_al16((size_t)m * K * 4));
+  QR_CHECK_WORKSPACE("qrlsh_index_probe_finish", workspace, workspace_bytes, qrlsh_index_finish_workspace_bytes(m, K, n_raw));
+  QrCarve c(workspace);
+  const FinishWs w = finish_layout(c, m, K, n_raw);
+  uint64_t *keys = w.keys, *sums = w.sums;
+  int32_t *pidx = w.pidx, *pmilli = w.pmilli;
   if (n_raw > 0) {
     const dim3 grid((unsigned)ceil_div64(n_raw, 256)), block(256);
     if (sig_dtype == QRLSH_SIG_U16)
@@ -673,10 +670,26 @@ __global__ __launch_bounds__(256) void index_merge_kernel(const uint64_t *__rest
 }
 
 // workspace: batch keys_tmp u64 [b][m] | batch ids u32 [b][m] | ids_tmp u32 [b][m] | q u32 [b][m] | sort workspace
+struct AppendWs {
+  uint64_t *ktmp;
+  uint32_t *bids, *itmp, *q;
+  void *sort_ws;
+  size_t sort_bytes;
+};
+static AppendWs append_layout(QrCarve &c, int64_t m, int32_t b) {
+  const size_t bm = (size_t)b * (size_t)m;
+  AppendWs w;
+  w.ktmp = c.take<uint64_t>(bm);
+  w.bids = c.take<uint32_t>(bm);
+  w.itmp = c.take<uint32_t>(bm);
+  w.q = c.take<uint32_t>(bm);
+  w.sort_bytes = qrlsh_sort_workspace_bytes(m, b);
+  w.sort_ws = c.take_bytes(w.sort_bytes, 1);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_index_append_workspace_bytes(int64_t m, int32_t b) {
   if (m <= 0 || b <= 0) return 0;
-  const size_t bm = (size_t)b * (size_t)m;
-  return qr_al16(bm * 8) + 3 * qr_al16(bm * 4) + qrlsh_sort_workspace_bytes(m, b);
+  return QR_LAYOUT_BYTES(append_layout, m, b);
 }
 
 QRLSH_EXPORT int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
@@ -688,21 +701,14 @@ QRLSH_EXPORT int qrlsh_index_append(const uint64_t *keys, const uint32_t *ids, c
   if (m == 0) return QRLSH_OK;  // nothing to add: the outputs are not written
   QR_CHECK_ARG(new_keys && keys_out && ids_out && dir_out && workspace && (n == 0 || (keys && ids && dir)),
                "qrlsh_index_append: null pointer");
-  if (workspace_bytes < qrlsh_index_append_workspace_bytes(m, b)) {
-    qrlsh_set_error("qrlsh_index_append: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_index_append_workspace_bytes(m, b));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_index_append", workspace, workspace_bytes, qrlsh_index_append_workspace_bytes(m, b));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const size_t bm = (size_t)b * (size_t)m;
-  char *ws = static_cast<char *>(workspace);
-  uint64_t *ktmp = reinterpret_cast<uint64_t *>(ws);
-  uint32_t *bids = reinterpret_cast<uint32_t *>(ws + qr_al16(bm * 8));
-  uint32_t *itmp = reinterpret_cast<uint32_t *>(ws + qr_al16(bm * 8) + qr_al16(bm * 4));
-  uint32_t *q = reinterpret_cast<uint32_t *>(ws + qr_al16(bm * 8) + 2 * qr_al16(bm * 4));
-  void *sws = ws + qr_al16(bm * 8) + 3 * qr_al16(bm * 4);
-  const int rc = qrlsh_sort_u64(new_keys, ktmp, bids, itmp, m, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0, sws,
-                                qrlsh_sort_workspace_bytes(m, b), stream);
+  QrCarve c(workspace);
+  const AppendWs w = append_layout(c, m, b);
+  uint64_t *ktmp = w.ktmp;
+  uint32_t *bids = w.bids, *itmp = w.itmp, *q = w.q;
+  const int rc = qrlsh_sort_u64(new_keys, ktmp, bids, itmp, m, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0, w.sort_ws,
+                                w.sort_bytes, stream);
   if (rc < 0) return rc;
   const uint64_t *sk = rc == 1 ? ktmp : new_keys;
   const uint32_t *si = rc == 1 ? itmp : bids;

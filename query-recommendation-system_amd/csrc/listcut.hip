@@ -38,23 +38,19 @@ struct LcWs {
   uint64_t *tile_off, *sums;
   uint32_t *bad;
   int64_t tiles;
-  size_t bytes;
 };
-static LcWs lc_layout(void *workspace, int64_t n_edges) {
+static LcWs lc_layout(QrCarve &c, int64_t n_edges) {
   LcWs w;
   w.tiles = ceil_div64(n_edges, LC_TILE);
-  char *p = static_cast<char *>(workspace);
-  size_t o = 0;
-  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(w.tiles + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(w.tiles, SCANL_CHUNK) + 1) * 8);
-  w.bad = reinterpret_cast<uint32_t *>(p + o), o += 16;
-  w.bytes = o;
+  w.tile_off = c.take<uint64_t>((size_t)(w.tiles + 1));
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(w.tiles, SCANL_CHUNK) + 1));
+  w.bad = c.take<uint32_t>(4);
   return w;
 }
 
 QRLSH_EXPORT size_t qrlsh_lists_cut_workspace_bytes(int64_t n_edges) {
   if (n_edges < 0) return 0;
-  return lc_layout(nullptr, n_edges).bytes;
+  return QR_LAYOUT_BYTES(lc_layout, n_edges);
 }
 
 // four consecutive entries from e on; past the end: -1 (no id)
@@ -171,7 +167,7 @@ static int lc_args(const char *who, const int32_t *src, int64_t n_edges, int64_t
   QR_CHECK_ARG(n >= 0 && n < (1ll << 31) && n_edges >= 0 && n_edges < (1ll << 31),
                "%s: n=%lld and n_edges=%lld must stay below 2^31", who, (long long)n, (long long)n_edges);
   QR_CHECK_ARG(workspace && (n_edges == 0 || src), "%s: null pointer", who);
-  QR_CHECK_ARG((uintptr_t)src % 16 == 0, "%s: the lists must be 16-byte aligned", who);
+  QR_CHECK_ALIGNED(who, "the lists", qr_addr(src), 16);
   QR_CHECK_ARG(workspace_bytes >= qrlsh_lists_cut_workspace_bytes(n_edges), "%s: workspace %zu < %zu bytes", who,
                workspace_bytes, qrlsh_lists_cut_workspace_bytes(n_edges));
   return QRLSH_OK;
@@ -183,11 +179,10 @@ QRLSH_EXPORT int qrlsh_lists_cut_count(const int32_t *src, int64_t n_edges, int6
   const int rc = lc_args("qrlsh_lists_cut_count", src, n_edges, n, K_old, K_new, workspace, workspace_bytes);
   if (rc != QRLSH_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LcWs w = lc_layout(workspace, n_edges);
-  if (hipMemsetAsync(w.bad, 0, 16, st) != hipSuccess || hipMemsetAsync(w.tile_off, 0, sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_lists_cut_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QrCarve c(workspace);
+  const LcWs w = lc_layout(c, n_edges);
+  QR_MEMSET("qrlsh_lists_cut_count", w.bad, 0, 16, st);
+  QR_MEMSET("qrlsh_lists_cut_count", w.tile_off, 0, sizeof(uint64_t), st);
   if (n_edges > 0) {
     QR_LAUNCH("lists_cut_count", lists_cut_kernel<false>, dim3((unsigned)w.tiles), dim3(LC_THREADS), 0, st, src,
               (const int32_t *)nullptr, (const int32_t *)nullptr, n_edges, n, (int)K_old, (int)K_new, w.tile_off, w.bad,
@@ -208,8 +203,9 @@ QRLSH_EXPORT int qrlsh_lists_cut_fill(const int32_t *src, const int32_t *dst, co
   QR_CHECK_ARG(total >= 0 && total <= n_edges, "qrlsh_lists_cut_fill: bad total %lld", (long long)total);
   if (total == 0) return QRLSH_OK;
   QR_CHECK_ARG(dst && val && src_out && dst_out && val_out, "qrlsh_lists_cut_fill: null pointer");
-  QR_CHECK_ARG(((uintptr_t)dst | (uintptr_t)val) % 16 == 0, "qrlsh_lists_cut_fill: the lists must be 16-byte aligned");
-  const LcWs w = lc_layout(const_cast<void *>(workspace), n_edges);
+  QR_CHECK_ALIGNED("qrlsh_lists_cut_fill", "the lists", qr_addr(dst) | qr_addr(val), 16);
+  QrCarve c(workspace);
+  const LcWs w = lc_layout(c, n_edges);
   QR_LAUNCH("lists_cut_fill", lists_cut_kernel<true>, dim3((unsigned)w.tiles), dim3(LC_THREADS), 0,
             static_cast<hipStream_t>(stream), src, dst, val, n_edges, n, (int)K_old, (int)K_new, w.tile_off, w.bad, total,
             src_out, dst_out, val_out);
@@ -245,11 +241,8 @@ QRLSH_EXPORT int qrlsh_lists_regrow_mark(const int32_t *src, int64_t n_edges, in
   QR_CHECK_ARG(pick_map_out && out2 && (n_edges == 0 || src), "qrlsh_lists_regrow_mark: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const IdMap pk = idmap_layout(pick_map_out, n);
-  if (hipMemsetAsync(pk.w, 0, (size_t)(pk.nw + 1) * 8, st) != hipSuccess ||
-      hipMemsetAsync(out2, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_lists_regrow_mark: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_lists_regrow_mark", pk.w, 0, (size_t)(pk.nw + 1) * 8, st);
+  QR_MEMSET("qrlsh_lists_regrow_mark", out2, 0, 2 * sizeof(uint64_t), st);
   if (n_edges > 0)
     QR_LAUNCH("lists_regrow_mark", lists_regrow_mark_kernel, dim3(rm_grid(n_edges, RM_THREADS)), dim3(RM_THREADS), 0, st, src,
               n_edges, n, (int)K_old, pk.w, out2);
@@ -283,7 +276,7 @@ QRLSH_EXPORT int qrlsh_index_pick_keys(const uint64_t *keys, const uint32_t *ids
                "qrlsh_index_pick_keys: bad sizes n=%lld b=%d n_pick=%lld", (long long)n, b, (long long)n_pick);
   if (n_pick == 0) return QRLSH_OK;
   QR_CHECK_ARG(keys && ids && pick_map && pick_keys_out, "qrlsh_index_pick_keys: null pointer");
-  const uint2 *pk = idmap_layout(const_cast<void *>(pick_map), n).w;
+  const uint2 *pk = idmap_layout(pick_map, n).w;
   QR_LAUNCH("index_pick_keys", index_pick_keys_kernel, dim3(rm_grid(n, RM_THREADS), (unsigned)b), dim3(RM_THREADS), 0,
             static_cast<hipStream_t>(stream), keys, ids, n, pk, n_pick, pick_keys_out);
   QR_LAUNCH_CHECK("qrlsh_index_pick_keys");

@@ -76,48 +76,42 @@ struct LuWs {
   uint64_t *sums;                           // scan scratch
   uint32_t *bad;                            // != 0: the stored lists break the contract
   void *sort_ws;
-  size_t sort_bytes, total;
+  size_t sort_bytes;
 };
 
 // n_kept: the stored entries when ids drop out, -1 when none do
-static LuWs lu_layout(void *workspace, int64_t n, int64_t rows_out, int64_t n_raw, int64_t n_kept) {
+static LuWs lu_layout(QrCarve &c, int64_t n, int64_t rows_out, int64_t n_raw, int64_t n_kept) {
   LuWs w;
-  char *p = static_cast<char *>(workspace);
-  size_t o = 0;
   const size_t nr = (size_t)n_raw, nn = (size_t)n, rows = (size_t)rows_out;
-  w.rec_a = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(nr * 8);
-  w.rec_b = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(nr * 8);
-  w.pay_a = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(nr * 4);
-  w.pay_b = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(nr * 4);
-  w.old_lo = reinterpret_cast<uint32_t *>(p + o);
-  w.old_hi = w.old_lo + nn;
-  w.rev_lo = w.old_hi + nn;
-  w.rev_hi = w.rev_lo + nn;
-  o += qr_al16(nn * 16);
-  w.kept = n_kept >= 0 ? reinterpret_cast<uint64_t *>(p + o) : nullptr;
-  if (n_kept >= 0) o += qr_al16((size_t)(n_kept + 1) * 8);
-  w.off = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((rows + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o);
-  o += qr_al16((size_t)(ceil_div64(n_kept > rows_out ? n_kept : rows_out, SCANL_CHUNK) + 1) * 8);
-  w.bad = reinterpret_cast<uint32_t *>(p + o), o += 16;
-  w.sort_ws = p + o;
+  w.rec_a = c.take<uint64_t>(nr);
+  w.rec_b = c.take<uint64_t>(nr);
+  w.pay_a = c.take<uint32_t>(nr);
+  w.pay_b = c.take<uint32_t>(nr);
+  w.old_lo = c.take<uint32_t>(nn * 4);
+  w.old_hi = qr_within(w.old_lo, nn);
+  w.rev_lo = qr_within(w.old_lo, 2 * nn);
+  w.rev_hi = qr_within(w.old_lo, 3 * nn);
+  w.kept = n_kept >= 0 ? c.take<uint64_t>((size_t)(n_kept + 1)) : nullptr;
+  w.off = c.take<uint64_t>(rows + 1);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(n_kept > rows_out ? n_kept : rows_out, SCANL_CHUNK) + 1));
+  w.bad = c.take<uint32_t>(4);
   w.sort_bytes = qrlsh_sort_workspace_bytes(n_raw, 1);
-  o += qr_al16(w.sort_bytes);
-  w.total = o;
+  w.sort_ws = c.take_bytes(w.sort_bytes);
   return w;
 }
-static LuWs lu_layout(void *workspace, const ListsMerge &g) {
-  return lu_layout(workspace, g.n, g.rows_out, g.n_raw, g.drop ? g.n_edges : -1);
+static LuWs lu_layout(const void *workspace, const ListsMerge &g) {
+  QrCarve c(workspace);
+  return lu_layout(c, g.n, g.rows_out, g.n_raw, g.drop ? g.n_edges : -1);
 }
 
 QRLSH_EXPORT size_t qrlsh_lists_update_workspace_bytes(int64_t n, int64_t m, int64_t n_edges, int64_t n_raw) {
   if (n < 0 || m < 0 || n_edges < 0 || n_raw < 0) return 0;
-  return lu_layout(nullptr, n, n + m, n_raw, -1).total;  // the stored lists are read in place
+  return QR_LAYOUT_BYTES(lu_layout, n, n + m, n_raw, -1);  // the stored lists are read in place
 }
 
 QRLSH_EXPORT size_t qrlsh_lists_replace_workspace_bytes(int64_t n, int64_t n_edges, int64_t n_raw) {
   if (n < 0 || n_edges < 0 || n_raw < 0) return 0;
-  return lu_layout(nullptr, n, n, n_raw, n_edges).total;
+  return QR_LAYOUT_BYTES(lu_layout, n, n, n_raw, n_edges);
 }
 
 // The order of a merged row, between a reverse record and a stored entry: value descending (inv = 1000 - milli
@@ -383,13 +377,10 @@ static int lists_merge_count(const char *who, const ListsMerge &g, const uint64_
   hipStream_t st = static_cast<hipStream_t>(stream);
   const LuWs w = lu_layout(workspace, g);
   const bool rows = g.n_edges > 0 && g.n > 0;
-  if (hipMemsetAsync(w.bad, g.n_edges > 0 && !rows ? 0xFF : 0, 16, st) != hipSuccess ||  // entries without rows to belong to
-      (g.rows_out == 0 && hipMemsetAsync(w.off, 0, sizeof(uint64_t), st) != hipSuccess) ||
-      (g.n > 0 && hipMemsetAsync(w.old_lo, 0, (size_t)g.n * 16, st) != hipSuccess) ||
-      (w.kept && hipMemsetAsync(w.kept, 0, sizeof(uint64_t), st) != hipSuccess)) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", who);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(who, w.bad, g.n_edges > 0 && !rows ? 0xFF : 0, 16, st);  // entries without rows to belong to
+  if (g.rows_out == 0) QR_MEMSET(who, w.off, 0, sizeof(uint64_t), st);
+  if (g.n > 0) QR_MEMSET(who, w.old_lo, 0, (size_t)g.n * 16, st);
+  if (w.kept) QR_MEMSET(who, w.kept, 0, sizeof(uint64_t), st);
   const dim3 block(LU_THREADS);
   if (g.n_raw > 0) {
     QR_LAUNCH("lists_records", lists_records_kernel, dim3((unsigned)ceil_div64(g.n_raw, LU_THREADS)), block, 0, st, raw,
@@ -398,11 +389,8 @@ static int lists_merge_count(const char *who, const ListsMerge &g, const uint64_
                                      w.sort_ws, w.sort_bytes, stream);
     if (where < 0) return where;
     if (where == 1) {  // the sorted records are always left in rec_a / pay_a
-      if (hipMemcpyAsync(w.rec_a, w.rec_b, (size_t)g.n_raw * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-          hipMemcpyAsync(w.pay_a, w.pay_b, (size_t)g.n_raw * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        qrlsh_set_error("%s: hipMemcpyAsync failed", who);
-        return QRLSH_EHIP;
-      }
+      QR_MEMCPY(who, w.rec_a, w.rec_b, (size_t)g.n_raw * 8, st);
+      QR_MEMCPY(who, w.pay_a, w.pay_b, (size_t)g.n_raw * 4, st);
     }
     if (g.n > 0) qr_lists_rev_rows(w.rec_a, g.n_raw, g.n, w.rev_lo, w.rev_hi, st);
   }
@@ -431,7 +419,7 @@ static int lists_merge_count(const char *who, const ListsMerge &g, const uint64_
 static int lists_merge_fill(const char *who, const ListsMerge &g, const void *workspace, int64_t total, int32_t *src_out,
                             int32_t *dst_out, int32_t *val_out, void *stream) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LuWs w = lu_layout(const_cast<void *>(workspace), g);
+  const LuWs w = lu_layout(workspace, g);
   const dim3 block(LU_THREADS);
   if (g.n_edges > 0 && g.n > 0)
     QR_LAUNCH("lists_fill_old", g.drop ? lists_fill_old_kernel<true> : lists_fill_old_kernel<false>,
@@ -465,11 +453,7 @@ static int lu_args(const char *who, const int32_t *src, const int32_t *dst, cons
                "%s: n + m and n_edges must stay below 2^31, n_raw and m * b below 2^32", who);
   QR_CHECK_ARG(workspace && (n_edges == 0 || (src && dst && val)) && (n_raw == 0 || (raw && skeys)) && (m == 0 || new_off),
                "%s: null pointer", who);
-  if (workspace_bytes < qrlsh_lists_update_workspace_bytes(n, m, n_edges, n_raw)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes,
-                    qrlsh_lists_update_workspace_bytes(n, m, n_edges, n_raw));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE(who, workspace, workspace_bytes, qrlsh_lists_update_workspace_bytes(n, m, n_edges, n_raw));
   return QRLSH_OK;
 }
 
@@ -523,11 +507,7 @@ static int rl_args(const char *who, const int32_t *src, const int32_t *dst, cons
   QR_CHECK_ARG(replaced_map && replaced_ids && r_off && workspace && (n_edges == 0 || (src && dst && val)) &&
                    (n_pick == 0 || (pick_map && pick_ids && p_off)),
                "%s: null pointer", who);
-  if (workspace_bytes < qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes,
-                    qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE(who, workspace, workspace_bytes, qrlsh_lists_replace_workspace_bytes(n, n_edges, n_raw));
   return QRLSH_OK;
 }
 
@@ -536,8 +516,8 @@ static ListsMerge rl_merge(const int32_t *src, const int32_t *dst, const int32_t
                            const void *pick_map, const uint32_t *pick_ids, int64_t n_pick, int64_t n_raw,
                            const int64_t *r_off, const int32_t *r_idx, const int32_t *r_milli, const int64_t *p_off,
                            const int32_t *p_idx, const int32_t *p_milli) {
-  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
-  return ListsMerge{src, dst, val, n_edges, n, n, (int)K, (int)b, idmap_layout(const_cast<void *>(replaced_map), n).w, pk,
+  const uint2 *pk = n_pick > 0 ? idmap_layout(pick_map, n).w : nullptr;
+  return ListsMerge{src, dst, val, n_edges, n, n, (int)K, (int)b, idmap_layout(replaced_map, n).w, pk,
                     replaced_ids, 0, m, n_raw, r_off, r_idx, r_milli, pick_ids, n_pick, p_off, p_idx, p_milli};
 }
 

@@ -379,10 +379,7 @@ QRLSH_EXPORT int qrlsh_check_csr(const int64_t *offsets, const int32_t *rows, in
                                  uint32_t *flags_out, void *stream) {
   QR_CHECK_ARG(nq >= 0 && nnz >= 0 && D > 0 && offsets && flags_out && (nnz == 0 || rows), "qrlsh_check_csr: bad arguments");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_check_csr: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_check_csr", flags_out, 0, sizeof(uint32_t), st);
   const int64_t m = (nq > nnz ? nq : nnz) + 1;
   QR_LAUNCH("check_csr", check_csr_kernel, dim3((unsigned)ceil_div64(m, 256)), dim3(256), 0, st, offsets, rows, nq, nnz, D,
             flags_out);
@@ -440,14 +437,14 @@ QRLSH_EXPORT int qrlsh_minhash(const int64_t *offsets, const int32_t *rows, int6
   QR_CHECK_ARG(nq == 0 || (offsets && perm_t && (sig_out || sig16_out)), "qrlsh_minhash: null pointer");
   QR_CHECK_ARG(!sig16_out || (D <= 65535 && perm_dtype == QRLSH_PERM_U16),
                "qrlsh_minhash: the compact uint16 signature needs D <= 65535 and a uint16 table (D=%d)", D);
-  QR_CHECK_ARG(((uintptr_t)sig16_out & 15) == 0, "qrlsh_minhash: 16-B alignment");
+  QR_CHECK_ALIGNED("qrlsh_minhash", "sig16_out", qr_addr(sig16_out), 16);
   QR_CHECK_ARG(perm_dtype == QRLSH_PERM_U16 || perm_dtype == QRLSH_PERM_I32, "qrlsh_minhash: bad perm_dtype %d",
                perm_dtype);
   const int esz = perm_dtype == QRLSH_PERM_U16 ? 2 : 4;
   QR_CHECK_ARG(((size_t)P_stride * esz) % 16 == 0, "qrlsh_minhash: P_stride*elem (%d*%d) must be a multiple of 16 B",
                P_stride, esz);
   QR_CHECK_ARG(perm_dtype != QRLSH_PERM_U16 || D <= 65536, "qrlsh_minhash: uint16 table needs D <= 65536 (D=%d)", D);
-  QR_CHECK_ARG(((uintptr_t)perm_t & 15) == 0 && ((uintptr_t)sig_out & 15) == 0, "qrlsh_minhash: 16-B alignment");
+  QR_CHECK_ALIGNED("qrlsh_minhash", "perm_t and sig_out", qr_addr(perm_t) | qr_addr(sig_out), 16);
   int r = 0;
   if (keys_out) {
     QR_CHECK_ARG(b > 0 && P % b == 0, "qrlsh_minhash: signature length %d not divisible by b=%d", P, b);

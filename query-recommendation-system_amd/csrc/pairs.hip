@@ -224,9 +224,13 @@ __global__ __launch_bounds__(CMP_THREADS) void compact_fill_kernel(const uint64_
 }
 
 // ---------------------------------------------------------------------------------------
+// workspace: per-tile counts, then their scan [b * tiles]
+static uint64_t *pairs_layout(QrCarve &c, int64_t nq, int32_t b) {
+  return c.take<uint64_t>((size_t)b * ceil_div64(nq, PAIR_TILE), 8);
+}
 QRLSH_EXPORT size_t qrlsh_pairs_workspace_bytes(int64_t nq, int32_t b) {
   if (nq <= 0 || b <= 0) return 16;
-  return (size_t)b * ceil_div64(nq, PAIR_TILE) * sizeof(uint64_t);
+  return QR_LAYOUT_BYTES(pairs_layout, nq, b);
 }
 
 QRLSH_EXPORT int qrlsh_pairs_count(const uint64_t *sorted_keys, int64_t nq, int32_t b, int32_t r, int32_t hash_bits,
@@ -238,20 +242,14 @@ QRLSH_EXPORT int qrlsh_pairs_count(const uint64_t *sorted_keys, int64_t nq, int3
   QR_CHECK_ARG(total_out && workspace, "qrlsh_pairs_count: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (nq == 0) {
-    if (hipMemsetAsync(total_out, 0, sizeof(uint64_t), st) != hipSuccess) {
-      qrlsh_set_error("hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_pairs_count", total_out, 0, sizeof(uint64_t), st);
     return QRLSH_OK;
   }
   QR_CHECK_ARG(sorted_keys, "qrlsh_pairs_count: null keys");
-  if (workspace_bytes < qrlsh_pairs_workspace_bytes(nq, b)) {
-    qrlsh_set_error("qrlsh_pairs_count: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_pairs_workspace_bytes(nq, b));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_pairs_count", workspace, workspace_bytes, qrlsh_pairs_workspace_bytes(nq, b));
   const int ntiles = (int)ceil_div64(nq, PAIR_TILE);
-  uint64_t *blk = static_cast<uint64_t *>(workspace);
+  QrCarve c(workspace);
+  uint64_t *blk = pairs_layout(c, nq, b);
   QR_LAUNCH("pairs_count", pairs_count_kernel, dim3(ntiles, b), dim3(PAIR_THREADS), 0, st, sorted_keys, nq, ntiles,
                      qr_empty_key(r), 64 - hash_bits, blk);
   QR_LAUNCH("scan_blocks", scan_u64_kernel, dim3(1), dim3(1024), 0, st, blk, (int64_t)ntiles * b, total_out);
@@ -266,19 +264,28 @@ QRLSH_EXPORT int qrlsh_pairs_fill(const uint64_t *sorted_keys, const uint32_t *s
   if (nq == 0) return QRLSH_OK;
   QR_CHECK_ARG(sorted_keys && sorted_ids && workspace && pairs_out, "qrlsh_pairs_fill: null pointer");
   const int ntiles = (int)ceil_div64(nq, PAIR_TILE);
+  QrCarve c(workspace);
   QR_LAUNCH("pairs_fill", pairs_fill_kernel, dim3(ntiles, b), dim3(PAIR_THREADS), 0, static_cast<hipStream_t>(stream),
                      sorted_keys, sorted_ids, nq, ntiles, qr_empty_key(r), 64 - hash_bits,
-                     static_cast<const uint64_t *>(workspace),
-                     pairs_out);
+                     (const uint64_t *)pairs_layout(c, nq, b), pairs_out);
   QR_LAUNCH_CHECK("qrlsh_pairs_fill");
   return QRLSH_OK;
 }
 
 // workspace: per-tile counts [nblk] | chunk totals of the large-array scan
+struct CompactWs {
+  uint64_t *blk, *sums;
+};
+static CompactWs compact_layout(QrCarve &c, int64_t n) {
+  const int64_t nblk = ceil_div64(n, CMP_TILE);
+  CompactWs w;
+  w.blk = c.take<uint64_t>((size_t)nblk, 8);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(nblk, SCANL_CHUNK) + 1), 8);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_compact_workspace_bytes(int64_t n) {
   if (n <= 0) return 16;
-  const int64_t nblk = ceil_div64(n, CMP_TILE);
-  return (size_t)(nblk + ceil_div64(nblk, SCANL_CHUNK) + 1) * sizeof(uint64_t);
+  return QR_LAYOUT_BYTES(compact_layout, n);
 }
 
 template <int PRED>
@@ -287,21 +294,17 @@ static int compact_count(const uint64_t *a, int64_t n, int K, int sh, void *work
   QR_CHECK_ARG(n >= 0 && total_out && workspace, "%s: bad arguments", name);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (n == 0) {
-    if (hipMemsetAsync(total_out, 0, sizeof(uint64_t), st) != hipSuccess) {
-      qrlsh_set_error("hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET(name, total_out, 0, sizeof(uint64_t), st);
     return QRLSH_OK;
   }
   QR_CHECK_ARG(a, "%s: null input", name);
-  if (workspace_bytes < qrlsh_compact_workspace_bytes(n)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", name, workspace_bytes, qrlsh_compact_workspace_bytes(n));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE(name, workspace, workspace_bytes, qrlsh_compact_workspace_bytes(n));
   const int64_t nblk = ceil_div64(n, CMP_TILE);
-  uint64_t *blk = static_cast<uint64_t *>(workspace);
+  QrCarve c(workspace);
+  const CompactWs w = compact_layout(c, n);
+  uint64_t *blk = w.blk;
   QR_LAUNCH(PRED == PRED_UNIQUE ? "unique_count" : "topk_count", (compact_count_kernel<PRED>), dim3((unsigned)nblk), dim3(CMP_THREADS), 0, st, a, n, K, sh, blk);
-  qr_scan_u64(blk, nblk, total_out, blk + nblk, st);
+  qr_scan_u64(blk, nblk, total_out, w.sums, st);
   QR_LAUNCH_CHECK(name);
   return QRLSH_OK;
 }
@@ -317,9 +320,10 @@ QRLSH_EXPORT int qrlsh_unique_fill(const uint64_t *sorted, int64_t n, const void
   QR_CHECK_ARG(n >= 0, "qrlsh_unique_fill: bad n");
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(sorted && workspace && out, "qrlsh_unique_fill: null pointer");
+  QrCarve c(workspace);
   QR_LAUNCH("unique_fill", (compact_fill_kernel<PRED_UNIQUE>), dim3((unsigned)ceil_div64(n, CMP_TILE)), dim3(CMP_THREADS), 0,
                      static_cast<hipStream_t>(stream), sorted, n, 0, 0, 0, (const uint32_t *)nullptr,
-                     static_cast<const uint64_t *>(workspace), out, nullptr, nullptr, nullptr);
+                     (const uint64_t *)compact_layout(c, n).blk, out, nullptr, nullptr, nullptr);
   QR_LAUNCH_CHECK("qrlsh_unique_fill");
   return QRLSH_OK;
 }
@@ -348,9 +352,10 @@ QRLSH_EXPORT int qrlsh_topk_fill_based(const uint64_t *sorted_edges, const uint3
   QR_CHECK_ARG((id_bits == 0) == (sorted_dst != nullptr), "qrlsh_topk_fill: sorted_dst goes with id_bits == 0");
   if (n_edges == 0) return QRLSH_OK;
   QR_CHECK_ARG(sorted_edges && workspace && src_out && dst_out && milli_out, "qrlsh_topk_fill: null pointer");
+  QrCarve c(workspace);
   QR_LAUNCH("topk_fill", (compact_fill_kernel<PRED_TOPK>), dim3((unsigned)ceil_div64(n_edges, CMP_TILE)),
                      dim3(CMP_THREADS), 0, static_cast<hipStream_t>(stream), sorted_edges, n_edges, K, id_bits + 11,
-                     id_bits, sorted_dst, static_cast<const uint64_t *>(workspace), nullptr, src_out, dst_out, milli_out,
+                     id_bits, sorted_dst, (const uint64_t *)compact_layout(c, n_edges).blk, nullptr, src_out, dst_out, milli_out,
                      (int32_t)src_base);
   QR_LAUNCH_CHECK("qrlsh_topk_fill");
   return QRLSH_OK;

@@ -279,9 +279,23 @@ static int64_t pt_stride(int64_t nu) { return (nu + 63) / 64 * 64; }
 
 // workspace: [transposed query lists: kq x nq doubles, kq x nq int32 (row / cell forms)][16 B: flags]
 //            [byte matrix rt: nq x round_up(nu, 64) (tile form)]
+struct PredictWs {
+  double *val_t;
+  int32_t *idx_t;
+  uint32_t *wide;
+  uint8_t *rt;
+};
+static PredictWs predict_layout(QrCarve &c, int64_t nu, int64_t nq, int32_t kq) {
+  PredictWs w;
+  w.val_t = c.take<double>((size_t)kq * (size_t)nq, 8);
+  w.idx_t = c.take<int32_t>((size_t)kq * (size_t)nq, 4);
+  w.wide = c.take<uint32_t>(4, 4);   // 4-byte aligned; 16 bytes reserved
+  w.rt = c.take<uint8_t>((size_t)nq * (size_t)pt_stride(nu), 1);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_predict_workspace_bytes(int64_t nu, int64_t nq, int32_t kq) {
   if (nu <= 0 || nq <= 0 || kq <= 0) return 0;
-  return (size_t)kq * (size_t)nq * (sizeof(double) + sizeof(int32_t)) + 16 + (size_t)nq * (size_t)pt_stride(nu);
+  return QR_LAYOUT_BYTES(predict_layout, nu, nq, kq);
 }
 
 QRLSH_EXPORT int qrlsh_predict(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
@@ -295,10 +309,7 @@ QRLSH_EXPORT int qrlsh_predict(const int32_t *ratings, int64_t nu, int64_t nq, c
                sum_order);
   QR_CHECK_ARG(too_long_out, "qrlsh_predict: too_long_out is required");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(too_long_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_predict: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_predict", too_long_out, 0, sizeof(uint32_t), st);
   if (nu == 0 || nq == 0) return QRLSH_OK;
   QR_CHECK_ARG(ratings && q_off && out && (ku == 0 || (u_idx && u_val)), "qrlsh_predict: null pointer");
   const bool tl = kq > 0 && workspace != nullptr;
@@ -314,20 +325,19 @@ QRLSH_EXPORT int qrlsh_predict(const int32_t *ratings, int64_t nu, int64_t nq, c
     QR_LAUNCH_CHECK("qrlsh_predict");
     return QRLSH_OK;
   }
-  double *val_t = static_cast<double *>(workspace);
-  int32_t *idx_t = reinterpret_cast<int32_t *>(val_t + (size_t)kq * nq);
-  uint32_t *wide = reinterpret_cast<uint32_t *>(idx_t + (size_t)kq * nq);   // 4-byte aligned; 16 bytes reserved
-  uint8_t *rt = reinterpret_cast<uint8_t *>(wide) + 16;
+  QrCarve c(workspace);
+  const PredictWs w = predict_layout(c, nu, nq, kq);
+  double *val_t = w.val_t;
+  int32_t *idx_t = w.idx_t;
+  uint32_t *wide = w.wide;
+  uint8_t *rt = w.rt;
   const bool tile = ku <= PT_MAXKU && ceil_div64(nq, PT_QUERIES) <= 2147483647ll && ceil_div64(nu, PT_USERS) <= 65535 &&
                     ceil_div64(nu, 64) <= 65535;
   const bool row = nq <= PR_MAXQ && nu <= 65535;
   if (tile) {
     // tile form; the row (or cell) form follows and does nothing unless a rating did not fit a byte
     const int64_t nus = pt_stride(nu);
-    if (hipMemsetAsync(wide, 0, 16, st) != hipSuccess) {
-      qrlsh_set_error("qrlsh_predict: hipMemsetAsync failed");
-      return QRLSH_EHIP;
-    }
+    QR_MEMSET("qrlsh_predict", wide, 0, 16, st);
     QR_LAUNCH("predict_transpose", predict_transpose_u8_kernel,
               dim3((unsigned)ceil_div64(nq, 64), (unsigned)ceil_div64(nu, 64)), dim3(256), 0, st, ratings, nu, nq, nus, rt,
               wide);
@@ -411,10 +421,7 @@ QRLSH_EXPORT int qrlsh_predict_columns(const int32_t *ratings, int64_t nu, int64
                "qrlsh_predict_columns: bad sum_order %d", sum_order);
   QR_CHECK_ARG(flags_out, "qrlsh_predict_columns: flags_out is required");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_predict_columns: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_predict_columns", flags_out, 0, sizeof(uint32_t), st);
   if (nu == 0 || m == 0) return QRLSH_OK;
   QR_CHECK_ARG(off && out && (nq == 0 || (ratings && idx && milli)), "qrlsh_predict_columns: null pointer");
   QR_LAUNCH("predict_columns", predict_columns_kernel, dim3((unsigned)m, (unsigned)ceil_div64(nu, PC_THREADS)),
@@ -534,10 +541,7 @@ int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_
     qrlsh_set_error("%s: m=%lld above the %lld rows served per call", who, (long long)m, (long long)(1ll << 24));
     return QRLSH_EUNSUPPORTED;
   }
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", who);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(who, flags_out, 0, sizeof(uint32_t), st);
   qr_lists_check("predict_users_check", q_off, q_idx, nq, users, m, nu, flags_out, st);
   if (nq > 0) {
     int64_t slices = ceil_div64(PU_AUTO_GROUPS, m);
@@ -561,7 +565,7 @@ int qr_predict_users(const char *who, const int32_t *ratings, int64_t nu, int64_
 QRLSH_EXPORT size_t qrlsh_predict_users_workspace_bytes(int64_t m, int64_t nq) {
   (void)m;
   (void)nq;
-  return 0;   // the sweep reads the lists where they are
+  return QrCarve(nullptr).bytes();   // nothing is taken: the sweep reads the lists where they are
 }
 
 QRLSH_EXPORT int qrlsh_predict_users(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,

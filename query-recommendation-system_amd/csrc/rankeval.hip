@@ -212,13 +212,25 @@ __global__ __launch_bounds__(RS_WAVES *WAVE) void rank_score_kernel(
 
 // workspace: [compact rows: m x round_up(nq, 4) int32][the selection's workspace (slice form)][part: m x sweep slices x 2
 // int64]
+struct RkWs {
+  int32_t *rows;
+  void *select;
+  long long *part;
+};
+// rows_bytes, select_bytes: qr_select_compact_plan's (multiples of 256)
+static RkWs rk_layout(QrCarve &c, int64_t m, int64_t nq, int32_t slices, size_t rows_bytes, size_t select_bytes) {
+  RkWs w;
+  w.rows = static_cast<int32_t *>(c.take_bytes(rows_bytes, 1));
+  w.select = c.take_bytes(select_bytes, 1);
+  w.part = c.take<long long>((size_t)m * (size_t)rk_sweep_slices(m, nq, slices) * 2, 256);
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_evaluate_ranking_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices) {
   if (m <= 0 || nq <= 0) return 0;
   size_t rows = 0, select = 0;
   if (qr_select_compact_plan("qrlsh_evaluate_ranking_workspace_bytes", m, nq, k, slices, &rows, &select) != QRLSH_OK)
     return 0;
-  const size_t part = (size_t)m * (size_t)rk_sweep_slices(m, nq, slices) * 2 * sizeof(long long);
-  return rows + select + (part + 255) / 256 * 256;
+  return QR_LAYOUT_BYTES(rk_layout, m, nq, slices, rows, select);
 }
 
 QRLSH_EXPORT int qrlsh_evaluate_ranking(const int32_t *train, const int32_t *truth, int64_t nu, int64_t nq,
@@ -254,22 +266,17 @@ QRLSH_EXPORT int qrlsh_evaluate_ranking(const int32_t *train, const int32_t *tru
   const int64_t S = rk_sweep_slices(m, nq, slices);
   const size_t need = qrlsh_evaluate_ranking_workspace_bytes(m, nq, k, slices);
   if (m > 0 && need > 0) {
-    QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    if (!workspace || workspace_bytes < need) {
-      qrlsh_set_error("%s: needs %zu workspace bytes, got %zu", who, need, workspace ? workspace_bytes : 0);
-      return QRLSH_EWORKSPACE;
-    }
+    QR_CHECK_ALIGNED(who, "the workspace", qr_addr(workspace), 16);
+    QR_CHECK_WORKSPACE(who, workspace, workspace_bytes, need);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
-      hipMemsetAsync(totals_out, 0, 16 * sizeof(int64_t), st) != hipSuccess) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", who);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(who, flags_out, 0, sizeof(uint32_t), st);
+  QR_MEMSET(who, totals_out, 0, 16 * sizeof(int64_t), st);
   if (m == 0) return QRLSH_OK;
-  uint8_t *ws = static_cast<uint8_t *>(workspace);
-  int32_t *rows = reinterpret_cast<int32_t *>(ws);
-  long long *part = reinterpret_cast<long long *>(ws + rows_bytes + select_bytes);
+  QrCarve c(workspace);
+  const RkWs w = rk_layout(c, m, nq, slices, rows_bytes, select_bytes);
+  int32_t *rows = w.rows;
+  long long *part = w.part;
   qr_lists_check("rank_check", q_off, q_idx, nq, users, m, nu, flags_out, st);
   if (nq > 0) {
     const dim3 grid((unsigned)(m * S));
@@ -285,7 +292,7 @@ QRLSH_EXPORT int qrlsh_evaluate_ranking(const int32_t *train, const int32_t *tru
                 stride, part);
   }
   const int rs = qr_select_compact(who, rows, nu, nq, users, m, k, lo, slices, idx_out, val_out, avail_out,
-                                   ws + rows_bytes, st);
+                                   w.select, st);
   if (rs != QRLSH_OK) return rs;
   QR_LAUNCH("rank_score", rank_score_kernel, dim3((unsigned)ceil_div64(m, RS_WAVES)), dim3(RS_WAVES * WAVE), 0, st, truth,
             nu, nq, users, m, (int)k, relevant, (const int32_t *)idx_out, (const int32_t *)avail_out,

@@ -379,38 +379,36 @@ __global__ __launch_bounds__(1024) void rank_grid_totals_kernel(const long long 
 
 // workspace: [off: m x S + 1 u64][the scan's chunk sums][lines: m x settings x 8 int64][gpart: ceil(m / 64) x settings x
 // 16 int64][col: cells int32][tru: cells int32][sides: (ncq + ncu) x cells doubles], every part 16-byte aligned
-struct RgPlan {
+struct RgWs {
   int64_t S, groups;
-  size_t off, sums, lines, gpart, col, tru, sides, bytes;
+  uint64_t *off, *sums;
+  long long *lines, *gpart;
+  int32_t *col, *tru;
+  double *sides;
 };
 
-static bool rg_plan(int64_t m, int64_t nq, int32_t ncq, int32_t ncu, int32_t settings, int64_t cells, RgPlan *p) {
-  if (m <= 0 || nq < 0 || ncq < 1 || ncq > QRLSH_GRID_MAX_CUTS || ncu < 1 || ncu > QRLSH_GRID_MAX_CUTS || settings < 1 ||
-      settings > QRLSH_GRID_MAX_SETTINGS || cells < 0 || m > (1ll << 24))
-    return false;
-  p->S = rg_slices(m, nq);
-  p->groups = ceil_div64(m, RGF_REQUESTS);
-  size_t at = 0;
-  auto take = [&](size_t bytes) {
-    const size_t here = at;
-    at += qr_al16(bytes);
-    return here;
-  };
-  p->off = take((size_t)(m * p->S + 1) * sizeof(uint64_t));
-  p->sums = take((size_t)(ceil_div64(m * p->S, SCANL_CHUNK) + 1) * sizeof(uint64_t));
-  p->lines = take((size_t)m * settings * RG_LINE * sizeof(long long));
-  p->gpart = take((size_t)p->groups * settings * RG_TOTALS * sizeof(long long));
-  p->col = take((size_t)cells * sizeof(int32_t));
-  p->tru = take((size_t)cells * sizeof(int32_t));
-  p->sides = take((size_t)(ncq + ncu) * (size_t)cells * sizeof(double));
-  p->bytes = at;
-  return true;
+static bool rg_sizes_ok(int64_t m, int64_t nq, int32_t ncq, int32_t ncu, int32_t settings, int64_t cells) {
+  return m > 0 && nq >= 0 && ncq >= 1 && ncq <= QRLSH_GRID_MAX_CUTS && ncu >= 1 && ncu <= QRLSH_GRID_MAX_CUTS &&
+         settings >= 1 && settings <= QRLSH_GRID_MAX_SETTINGS && cells >= 0 && m <= (1ll << 24);
+}
+static RgWs rg_layout(QrCarve &c, int64_t m, int64_t nq, int32_t ncq, int32_t ncu, int32_t settings, int64_t cells) {
+  RgWs w;
+  w.S = rg_slices(m, nq);
+  w.groups = ceil_div64(m, RGF_REQUESTS);
+  w.off = c.take<uint64_t>((size_t)(m * w.S + 1));
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(m * w.S, SCANL_CHUNK) + 1));
+  w.lines = c.take<long long>((size_t)m * settings * RG_LINE);
+  w.gpart = c.take<long long>((size_t)w.groups * settings * RG_TOTALS);
+  w.col = c.take<int32_t>((size_t)cells);
+  w.tru = c.take<int32_t>((size_t)cells);
+  w.sides = c.take<double>((size_t)(ncq + ncu) * (size_t)cells);
+  return w;
 }
 
 QRLSH_EXPORT size_t qrlsh_evaluate_ranking_grid_workspace_bytes(int64_t m, int64_t nq, int32_t ncq, int32_t ncu,
                                                                 int32_t settings, int64_t cells) {
-  RgPlan p;
-  return rg_plan(m, nq, ncq, ncu, settings, cells, &p) ? p.bytes : 0;
+  if (!rg_sizes_ok(m, nq, ncq, ncu, settings, cells)) return 0;
+  return QR_LAYOUT_BYTES(rg_layout, m, nq, ncq, ncu, settings, cells);
 }
 
 QRLSH_EXPORT int qrlsh_evaluate_ranking_grid(const int32_t *train, const int32_t *truth, int64_t nu, int64_t nq,
@@ -448,32 +446,23 @@ QRLSH_EXPORT int qrlsh_evaluate_ranking_grid(const int32_t *train, const int32_t
                     (long long)(1ll << 24));
     return QRLSH_EUNSUPPORTED;
   }
-  RgPlan p;
-  if (m > 0) {
-    rg_plan(m, nq, ncq, ncu, settings, cells, &p);   // cannot fail: every limit is checked above
-    QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "%s: the workspace must be 16-byte aligned", who);
-    if (!workspace || workspace_bytes < p.bytes) {
-      qrlsh_set_error("%s: needs %zu workspace bytes, got %zu", who, p.bytes, workspace ? workspace_bytes : 0);
-      return QRLSH_EWORKSPACE;
-    }
+  if (m > 0) {   // (every limit of the size is checked above)
+    QR_CHECK_ALIGNED(who, "the workspace", qr_addr(workspace), 16);
+    QR_CHECK_WORKSPACE(who, workspace, workspace_bytes,
+                       qrlsh_evaluate_ranking_grid_workspace_bytes(m, nq, ncq, ncu, settings, cells));
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flags_out, 0, sizeof(uint32_t), st) != hipSuccess ||
-      (m == 0 && hipMemsetAsync(totals_out, 0, (size_t)settings * RG_TOTALS * sizeof(int64_t), st) != hipSuccess) ||
-      (m == 0 && cells_out && hipMemsetAsync(cells_out, 0, sizeof(int64_t), st) != hipSuccess)) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", who);
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET(who, flags_out, 0, sizeof(uint32_t), st);
+  if (m == 0) QR_MEMSET(who, totals_out, 0, (size_t)settings * RG_TOTALS * sizeof(int64_t), st);
+  if (m == 0 && cells_out) QR_MEMSET(who, cells_out, 0, sizeof(int64_t), st);
   if (m == 0) return QRLSH_OK;
-  uint8_t *ws = static_cast<uint8_t *>(workspace);
-  uint64_t *off = reinterpret_cast<uint64_t *>(ws + p.off);
-  uint64_t *sums = reinterpret_cast<uint64_t *>(ws + p.sums);
-  long long *lines = per_request_out ? reinterpret_cast<long long *>(per_request_out)
-                                     : reinterpret_cast<long long *>(ws + p.lines);
-  long long *gpart = reinterpret_cast<long long *>(ws + p.gpart);
-  int32_t *col = reinterpret_cast<int32_t *>(ws + p.col);
-  int32_t *tru = reinterpret_cast<int32_t *>(ws + p.tru);
-  double *sides = reinterpret_cast<double *>(ws + p.sides);
+  QrCarve c(workspace);
+  const RgWs p = rg_layout(c, m, nq, ncq, ncu, settings, cells);
+  uint64_t *off = p.off, *sums = p.sums;
+  long long *lines = per_request_out ? reinterpret_cast<long long *>(per_request_out) : p.lines;
+  long long *gpart = p.gpart;
+  int32_t *col = p.col, *tru = p.tru;
+  double *sides = p.sides;
   const int64_t S = p.S;
   const dim3 slices_grid((unsigned)(m * S));   // <= 2^24 + 4096
   qr_lists_check("rank_grid_check", q_off, q_idx, nq, users, m, nu, flags_out, st);

@@ -425,30 +425,32 @@ int64_t rc_slices(int64_t m, int64_t nq, int32_t slices) {
   return S < 1 ? 1 : S;
 }
 
-size_t rc_round(size_t b) { return (b + 255) & ~(size_t)255; }
+constexpr size_t RC_ALIGN = 256;   // every region of this file's workspaces is rounded up to it
 
 // workspace: [RowState m][candidates m x k u64][histograms m x S][row sums m (S > 1)][tie quotas m x S int32]
-struct RcLayout {
-  size_t state, cand, hist, rowhist, tq, total;
+struct RcWs {
+  RowState *rs;
+  uint64_t *cand;
+  uint32_t *hist, *rowhist;
+  int32_t *tq;
 };
-RcLayout rc_layout(int64_t m, int32_t k, int64_t S) {
-  RcLayout L;
-  L.state = 0;
-  L.cand = rc_round((size_t)m * sizeof(RowState));
-  L.hist = L.cand + rc_round((size_t)m * k * sizeof(uint64_t));
-  L.rowhist = L.hist + rc_round((size_t)m * S * RC_HSTRIDE * sizeof(uint32_t));
-  L.tq = L.rowhist + (S > 1 ? rc_round((size_t)m * RC_HSTRIDE * sizeof(uint32_t)) : 0);
-  L.total = L.tq + rc_round((size_t)m * S * sizeof(int32_t));
-  return L;
+RcWs rc_layout(QrCarve &c, int64_t m, int32_t k, int64_t S) {
+  RcWs w;
+  w.rs = c.take<RowState>((size_t)m, RC_ALIGN);
+  w.cand = c.take<uint64_t>((size_t)m * k, RC_ALIGN);
+  w.hist = c.take<uint32_t>((size_t)m * S * RC_HSTRIDE, RC_ALIGN);
+  w.rowhist = c.take<uint32_t>(S > 1 ? (size_t)m * RC_HSTRIDE : 0, RC_ALIGN);
+  w.tq = c.take<int32_t>((size_t)m * S, RC_ALIGN);
+  return w;
 }
 
 // The selection over m rows, once the arguments are checked: the rows form (S == 0 or nq == 0; no workspace) or the
-// slice form over `ws` (rc_layout(m, k, S) bytes).  COMPACT = false: rows users[.] of ratings / pred, stride = nq;
+// slice form over the workspace `w` (rc_layout(m, k, S)).  COMPACT = false: rows users[.] of ratings / pred, stride = nq;
 // true: rows 0 .. m - 1 of the compact buffer `pred`.
 template <bool COMPACT>
 int rc_select(const char *who, const int32_t *ratings, const int32_t *pred, int64_t stride, int64_t nu, int64_t nq,
               const int32_t *users, int64_t m, int32_t k, int32_t lo, int64_t S, int32_t *idx_out, int32_t *val_out,
-              int32_t *avail_out, uint8_t *ws, hipStream_t st) {
+              int32_t *avail_out, const RcWs &w, hipStream_t st) {
   if (S == 0 || nq == 0) {
     // rows form (also every row of an empty matrix: avail 0, padded, bad ids flagged)
     QR_LAUNCH("recommend_rows", recommend_rows_kernel<COMPACT>, dim3((unsigned)m), dim3(RC_THREADS), 0, st, ratings, pred,
@@ -456,16 +458,11 @@ int rc_select(const char *who, const int32_t *ratings, const int32_t *pred, int6
     QR_LAUNCH_CHECK(who);
     return QRLSH_OK;
   }
-  const RcLayout L = rc_layout(m, k, S);
-  RowState *rs = reinterpret_cast<RowState *>(ws + L.state);
-  uint64_t *cand = reinterpret_cast<uint64_t *>(ws + L.cand);
-  uint32_t *hist = reinterpret_cast<uint32_t *>(ws + L.hist);
-  uint32_t *rowhist = reinterpret_cast<uint32_t *>(ws + L.rowhist);
-  int32_t *tq = reinterpret_cast<int32_t *>(ws + L.tq);
-  if (S > 1 && hipMemsetAsync(rowhist, 0, (size_t)m * RC_HSTRIDE * sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("%s: hipMemsetAsync failed", who);
-    return QRLSH_EHIP;
-  }
+  RowState *rs = w.rs;
+  uint64_t *cand = w.cand;
+  uint32_t *hist = w.hist, *rowhist = w.rowhist;
+  int32_t *tq = w.tq;
+  if (S > 1) QR_MEMSET(who, rowhist, 0, (size_t)m * RC_HSTRIDE * sizeof(uint32_t), st);
   const unsigned groups = (unsigned)(m * S);
   const uint32_t lo_key = (uint32_t)lo ^ 0x80000000u;
   for (int pass = 0; pass < 4; ++pass) {
@@ -486,13 +483,29 @@ int rc_select(const char *who, const int32_t *ratings, const int32_t *pred, int6
 
 // qrlsh_recommend_users' compact rows: a stride of whole 16-byte vectors, so that every row starts on one
 int64_t rc_compact_stride(int64_t nq) { return (nq + 3) & ~(int64_t)3; }
+
+// the selection's workspace where there is one: the slice form over a matrix with columns
+RcWs rc_select_layout(QrCarve &c, int64_t m, int64_t nq, int32_t k, int64_t S) {
+  return S > 0 && m > 0 && nq > 0 ? rc_layout(c, m, k, S) : RcWs{};
+}
+// workspace: [compact eligible-mode rows: m x round_up(nq, 4) int32][the selection's workspace (slice form)]
+struct RuWs {
+  int32_t *rows;
+  RcWs select;
+};
+RuWs ru_layout(QrCarve &c, int64_t m, int64_t nq, int32_t k, int64_t S) {
+  RuWs w;
+  w.rows = c.take<int32_t>((size_t)m * (size_t)rc_compact_stride(nq), RC_ALIGN);
+  w.select = rc_select_layout(c, m, nq, k, S);
+  return w;
+}
 }  // namespace
 
 QRLSH_EXPORT size_t qrlsh_recommend_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices) {
   if (m <= 0 || nq <= 0 || k < 1 || k > QRLSH_RECOMMEND_MAX_K || slices < 0 || slices > RC_MAXS) return 0;
   const int64_t S = rc_slices(m, nq, slices);
   if (S == 0 || m > RC_MAX_GROUPS || m * S > RC_MAX_GROUPS) return 0;
-  return rc_layout(m, k, S).total;
+  return QR_LAYOUT_BYTES(rc_select_layout, m, nq, k, S);
 }
 
 QRLSH_EXPORT int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pred, int64_t nu, int64_t nq,
@@ -509,23 +522,18 @@ QRLSH_EXPORT int qrlsh_recommend_topk(const int32_t *ratings, const int32_t *pre
   QR_CHECK_ARG(m == 0 || (idx_out && val_out && avail_out), "qrlsh_recommend_topk: null output pointer");
   if (m == 0) return QRLSH_OK;
   QR_CHECK_ARG(nq == 0 || nu == 0 || (ratings && pred), "qrlsh_recommend_topk: null matrix pointer");
-  QR_CHECK_ARG((((uintptr_t)ratings | (uintptr_t)pred) & 15u) == 0,
-               "qrlsh_recommend_topk: ratings and pred must be 16-byte aligned");
+  QR_CHECK_ALIGNED("qrlsh_recommend_topk", "ratings and pred", qr_addr(ratings) | qr_addr(pred), 16);
   const int64_t S = rc_slices(m, nq, slices);
   if (m > RC_MAX_GROUPS || m * (S > 0 ? S : 1) > RC_MAX_GROUPS) {
     qrlsh_set_error("qrlsh_recommend_topk: m=%lld x slices=%lld above the %lld workgroups served", (long long)m,
                     (long long)S, (long long)RC_MAX_GROUPS);
     return QRLSH_EUNSUPPORTED;
   }
-  if (S > 0 && nq > 0) {
-    const size_t need = rc_layout(m, k, S).total;
-    if (!workspace || workspace_bytes < need) {
-      qrlsh_set_error("qrlsh_recommend_topk: needs %zu workspace bytes, got %zu", need, workspace ? workspace_bytes : 0);
-      return QRLSH_EWORKSPACE;
-    }
-  }
+  QR_CHECK_WORKSPACE("qrlsh_recommend_topk", workspace, workspace_bytes,
+                     qrlsh_recommend_workspace_bytes(m, nq, k, slices));
+  QrCarve c(workspace);
   return rc_select<false>("qrlsh_recommend_topk", ratings, pred, nq, nu, nq, users, m, k, lo, S, idx_out, val_out,
-                          avail_out, static_cast<uint8_t *>(workspace), static_cast<hipStream_t>(stream));
+                          avail_out, rc_select_layout(c, m, nq, k, S), static_cast<hipStream_t>(stream));
 }
 
 // ---- the selection over compact rows for other files (common.h): qrlsh_evaluate_ranking's sweep in rankeval.hip writes
@@ -543,24 +551,28 @@ int qr_select_compact_plan(const char *who, int64_t m, int64_t nq, int32_t k, in
                     (long long)RC_MAX_GROUPS);
     return QRLSH_EUNSUPPORTED;
   }
-  *rows_bytes = rc_round((size_t)m * (size_t)rc_compact_stride(nq) * sizeof(int32_t));
-  *select_bytes = S > 0 && m > 0 && nq > 0 ? rc_layout(m, k, S).total : 0;
+  QrCarve all(nullptr), select(nullptr);
+  ru_layout(all, m, nq, k, S);
+  rc_select_layout(select, m, nq, k, S);
+  *rows_bytes = all.bytes() - select.bytes();
+  *select_bytes = select.bytes();
   return QRLSH_OK;
 }
 
 int qr_select_compact(const char *who, const int32_t *rows, int64_t nu, int64_t nq, const int32_t *users, int64_t m,
                       int32_t k, int32_t lo, int32_t slices, int32_t *idx_out, int32_t *val_out, int32_t *avail_out,
                       void *select_ws, hipStream_t st) {
-  return rc_select<true>(who, nullptr, rows, rc_compact_stride(nq), nu, nq, users, m, k, lo, rc_slices(m, nq, slices),
-                         idx_out, val_out, avail_out, static_cast<uint8_t *>(select_ws), st);
+  const int64_t S = rc_slices(m, nq, slices);
+  QrCarve c(select_ws);
+  return rc_select<true>(who, nullptr, rows, rc_compact_stride(nq), nu, nq, users, m, k, lo, S, idx_out, val_out,
+                         avail_out, rc_select_layout(c, m, nq, k, S), st);
 }
 
-// workspace: [compact eligible-mode rows: m x round_up(nq, 4) int32][the selection's workspace (slice form)]
 QRLSH_EXPORT size_t qrlsh_recommend_users_workspace_bytes(int64_t m, int64_t nq, int32_t k, int32_t slices) {
   if (m <= 0 || nq <= 0 || k < 1 || k > QRLSH_RECOMMEND_MAX_K || slices < 0 || slices > RC_MAXS) return 0;
   const int64_t S = rc_slices(m, nq, slices);
   if (m > RC_MAX_GROUPS || m * (S > 0 ? S : 1) > RC_MAX_GROUPS) return 0;
-  return rc_round((size_t)m * (size_t)rc_compact_stride(nq) * sizeof(int32_t)) + (S > 0 ? rc_layout(m, k, S).total : 0);
+  return QR_LAYOUT_BYTES(ru_layout, m, nq, k, S);
 }
 
 QRLSH_EXPORT int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off,
@@ -583,16 +595,14 @@ QRLSH_EXPORT int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64
   }
   const size_t need = qrlsh_recommend_users_workspace_bytes(m, nq, k, slices);
   if (m > 0 && need > 0) {
-    QR_CHECK_ARG(((uintptr_t)workspace & 15u) == 0, "qrlsh_recommend_users: the workspace must be 16-byte aligned");
-    if (!workspace || workspace_bytes < need) {
-      qrlsh_set_error("qrlsh_recommend_users: needs %zu workspace bytes, got %zu", need, workspace ? workspace_bytes : 0);
-      return QRLSH_EWORKSPACE;
-    }
+    QR_CHECK_ALIGNED("qrlsh_recommend_users", "the workspace", qr_addr(workspace), 16);
+    QR_CHECK_WORKSPACE("qrlsh_recommend_users", workspace, workspace_bytes, need);
   }
   hipStream_t st = static_cast<hipStream_t>(stream);
-  uint8_t *ws = static_cast<uint8_t *>(workspace);
+  QrCarve c(workspace);
+  const RuWs w = ru_layout(c, m, nq, k, S);
   const int64_t stride = rc_compact_stride(nq);
-  int32_t *rows = reinterpret_cast<int32_t *>(ws);
+  int32_t *rows = w.rows;
   // the remaining checks (sizes, sum_order, pointers) are the sweep's, made before any device work as well; m = 0
   // returns from there
   const int rc = qr_predict_users("qrlsh_recommend_users", ratings, nu, nq, q_off, q_idx, q_milli, u_idx, u_val, ku,
@@ -600,5 +610,5 @@ QRLSH_EXPORT int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64
                                   flags_out, st);
   if (rc != QRLSH_OK || m == 0) return rc;
   return rc_select<true>("qrlsh_recommend_users", nullptr, rows, stride, nu, nq, users, m, k, lo, S, idx_out, val_out,
-                         avail_out, nq > 0 ? ws + rc_round((size_t)m * (size_t)stride * sizeof(int32_t)) : nullptr, st);
+                         avail_out, w.select, st);
 }

@@ -27,7 +27,7 @@
 
 QRLSH_EXPORT size_t qrlsh_idmap_workspace_bytes(int64_t n) {
   if (n < 0) return 0;
-  return idmap_layout(nullptr, n).bytes;
+  return QR_LAYOUT_BYTES(idmap_layout, n);
 }
 
 __global__ __launch_bounds__(RM_THREADS) void idmap_mark_kernel(const uint32_t *__restrict__ ids, int64_t m, int64_t n,
@@ -68,17 +68,11 @@ QRLSH_EXPORT int qrlsh_idmap_build(const uint32_t *ids, int64_t m, int64_t n, vo
   QR_CHECK_ARG(m >= 0 && n >= 0 && n < (1ll << 32) - 1, "qrlsh_idmap_build: bad sizes m=%lld n=%lld", (long long)m,
                (long long)n);
   QR_CHECK_ARG(map && out2 && (m == 0 || ids), "qrlsh_idmap_build: null pointer");
-  if (map_bytes < qrlsh_idmap_workspace_bytes(n)) {
-    qrlsh_set_error("qrlsh_idmap_build: map %zu < %zu bytes", map_bytes, qrlsh_idmap_workspace_bytes(n));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_idmap_build", map, map_bytes, qrlsh_idmap_workspace_bytes(n));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const IdMap w = idmap_layout(map, n);
-  if (hipMemsetAsync(w.w, 0, (size_t)(w.nw + 1) * 8, st) != hipSuccess ||
-      hipMemsetAsync(out2, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_idmap_build: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_idmap_build", w.w, 0, (size_t)(w.nw + 1) * 8, st);
+  QR_MEMSET("qrlsh_idmap_build", out2, 0, 2 * sizeof(uint64_t), st);
   if (m > 0)
     QR_LAUNCH("idmap_mark", idmap_mark_kernel, dim3(rm_grid(m, RM_THREADS)), dim3(RM_THREADS), 0, st, ids, m, n, w.w, out2);
   idmap_finish(w, out2, st);
@@ -104,7 +98,7 @@ QRLSH_EXPORT int qrlsh_idmap_list(const void *map, int64_t n, uint32_t *ids_out,
   QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && map, "qrlsh_idmap_list: bad arguments");
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(ids_out, "qrlsh_idmap_list: null ids_out");
-  const IdMap w = idmap_layout(const_cast<void *>(map), n);
+  const IdMap w = idmap_layout(map, n);
   QR_LAUNCH("idmap_list", idmap_list_kernel, dim3((unsigned)ceil_div64(w.nw, RM_THREADS)), dim3(RM_THREADS), 0,
             static_cast<hipStream_t>(stream), (const uint2 *)w.w, w.nw, ids_out);
   QR_LAUNCH_CHECK("qrlsh_idmap_list");
@@ -124,7 +118,7 @@ QRLSH_EXPORT int qrlsh_idmap_positions(const void *map, int64_t n, int64_t *pos_
   QR_CHECK_ARG(n >= 0 && n < (1ll << 32) - 1 && map, "qrlsh_idmap_positions: bad arguments");
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(pos_out, "qrlsh_idmap_positions: null pos_out");
-  const IdMap w = idmap_layout(const_cast<void *>(map), n);
+  const IdMap w = idmap_layout(map, n);
   QR_LAUNCH("idmap_positions", idmap_positions_kernel, dim3(rm_grid(n, RM_THREADS)), dim3(RM_THREADS), 0,
             static_cast<hipStream_t>(stream), (const uint2 *)w.w, n, pos_out);
   QR_LAUNCH_CHECK("qrlsh_idmap_positions");
@@ -163,8 +157,8 @@ QRLSH_EXPORT int qrlsh_rows_remove(const void *rows, int64_t row_bytes, const in
                "qrlsh_rows_remove: bad sizes n=%lld row_bytes=%lld (a multiple of 2)", (long long)n, (long long)row_bytes);
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(rows && removed_map && rows_out && (!norm2 || norm2_out), "qrlsh_rows_remove: null pointer");
-  QR_CHECK_ARG(((uintptr_t)rows | (uintptr_t)rows_out) % 16 == 0, "qrlsh_rows_remove: rows must be 16-byte aligned");
-  const uint2 *rm = idmap_layout(const_cast<void *>(removed_map), n).w;
+  QR_CHECK_ALIGNED("qrlsh_rows_remove", "rows", qr_addr(rows) | qr_addr(rows_out), 16);
+  const uint2 *rm = idmap_layout(removed_map, n).w;
   hipStream_t st = static_cast<hipStream_t>(stream);
   // every row starts on a multiple of its width from a 16-byte aligned base: the widest vector that divides the width
   if (row_bytes % 16 == 0) rows_remove_launch<uint4>(rows, row_bytes, norm2, n, rm, rows_out, norm2_out, st);
@@ -229,10 +223,19 @@ __global__ __launch_bounds__(RM_THREADS) void index_remove_kernel(
 }
 
 // workspace: tile counts / offsets u64 [b * tiles + 1] | scan sums
+struct IrWs {
+  uint64_t *tile_off, *sums;
+};
+static IrWs ir_layout(QrCarve &c, int64_t n, int32_t b) {
+  const int64_t all = ceil_div64(n, RM_TILE) * b;
+  IrWs w;
+  w.tile_off = c.take<uint64_t>((size_t)(all + 1));
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(all, SCANL_CHUNK) + 1));
+  return w;
+}
 QRLSH_EXPORT size_t qrlsh_index_remove_workspace_bytes(int64_t n, int32_t b) {
   if (n <= 0 || b <= 0) return 0;
-  const int64_t tiles = ceil_div64(n, RM_TILE) * b;
-  return qr_al16((size_t)(tiles + 1) * 8) + qr_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
+  return QR_LAYOUT_BYTES(ir_layout, n, b);
 }
 
 QRLSH_EXPORT int qrlsh_index_remove(const uint64_t *keys, const uint32_t *ids, int64_t n, int32_t b, const void *removed_map,
@@ -247,17 +250,14 @@ QRLSH_EXPORT int qrlsh_index_remove(const uint64_t *keys, const uint32_t *ids, i
   QR_CHECK_ARG(keys && ids && removed_map && keys_out && ids_out && dir_out && workspace &&
                    (n_pick == 0 || (pick_map && pick_keys_out)),
                "qrlsh_index_remove: null pointer");
-  if (workspace_bytes < qrlsh_index_remove_workspace_bytes(n, b)) {
-    qrlsh_set_error("qrlsh_index_remove: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_index_remove_workspace_bytes(n, b));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_index_remove", workspace, workspace_bytes, qrlsh_index_remove_workspace_bytes(n, b));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const int64_t n_out = n - n_removed, tiles = ceil_div64(n, RM_TILE), all = tiles * b;
-  uint64_t *tile_off = static_cast<uint64_t *>(workspace);
-  uint64_t *sums = reinterpret_cast<uint64_t *>(static_cast<char *>(workspace) + qr_al16((size_t)(all + 1) * 8));
-  const uint2 *rm = idmap_layout(const_cast<void *>(removed_map), n).w;
-  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+  QrCarve c(workspace);
+  const IrWs w = ir_layout(c, n, b);
+  uint64_t *tile_off = w.tile_off, *sums = w.sums;
+  const uint2 *rm = idmap_layout(removed_map, n).w;
+  const uint2 *pk = n_pick > 0 ? idmap_layout(pick_map, n).w : nullptr;
   const dim3 grid((unsigned)tiles, (unsigned)b), block(RM_THREADS);
   QR_LAUNCH("index_remove_count", index_remove_kernel<false>, grid, block, 0, st, keys, ids, n, n_out, n_out * b, rm, pk,
             n_pick, tile_off, keys_out, ids_out, pick_keys_out);
@@ -302,14 +302,11 @@ QRLSH_EXPORT int qrlsh_lists_remove_mark(const int32_t *src, const int32_t *dst,
   QR_CHECK_ARG(removed_map && pick_map_out && out2 && (n_edges == 0 || (src && dst)), "qrlsh_lists_remove_mark: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const IdMap pk = idmap_layout(pick_map_out, n);
-  if (hipMemsetAsync(pk.w, 0, (size_t)(pk.nw + 1) * 8, st) != hipSuccess ||
-      hipMemsetAsync(out2, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_lists_remove_mark: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_lists_remove_mark", pk.w, 0, (size_t)(pk.nw + 1) * 8, st);
+  QR_MEMSET("qrlsh_lists_remove_mark", out2, 0, 2 * sizeof(uint64_t), st);
   if (n_edges > 0)
     QR_LAUNCH("lists_remove_mark", lists_remove_mark_kernel, dim3(rm_grid(n_edges, RM_THREADS)), dim3(RM_THREADS), 0, st, src,
-              dst, n_edges, n, (int)K, (const uint2 *)idmap_layout(const_cast<void *>(removed_map), n).w, pk.w, out2);
+              dst, n_edges, n, (int)K, (const uint2 *)idmap_layout(removed_map, n).w, pk.w, out2);
   idmap_finish(pk, out2, st);
   QR_LAUNCH_CHECK("qrlsh_lists_remove_mark");
   return QRLSH_OK;
@@ -319,25 +316,21 @@ struct LrWs {
   uint64_t *tile_off, *sums, *pick_base;
   uint32_t *bad;
   int64_t tiles, rows;
-  size_t bytes;
 };
-static LrWs lr_layout(void *workspace, int64_t n, int64_t n_edges) {
+static LrWs lr_layout(QrCarve &c, int64_t n, int64_t n_edges) {
   LrWs w;
   w.tiles = ceil_div64(n_edges, RM_TILE);
   w.rows = n < n_edges ? n : n_edges;  // no more picked rows than rows, or than entries
-  char *p = static_cast<char *>(workspace);
-  size_t o = 0;
-  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(w.tiles + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(w.tiles, SCANL_CHUNK) + 1) * 8);
-  w.pick_base = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)w.rows * 8);
-  w.bad = reinterpret_cast<uint32_t *>(p + o), o += 16;
-  w.bytes = o;
+  w.tile_off = c.take<uint64_t>((size_t)(w.tiles + 1));
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(w.tiles, SCANL_CHUNK) + 1));
+  w.pick_base = c.take<uint64_t>((size_t)w.rows);
+  w.bad = c.take<uint32_t>(4);
   return w;
 }
 
 QRLSH_EXPORT size_t qrlsh_lists_remove_workspace_bytes(int64_t n, int64_t n_edges) {
   if (n < 0 || n_edges < 0) return 0;
-  return lr_layout(nullptr, n, n_edges).bytes;
+  return QR_LAYOUT_BYTES(lr_layout, n, n_edges);
 }
 
 // one workgroup per tile of stored entries.  An entry is kept when its src and dst stay and its row is not picked.
@@ -419,10 +412,7 @@ static int lr_args(const char *who, const int32_t *src, const int32_t *dst, cons
                (long long)n_edges, (long long)n_pick);
   QR_CHECK_ARG(removed_map && workspace && (n_edges == 0 || (src && dst && val)) && (n_pick == 0 || (pick_map && re_off)),
                "%s: null pointer", who);
-  if (workspace_bytes < qrlsh_lists_remove_workspace_bytes(n, n_edges)) {
-    qrlsh_set_error("%s: workspace %zu < %zu bytes", who, workspace_bytes, qrlsh_lists_remove_workspace_bytes(n, n_edges));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE(who, workspace, workspace_bytes, qrlsh_lists_remove_workspace_bytes(n, n_edges));
   return QRLSH_OK;
 }
 
@@ -435,15 +425,14 @@ QRLSH_EXPORT int qrlsh_lists_remove_count(const int32_t *src, const int32_t *dst
                          workspace, workspace_bytes);
   if (rc != QRLSH_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LrWs w = lr_layout(workspace, n, n_edges);
-  if (hipMemsetAsync(w.bad, 0, 16, st) != hipSuccess || hipMemsetAsync(w.tile_off, 0, sizeof(uint64_t), st) != hipSuccess ||
-      (w.rows > 0 && hipMemsetAsync(w.pick_base, 0, (size_t)w.rows * 8, st) != hipSuccess)) {
-    qrlsh_set_error("qrlsh_lists_remove_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QrCarve c(workspace);
+  const LrWs w = lr_layout(c, n, n_edges);
+  QR_MEMSET("qrlsh_lists_remove_count", w.bad, 0, 16, st);
+  QR_MEMSET("qrlsh_lists_remove_count", w.tile_off, 0, sizeof(uint64_t), st);
+  if (w.rows > 0) QR_MEMSET("qrlsh_lists_remove_count", w.pick_base, 0, (size_t)w.rows * 8, st);
   if (n_edges > 0) {
-    const uint2 *rm = idmap_layout(const_cast<void *>(removed_map), n).w;
-    const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+    const uint2 *rm = idmap_layout(removed_map, n).w;
+    const uint2 *pk = n_pick > 0 ? idmap_layout(pick_map, n).w : nullptr;
     QR_LAUNCH("lists_remove_count", lists_remove_kernel<false>, dim3((unsigned)w.tiles), dim3(RM_THREADS), 0, st, src, dst,
               val, n_edges, n, rm, pk, re_off, n_pick, w.tile_off, w.bad, (int64_t)0, w.pick_base, nullptr, nullptr, nullptr);
     qr_scan_u64(w.tile_off, w.tiles, w.tile_off + w.tiles, w.sums, st);
@@ -467,10 +456,11 @@ QRLSH_EXPORT int qrlsh_lists_remove_fill(const int32_t *src, const int32_t *dst,
   if (total == 0) return QRLSH_OK;
   QR_CHECK_ARG(src_out && dst_out && val_out && (n_pick == 0 || re_self), "qrlsh_lists_remove_fill: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const LrWs w = lr_layout(workspace, n, n_edges);
+  QrCarve c(workspace);
+  const LrWs w = lr_layout(c, n, n_edges);
   if (n_edges > 0) {
-    const uint2 *rm = idmap_layout(const_cast<void *>(removed_map), n).w;
-    const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+    const uint2 *rm = idmap_layout(removed_map, n).w;
+    const uint2 *pk = n_pick > 0 ? idmap_layout(pick_map, n).w : nullptr;
     QR_LAUNCH("lists_remove_fill", lists_remove_kernel<true>, dim3((unsigned)w.tiles), dim3(RM_THREADS), 0, st, src, dst, val,
               n_edges, n, rm, pk, re_off, n_pick, w.tile_off, w.bad, total, w.pick_base, src_out, dst_out, val_out);
   }

@@ -63,7 +63,7 @@ QRLSH_EXPORT int qrlsh_rows_replace(void *rows, int64_t row_bytes, int64_t *norm
                (long long)row_bytes);
   if (m == 0) return QRLSH_OK;
   QR_CHECK_ARG(rows && ids && new_rows && (!norm2 || new_norm2), "qrlsh_rows_replace: null pointer");
-  QR_CHECK_ARG(((uintptr_t)rows | (uintptr_t)new_rows) % 16 == 0, "qrlsh_rows_replace: rows must be 16-byte aligned");
+  QR_CHECK_ALIGNED("qrlsh_rows_replace", "rows", qr_addr(rows) | qr_addr(new_rows), 16);
   hipStream_t st = static_cast<hipStream_t>(stream);
   if (row_bytes % 16 == 0) rows_replace_launch<uint4>(rows, row_bytes, norm2, n, ids, new_rows, new_norm2, m, st);
   else if (row_bytes % 8 == 0) rows_replace_launch<uint2>(rows, row_bytes, norm2, n, ids, new_rows, new_norm2, m, st);
@@ -218,32 +218,28 @@ struct RpWs {
   uint64_t *ktmp, *left_a, *left_b, *tile_off, *sums;
   uint32_t *bx, *xtmp, *s;
   void *sort_ws;
-  size_t sort_bytes, bytes;
+  size_t sort_bytes;
 };
-static RpWs rp_layout(void *workspace, int64_t n, int64_t m, int32_t b) {
+static RpWs rp_layout(QrCarve &c, int64_t n, int64_t m, int32_t b) {
   RpWs w;
   const size_t bm = (size_t)b * (size_t)m;
   const int64_t tiles = ceil_div64(n, RM_TILE) * b;
-  char *p = static_cast<char *>(workspace);
-  size_t o = 0;
-  w.ktmp = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(bm * 8);
-  w.left_a = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(bm * 8);
-  w.left_b = reinterpret_cast<uint64_t *>(p + o), o += qr_al16(bm * 8);
-  w.bx = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(bm * 4);
-  w.xtmp = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(bm * 4);
-  w.s = reinterpret_cast<uint32_t *>(p + o), o += qr_al16(bm * 4);
-  w.tile_off = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(tiles + 1) * 8);
-  w.sums = reinterpret_cast<uint64_t *>(p + o), o += qr_al16((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1) * 8);
-  w.sort_ws = p + o;
+  w.ktmp = c.take<uint64_t>(bm);
+  w.left_a = c.take<uint64_t>(bm);
+  w.left_b = c.take<uint64_t>(bm);
+  w.bx = c.take<uint32_t>(bm);
+  w.xtmp = c.take<uint32_t>(bm);
+  w.s = c.take<uint32_t>(bm);
+  w.tile_off = c.take<uint64_t>((size_t)(tiles + 1));
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(tiles, SCANL_CHUNK) + 1));
   w.sort_bytes = qrlsh_sort_workspace_bytes(m, b);
-  o += qr_al16(w.sort_bytes);
-  w.bytes = o;
+  w.sort_ws = c.take_bytes(w.sort_bytes);
   return w;
 }
 
 QRLSH_EXPORT size_t qrlsh_index_replace_workspace_bytes(int64_t n, int64_t m, int32_t b) {
   if (n <= 0 || m <= 0 || b <= 0) return 0;
-  return rp_layout(nullptr, n, m, b).bytes;
+  return QR_LAYOUT_BYTES(rp_layout, n, m, b);
 }
 
 QRLSH_EXPORT int qrlsh_index_replace(const uint64_t *keys, const uint32_t *ids, const uint32_t *dir, int64_t n, int32_t b,
@@ -258,16 +254,13 @@ QRLSH_EXPORT int qrlsh_index_replace(const uint64_t *keys, const uint32_t *ids, 
   QR_CHECK_ARG(keys && ids && dir && replaced_map && replaced_ids && new_keys && keys_out && ids_out && dir_out &&
                    workspace && (n_pick == 0 || (pick_map && pick_keys_out)),
                "qrlsh_index_replace: null pointer");
-  if (workspace_bytes < qrlsh_index_replace_workspace_bytes(n, m, b)) {
-    qrlsh_set_error("qrlsh_index_replace: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_index_replace_workspace_bytes(n, m, b));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_index_replace", workspace, workspace_bytes, qrlsh_index_replace_workspace_bytes(n, m, b));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const RpWs w = rp_layout(workspace, n, m, b);
+  QrCarve c(workspace);
+  const RpWs w = rp_layout(c, n, m, b);
   const int64_t tiles = ceil_div64(n, RM_TILE), all = tiles * b;
-  const uint2 *rm = idmap_layout(const_cast<void *>(replaced_map), n).w;
-  const uint2 *pk = n_pick > 0 ? idmap_layout(const_cast<void *>(pick_map), n).w : nullptr;
+  const uint2 *rm = idmap_layout(replaced_map, n).w;
+  const uint2 *pk = n_pick > 0 ? idmap_layout(pick_map, n).w : nullptr;
   int rc = qrlsh_sort_u64(new_keys, w.ktmp, w.bx, w.xtmp, m, b, 32, 64, QRLSH_SORT_MIX | QRLSH_SORT_IOTA, 0, w.sort_ws,
                           w.sort_bytes, stream);
   if (rc < 0) return rc;

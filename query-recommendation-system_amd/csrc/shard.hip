@@ -16,26 +16,23 @@ struct IdSetWs {
   uint32_t *bm;
   uint64_t *prefix, *scratch;
   int64_t nw;
-  size_t bytes;
 };
-static IdSetWs idset_ws(void *workspace, int64_t nids) {
+static IdSetWs idset_layout(QrCarve &c, int64_t nids) {
   IdSetWs w;
   w.nw = (nids + 31) / 32;
-  char *p = static_cast<char *>(workspace);
-  size_t off = 0;
-  w.bm = reinterpret_cast<uint32_t *>(p + off);
-  off += ((size_t)w.nw * 4 + 15) & ~(size_t)15;
-  w.prefix = reinterpret_cast<uint64_t *>(p + off);
-  off += (size_t)(w.nw + 2) * 8;
-  w.scratch = reinterpret_cast<uint64_t *>(p + off);
-  off += (size_t)(ceil_div64(w.nw + 1, SCANL_CHUNK) + 2) * 8;
-  w.bytes = off;
+  w.bm = c.take<uint32_t>((size_t)w.nw);
+  w.prefix = c.take<uint64_t>((size_t)(w.nw + 2), 8);
+  w.scratch = c.take<uint64_t>((size_t)(ceil_div64(w.nw + 1, SCANL_CHUNK) + 2), 8);
   return w;
+}
+static IdSetWs idset_layout(const void *workspace, int64_t nids) {
+  QrCarve c(workspace);
+  return idset_layout(c, nids);
 }
 
 QRLSH_EXPORT size_t qrlsh_idset_workspace_bytes(int64_t nids) {
   if (nids <= 0) return 64;
-  return idset_ws(nullptr, nids).bytes;
+  return QR_LAYOUT_BYTES(idset_layout, nids);
 }
 
 // both endpoints of every pair that fall outside [q0, q0 + nql) set their bit
@@ -114,16 +111,10 @@ QRLSH_EXPORT int qrlsh_idset_build(const uint64_t *pairs, int64_t n, int64_t q0,
   QR_CHECK_ARG(n >= 0 && q0 >= 0 && nql >= 0 && nids > 0 && nids <= (1ll << 32) && shard >= 1 && world >= 1,
                "qrlsh_idset_build: bad sizes n=%lld nids=%lld", (long long)n, (long long)nids);
   QR_CHECK_ARG(workspace && bounds_out && (n == 0 || pairs), "qrlsh_idset_build: null pointer");
-  if (workspace_bytes < qrlsh_idset_workspace_bytes(nids)) {
-    qrlsh_set_error("qrlsh_idset_build: workspace %zu < %zu bytes", workspace_bytes, qrlsh_idset_workspace_bytes(nids));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_idset_build", workspace, workspace_bytes, qrlsh_idset_workspace_bytes(nids));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const IdSetWs w = idset_ws(workspace, nids);
-  if (hipMemsetAsync(w.bm, 0, (size_t)w.nw * 4, st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_idset_build: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  const IdSetWs w = idset_layout(workspace, nids);
+  QR_MEMSET("qrlsh_idset_build", w.bm, 0, (size_t)w.nw * 4, st);
   if (n)
     QR_LAUNCH("idset_mark", idset_mark_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, pairs, n,
               (uint64_t)q0, (uint64_t)nql, w.bm);
@@ -139,7 +130,7 @@ QRLSH_EXPORT int qrlsh_idset_build(const uint64_t *pairs, int64_t n, int64_t q0,
 
 QRLSH_EXPORT int qrlsh_idset_list(const void *workspace, int64_t nids, uint64_t *ids_out, void *stream) {
   QR_CHECK_ARG(nids > 0 && workspace && ids_out, "qrlsh_idset_list: bad arguments");
-  const IdSetWs w = idset_ws(const_cast<void *>(workspace), nids);
+  const IdSetWs w = idset_layout(workspace, nids);
   QR_LAUNCH("idset_list", idset_list_kernel, dim3((unsigned)ceil_div64(w.nw, 256)), dim3(256), 0,
             static_cast<hipStream_t>(stream), (const uint32_t *)w.bm, (const uint64_t *)w.prefix, w.nw, ids_out);
   QR_LAUNCH_CHECK("qrlsh_idset_list");
@@ -151,7 +142,7 @@ QRLSH_EXPORT int qrlsh_idset_remap(const uint64_t *pairs, int64_t n, int64_t q0,
   QR_CHECK_ARG(n >= 0 && q0 >= 0 && nql >= 0 && nids > 0, "qrlsh_idset_remap: bad sizes");
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(pairs && out && workspace, "qrlsh_idset_remap: null pointer");
-  const IdSetWs w = idset_ws(const_cast<void *>(workspace), nids);
+  const IdSetWs w = idset_layout(workspace, nids);
   QR_LAUNCH("idset_remap", idset_remap_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0,
             static_cast<hipStream_t>(stream), pairs, n, (uint64_t)q0, (uint64_t)nql, (const uint32_t *)w.bm,
             (const uint64_t *)w.prefix, out);
@@ -183,7 +174,7 @@ QRLSH_EXPORT int qrlsh_gather_rows(const void *sig, int64_t row_bytes, const int
                (long long)row_bytes);
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(sig && norm2 && ids && rows_out && norms_out, "qrlsh_gather_rows: null pointer");
-  QR_CHECK_ARG((((uintptr_t)sig | (uintptr_t)rows_out) & 15) == 0, "qrlsh_gather_rows: 16-B alignment");
+  QR_CHECK_ALIGNED("qrlsh_gather_rows", "sig and rows_out", qr_addr(sig) | qr_addr(rows_out), 16);
   const int vpr = (int)(row_bytes / 16);
   int64_t blocks = ceil_div64(n * vpr, 256);
   if (blocks > 256 * 32) blocks = 256 * 32;
@@ -270,8 +261,12 @@ __global__ __launch_bounds__(256) void sets_fill_kernel(const uint64_t *__restri
   for (uint64_t k = lig; k < len; k += 16) rows_out[o0 + k] = (int32_t)(uint32_t)(typename std::make_unsigned<RowT>::type)src[k];
 }
 
+// workspace: the total of the scan, then its chunk sums
+static uint64_t *gather_sets_layout(QrCarve &c, int64_t n) {
+  return c.take<uint64_t>((size_t)(ceil_div64((n > 0 ? n : 0) + 1, SCANL_CHUNK) + 2), 8);
+}
 QRLSH_EXPORT size_t qrlsh_gather_sets_workspace_bytes(int64_t n) {
-  return (size_t)(ceil_div64((n > 0 ? n : 0) + 1, SCANL_CHUNK) + 2) * sizeof(uint64_t);
+  return QR_LAYOUT_BYTES(gather_sets_layout, n);
 }
 
 // offsets_out[n + 1] (uint64): exclusive scan of the chosen queries' set sizes, [n] = the number of row ids
@@ -281,10 +276,7 @@ QRLSH_EXPORT int qrlsh_gather_sets_count(const uint64_t *ids, int64_t n, const v
   QR_CHECK_ARG(n >= 0 && nql > 0 && world > 0 && (off_bytes == 4 || off_bytes == 8) && offsets_out && workspace,
                "qrlsh_gather_sets_count: bad arguments");
   QR_CHECK_ARG(n == 0 || (ids && offs), "qrlsh_gather_sets_count: null pointer");
-  if (workspace_bytes < qrlsh_gather_sets_workspace_bytes(n)) {
-    qrlsh_set_error("qrlsh_gather_sets_count: workspace %zu < %zu bytes", workspace_bytes, qrlsh_gather_sets_workspace_bytes(n));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_gather_sets_count", workspace, workspace_bytes, qrlsh_gather_sets_workspace_bytes(n));
   hipStream_t st = static_cast<hipStream_t>(stream);
   const dim3 grid((unsigned)ceil_div64(n + 1, 256)), block(256);
   if (off_bytes == 4)
@@ -293,7 +285,8 @@ QRLSH_EXPORT int qrlsh_gather_sets_count(const uint64_t *ids, int64_t n, const v
   else
     QR_LAUNCH("sets_len", (sets_len_kernel<int64_t>), grid, block, 0, st, ids, n, static_cast<const int64_t *>(offs), nql,
               offsets_out);
-  uint64_t *sums = static_cast<uint64_t *>(workspace);
+  QrCarve c(workspace);
+  uint64_t *sums = gather_sets_layout(c, n);
   qr_scan_u64(offsets_out, n + 1, sums, sums + 1, st);   // (offsets_out[n] = the total; sums[0] receives it too)
   QR_LAUNCH_CHECK("qrlsh_gather_sets_count");
   return QRLSH_OK;

@@ -359,10 +359,13 @@ __global__ __launch_bounds__(SORT_THREADS, 4) void sort_scatter_staged_kernel(co
   }
 }
 
+// workspace: the digit histograms of every (batch, tile), and a row of totals per batch
+static uint32_t *sort_layout(QrCarve &c, int64_t n, int32_t nbatch) {
+  return c.take<uint32_t>((size_t)nbatch * RADIX * (ceil_div64(n, SORT_TILE) + 1));
+}
 QRLSH_EXPORT size_t qrlsh_sort_workspace_bytes(int64_t n, int32_t nbatch) {
   if (n <= 0 || nbatch <= 0) return 16;
-  const int64_t ntiles = ceil_div64(n, SORT_TILE);
-  return (size_t)nbatch * RADIX * (ntiles + 1) * sizeof(uint32_t);
+  return QR_LAYOUT_BYTES(sort_layout, n, nbatch);
 }
 
 template <int MIX>
@@ -411,14 +414,11 @@ QRLSH_EXPORT int qrlsh_sort_u64(uint64_t *keys_a, uint64_t *keys_b, uint32_t *va
   QR_CHECK_ARG((vals_a == nullptr) == (vals_b == nullptr), "qrlsh_sort_u64: vals_a/vals_b must both be set or NULL");
   if (n == 0 || bit_lo == bit_hi) return 0;
   QR_CHECK_ARG(keys_a && keys_b && workspace, "qrlsh_sort_u64: null pointer");
-  if (workspace_bytes < qrlsh_sort_workspace_bytes(n, nbatch)) {
-    qrlsh_set_error("qrlsh_sort_u64: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_sort_workspace_bytes(n, nbatch));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_sort_u64", workspace, workspace_bytes, qrlsh_sort_workspace_bytes(n, nbatch));
   QR_CHECK_ARG(ceil_div64(n, SORT_TILE) <= 2147483647ll && nbatch <= 65535, "qrlsh_sort_u64: grid too large");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  uint32_t *ghist = static_cast<uint32_t *>(workspace);
+  QrCarve c(workspace);
+  uint32_t *ghist = sort_layout(c, n, nbatch);
   const bool iota = (flags & QRLSH_SORT_IOTA) != 0;
   if (flags & QRLSH_SORT_MIX)
     return sort_passes<SM_MIX>(keys_a, keys_b, vals_a, vals_b, n, nbatch, bit_lo, bit_hi, iota, 0, ghist, st);

@@ -132,11 +132,8 @@ QRLSH_EXPORT int qrlsh_table_rows_mark(const int32_t *qrows, int64_t n, int32_t 
   QR_CHECK_ARG(changed_map && out2, "qrlsh_table_rows_mark: null output");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const IdMap mp = idmap_layout(changed_map, n);
-  if (hipMemsetAsync(mp.w, 0, (size_t)(mp.nw + 1) * 8, st) != hipSuccess ||
-      hipMemsetAsync(out2, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_table_rows_mark: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_table_rows_mark", mp.w, 0, (size_t)(mp.nw + 1) * 8, st);
+  QR_MEMSET("qrlsh_table_rows_mark", out2, 0, 2 * sizeof(uint64_t), st);
   if (n > 0 && m > 0) {
     const dim3 grid(rm_grid(n, TR_THREADS)), block(TR_THREADS);
 #define TR_MARK(T16, S16)                                                                                              \

@@ -519,33 +519,27 @@ __global__ __launch_bounds__(256, 4) void topk_select_long_kernel(const uint64_t
 struct SelWs {
   uint32_t *fstart, *rstart, *medlist, *longlist;
   uint64_t *off, *nlong, *sums;
-  size_t bytes;
 };
-static SelWs sel_ws(void *workspace, int64_t nq) {
+static SelWs sel_layout(QrCarve &c, int64_t nq) {
   SelWs w;
-  char *p = static_cast<char *>(workspace);
-  size_t o = 0;
-  w.fstart = reinterpret_cast<uint32_t *>(p + o);
-  o += ((size_t)(nq + 1) * 4 + 15) & ~(size_t)15;
-  w.rstart = reinterpret_cast<uint32_t *>(p + o);
-  o += ((size_t)(nq + 1) * 4 + 15) & ~(size_t)15;
-  w.medlist = reinterpret_cast<uint32_t *>(p + o);
-  o += ((size_t)(nq + 1) * 4 + 15) & ~(size_t)15;
-  w.longlist = reinterpret_cast<uint32_t *>(p + o);
-  o += ((size_t)(nq + 1) * 4 + 15) & ~(size_t)15;
-  w.off = reinterpret_cast<uint64_t *>(p + o);
-  o += (size_t)(nq + 2) * 8;
-  w.nlong = reinterpret_cast<uint64_t *>(p + o);
-  o += 16;
-  w.sums = reinterpret_cast<uint64_t *>(p + o);
-  o += (size_t)(ceil_div64(nq + 1, LEN_QPB) + 2) * 8;   // (one per workgroup of topk_len_kernel)
-  w.bytes = o;
+  const size_t row = qr_al16((size_t)(nq + 1) * 4) / 4;   // words of one array, rounded
+  w.fstart = c.take<uint32_t>(2 * row);                   // fstart | rstart: one memset covers both
+  w.rstart = qr_within(w.fstart, row);
+  w.medlist = c.take<uint32_t>(row);
+  w.longlist = c.take<uint32_t>(row);
+  w.off = c.take<uint64_t>((size_t)(nq + 2), 8);
+  w.nlong = c.take<uint64_t>(2);
+  w.sums = c.take<uint64_t>((size_t)(ceil_div64(nq + 1, LEN_QPB) + 2), 8);   // (one per workgroup of topk_len_kernel)
   return w;
+}
+static SelWs sel_layout(const void *workspace, int64_t nq) {
+  QrCarve c(workspace);
+  return sel_layout(c, nq);
 }
 
 QRLSH_EXPORT size_t qrlsh_topk_select_workspace_bytes(int64_t nq) {
   if (nq <= 0) return 64;
-  return sel_ws(nullptr, nq).bytes;
+  return QR_LAYOUT_BYTES(sel_layout, nq);
 }
 
 QRLSH_EXPORT int qrlsh_topk_select_count(const uint64_t *pairs, int64_t n, const uint64_t *rev_sorted,
@@ -561,28 +555,15 @@ QRLSH_EXPORT int qrlsh_topk_select_count(const uint64_t *pairs, int64_t n, const
   // pairs == NULL: the lists are made of the n reverse words alone (the sharded driver: every directed edge a rank
   // receives is such a word, src = its own query)
   QR_CHECK_ARG(total_out && workspace && (n == 0 || rev_sorted), "qrlsh_topk_select_count: null pointer");
-  if (workspace_bytes < qrlsh_topk_select_workspace_bytes(nq)) {
-    qrlsh_set_error("qrlsh_topk_select_count: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_topk_select_workspace_bytes(nq));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_topk_select_count", workspace, workspace_bytes, qrlsh_topk_select_workspace_bytes(nq));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const SelWs w = sel_ws(workspace, nq);
-  if (hipMemsetAsync(w.nlong, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_topk_select_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  const SelWs w = sel_layout(workspace, nq);
+  QR_MEMSET("qrlsh_topk_select_count", w.nlong, 0, 2 * sizeof(uint64_t), st);
   const dim3 blk(256);
   // both start arrays (contiguous in the workspace) to "unset", boundaries, then the long stretches
-  if (hipMemsetAsync(w.fstart, 0xFF, (size_t)((char *)w.medlist - (char *)w.fstart), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_topk_select_count: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_topk_select_count", w.fstart, 0xFF, (size_t)((char *)w.medlist - (char *)w.fstart), st);
   const int lists = pairs ? 2 : 1, y0 = pairs ? 0 : 1;
-  if (!pairs && hipMemsetAsync(w.fstart, 0, (size_t)((char *)w.rstart - (char *)w.fstart), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_topk_select_count: hipMemsetAsync failed");   // every forward run is empty
-    return QRLSH_EHIP;
-  }
+  if (!pairs) QR_MEMSET("qrlsh_topk_select_count", w.fstart, 0, (size_t)((char *)w.rstart - (char *)w.fstart), st);   // every forward run is empty
   QR_LAUNCH("topk_bounds", edge_bounds_kernel, dim3((unsigned)ceil_div64(n + 1, 256 * EB_RUN), lists), blk, 0, st, pairs,
             rev_sorted, n, nq, id_bits, rev_dst ? 1 : 0, w.fstart, w.rstart, y0);
   QR_LAUNCH("topk_bounds", edge_bounds_fix_kernel, dim3((unsigned)ceil_div64(nq + 1, 256), lists), blk, 0, st, pairs,
@@ -609,7 +590,7 @@ QRLSH_EXPORT int qrlsh_topk_select_fill(const uint64_t *pairs, const int32_t *mi
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG((pairs == nullptr) == (milli == nullptr) && rev_sorted && workspace && src_out && dst_out && milli_out,
                "qrlsh_topk_select_fill: null pointer (pairs and milli: both or neither)");
-  const SelWs w = sel_ws(const_cast<void *>(workspace), nq);
+  const SelWs w = sel_layout(workspace, nq);
   hipStream_t st = static_cast<hipStream_t>(stream);
   const uint32_t *fsp = w.fstart, *rsp = w.rstart;
   const uint64_t *offp = w.off;

@@ -51,11 +51,8 @@ QRLSH_EXPORT int qrlsh_ratings_columns_changed(const int32_t *ratings, int64_t n
   QR_CHECK_ARG((ratings || nq == 0) && cols && changed_map_out && out2, "qrlsh_ratings_columns_changed: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const IdMap mp = idmap_layout(changed_map_out, nu);
-  if (hipMemsetAsync(mp.w, 0, (size_t)(mp.nw + 1) * 8, st) != hipSuccess ||
-      hipMemsetAsync(out2, 0, 2 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_ratings_columns_changed: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_ratings_columns_changed", mp.w, 0, (size_t)(mp.nw + 1) * 8, st);
+  QR_MEMSET("qrlsh_ratings_columns_changed", out2, 0, 2 * sizeof(uint64_t), st);
   QR_LAUNCH("ratings_columns_changed", ratings_columns_changed_kernel, dim3(rm_grid(nu * m, UC_THREADS)), dim3(UC_THREADS),
             0, st, ratings, nu, nq, cols, block, m, mp.w, out2);
   idmap_finish(mp, out2, st);
@@ -161,12 +158,9 @@ QRLSH_EXPORT int qrlsh_ratings_columns_move(const int32_t *in, int64_t nu, int64
                (long long)nq2, (long long)m);
   if (m == 0 || nu == 0) return QRLSH_OK;
   QR_CHECK_ARG(flag_out && (nq2 == 0 || (src && out)) && (in || nq == 0), "qrlsh_ratings_columns_move: null pointer");
-  QR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "qrlsh_ratings_columns_move: out must be 16-byte aligned");
+  QR_CHECK_ALIGNED("qrlsh_ratings_columns_move", "out", qr_addr(out), 16);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flag_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_ratings_columns_move: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_ratings_columns_move", flag_out, 0, sizeof(uint32_t), st);
   if (nq2 == 0) return QRLSH_OK;
   const int64_t trips = ceil_div64(ceil_div64(nu, 4), UC_ROWS);
   const unsigned gy = 4u * (unsigned)(trips < UC_MAXY ? trips : UC_MAXY);

@@ -55,10 +55,7 @@ QRLSH_EXPORT int qrlsh_ratings_set(int32_t *ratings, int64_t nu, int64_t nq, con
   if (m == 0) return QRLSH_OK;
   QR_CHECK_ARG(ratings && users && queries && values && flag_out, "qrlsh_ratings_set: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flag_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_ratings_set: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_ratings_set", flag_out, 0, sizeof(uint32_t), st);
   QR_LAUNCH("ratings_set", ratings_set_kernel, dim3(rm_grid(m, US_THREADS)), dim3(US_THREADS), 0, st, ratings, nu, nq,
             users, queries, values, m, flag_out);
   QR_LAUNCH_CHECK("qrlsh_ratings_set");
@@ -144,7 +141,7 @@ QRLSH_EXPORT int qrlsh_user_rows_stats(const int32_t *ratings, int64_t nu, int64
   if (m == 0) return QRLSH_OK;
   QR_CHECK_ARG(m < (1ll << 31), "qrlsh_user_rows_stats: m=%lld", (long long)m);
   QR_CHECK_ARG((ratings || nq == 0) && mean && norm2, "qrlsh_user_rows_stats: null pointer");
-  QR_CHECK_ARG((reinterpret_cast<uintptr_t>(ratings) & 15) == 0, "qrlsh_user_rows_stats: ratings must be 16-byte aligned");
+  QR_CHECK_ALIGNED("qrlsh_user_rows_stats", "ratings", qr_addr(ratings), 16);
   QR_LAUNCH("user_rows_stats", user_rows_stats_kernel, dim3((unsigned)m), dim3(UST_THREADS), 0,
             static_cast<hipStream_t>(stream), ratings, nu, nq, rows, mean, norm2);
   QR_LAUNCH_CHECK("qrlsh_user_rows_stats");
@@ -276,9 +273,13 @@ __global__ __launch_bounds__(US_THREADS) void user_pairs_finish_kernel(const int
   milli[i] = (int32_t)rint(cs * 1000.0);
 }
 
+// workspace: one partial dot product per (slice of the columns, pair)
+static int64_t *pairs_score_layout(QrCarve &c, int64_t nq, int64_t n) {
+  return c.take<int64_t>((size_t)us_slices(nq, n).count * (size_t)n, 8);
+}
 QRLSH_EXPORT size_t qrlsh_user_pairs_score_workspace_bytes(int64_t nq, int64_t n) {
   if (nq <= 0 || n <= 0) return 16;
-  return (size_t)us_slices(nq, n).count * (size_t)n * sizeof(int64_t);
+  return QR_LAYOUT_BYTES(pairs_score_layout, nq, n);
 }
 
 QRLSH_EXPORT int qrlsh_user_pairs_score(const int32_t *ratings, int64_t nu, int64_t nq, const double *mean,
@@ -289,14 +290,11 @@ QRLSH_EXPORT int qrlsh_user_pairs_score(const int32_t *ratings, int64_t nu, int6
   if (n == 0) return QRLSH_OK;
   QR_CHECK_ARG(mean && norm2 && pairs && milli_out && workspace && (ratings || nq == 0),
                "qrlsh_user_pairs_score: null pointer");
-  QR_CHECK_ARG((reinterpret_cast<uintptr_t>(ratings) & 15) == 0, "qrlsh_user_pairs_score: ratings must be 16-byte aligned");
-  if (workspace_bytes < qrlsh_user_pairs_score_workspace_bytes(nq, n)) {
-    qrlsh_set_error("qrlsh_user_pairs_score: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_user_pairs_score_workspace_bytes(nq, n));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_ALIGNED("qrlsh_user_pairs_score", "ratings", qr_addr(ratings), 16);
+  QR_CHECK_WORKSPACE("qrlsh_user_pairs_score", workspace, workspace_bytes, qrlsh_user_pairs_score_workspace_bytes(nq, n));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int64_t *partial = static_cast<int64_t *>(workspace);
+  QrCarve c(workspace);
+  int64_t *partial = pairs_score_layout(c, nq, n);
   int64_t slices = 0;
   if (nq > 0) {
     const UsSlices s = us_slices(nq, n);
@@ -442,13 +440,10 @@ QRLSH_EXPORT int qrlsh_user_lists_mark(const int32_t *idx, const int32_t *len, i
   QR_CHECK_ARG(idx && len && changed_map && label && c_off && pick_map_out && out3, "qrlsh_user_lists_mark: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
   const IdMap pk = idmap_layout(pick_map_out, nu);
-  if (hipMemsetAsync(pk.w, 0, (size_t)(pk.nw + 1) * 8, st) != hipSuccess ||
-      hipMemsetAsync(out3, 0, 3 * sizeof(uint64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_user_lists_mark: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_user_lists_mark", pk.w, 0, (size_t)(pk.nw + 1) * 8, st);
+  QR_MEMSET("qrlsh_user_lists_mark", out3, 0, 3 * sizeof(uint64_t), st);
   QR_LAUNCH("user_lists_mark", user_lists_mark_kernel, dim3(rm_grid(nu * K, US_THREADS)), dim3(US_THREADS), 0, st, idx, len,
-            nu, (int)K, (const uint2 *)idmap_layout(const_cast<void *>(changed_map), nu).w, label, c_off, nc, pk.w, out3);
+            nu, (int)K, (const uint2 *)idmap_layout(changed_map, nu).w, label, c_off, nc, pk.w, out3);
   idmap_finish(pk, out3, st);
   QR_LAUNCH_CHECK("qrlsh_user_lists_mark");
   return QRLSH_OK;
@@ -557,8 +552,8 @@ QRLSH_EXPORT int qrlsh_user_lists_apply(int32_t *idx, int32_t *milli, int32_t *l
                "qrlsh_user_lists_apply: null pointer");
   QR_LAUNCH("user_lists_apply", user_lists_apply_kernel, dim3((unsigned)(nu < 16384 ? nu : 16384)),
             dim3(WAVE), 0, static_cast<hipStream_t>(stream), idx, milli, len, nu, (int)K,
-            (const uint2 *)idmap_layout(const_cast<void *>(changed_map), nu).w,
-            (const uint2 *)idmap_layout(const_cast<void *>(pick_map), nu).w, label, c_off, c_mem, c_pos, nc, off, pair_milli,
+            (const uint2 *)idmap_layout(changed_map, nu).w,
+            (const uint2 *)idmap_layout(pick_map, nu).w, label, c_off, c_mem, c_pos, nc, off, pair_milli,
             n_pairs);
   QR_LAUNCH_CHECK("qrlsh_user_lists_apply");
   return QRLSH_OK;

@@ -179,9 +179,13 @@ static bool ur_nearest_sizes_ok(int64_t nu, int64_t nq, int64_t m) {
          (nu == 0 || m <= ((1ll << 32) - 1) / nu);
 }
 
+// workspace: the dot product of every (user, batch row)
+static int64_t *rows_nearest_layout(QrCarve &c, int64_t nu, int64_t m) {
+  return c.take<int64_t>((size_t)nu * (size_t)m, 8);
+}
 QRLSH_EXPORT size_t qrlsh_user_rows_nearest_workspace_bytes(int64_t nu, int64_t m) {
   if (nu <= 0 || m <= 0 || nu >= (1ll << 31) || m > ((1ll << 32) - 1) / nu) return 16;
-  return (size_t)nu * (size_t)m * sizeof(int64_t);
+  return QR_LAYOUT_BYTES(rows_nearest_layout, nu, m);
 }
 
 QRLSH_EXPORT int qrlsh_user_rows_nearest(const int32_t *ratings, int64_t nu, int64_t nq, const double *mean,
@@ -194,20 +198,13 @@ QRLSH_EXPORT int qrlsh_user_rows_nearest(const int32_t *ratings, int64_t nu, int
   QR_CHECK_ARG(rows_mean && rows_norm2 && best_user_out && best_milli_out && workspace && (rows || nq == 0) &&
                    (nu == 0 || (mean && norm2 && (ratings || nq == 0))),
                "qrlsh_user_rows_nearest: null pointer");
-  QR_CHECK_ARG((reinterpret_cast<uintptr_t>(ratings) & 15) == 0 && (reinterpret_cast<uintptr_t>(rows) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(workspace) & 7) == 0,
-               "qrlsh_user_rows_nearest: ratings and rows must be 16-byte aligned");
-  if (workspace_bytes < qrlsh_user_rows_nearest_workspace_bytes(nu, m)) {
-    qrlsh_set_error("qrlsh_user_rows_nearest: workspace %zu < %zu bytes", workspace_bytes,
-                    qrlsh_user_rows_nearest_workspace_bytes(nu, m));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_ALIGNED("qrlsh_user_rows_nearest", "ratings and rows", qr_addr(ratings) | qr_addr(rows), 16);
+  QR_CHECK_ALIGNED("qrlsh_user_rows_nearest", "the workspace", qr_addr(workspace), 8);
+  QR_CHECK_WORKSPACE("qrlsh_user_rows_nearest", workspace, workspace_bytes, qrlsh_user_rows_nearest_workspace_bytes(nu, m));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  int64_t *dots = static_cast<int64_t *>(workspace);
-  if (nu > 0 && hipMemsetAsync(dots, 0, (size_t)nu * (size_t)m * sizeof(int64_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_user_rows_nearest: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QrCarve c(workspace);
+  int64_t *dots = rows_nearest_layout(c, nu, m);
+  if (nu > 0) QR_MEMSET("qrlsh_user_rows_nearest", dots, 0, (size_t)nu * (size_t)m * sizeof(int64_t), st);
   if (nu > 0 && nq > 0) {
     const int64_t tiles = ceil_div64(m, UR_TM), groups = ceil_div64(ceil_div64(nu, 4), UR_GROUP);
     const dim3 grid((unsigned)ceil_div64(nq, UR_COLS), (unsigned)(tiles < UR_MAXY ? tiles : UR_MAXY),
@@ -280,12 +277,9 @@ QRLSH_EXPORT int qrlsh_ratings_rows_move(const int32_t *in, int64_t nu, int64_t 
   if (nu2 == 0) return QRLSH_OK;
   QR_CHECK_ARG(flag_out && src && (nq == 0 || (out && (in || nu == 0) && (block || m == 0))),
                "qrlsh_ratings_rows_move: null pointer");
-  QR_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0, "qrlsh_ratings_rows_move: out must be 16-byte aligned");
+  QR_CHECK_ALIGNED("qrlsh_ratings_rows_move", "out", qr_addr(out), 16);
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flag_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_ratings_rows_move: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_ratings_rows_move", flag_out, 0, sizeof(uint32_t), st);
   // nq == 0: one column tile of no columns, so that a src outside range is still seen
   const int64_t tiles = nq > 0 ? ceil_div64(nq, UM_TILE) : 1;
   QR_LAUNCH("ratings_rows_move", ratings_rows_move_kernel, dim3((unsigned)tiles, (unsigned)(nu2 < UM_MAXY ? nu2 : UM_MAXY)),
@@ -343,10 +337,7 @@ QRLSH_EXPORT int qrlsh_user_lists_renumber(const int32_t *idx, const int32_t *mi
   QR_CHECK_ARG(src && idx_out && milli_out && len_out && flag_out && (nu == 0 || (idx && milli && len && new_pos)),
                "qrlsh_user_lists_renumber: null pointer");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (hipMemsetAsync(flag_out, 0, sizeof(uint32_t), st) != hipSuccess) {
-    qrlsh_set_error("qrlsh_user_lists_renumber: hipMemsetAsync failed");
-    return QRLSH_EHIP;
-  }
+  QR_MEMSET("qrlsh_user_lists_renumber", flag_out, 0, sizeof(uint32_t), st);
   QR_LAUNCH("user_lists_renumber", user_lists_renumber_kernel, dim3(rm_grid(nu2 * K, UR_THREADS)), dim3(UR_THREADS), 0, st,
             idx, milli, len, nu, (int)K, src, nu2, new_pos, idx_out, milli_out, len_out, flag_out);
   QR_LAUNCH_CHECK("qrlsh_user_lists_renumber");

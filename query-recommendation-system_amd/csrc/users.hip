@@ -209,10 +209,14 @@ __global__ __launch_bounds__(256) void gram_reduce_kernel(const double *__restri
   gram[idx] = s;
 }
 
+// workspace: one partial Gram matrix per slice of the columns
+static int64_t gram_slices(int64_t nq) { return nq >= 65536 ? 16 : nq >= 4096 ? 4 : 1; }
+static double *gram_layout(QrCarve &c, int64_t nu, int64_t nq) {
+  return c.take<double>((size_t)gram_slices(nq) * (size_t)nu * (size_t)nu, 8);
+}
 QRLSH_EXPORT size_t qrlsh_user_gram_workspace_bytes(int64_t nu, int64_t nq) {
   if (nu <= 0 || nq <= 0) return 16;
-  const int64_t slices = nq >= 65536 ? 16 : nq >= 4096 ? 4 : 1;
-  return (size_t)slices * (size_t)nu * (size_t)nu * sizeof(double);
+  return QR_LAYOUT_BYTES(gram_layout, nu, nq);
 }
 
 QRLSH_EXPORT int qrlsh_user_gram(const int32_t *ratings, int64_t nu, int64_t nq, double *mean_out, double *inv_scale_out,
@@ -220,21 +224,19 @@ QRLSH_EXPORT int qrlsh_user_gram(const int32_t *ratings, int64_t nu, int64_t nq,
   QR_CHECK_ARG(nu > 0 && nq > 0 && nu < (1ll << 20) && nq <= (1ll << 24), "qrlsh_user_gram: bad sizes nu=%lld nq=%lld",
                (long long)nu, (long long)nq);
   QR_CHECK_ARG(ratings && mean_out && inv_scale_out && gram_out && workspace, "qrlsh_user_gram: null pointer");
-  if (workspace_bytes < qrlsh_user_gram_workspace_bytes(nu, nq)) {
-    qrlsh_set_error("qrlsh_user_gram: workspace %zu < %zu bytes", workspace_bytes, qrlsh_user_gram_workspace_bytes(nu, nq));
-    return QRLSH_EWORKSPACE;
-  }
+  QR_CHECK_WORKSPACE("qrlsh_user_gram", workspace, workspace_bytes, qrlsh_user_gram_workspace_bytes(nu, nq));
   hipStream_t st = static_cast<hipStream_t>(stream);
-  const int slices = nq >= 65536 ? 16 : nq >= 4096 ? 4 : 1;
+  const int slices = (int)gram_slices(nq);
+  QrCarve c(workspace);
+  double *partial = gram_layout(c, nu, nq);
   const int64_t slice_cols = ceil_div64(ceil_div64(nq, slices), GR_K) * GR_K;
   const int ntile = (int)ceil_div64(nu, GR_T);
   QR_LAUNCH("user_colstats", column_stats_kernel, dim3((unsigned)ceil_div64(nq, 256)), dim3(256), 0, st, ratings, nu, nq,
             mean_out, inv_scale_out);
   QR_LAUNCH("user_gram", user_gram_kernel, dim3((unsigned)(ntile * (ntile + 1) / 2), (unsigned)slices), dim3(256), 0, st,
-            ratings, nu, nq, (const double *)mean_out, (const double *)inv_scale_out, slice_cols, ntile,
-            static_cast<double *>(workspace));
+            ratings, nu, nq, (const double *)mean_out, (const double *)inv_scale_out, slice_cols, ntile, partial);
   QR_LAUNCH("user_gram_reduce", gram_reduce_kernel, dim3((unsigned)ceil_div64(nu * nu, 256)), dim3(256), 0, st,
-            (const double *)workspace, nu, slices, gram_out);
+            (const double *)partial, nu, slices, gram_out);
   QR_LAUNCH_CHECK("qrlsh_user_gram");
   return QRLSH_OK;
 }

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _ptr, _stream
 
 MAX_POOL = _lib.DIVERSIFY_MAX_POOL
@@ -73,8 +74,7 @@ def _block(lib, m, n, max_row, device):
     blk = m
     while blk > 1 and int(lib.qrlsh_diversify_workspace_bytes(blk, n, max_row)) > WORKSPACE_BUDGET:
         blk = (blk + 1) // 2
-    nbytes = max(int(lib.qrlsh_diversify_workspace_bytes(blk, n, max_row)), 16)
-    return blk, torch.empty((nbytes,), dtype=torch.uint8, device=device)
+    return blk, ops._ws(lib.qrlsh_diversify_workspace_bytes(blk, n, max_row), device)
 
 
 def _raise_flags(word, nq):

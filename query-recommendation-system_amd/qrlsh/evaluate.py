@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _ptr, _stream
 from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT, ServeInputs
 
@@ -133,7 +134,7 @@ def evaluate(ratings, q_src, q_dst, q_milli, user_sims, truth=None, fraction=1.0
     per_user = torch.empty((a.nu, 16), dtype=torch.int64, device=dev)
     back = torch.zeros((17,), dtype=torch.int64, device=dev)    # [totals: 16][flags: the low half of word 16]
     pred = torch.empty((a.nu, a.nq), dtype=torch.int32, device=dev) if want_predictions else None
-    ws = torch.empty((max(int(lib.qrlsh_evaluate_workspace_bytes(a.nu, a.nq)), 16),), dtype=torch.uint8, device=dev)
+    ws = ops._ws(lib.qrlsh_evaluate_workspace_bytes(a.nu, a.nq), dev)
     _lib.check(lib.qrlsh_evaluate(_ptr(a.r), _ptr(t), a.nu, a.nq, _ptr(a.q_off), _ptr(a.q_idx), _ptr(a.q_milli),
                                   _ptr(a.u_idx), _ptr(a.u_val), a.ku, float(query_weight), float(user_weight),
                                   float(default_mean), a.sum_order, seed, keep, _ptr(per_user), _ptr(back), _ptr(pred),

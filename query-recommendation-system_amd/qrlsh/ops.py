@@ -224,8 +224,7 @@ def sort_u64(keys, vals=None, bit_lo=0, bit_hi=64, mix=False, iota=False, fold=0
             raise ValueError("vals must match keys")
     kb = torch.empty_like(k2)
     vb = torch.empty_like(vals) if vals is not None else None
-    nbytes = lib.qrlsh_sort_workspace_bytes(n, nbatch)
-    ws = _ws(nbytes, keys.device)
+    ws = _ws(lib.qrlsh_sort_workspace_bytes(n, nbatch), keys.device)
     flags = (_lib.SORT_MIX if mix else 0) | (_lib.SORT_IOTA if iota else 0)
     aux = 0
     if fold:
@@ -1286,7 +1285,7 @@ def lists_regrow_mark(src, n, K_old):
 def idmap_empty(n, device):
     """the IdMap over [0, n) without members: zeroed memory is one (no bits, every prefix count 0); no read-back"""
     lib = _lib.load()
-    return IdMap(torch.zeros((max(int(lib.qrlsh_idmap_workspace_bytes(n)), 16),), dtype=torch.uint8, device=device), n, 0)
+    return IdMap(_ws(lib.qrlsh_idmap_workspace_bytes(n), device).zero_(), n, 0)
 
 
 def index_pick_keys(keys, ids, pick):

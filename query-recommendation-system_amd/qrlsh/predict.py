@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _ptr, _stream
 
 QUERY_WEIGHT = 0.6   # recommender.py:32-34
@@ -74,7 +75,7 @@ def fill_predictions(ratings, q_src, q_dst, q_milli, user_sims, query_weight=QUE
     if kq > MAX_NEIGHBOURS:
         raise ValueError("a query has more than %d neighbours (%d; max_candidates overridden?); the prediction kernel "
                          "handles at most %d" % (MAX_NEIGHBOURS, kq, MAX_NEIGHBOURS))
-    ws = torch.empty((max(int(lib.qrlsh_predict_workspace_bytes(nu, nq, kq)), 16),), dtype=torch.uint8, device=device)
+    ws = ops._ws(lib.qrlsh_predict_workspace_bytes(nu, nq, kq), device)
     _lib.check(lib.qrlsh_predict(_ptr(r), nu, nq, _ptr(q_off), _ptr(q_idx), _ptr(q_val), _ptr(u_idx), _ptr(u_val),
                                  u_idx.shape[1] if ku else 0, float(query_weight), float(user_weight),
                                  float(default_mean),

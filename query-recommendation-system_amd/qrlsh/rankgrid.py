@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _ptr, _stream
 from .predict import ServeInputs
 from .ranking import check_arguments, _gain_tables
@@ -162,7 +163,7 @@ def evaluate_ranking_grid(train, truth, q_src, q_dst, q_milli, user_sims, k, rel
     ut = a.ut
     if ut is None and blk < m:
         ut = torch.arange(a.nu, dtype=torch.int32, device=dev)
-    ws = torch.empty((max(need(blk), 16),), dtype=torch.uint8, device=dev)
+    ws = ops._ws(need(blk), dev)
     st = _stream()
 
     def launch(lo, hi):

@@ -12,6 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _ptr, _stream
 from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT, ServeInputs
 
@@ -166,7 +167,7 @@ def _score(a, t, k, relevant, candidates, gain, prefix, lo, slices, weights):
     ut = a.ut
     if ut is None and blk < m:
         ut = torch.arange(a.nu, dtype=torch.int32, device=dev)
-    ws = torch.empty((max(int(size(blk, nq, k, int(slices))), 16),), dtype=torch.uint8, device=dev)
+    ws = ops._ws(size(blk, nq, k, int(slices)), dev)
     starts = range(0, m, blk)
     back = torch.zeros((len(starts), 17), dtype=torch.int64, device=dev)   # per block [totals: 16][flags: low half]
     args = a.lists_args(*weights)

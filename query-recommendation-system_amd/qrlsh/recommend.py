@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import ops
 from .ops import _ptr, _stream
 
 MAX_K = _lib.RECOMMEND_MAX_K
@@ -101,8 +102,7 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
     ut = None if u is None else (u if isinstance(u, torch.Tensor) else torch.from_numpy(u.astype(np.int64)))
     if ut is not None:   # ids past int32 must stay out of range, not wrap into it
         ut = ut.to(device=device, dtype=torch.int64).clamp(-1, nu).to(torch.int32).contiguous()
-    ws = torch.empty((max(int(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices))), 16),), dtype=torch.uint8,
-                     device=device)
+    ws = ops._ws(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices)), device)
     st = _stream()
     for i0 in range(0, m, blk):
         i1 = min(m, i0 + blk)
@@ -161,8 +161,7 @@ def _serve(a, k, lo, slices, query_weight, user_weight, default_mean, device):
     ut = a.ut
     if ut is None and blk < m:
         ut = torch.arange(a.nu, dtype=torch.int32, device=device)
-    ws = torch.empty((max(int(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices))), 16),),
-                     dtype=torch.uint8, device=device)
+    ws = ops._ws(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices)), device)
     starts = range(0, m, blk)
     flags = torch.zeros((len(starts),), dtype=torch.int32, device=device)
     args = a.lists_args(predict.QUERY_WEIGHT if query_weight is None else query_weight,

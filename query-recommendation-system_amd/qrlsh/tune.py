@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from .evaluate import keep_word, _seed_word
+from . import ops
 from .ops import _ptr, _stream
 from .predict import ServeInputs
 
@@ -149,8 +150,7 @@ def evaluate_grid(ratings, q_src, q_dst, q_milli, user_sims, weights, q_cuts=Non
         s = ncq * ncu * nw
         per_user = torch.empty((a.nu, ncq, ncu, nw, 8), dtype=torch.int64, device=dev) if want_per_user else None
         back = torch.zeros((s * 8 + 1,), dtype=torch.int64, device=dev)   # [totals][flags: the low half of a word]
-        ws = torch.empty((max(int(lib.qrlsh_evaluate_grid_workspace_bytes(a.nu, a.nq, s)), 16),), dtype=torch.uint8,
-                         device=dev)
+        ws = ops._ws(lib.qrlsh_evaluate_grid_workspace_bytes(a.nu, a.nq, s), dev)
         _lib.check(lib.qrlsh_evaluate_grid(_ptr(a.r), _ptr(t), a.nu, a.nq, _ptr(a.q_off), _ptr(a.q_idx),
                                            _ptr(a.q_milli), _ptr(a.u_idx), _ptr(a.u_val), a.ku, _ptr(d_qc), ncq,
                                            _ptr(d_uc), ncu, _ptr(d_w[lo:hi]), nw, a.sum_order, seed, keep,
