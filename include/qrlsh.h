@@ -782,6 +782,54 @@ int qrlsh_recommend_users(const int32_t *ratings, int64_t nu, int64_t nq, const 
                           int32_t *val_out, int32_t *avail_out, uint32_t *flags_out, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ---- serving chosen queries: their columns, their top-k users and their utility from the live lists ----------------
+ * The question the other way round: "whom do I show query j?" and "how useful is query j to the user base?", for
+ * queries that ARE columns of the matrix (qrlsh_predict_columns covers new ones, whose user side is 0).  Same
+ * arithmetic as qrlsh_predict cell for cell (float64, no FMA, half to even, both sum orders); no [nu][nq] prediction
+ * matrix.  ratings, the query lists (CSR, milli) and the user lists u_idx / u_val [nu][ku] as qrlsh_predict_users
+ * takes them.  u_idx entries >= 0 are TRUSTED to lie in [0, nu), exactly as qrlsh_predict_users trusts them.
+ * queries int32 [m]: any order, repeats allowed; NULL = all nq columns in order (then m = nq).
+ * cols_tmp int32 [m][nu] (required): caller-provided scratch of the same size as the output (the convention of
+ * qrlsh_index_build's keys_tmp / ids_tmp; there is no size export).  It receives the raw columns ratings[.][queries[x]],
+ * gathered once per call; the user side of every cell reads them, never cells this call has written.
+ * qrlsh_predict_queries: out int32 [m][nu], query-major = the completed columns (the rating where rated, else the
+ * prediction): columns queries[.] of qrlsh_predict's output, transposed.  out = NULL: only util_out is made.
+ * qrlsh_recommend_queries: writes the columns in eligible mode (0 where rated; stride rounded up to 16 bytes) into its
+ * workspace and selects from them with qrlsh_recommend_users' selection, the roles swapped: idx_out / val_out [m][k] =
+ * per request the USERS with the largest predictions among the eligible cells of the column (unrated, prediction != 0),
+ * value descending, then user ascending; padding -1 / 0; avail_out [m] = the eligible users, -1 for a query id outside
+ * [0, nq) (its row padded).  `lo` and `slices` as qrlsh_recommend_topk takes them; the result depends on neither.
+ * The workspace is qrlsh_recommend_users_workspace_bytes(m, nu, k, slices) bytes, 16-byte aligned: that call's layout
+ * (compact rows, then the selection's own) with rows of length nu.
+ * util_out int64 [m][8], zeroed by the caller (the words are ADDED: exact in any launch order), or NULL: per request
+ *   [0] users who rated the query, [1] the sum of their ratings, [2] unrated users with a non-zero prediction, [3] the
+ *   sum of those predictions, [4] unrated users with prediction 0 (missed), and the unrated users by the sides of the
+ *   blend that are non-zero: [5] the query side alone, [6] the user side alone, [7] both (neither: counted in [4] only).
+ *   A request outside [0, nq) adds nothing.
+ * One gather kernel (nu strided reads per request), then one sweep of (user slice, request) workgroups, the requests of a
+ * slice together; per workgroup, decided on the device: the compact column staged in LDS as bytes (nu <= 131072 and
+ * every value in 0 .. 255), or read from memory.  The query side costs one memory transaction per (user, neighbour of
+ * the query).
+ * *flags_out (device uint32, required) = 0, or bit 0: a query list longer than 64, bit 1: a list index outside
+ * [0, nq), bit 2: a requested query id outside [0, nq).  Such lists are never walked (the unrated cells get 0) and such
+ * columns are never read (all 0); the result is not to be used -- the caller reads the flags back.
+ * Limits: ku <= 64, 1 <= k <= QRLSH_RECOMMEND_MAX_K, nq < 2^31, nu < 2^31, sum_order one of the two (QRLSH_EINVAL
+ * otherwise); m <= 2^24 and m x max(slices, 1) <= 2^24 (QRLSH_EUNSUPPORTED above).  Every check precedes any device
+ * work.  m = 0 returns at once (nothing is written, *flags_out included); nu = 0 gives avail 0 and padded rows.  No
+ * allocation, one stream, no read-back.
+ */
+int qrlsh_predict_queries(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off, const int32_t *q_idx,
+                          const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                          double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                          const int32_t *queries, int64_t m, int32_t *out, int32_t *cols_tmp, int64_t *util_out,
+                          uint32_t *flags_out, void *stream);
+int qrlsh_recommend_queries(const int32_t *ratings, int64_t nu, int64_t nq, const int64_t *q_off, const int32_t *q_idx,
+                            const int32_t *q_milli, const int32_t *u_idx, const double *u_val, int32_t ku,
+                            double query_weight, double user_weight, double default_mean, int32_t sum_order,
+                            const int32_t *queries, int64_t m, int32_t k, int32_t lo, int32_t slices, int32_t *idx_out,
+                            int32_t *val_out, int32_t *avail_out, int64_t *util_out, uint32_t *flags_out,
+                            int32_t *cols_tmp, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- diversified lists: rerank a served pool by the stored neighbour lists; the redundancy of a served list ----------
  * The project's own rule (the reference has no counterpart); integer arithmetic only.  Query lists in CSR with milli
  * values (0 .. 1000) as qrlsh_recommend_users takes them, rows of any length.

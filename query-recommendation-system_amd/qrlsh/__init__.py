@@ -38,6 +38,7 @@ from .synth import synth_csr, poisson_cdf_u32  # noqa: F401
 from .answers import build_answer_index, encode_queries, answer_sets, AnswerIndex  # noqa: F401
 from .recommend import top_k, for_users  # noqa: F401
 from .predict import predict_users, user_lists  # noqa: F401
+from .servequeries import predict_queries, for_queries, query_utility, QueryUtility  # noqa: F401
 from .diversify import diversify, for_users_diverse, list_redundancy, Redundancy  # noqa: F401
 from .diversify import diversify_grid, evaluate_diversity, DiversityGrid  # noqa: F401
 from .evaluate import holdout, evaluate, evaluate_cells, Evaluation  # noqa: F401

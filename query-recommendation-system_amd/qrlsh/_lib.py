@@ -168,6 +168,11 @@ SIGNATURES = {
     "qrlsh_recommend_users": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
                                              ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
                                              _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_predict_queries": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                             ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "qrlsh_recommend_queries": (ctypes.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,
+                                               ctypes.c_double, ctypes.c_double, _i32, _vp, _i64, _i32, _i32, _i32, _vp,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_diversify_workspace_bytes": (_sz, [_i64, _i32, _i64]),
     "qrlsh_diversify": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp,
                                        _vp, _vp, _vp, _sz, _vp]),

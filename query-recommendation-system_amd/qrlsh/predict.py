@@ -105,9 +105,11 @@ def lists_csr(coo, nq, device):
 
 class ServeInputs:
     """The checked arguments of predict_users / recommend.for_users, and (after upload()) their device form.
-    Every check that needs no device runs in the constructor, before anything is uploaded or the library loaded."""
+    Every check that needs no device runs in the constructor, before anything is uploaded or the library loaded.
+    ids = "queries": `users` holds query ids instead (predict_queries / for_queries / query_utility): the same checks
+    against nq, None = every column."""
 
-    def __init__(self, ratings, q_src, q_dst, q_milli, user_sims, users, sum_order):
+    def __init__(self, ratings, q_src, q_dst, q_milli, user_sims, users, sum_order, ids="users"):
         from .recommend import _matrix
         if sum_order not in ("pairwise", "sequential"):
             raise ValueError("sum_order must be 'pairwise' or 'sequential'")
@@ -116,6 +118,10 @@ class ServeInputs:
         self.nu, self.nq = (int(d) for d in self.ratings.shape)
         if self.nq >= 2**31:
             raise ValueError("at most 2^31 - 1 queries per row")
+        self.what = "user" if ids == "users" else "query"
+        self.bound = self.nu if ids == "users" else self.nq   # the ids lie in [0, bound)
+        if ids != "users" and self.nu >= 2**31:
+            raise ValueError("at most 2^31 - 1 users per column")
         coo = []
         for name, x in (("q_src", q_src), ("q_dst", q_dst), ("q_milli", q_milli)):
             t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
@@ -141,17 +147,18 @@ class ServeInputs:
         self.user_sims = user_sims
         self.device_ids = False
         if users is None:
-            self.users, self.m = None, self.nu
+            self.users, self.m = None, self.bound
         elif isinstance(users, torch.Tensor):
             if users.dim() != 1 or users.dtype.is_floating_point or users.dtype == torch.bool:
-                raise ValueError("users must be a 1-D integer tensor")
+                raise ValueError("%s must be a 1-D integer tensor" % ids)
             self.users, self.m, self.device_ids = users, int(users.numel()), True
         else:
             ua = np.asarray(users)
             if ua.ndim != 1 or not (ua.size == 0 or np.issubdtype(ua.dtype, np.integer)):
-                raise ValueError("users must be a 1-D sequence of integer row ids")
-            if ua.size and (ua.min() < 0 or ua.max() >= self.nu):
-                raise ValueError("user id outside [0, %d)" % self.nu)
+                raise ValueError("%s must be a 1-D sequence of integer %s ids"
+                                 % (ids, "row" if ids == "users" else "column"))
+            if ua.size and (ua.min() < 0 or ua.max() >= self.bound):
+                raise ValueError("%s id outside [0, %d)" % (self.what, self.bound))
             self.users, self.m = ua, int(ua.size)
 
     def upload(self, device):
@@ -165,7 +172,7 @@ class ServeInputs:
         u = self.users
         if u is not None:   # ids past int32 must stay out of range, not wrap into it
             u = u if isinstance(u, torch.Tensor) else torch.from_numpy(u.astype(np.int64))
-            u = u.to(device=device, dtype=torch.int64).clamp(-1, self.nu).to(torch.int32).contiguous()
+            u = u.to(device=device, dtype=torch.int64).clamp(-1, self.bound).to(torch.int32).contiguous()
         self.ut = u
         return self
 
@@ -186,10 +193,10 @@ class ServeInputs:
         if f & 2:
             raise ValueError("a query's neighbour index is outside [0, %d)" % self.nq)
         if f & 4:
-            bad = torch.nonzero((self.ut < 0) | (self.ut >= self.nu))
+            bad = torch.nonzero((self.ut < 0) | (self.ut >= self.bound))
             pos = int(bad[0, 0].item()) if bad.numel() else -1
-            raise ValueError("user id %s (position %d) outside [0, %d)"
-                             % (int(self.users[pos].item()) if pos >= 0 else "?", pos, self.nu))
+            raise ValueError("%s id %s (position %d) outside [0, %d)"
+                             % (self.what, int(self.users[pos].item()) if pos >= 0 else "?", pos, self.bound))
 
 
 def predict_users(ratings, q_src, q_dst, q_milli, user_sims, users, query_weight=QUERY_WEIGHT, user_weight=USER_WEIGHT,

@@ -872,6 +872,61 @@ class Recommender:
         ids = np.arange(self.usersIDs.size) if users is None else np.asarray(ops.to_host(users), dtype=np.int64)
         return pd.DataFrame(ops.to_host(rows), index=self.usersIDs[ids], columns=self.queriesIDs).astype(int)
 
+    # ---- serving chosen queries from the live lists: their audience, their columns, their utility --------------------
+    def _query_positions(self, positions):
+        if positions is not None and not isinstance(positions, torch.Tensor):
+            positions = np.asarray(positions)
+        return positions
+
+    def recommend_queries(self, positions, k, sum_order=None, user_sim=None, ratings=None):
+        """"Whom do I show query j?" for queries that are columns of the matrix (recommend_new_queries covers new ones):
+        per requested position the k users with the largest non-zero predictions among those who have not rated it,
+        value descending then user ascending -- recommend()'s selection over the transposed columns of
+        compute_scores(reuse_lists=True)[1], from the live lists and the live user lists in step (ValueError when there
+        are no live lists), so current after every live operation.  positions: 0-based columns (any order; a host
+        sequence or a device tensor), None = every column.  user_sim / ratings as recommend_users takes them.
+        -> {j: {'users': int64[user rows, 0-based], 'values': int64, 'available': int}}, recommend_new_queries' shape.
+        Raises ValueError for a bad k, sum_order or position."""
+        from qrlsh import recommend as rec
+        from qrlsh import servequeries as sq
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= rec.MAX_K:
+            raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
+        positions = self._query_positions(positions)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        users, val, avail = sq.for_queries(ratings, lists[0], lists[1], lists[2], user_sim, positions, int(k),
+                                           sum_order=sum_order, query_weight=self.query_weight,
+                                           user_weight=self.user_weight, default_mean=self.default_mean,
+                                           device=self.device)
+        users, val, avail = ops.to_host(users), ops.to_host(val), ops.to_host(avail)
+        ids = range(len(avail)) if positions is None else [int(x) for x in ops.to_host(positions)]
+        out = {}
+        for i, j in enumerate(ids):
+            n = min(int(k), int(avail[i]))
+            out[j] = {"users": users[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
+                      "available": int(avail[i])}
+        return out
+
+    def predict_queries(self, positions, sum_order=None, user_sim=None, ratings=None):
+        """DataFrame usersIDs x queriesIDs[positions]: those columns of compute_scores(reuse_lists=True)'s
+        finalPredictions, from the live lists (arguments as recommend_queries takes them)."""
+        from qrlsh import servequeries as sq
+        positions = self._query_positions(positions)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        cols = sq.predict_queries(ratings, lists[0], lists[1], lists[2], user_sim, positions, self.query_weight,
+                                  self.user_weight, self.default_mean, self.device, sum_order=sum_order)
+        ids = np.arange(self.queriesIDs.size) if positions is None else np.asarray(ops.to_host(positions), dtype=np.int64)
+        return pd.DataFrame(ops.to_host(cols).T, index=self.usersIDs, columns=self.queriesIDs[ids]).astype(int)
+
+    def query_utility(self, positions=None, sum_order=None, user_sim=None, ratings=None):
+        """"How useful is query j to the whole user base?" -> qrlsh.QueryUtility over the requested positions (default:
+        every column): per query the users who rated it, predicted and missed users, the sums, the blend's branches,
+        and .utility / .mean_rating / .mean_prediction / .coverage (arguments as recommend_queries takes them)."""
+        from qrlsh import servequeries as sq
+        positions = self._query_positions(positions)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        return sq.query_utility(ratings, lists[0], lists[1], lists[2], user_sim, positions, self.query_weight,
+                                self.user_weight, self.default_mean, self.device, sum_order=sum_order)
+
     # ---- how good is the served model: the prediction error on rated cells (qrlsh.evaluate) -----------------------
     def evaluate(self, fraction=1.0, seed=0, holdout=False, cells=None, sum_order=None, user_sim=None):
         """The prediction error of the model served now, on the device -> qrlsh.Evaluation (.mae, .rmse, .bias,
