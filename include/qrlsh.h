@@ -910,6 +910,56 @@ int qrlsh_diversify_grid(const int32_t *cand_idx, const int32_t *cand_val, const
                          int32_t *count_out, int64_t *per_request_out, int64_t *totals_out, uint32_t *flag_out,
                          void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- list fidelity: the exact answer-set overlap of the neighbour lists ---------------------------------------------
+ * How many of a query's TRUE nearest neighbours does its served list hold?  True = Jaccard over the answer sets, the
+ * quantity MinHash estimates.  offsets int64 [nq + 1] / rows int32: the CSR answer sets, rows ascending and distinct per
+ * query (TRUSTED to be a CSR, as qrlsh_minhash trusts it after qrlsh_check_csr).  Integer arithmetic only:
+ *   J(s, j) = inter / union with union = |A(s)| + |A(j)| - inter, and 0 when union == 0;
+ *   J_a > J_b is decided by inter_a * union_b > inter_b * union_a in int64.
+ * qrlsh_edge_overlaps: src / dst int32 [n], any edges (the COO of the live lists is the use in mind);
+ *   inter_out int32 [n]: inter_out[e] = |A(src[e]) & A(dst[e])|.  src == dst gives |A|, two empty sets 0.  A group of 16
+ *   lanes per edge walks the shorter set and binary-searches the longer one.  *flags_out (device uint32, zeroed by the
+ *   caller, required) gets bit 0: an edge end outside [0, nq) (its inter_out is 0, nothing is gathered).  n = 0 returns at
+ *   once; n <= 2^35 - 16 (QRLSH_EUNSUPPORTED above).
+ * qrlsh_list_fidelity: the query lists in CSR as qrlsh_recommend_users takes them (q_off int64 [nq + 1], q_idx int32;
+ *   the stored order is the order of the row, the values are not read).  queries int32 [m]: the chosen queries, any
+ *   order, repeats allowed; NULL = queries 0 .. m - 1 (m <= nq).  Request x with chosen query s is held to its first
+ *   L = min(row length, K) entries -- a prefix, the list a run with that K would have stored -- against ALL nq queries.
+ *   Per stored entry e (target d_e), int32 [m][64], 0 past L:
+ *     inter_out, union_out = of (s, d_e);  better_out = the j != s with J(s, j) > J_e;
+ *     equal_out = the j != s, j != d_e with J(s, j) == J_e.      An entry that names s itself is scored like any other.
+ *   words_out int64 [m][8]: 0 listed (L); 1 |A(s)|; 2 positives = the j != s with inter > 0; 3 hits = entries with
+ *     better < K (in the exact top K under SOME tie-break); 4 sure = entries with better + equal < K (under EVERY
+ *     tie-break); 5 reachable = min(K, positives); 6 disjoint = entries with inter == 0; 7 inversions = pairs of entries
+ *     e before f in stored order with J_e < J_f.
+ *   totals_out int64 [8], required, ADDED to (the caller zeroes it; request blocks accumulate on the device): the column
+ *     sums of the words.  The five [m][.] outputs are written whole by every call.
+ *   Four steps on one stream: the outputs zeroed; the intersection kernel of qrlsh_edge_overlaps over the chosen rows;
+ *   the sweep -- a 1024-thread workgroup per (group of G requests, slice of the ids j) stages the G answer sets as one
+ *   interleaved bitmap over the D table rows in LDS (G bits per row), the G x 64 stored (inter, union) and their
+ *   counters beside it, reads the CSR rows of its slice ONCE for the whole group, one LDS read per row id, and takes
+ *   only the (request, j) with inter > 0 and j != s on to the <= 64 comparisons -- and a finish that turns the counters
+ *   into the words.  Counters leave a workgroup by integer atomic adds: exact in any launch order, the same for every
+ *   slice count.  Nothing of size m x nq is written; there is no workspace.
+ *   G = qrlsh_list_fidelity_group(D): the largest of 32, 16, 8, 4, 2, 1 with ceil(D G / 32) + 256 G + 128 words within
+ *   the 160 KiB of LDS of a CU (0 for a D outside [0, 2^20]).  slices: 0 = automatic (about 1024 workgroups in all,
+ *   slices of at least 4096 ids), else 1 .. 256.
+ *   *flags_out (device uint32, zeroed by the caller, required): bit 0 a chosen query's list row is longer than 64 (not
+ *   walked; that request's words and entries are 0), bit 1 a neighbour index outside [0, nq) among the first L (that
+ *   entry's inter and union are 0, nothing is gathered), bit 2 a chosen query outside [0, nq) (all 0), bit 3 an
+ *   answer-set row id outside [0, D) (never tested against LDS).  A flagged result is not to be used.
+ *   Limits: 1 <= K <= QRLSH_FIDELITY_MAX_K, nq < 2^31, 0 <= D <= 2^20, 0 <= slices <= 256 (QRLSH_EINVAL otherwise); m <=
+ *   2^24 (QRLSH_EUNSUPPORTED above).  Every check precedes any device work; m = 0 returns at once, the totals untouched.
+ * No allocation, one stream, no read-back. */
+#define QRLSH_FIDELITY_MAX_K 64
+int32_t qrlsh_list_fidelity_group(int64_t D);
+int qrlsh_edge_overlaps(const int64_t *offsets, const int32_t *rows, int64_t nq, const int32_t *src, const int32_t *dst,
+                        int64_t n, int32_t *inter_out, uint32_t *flags_out, void *stream);
+int qrlsh_list_fidelity(const int64_t *offsets, const int32_t *rows, int64_t nq, int64_t D, const int64_t *q_off,
+                        const int32_t *q_idx, const int32_t *queries, int64_t m, int32_t K, int32_t slices,
+                        int32_t *inter_out, int32_t *union_out, int32_t *better_out, int32_t *equal_out,
+                        int64_t *words_out, int64_t *totals_out, uint32_t *flags_out, void *stream);
+
 /* ---- evaluation: the prediction error on rated cells, hold-out and leave-one-out -----------------------------------
  * The blend of cell (i, j) never reads ratings[i][j]: a rated cell can be predicted as if it were unrated and compared
  * with its rating.  Predictions and ratings are integers, so every statistic is an exact integer sum, independent of the

@@ -41,6 +41,7 @@ from .predict import predict_users, user_lists  # noqa: F401
 from .servequeries import predict_queries, for_queries, query_utility, QueryUtility  # noqa: F401
 from .diversify import diversify, for_users_diverse, list_redundancy, Redundancy  # noqa: F401
 from .diversify import diversify_grid, evaluate_diversity, DiversityGrid  # noqa: F401
+from .fidelity import edge_overlaps, list_fidelity, ListFidelity  # noqa: F401
 from .evaluate import holdout, evaluate, evaluate_cells, Evaluation  # noqa: F401
 from .ranking import dcg_gains, evaluate_ranking, RankingEvaluation  # noqa: F401
 from .tune import evaluate_grid, GridEvaluation  # noqa: F401

@@ -29,6 +29,8 @@ SUM_SEQUENTIAL = 1
 RECOMMEND_MAX_K = 1024
 DIVERSIFY_MAX_POOL = 1024
 DIVERSIFY_MAX_PENALTY = 1 << 20
+FIDELITY_MAX_K = 64       # entries per list row that qrlsh_list_fidelity scores (QRLSH_FIDELITY_MAX_K)
+FIDELITY_MAX_D = 1 << 20  # table rows its LDS bitmap covers
 RANK_ALL = 0
 RANK_HELDOUT = 1
 INDEX_MAX_K = 256
@@ -179,6 +181,10 @@ SIGNATURES = {
     "qrlsh_diversify_grid": (ctypes.c_int, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _i64,
                                             _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_list_redundancy": (ctypes.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_list_fidelity_group": (_i32, [_i64]),
+    "qrlsh_edge_overlaps": (ctypes.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "qrlsh_list_fidelity": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                           _vp, _vp, _vp]),
     "qrlsh_ratings_holdout": (ctypes.c_int, [_vp, _i64, _i64, _u64, _u64, _vp, _vp, _vp]),
     "qrlsh_evaluate_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_evaluate": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,

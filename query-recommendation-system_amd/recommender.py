@@ -860,6 +860,53 @@ class Recommender:
             idx[i, :len(r)] = r
         return dv.list_redundancy(idx, lists[0], lists[1], lists[2], int(self.queriesIDs.size), device=self.device)
 
+    # ---- how good are the lists themselves: the exact answer-set overlap (qrlsh.fidelity) ----------------------------
+    def _fidelity_inputs(self):
+        """(offsets, rows, D, lists, K of the lists) as served now: the answer sets from the live table in slot numbering
+        once rows have come or gone, otherwise through the cached AnswerIndex"""
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        lt = getattr(self, "_live_table", None)
+        if lt is not None:
+            offsets, rows = lt.answer_sets()
+            D = int(lt.D)
+        else:
+            offsets, rows = self.answer_sets_device()
+            D = int(self.dataset.shape[0])
+        qi = getattr(self, "_query_index", None)
+        K = int(qi.lists_K) if qi is not None else int(self.last_result.K)
+        return offsets, rows, D, lists, K
+
+    def list_fidelity(self, positions=None, sample=1024, seed=0, K=None):
+        """How many of a query's true nearest neighbours -- by Jaccard over the answer sets, the quantity MinHash
+        estimates -- does its served list hold?  -> qrlsh.ListFidelity (.recall, .sure_recall, .disjoint_share,
+        .inversion_share, .per_request, .entries, .totals) over the live lists and the answer sets as served now, so
+        current after add_queries / remove_queries / replace_queries(update_lists=True), add_rows / remove_rows and
+        set_list_lengths; nothing is modified.  positions: 0-based queries (any order; a host sequence or a device
+        tensor), None = `sample` of them drawn by `seed` (qrlsh.fidelity.sample_positions; all when sample >= their
+        number).  K: the list length to judge, 1..64 (the first min(len, K) entries of every row), None = the lists' own.
+        ValueError when there are no live lists, for a bad K, sample, seed or position, and for more than 2^20 table rows."""
+        from qrlsh import fidelity as fd
+        offsets, rows, D, lists, own_K = self._fidelity_inputs()
+        nq = int(self.queriesIDs.size)
+        K = fd._int_in(own_K if K is None else K, 1, fd.MAX_K, "K")
+        if positions is None:
+            positions = fd.sample_positions(nq, sample, seed)
+        positions = self._query_positions(positions)
+        return fd.list_fidelity(offsets, rows, D, lists[0], lists[1], lists[2], nq, K, queries=positions,
+                                device=self.device)
+
+    def edge_overlaps(self):
+        """The exact overlap of every stored edge of the live lists -> (src, dst, val, inter) int32 device tensors and
+        sizes int64 device tensor [queries]: inter[e] = |A(src[e]) & A(dst[e])| and sizes[q] = |A(q)|, so Jaccard of edge e
+        is inter / (sizes[src] + sizes[dst] - inter) beside its stored val (milli).  Current after every live operation;
+        nothing is modified.  ValueError when there are no live lists."""
+        from qrlsh import fidelity as fd
+        offsets, rows, _, lists, _ = self._fidelity_inputs()
+        inter = fd.edge_overlaps(offsets, rows, lists[0], lists[1], device=self.device)
+        return lists[0], lists[1], lists[2], inter, offsets[1:] - offsets[:-1]
+
     def predict_users(self, users, sum_order=None, user_sim=None, ratings=None):
         """DataFrame requested users x queriesIDs: their rows of compute_scores(reuse_lists=True)'s finalPredictions,
         from the live lists (arguments as recommend_users takes them)."""
