@@ -960,6 +960,40 @@ int qrlsh_list_fidelity(const int64_t *offsets, const int32_t *rows, int64_t nq,
                         int32_t *inter_out, int32_t *union_out, int32_t *better_out, int32_t *equal_out,
                         int64_t *words_out, int64_t *totals_out, uint32_t *flags_out, void *stream);
 
+/* ---- exact lists: the top K by Jaccard over the answer sets, in the served list format -------------------------------
+ * What qrlsh_list_fidelity holds the served lists to, produced.  offsets int64 [nq + 1] / rows int32: the CSR answer sets
+ * over D table rows, rows ascending and distinct per query (TRUSTED to be a CSR, as above).  queries int32 [m]: the chosen
+ * queries, any order, repeats allowed; NULL = queries 0 .. m - 1 (m <= nq).  J, and the comparison of two J, as above:
+ * integers only, J_a > J_b decided by inter_a * union_b > inter_b * union_a in int64.
+ * The result of request x with chosen query s: the j != s with |A(s) & A(j)| > 0, ordered by J(s, j) descending, ties by
+ *   j ascending, cut at K.  That order is total, so the result is unique: it depends on neither the launch order nor the
+ *   slice count.  A query that shares no row with s is never listed, however short the list.
+ * Outputs, every word written by every call (nothing is accumulated):
+ *   dst_out int32 [m][K]: the neighbours, padded with -1;  inter_out, union_out int32 [m][K]: of (s, dst), padded with 0;
+ *   counts_out int32 [m][2] = (listed = min(K, positives), positives = the j != s with inter > 0).
+ * *flags_out (device uint32, zeroed by the caller, required): bit 2 a chosen query outside [0, nq) (its row is all
+ *   padding, its counts 0), bit 3 an answer-set row id outside [0, D) (never tested against LDS).  The bits are
+ *   qrlsh_list_fidelity's; bits 0 and 1 are not used.  A flagged result is not to be used.
+ * scratch: the partial lists of the slices, m * S * K * 3 int32 words with S = qrlsh_exact_neighbours_slices(nq, m, D,
+ *   slices), the resolved slice count (0 for arguments the call would refuse): slices itself when it is not 0, else
+ *   qrlsh_list_fidelity's automatic rule over ceil(m / G) workgroups per slice.  4-byte aligned; it need not be
+ *   initialised and holds nothing afterwards.  QRLSH_EWORKSPACE when scratch_bytes is smaller.
+ * Three steps on one stream: counts_out zeroed; the sweep -- qrlsh_list_fidelity's: a 1024-thread workgroup per (group of
+ *   G = qrlsh_list_fidelity_group(D) requests, slice of the ids j), the G answer sets as one interleaved bitmap in LDS,
+ *   the CSR rows of the slice read once for the whole group; the 256 words of a request hold its best K so far (inter,
+ *   union, id, in order) and the K-th entry as a threshold word.  A (request, j) with inter > 0 is compared once, with
+ *   the threshold; only one that may enter takes the request's LDS lock (a try-lock loop, the insertion and the release
+ *   inside the successful branch) and is inserted.  Each (request, slice) leaves its K entries in the scratch; a finish
+ *   with one wave per request merges the S partial lists under the same order and writes padding and counts.
+ * Limits: qrlsh_list_fidelity's -- 1 <= K <= QRLSH_FIDELITY_MAX_K, nq < 2^31, 0 <= D <= 2^20, 0 <= slices <= 256
+ *   (QRLSH_EINVAL otherwise); m <= 2^24 (QRLSH_EUNSUPPORTED above).  Every check precedes any device work; m = 0 or
+ *   nq = 0 returns at once with nothing written.
+ * No allocation, one stream, no read-back. */
+int32_t qrlsh_exact_neighbours_slices(int64_t nq, int64_t m, int64_t D, int32_t slices);
+int qrlsh_exact_neighbours(const int64_t *offsets, const int32_t *rows, int64_t nq, int64_t D, const int32_t *queries,
+                           int64_t m, int32_t K, int32_t slices, int32_t *dst_out, int32_t *inter_out, int32_t *union_out,
+                           int32_t *counts_out, uint32_t *flags_out, void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- evaluation: the prediction error on rated cells, hold-out and leave-one-out -----------------------------------
  * The blend of cell (i, j) never reads ratings[i][j]: a rated cell can be predicted as if it were unrated and compared
  * with its rating.  Predictions and ratings are integers, so every statistic is an exact integer sum, independent of the

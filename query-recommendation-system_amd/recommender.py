@@ -771,8 +771,17 @@ class Recommender:
         return out
 
     # ---- serving chosen users from the live lists: no prediction matrix -------------------------------------------
-    def _serving_inputs(self, sum_order, user_sim, ratings):
-        lists = self._live_lists()
+    def _lists_or_live(self, lists):
+        """a caller's (src, dst, milli) triple covering all served queries (e.g. ExactLists.coo()), or (None) the live lists"""
+        if lists is None:
+            return self._live_lists()
+        lists = tuple(lists)
+        if len(lists) != 3:
+            raise ValueError("lists must be a (src, dst, milli) triple")
+        return lists
+
+    def _serving_inputs(self, sum_order, user_sim, ratings, lists=None):
+        lists = self._lists_or_live(lists)
         if lists is None:
             raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
         sum_order = self.sum_order if sum_order is None else sum_order
@@ -785,10 +794,12 @@ class Recommender:
             user_sim = self.compute_userSimilarities()
         return lists, sum_order, user_sim, self.ratings if ratings is None else ratings
 
-    def recommend_users(self, users, k, sum_order=None, user_sim=None, ratings=None):
+    def recommend_users(self, users, k, sum_order=None, user_sim=None, ratings=None, lists=None):
         """recommend(compute_scores(reuse_lists=True)[1], k, users) for the requested users only, without the
         prediction of every user's row: the query side comes from the live lists (current_query_similarities; ValueError
         when there are none), so the answer is current after add_queries / remove_queries(update_lists=True).
+        lists: a (src, dst, milli) triple covering all served queries, used in place of the live lists (e.g.
+        exact_query_lists().coo()); None = the live lists.
         user_sim: compute_userSimilarities' dict or qrlsh.user_lists' prepared tuple (default: computed here);
         ratings: the utility matrix where the caller holds it, e.g. its device copy (default: self.ratings).
         -> the dict recommend() returns.  Raises ValueError for a bad k, sum_order or user id."""
@@ -797,7 +808,7 @@ class Recommender:
             raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
         if users is not None and not isinstance(users, torch.Tensor):
             users = np.asarray(users)
-        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
+        lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings, lists)
         idx, val, avail = rec.for_users(ratings, lists[0], lists[1], lists[2], user_sim, users, int(k),
                                         sum_order=sum_order, query_weight=self.query_weight,
                                         user_weight=self.user_weight, default_mean=self.default_mean,
@@ -861,24 +872,27 @@ class Recommender:
         return dv.list_redundancy(idx, lists[0], lists[1], lists[2], int(self.queriesIDs.size), device=self.device)
 
     # ---- how good are the lists themselves: the exact answer-set overlap (qrlsh.fidelity) ----------------------------
-    def _fidelity_inputs(self):
-        """(offsets, rows, D, lists, K of the lists) as served now: the answer sets from the live table in slot numbering
-        once rows have come or gone, otherwise through the cached AnswerIndex"""
-        lists = self._live_lists()
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+    def _answer_set_inputs(self):
+        """(offsets, rows, D) as served now: the answer sets from the live table in slot numbering once rows have come or
+        gone, otherwise through the cached AnswerIndex"""
         lt = getattr(self, "_live_table", None)
         if lt is not None:
             offsets, rows = lt.answer_sets()
-            D = int(lt.D)
-        else:
-            offsets, rows = self.answer_sets_device()
-            D = int(self.dataset.shape[0])
+            return offsets, rows, int(lt.D)
+        offsets, rows = self.answer_sets_device()
+        return offsets, rows, int(self.dataset.shape[0])
+
+    def _fidelity_inputs(self):
+        """(offsets, rows, D, lists, K of the lists) as served now"""
+        lists = self._live_lists()
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        offsets, rows, D = self._answer_set_inputs()
         qi = getattr(self, "_query_index", None)
         K = int(qi.lists_K) if qi is not None else int(self.last_result.K)
         return offsets, rows, D, lists, K
 
-    def list_fidelity(self, positions=None, sample=1024, seed=0, K=None):
+    def list_fidelity(self, positions=None, sample=1024, seed=0, K=None, lists=None):
         """How many of a query's true nearest neighbours -- by Jaccard over the answer sets, the quantity MinHash
         estimates -- does its served list hold?  -> qrlsh.ListFidelity (.recall, .sure_recall, .disjoint_share,
         .inversion_share, .per_request, .entries, .totals) over the live lists and the answer sets as served now, so
@@ -886,9 +900,17 @@ class Recommender:
         set_list_lengths; nothing is modified.  positions: 0-based queries (any order; a host sequence or a device
         tensor), None = `sample` of them drawn by `seed` (qrlsh.fidelity.sample_positions; all when sample >= their
         number).  K: the list length to judge, 1..64 (the first min(len, K) entries of every row), None = the lists' own.
+        lists: a (src, dst, milli) triple covering all served queries, judged in place of the live lists (which are then
+        not needed); K is required with it.
         ValueError when there are no live lists, for a bad K, sample, seed or position, and for more than 2^20 table rows."""
         from qrlsh import fidelity as fd
-        offsets, rows, D, lists, own_K = self._fidelity_inputs()
+        if lists is None:
+            offsets, rows, D, lists, own_K = self._fidelity_inputs()
+        else:
+            if K is None:
+                raise ValueError("K is required with lists: they carry no list length of their own")
+            lists, own_K = self._lists_or_live(lists), K
+            offsets, rows, D = self._answer_set_inputs()
         nq = int(self.queriesIDs.size)
         K = fd._int_in(own_K if K is None else K, 1, fd.MAX_K, "K")
         if positions is None:
@@ -906,6 +928,28 @@ class Recommender:
         offsets, rows, _, lists, _ = self._fidelity_inputs()
         inter = fd.edge_overlaps(offsets, rows, lists[0], lists[1], device=self.device)
         return lists[0], lists[1], lists[2], inter, offsets[1:] - offsets[:-1]
+
+    def exact_query_lists(self, K=None, positions=None):
+        """The exact neighbour lists of the queries as served now -> qrlsh.ExactLists (.dst, .inter, .union, .listed,
+        .positives, .coo()): per requested position the top K queries by Jaccard over the answer sets, J descending,
+        ties by position ascending -- what list_fidelity holds the served lists to.  Read from the answer sets as they
+        stand, so current after add_queries / remove_queries / replace_queries, add_rows and remove_rows; nothing is
+        modified and NOTHING IS INSTALLED: the live lists stay the LSH lists (QueryIndex would maintain installed lists by
+        LSH from the next operation on).  .coo() is the `lists` argument of evaluate, evaluate_ranking, recommend_users
+        and list_fidelity when positions is None.  K: 1..64, None = the live lists' own (ValueError when there are none);
+        positions: 0-based queries (any order; a host sequence or a device tensor), None = all -- every query against
+        every query: minutes at 10 M queries.
+        ValueError for a bad K or position and for more than 2^20 table rows."""
+        from qrlsh import exactlists as el
+        from qrlsh import fidelity as fd
+        if K is None:
+            K = self._fidelity_inputs()[4]
+        K = fd._int_in(K, 1, fd.MAX_K, "K")
+        offsets, rows, D = self._answer_set_inputs()
+        if int(offsets.numel()) - 1 != int(self.queriesIDs.size):
+            raise ValueError("the answer sets cover %d queries, %d are served" % (int(offsets.numel()) - 1,
+                                                                               int(self.queriesIDs.size)))
+        return el.exact_neighbours(offsets, rows, D, K, queries=self._query_positions(positions), device=self.device)
 
     def predict_users(self, users, sum_order=None, user_sim=None, ratings=None):
         """DataFrame requested users x queriesIDs: their rows of compute_scores(reuse_lists=True)'s finalPredictions,
@@ -975,7 +1019,7 @@ class Recommender:
                                 self.user_weight, self.default_mean, self.device, sum_order=sum_order)
 
     # ---- how good is the served model: the prediction error on rated cells (qrlsh.evaluate) -----------------------
-    def evaluate(self, fraction=1.0, seed=0, holdout=False, cells=None, sum_order=None, user_sim=None):
+    def evaluate(self, fraction=1.0, seed=0, holdout=False, cells=None, sum_order=None, user_sim=None, lists=None):
         """The prediction error of the model served now, on the device -> qrlsh.Evaluation (.mae, .rmse, .bias,
         .coverage, .by_branch, .per_user, .totals).  The query side comes from the live lists (ValueError when there are
         none); the sample is about `fraction` of the rated cells, chosen by `seed` (qrlsh.evaluate.is_kept).
@@ -990,6 +1034,8 @@ class Recommender:
         they stand.  Neither self.ratings nor user_index is modified.
         cells=(users, queries, values): an explicit test set instead of the sample (0-based positions; every triplet
         counts), predicted from the ratings as they stand as if each cell were unrated.
+        lists: a (src, dst, milli) triple covering all served queries, used as the query side in place of the live lists
+        (e.g. exact_query_lists().coo()); None = the live lists.
         ValueError for a fraction outside [0, 1], a bad sum_order, or cells together with holdout."""
         from qrlsh.evaluate import keep_word, evaluate as sweep, evaluate_cells
         keep_word(fraction)
@@ -998,18 +1044,18 @@ class Recommender:
         weights = dict(query_weight=self.query_weight, user_weight=self.user_weight, default_mean=self.default_mean,
                        device=self.device)
         if not holdout:
-            lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, None)
+            lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, None, lists)
             if cells is not None:
                 users, queries, values = cells
                 return evaluate_cells(ratings, lists[0], lists[1], lists[2], user_sim, users, queries, values,
                                       sum_order=sum_order, **weights)
             return sweep(ratings, lists[0], lists[1], lists[2], user_sim, fraction=fraction, seed=seed,
                          sum_order=sum_order, **weights)
-        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
+        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim, lists)
         return sweep(train, lists[0], lists[1], lists[2], user_sim, truth=truth, fraction=fraction, seed=seed,
                      sum_order=sum_order, **weights)
 
-    def _holdout_inputs(self, fraction, seed, sum_order, user_sim):
+    def _holdout_inputs(self, fraction, seed, sum_order, user_sim, lists=None):
         """The hold-out split evaluate(holdout=True), evaluate_ranking and tune share: the live lists (ValueError when
         there are none), the checked sum_order, a train copy on the device with the kept rated cells zeroed, the full
         matrix, and the user side over the train copy (a user index in step: UserLists.build over it with the index's
@@ -1017,7 +1063,7 @@ class Recommender:
         modified.  -> (lists, sum_order, train, truth, user_sim)"""
         from qrlsh.evaluate import holdout as train_copy
         from qrlsh.userlists import UserLists
-        lists = self._live_lists()
+        lists = self._lists_or_live(lists)
         if lists is None:
             raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
         sum_order = self.sum_order if sum_order is None else sum_order
@@ -1072,7 +1118,7 @@ class Recommender:
 
     # ---- and are the lists it serves any good: precision / recall / NDCG at k on held-out cells (qrlsh.ranking) -----
     def evaluate_ranking(self, k, relevant, fraction=0.1, seed=0, candidates="all", users=None, sum_order=None,
-                         user_sim=None):
+                         user_sim=None, lists=None):
         """Score the top-k lists of the model served now against held-out ratings, on the device ->
         qrlsh.RankingEvaluation (.precision, .recall, .ndcg, .hit_rate, .known_share, .macro(), .per_user, .totals,
         .idx / .val / .avail).  The split and the user side are those of evaluate(holdout=True): about `fraction` of
@@ -1081,15 +1127,16 @@ class Recommender:
         the compute_userSimilarities route over it); the query side comes from the live lists as they stand
         (ValueError when there are none).  Each requested user (default: all) is served its list from the train copy,
         and the list is held to self.ratings: a held-out cell rated >= relevant is a hit.  candidates: "all" ranks
-        every unrated cell of the train copy, "heldout" the held-out cells only.  Neither self.ratings nor user_index
-        is modified.  ValueError for a bad k, relevant, candidates, fraction, sum_order or user id."""
+        every unrated cell of the train copy, "heldout" the held-out cells only.  lists: a (src, dst, milli) triple
+        covering all served queries, used in place of the live lists; None = the live lists.  Neither self.ratings nor
+        user_index is modified.  ValueError for a bad k, relevant, candidates, fraction, sum_order or user id."""
         from qrlsh.evaluate import keep_word
         from qrlsh.ranking import check_arguments, evaluate_ranking as score
         keep_word(fraction)
         check_arguments(k, relevant, candidates)
         if users is not None and not isinstance(users, torch.Tensor):
             users = np.asarray(users)
-        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
+        lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim, lists)
         return score(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, users=users,
                      candidates=candidates, sum_order=sum_order, query_weight=self.query_weight,
                      user_weight=self.user_weight, default_mean=self.default_mean, device=self.device)
