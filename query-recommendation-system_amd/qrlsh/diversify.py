@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from . import ops
+from ._args import _int_in
 from .ops import _ptr, _stream
 
 MAX_POOL = _lib.DIVERSIFY_MAX_POOL
@@ -34,15 +35,9 @@ GRID_LINE, GRID_TOTALS = 12, 24
 GRID_METRICS = ("ndcg", "precision", "recall", "hit_rate")
 
 
-def _int_in(x, lo, hi, name):
-    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
-        raise ValueError("%s must be an integer in %d..%d, got %r" % (name, lo, hi, x))
-    return int(x)
-
-
 def _check_rule(k, penalty, max_sim):
-    return (_int_in(k, 1, MAX_POOL, "k"), _int_in(penalty, 0, MAX_PENALTY, "penalty"),
-            _int_in(max_sim, 0, 1001, "max_sim"))
+    return (_int_in(k, "k", 1, MAX_POOL), _int_in(penalty, "penalty", 0, MAX_PENALTY),
+            _int_in(max_sim, "max_sim", 0, 1001))
 
 
 def _int_array(x, ndim, name):
@@ -123,7 +118,7 @@ def diversify(cand_idx, cand_val, avail, q_src, q_dst, q_milli, nq, k, penalty=0
     for a neighbour index or a candidate column outside [0, nq) and a candidate twice in one pool (through the
     library's flags, read back once; nothing is returned then)."""
     k, penalty, max_sim = _check_rule(k, penalty, max_sim)
-    nq = _int_in(nq, 0, 2**31 - 1, "nq")
+    nq = _int_in(nq, "nq", 0, 2**31 - 1)
     ci, cv, av = _int_array(cand_idx, 2, "cand_idx"), _int_array(cand_val, 2, "cand_val"), _int_array(avail, 1, "avail")
     if tuple(ci.shape) != tuple(cv.shape) or av.shape[0] != ci.shape[0]:
         raise ValueError("cand_idx %s, cand_val %s and avail %s do not belong together"
@@ -144,7 +139,7 @@ def default_pool(k):
 
 
 def _check_pool(k, pool):
-    pool = default_pool(k) if pool is None else _int_in(pool, 1, MAX_POOL, "pool")
+    pool = default_pool(k) if pool is None else _int_in(pool, "pool", 1, MAX_POOL)
     if pool < k:
         raise ValueError("k <= pool <= %d is required, got k=%d pool=%d" % (MAX_POOL, k, pool))
     return pool
@@ -192,7 +187,7 @@ def list_redundancy(idx, q_src, q_dst, q_milli, nq, device="cuda"):
     the lists and nq as diversify takes them.  -> Redundancy (host arrays; one read-back).
     Raises ValueError for a bad shape or nq (before anything is uploaded), and for a neighbour index or a column
     outside [0, nq) and a column twice in one list (through the library's flags)."""
-    nq = _int_in(nq, 0, 2**31 - 1, "nq")
+    nq = _int_in(nq, "nq", 0, 2**31 - 1)
     li = _int_array(idx, 2, "idx")
     m, k = (int(d) for d in li.shape)
     if not 1 <= k <= MAX_POOL:
@@ -224,7 +219,7 @@ def _check_settings(settings):
         rows = []
     if not rows or any(len(r) != 2 for r in rows):
         raise ValueError("settings must be a non-empty sequence of (penalty, max_sim) pairs")
-    return [(_int_in(p, 0, MAX_PENALTY, "penalty"), _int_in(ms, 0, 1001, "max_sim")) for p, ms in rows]
+    return [(_int_in(p, "penalty", 0, MAX_PENALTY), _int_in(ms, "max_sim", 0, 1001)) for p, ms in rows]
 
 
 def _ratios(a, b):
@@ -386,7 +381,7 @@ def diversify_grid(cand_idx, cand_val, avail, q_src, q_dst, q_milli, nq, k, sett
     through the library's flags as diversify does, and for a device user id outside the truth's rows."""
     k = _check_rule(k, 0, 1001)[0]
     settings = _check_settings(settings)
-    nq = _int_in(nq, 0, 2**31 - 1, "nq")
+    nq = _int_in(nq, "nq", 0, 2**31 - 1)
     ci, cv, av = _int_array(cand_idx, 2, "cand_idx"), _int_array(cand_val, 2, "cand_val"), _int_array(avail, 1, "avail")
     if tuple(ci.shape) != tuple(cv.shape) or av.shape[0] != ci.shape[0]:
         raise ValueError("cand_idx %s, cand_val %s and avail %s do not belong together"

@@ -10,7 +10,8 @@ import torch
 
 from . import _lib
 from . import ops
-from .fidelity import MAX_D, MAX_K, _csr, _ids32, _int_array, _int_in
+from ._args import _int_in
+from .fidelity import MAX_D, MAX_K, _csr, _ids32, _int_array
 from .ops import _ptr, _stream
 
 WORKSPACE_BUDGET = 1 << 30   # bytes of partial lists per library call; more requests run as successive calls
@@ -80,9 +81,9 @@ def exact_neighbours(offsets, rows, D, K, queries=None, slices=0, device="cuda")
     Raises ValueError before anything is uploaded for a bad K, D (at most 2^20), slices or shape and a host query id
     outside [0, nq); through the library's flags for a device query id outside [0, nq) and an answer-set row id outside
     [0, D) (nothing is returned then)."""
-    K = _int_in(K, 1, MAX_K, "K")
-    D = _int_in(D, 0, MAX_D, "D")
-    slices = _int_in(slices, 0, 256, "slices")
+    K = _int_in(K, "K", 1, MAX_K)
+    D = _int_in(D, "D", 0, MAX_D)
+    slices = _int_in(slices, "slices", 0, 256)
     off, r = _csr(offsets, rows)
     nq = int(off.numel()) - 1
     ids = None

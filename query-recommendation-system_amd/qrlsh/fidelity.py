@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._args import _int_in
 from .ops import _ptr, _stream
 
 MAX_K = _lib.FIDELITY_MAX_K
@@ -22,12 +23,6 @@ _FLAG_TEXT = ((1, "a chosen query's list row is longer than %d entries" % MAX_K)
               (2, "a query's neighbour index is outside [0, %(nq)d)"),
               (4, "a chosen query is outside [0, %(nq)d)"),
               (8, "an answer-set row id is outside [0, %(D)d)"))
-
-
-def _int_in(x, lo, hi, name):
-    if isinstance(x, bool) or not isinstance(x, (int, np.integer)) or not lo <= int(x) <= hi:
-        raise ValueError("%s must be an integer in %d..%d, got %r" % (name, lo, hi, x))
-    return int(x)
 
 
 def _int_array(x, name):
@@ -74,9 +69,9 @@ def sample_positions(nq, sample, seed=0):
     """The seeded sample of Recommender.list_fidelity: the min(sample, nq) positions p of 0 .. nq - 1 with the smallest
     mix64(seed ^ p) (ties to the smaller p), ascending.  A position's key depends on nothing but seed and p, so the samples
     of a growing nq are nested in the sense that a position leaves only when one with a smaller key arrives."""
-    nq = _int_in(nq, 0, 2**31 - 1, "nq")
-    sample = _int_in(sample, 0, 2**31 - 1, "sample")
-    seed = _int_in(seed, 0, 2**64 - 1, "seed")
+    nq = _int_in(nq, "nq", 0, 2**31 - 1)
+    sample = _int_in(sample, "sample", 0, 2**31 - 1)
+    seed = _int_in(seed, "seed", 0, 2**64 - 1)
     keys = mix64_array(np.arange(nq, dtype=np.uint64) ^ np.uint64(seed))
     order = np.argsort(keys, kind="stable")[:min(sample, nq)]
     return np.sort(order).astype(np.int64)
@@ -152,10 +147,10 @@ def list_fidelity(offsets, rows, D, q_src, q_dst, q_milli, nq, K, queries=None, 
     Raises ValueError before anything is uploaded for a bad K, nq, D (at most 2^20), slices or shape and a host query id
     outside [0, nq); through the library's flags for a list row longer than 64, a neighbour index or a device query id
     outside [0, nq) and an answer-set row id outside [0, D) (nothing is returned then)."""
-    K = _int_in(K, 1, MAX_K, "K")
-    nq = _int_in(nq, 0, 2**31 - 1, "nq")
-    D = _int_in(D, 0, MAX_D, "D")
-    slices = _int_in(slices, 0, 256, "slices")
+    K = _int_in(K, "K", 1, MAX_K)
+    nq = _int_in(nq, "nq", 0, 2**31 - 1)
+    D = _int_in(D, "D", 0, MAX_D)
+    slices = _int_in(slices, "slices", 0, 256)
     off, r = _csr(offsets, rows)
     if off.numel() != nq + 1:
         raise ValueError("offsets holds %d entries, nq + 1 = %d" % (off.numel(), nq + 1))

@@ -25,17 +25,12 @@ import numpy as np
 import torch
 
 from . import _lib, ops
+from ._args import _int_in
 from .pipeline import max_candidates
 from .predict import QUERY_WEIGHT, USER_WEIGHT, DEFAULT_MEAN
 
 MAX_K = _lib.INDEX_MAX_K
 SUM_ORDERS = {"pairwise": _lib.SUM_PAIRWISE, "sequential": _lib.SUM_SEQUENTIAL}
-
-
-def _int_arg(v, name, lo, hi):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError("%s must be an integer in %d..%d, got %r" % (name, lo, hi, v))
-    return int(v)
 
 
 def _ids_arg(ids, dev):
@@ -78,7 +73,7 @@ class QueryIndex:
             raise TypeError("sig must be a 2-D int32 or int16 (compact) tensor")
         ops._need(sig, sig.dtype, "sig", 2)
         n, P = sig.shape
-        b = _int_arg(b, "b", 1, 65535)
+        b = _int_in(b, "b", 1, 65535)
         if P % b != 0:
             raise ValueError("signature length %d not divisible by b=%d" % (P, b))
         if n >= 2**32 - 1:
@@ -96,7 +91,7 @@ class QueryIndex:
         self._default_K = K is None
         if K is None:
             K = self._K_rule(n)
-        self.K = _int_arg(K, "K", 1, MAX_K)
+        self.K = _int_in(K, "K", 1, MAX_K)
         self.sig, self.n, self.P, self.b, self.r = sig, n, P, b, P // b
         self.table = table
         self.norm2 = norm2 if norm2 is not None else ops.row_norms(ops.sig_to_int32(sig))
@@ -170,7 +165,7 @@ class QueryIndex:
     # ---- growing the index -----------------------------------------------------------------------------------------
     def reserve(self, total):
         """room for `total` indexed queries in the row and norm buffers (no effect when they already hold as many)"""
-        total = _int_arg(total, "total", 0, 2**32 - 2)
+        total = _int_in(total, "total", 0, 2**32 - 2)
         if total <= self._sig_buf.shape[0]:
             return
         dev = self.sig.device
@@ -398,7 +393,7 @@ class QueryIndex:
         -> the number of rows probed again (0 for a cut), also in .last_picked.  ValueError, nothing changed: K2 outside
         1..MAX_K, an index without lists, n >= 2^31, or stored lists that break their contract (src not ascending, an id
         outside [0, n), a row longer than lists_K)."""
-        K2 = _int_arg(K2, "K2", 1, MAX_K)
+        K2 = _int_in(K2, "K2", 1, MAX_K)
         if self.lists is None:
             raise ValueError("this index holds no lists (none were given, or a call without update_lists=True dropped them)")
         if self.n >= 2**31:
@@ -433,9 +428,9 @@ class QueryIndex:
         among ALL other indexed queries (itself excluded; rows with the same signature and another id stay in, at
         1000).  keys [b, m]: the band keys these queries were indexed under when they were the caller's (default:
         computed from the rows, as the constructor does).  -> (off, idx, milli, avail) as neighbours()."""
-        K = self.K if K is None else _int_arg(K, "K", 1, MAX_K)
-        first_id = _int_arg(first_id, "first_id", 0, max(self.n, 0))
-        m = _int_arg(m, "m", 0, self.n - first_id)
+        K = self.K if K is None else _int_in(K, "K", 1, MAX_K)
+        first_id = _int_in(first_id, "first_id", 0, max(self.n, 0))
+        m = _int_in(m, "m", 0, self.n - first_id)
         dev = self.sig.device
         if m == 0:
             z = torch.zeros((1,), dtype=torch.int64, device=dev)
@@ -459,7 +454,7 @@ class QueryIndex:
         keys: theirs, or None (computed).  K: list length, default the index's (1..256).
         -> (off int64 [m + 1], idx int32, milli int32, avail int32 [m]) device tensors: CSR lists of indexed ids by
         milli descending, then id ascending; avail = distinct candidates before the cut."""
-        K = self.K if K is None else _int_arg(K, "K", 1, MAX_K)
+        K = self.K if K is None else _int_in(K, "K", 1, MAX_K)
         sig, norm2, keys = self._probe_rows(sig, norm2, keys)
         m = sig.shape[0]
         dev = self.sig.device

@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from . import ops
+from ._args import _int_in
 from .ops import _ptr, _stream
 from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT, ServeInputs
 
@@ -85,17 +86,15 @@ class RankingEvaluation:
 def check_arguments(k, relevant, candidates="all", lo=0, slices=0):
     """ValueError for a bad k, relevant, candidates, lo or slices (no device, no library) -> int(k)"""
     from . import recommend
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= recommend.MAX_K:
-        raise ValueError("k must be an integer in 1..%d, got %r" % (recommend.MAX_K, k))
+    k = _int_in(k, "k", 1, recommend.MAX_K)
     if isinstance(relevant, bool) or not isinstance(relevant, (int, np.integer)) or not 1 <= int(relevant) < 2**31:
         raise ValueError("relevant must be an int32 >= 1, got %r" % (relevant,))
     if not isinstance(candidates, str) or candidates not in CANDIDATES:
         raise ValueError("candidates must be 'all' or 'heldout', got %r" % (candidates,))
-    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= recommend.MAX_SLICES:
-        raise ValueError("slices must be an integer in 0..%d, got %r" % (recommend.MAX_SLICES, slices))
+    _int_in(slices, "slices", 0, recommend.MAX_SLICES)
     if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
         raise ValueError("lo must be an int32, got %r" % (lo,))
-    return int(k)
+    return k
 
 
 def _gain_tables(gains, k, m):

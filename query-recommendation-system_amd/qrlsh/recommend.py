@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from . import ops
+from ._args import _int_in
 from .ops import _ptr, _stream
 
 MAX_K = _lib.RECOMMEND_MAX_K
@@ -54,13 +55,7 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
     the number of eligible cells; idx -1 / val 0 past min(k, avail).
     Raises ValueError for a bad k, slices or shape and for a user id outside [0, nu) (host ids are checked before
     anything is uploaded; ids given as a device tensor through the library's per-row flag)."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
-        raise ValueError("k must be an integer in 1..%d, got %r" % (MAX_K, k))
-    k = int(k)
-    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= MAX_SLICES:
-        raise ValueError("slices must be an integer in 0..%d, got %r" % (MAX_SLICES, slices))
-    if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
-        raise ValueError("lo must be an int32, got %r" % (lo,))
+    k = _check_select_args(k, lo, slices)
     r = _matrix(ratings, "ratings")
     p = _matrix(predictions, "predictions")
     if tuple(r.shape) != tuple(p.shape):
@@ -116,12 +111,9 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
 
 
 def _check_select_args(k, lo, slices):
-    """for_users' checks of k, lo and slices (top_k's own are the same) -> k as an int"""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_K:
-        raise ValueError("k must be an integer in 1..%d, got %r" % (MAX_K, k))
-    k = int(k)
-    if isinstance(slices, bool) or not isinstance(slices, (int, np.integer)) or not 0 <= int(slices) <= MAX_SLICES:
-        raise ValueError("slices must be an integer in 0..%d, got %r" % (MAX_SLICES, slices))
+    """top_k's and for_users' checks of k, lo and slices -> k as an int"""
+    k = _int_in(k, "k", 1, MAX_K)
+    _int_in(slices, "slices", 0, MAX_SLICES)
     if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not -2**31 <= int(lo) < 2**31:
         raise ValueError("lo must be an int32, got %r" % (lo,))
     return k

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops, users as _users
+from ._args import _int_in
 from .ops import _ptr, _stream
 
 MAX_K = _lib.USER_LISTS_MAX_K
@@ -76,8 +77,7 @@ class UserLists:
             raise ValueError("ratings must have 1 .. 2^31 - 1 rows and fewer than 2^31 columns")
         if K is None:
             K = _users.max_candidates(nu)
-        if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= int(K) <= MAX_K:
-            raise ValueError("K must be an integer in 1..%d, got %r" % (MAX_K, K))
+        K = _int_in(K, "K", 1, MAX_K)
         lab = np.asarray(labels.cpu() if isinstance(labels, torch.Tensor) else labels).reshape(-1)
         if lab.size != nu or not np.issubdtype(lab.dtype, np.integer):
             raise ValueError("labels must hold one integer per user (%d)" % nu)
@@ -85,7 +85,7 @@ class UserLists:
         if r.data_ptr() % 16:
             r = r.clone()
         self = cls()
-        self.ratings, self.nu, self.nq, self.K = r, nu, nq, int(K)
+        self.ratings, self.nu, self.nq, self.K = r, nu, nq, K
         dev = r.device
         self._set_clusters(lab.astype(np.int64))
         # the first lists, in the dense form
@@ -514,9 +514,7 @@ class UserLists:
         full rows) beside the update's own.
         -> the number of rows rescored (0 for a cut), also in .last_picked.  ValueError for K2 outside 1..64 (nothing
         changed)."""
-        if isinstance(K2, bool) or not isinstance(K2, (int, np.integer)) or not 1 <= int(K2) <= MAX_K:
-            raise ValueError("K2 must be an integer in 1..%d, got %r" % (MAX_K, K2))
-        K1, K2 = self.K, int(K2)
+        K1, K2 = self.K, _int_in(K2, "K2", 1, MAX_K)
         if K2 == K1:
             self.last_picked = 0
             return 0

@@ -26,6 +26,7 @@ import torch
 
 import qrlsh
 from qrlsh import ops, pipeline
+from qrlsh._args import _int_in
 from lsh import LSH  # noqa: F401  (same import the reference has)
 
 # constants (recommender.py:30-34)
@@ -53,6 +54,63 @@ def _as_numpy(x):
     return x.to_numpy() if hasattr(x, "to_numpy") else np.asarray(x)
 
 
+def _diversify():
+    """the module qrlsh.diversify (the package attribute of that name is the function)"""
+    import importlib
+    return importlib.import_module("qrlsh.diversify")
+
+
+def _ids_arg(ids):
+    """chosen users or positions as the device wrappers take them: a tensor stays, None (= all) stays, anything else
+    becomes an array"""
+    return ids if ids is None or isinstance(ids, torch.Tensor) else np.asarray(ids)
+
+
+def _positions(positions, below=None, distinct=None):
+    """positions -> flat int64 host array, ValueError unless they are integers.  below=n: unique and sorted, all in
+    [0, n); distinct=(m, n): m different ones in [0, n), in the caller's order"""
+    pos = np.asarray(_as_numpy(positions)).reshape(-1)
+    if pos.size and not np.issubdtype(pos.dtype, np.integer):
+        raise ValueError("positions must be integers")
+    pos = pos.astype(np.int64)
+    if below is not None:
+        pos = np.unique(pos)
+        if pos.size and (pos[0] < 0 or pos[-1] >= below):
+            raise ValueError("position outside [0, %d)" % below)
+    if distinct is not None:
+        m, n = distinct
+        if pos.size != m or np.unique(pos).size != m or (m and (pos.min() < 0 or pos.max() >= n)):
+            raise ValueError("positions must be %d distinct integers in [0, %d)" % (m, n))
+    return pos
+
+
+def _ratings_block(ratings, rows, cols):
+    """an integer ratings block of `cols` columns as int64: [users, m] with `rows` rows, [m, queries] with any (None)"""
+    block = np.asarray(_as_numpy(ratings))
+    if block.ndim != 2 or block.shape[1] != cols or rows not in (None, block.shape[0]) or \
+            not np.issubdtype(block.dtype, np.integer):
+        raise ValueError("ratings must be an integer [m, queries] = [m, %d] block" % cols if rows is None else
+                         "ratings must be an integer [users, m] = [%d, %d] block" % (rows, cols))
+    return block.astype(np.int64)
+
+
+def _served(chosen, first, values, avail, length, key, redundancy=None):
+    """The dict the recommend* calls return, from the device's padded rows: {id: {key: int64, 'values': int64,
+    'available': int[, 'redundancy': int64]}} with id = chosen[i] (None: i) and row i cut to its first length[i] entries;
+    length = k stands for min(k, avail[i])"""
+    first, values, avail = ops.to_host(first), ops.to_host(values), ops.to_host(avail)
+    length = np.minimum(int(length), avail) if np.ndim(length) == 0 else ops.to_host(length)
+    redundancy = None if redundancy is None else ops.to_host(redundancy)
+    out = {}
+    for i, x in enumerate(range(len(avail)) if chosen is None else [int(x) for x in ops.to_host(chosen)]):
+        n = int(length[i])
+        out[x] = {key: first[i, :n].astype(np.int64), "values": values[i, :n].astype(np.int64),
+                  "available": int(avail[i])}
+        if redundancy is not None:
+            out[x]["redundancy"] = redundancy[i, :n].astype(np.int64)
+    return out
+
+
 class Recommender:
 
     device = "cuda"
@@ -73,6 +131,16 @@ class Recommender:
     default_mean = DEFAULT_MEAN
     diversity_penalty = 0      # the rerank recommend_users_diverse applies when called without one: the plain list;
     diversity_max_sim = 1001   # tune_diversity(apply=True) sets the two on the instance
+
+    # the state of a run, None until its setter has run
+    last_result = None         # compute_querySimilarities: the run's HotPathResult
+    last_table = None          # compute_querySimilarities: the permutation table the run was drawn with
+    _query_index = None        # _run_index, on the first live call after a run; compute_querySimilarities resets it
+    _live_table = None         # _live_rows, on the first add_rows / remove_rows; compute_querySimilarities resets it
+    row_slots = None           # _live_rows, with _live_table: the table slot of every dataset position
+    _answer_index = None       # answer_sets_device: the dataset's AnswerIndex,
+    _answer_index_key = None   # and the id() of the dataset it encodes
+    user_index = None          # live_user_similarities: the UserLists that follow self.ratings
 
     def init(self, users, queries, queriesIDs, dataset, ratings):
         """recommender.py:51-64.  Takes what main.py:23-85 passes -- `datatable` Frames (anything Frame-like:
@@ -111,14 +179,15 @@ class Recommender:
     def answer_sets_device(self):
         """CSR answer sets on the device: (offsets int64 [nq+1], rows int32 [nnz]); the table is
         dictionary-encoded into per-(feature, value) bitmaps once and cached."""
+        return self._answer_sets_of(self.queries)
+
+    def _answer_sets_of(self, queries):
+        """CSR answer sets of `queries` through the dataset's AnswerIndex, (re)built when the dataset is another one"""
         from qrlsh import answers
-        idx = getattr(self, "_answer_index", None)
-        if idx is None or getattr(self, "_answer_index_key", None) != id(self.dataset):
+        if self._answer_index is None or self._answer_index_key != id(self.dataset):
             cols = [self.dataset[f].to_numpy() for f in self.datasetFeatures]
-            idx = answers.build_answer_index(cols, self.device)
-            self._answer_index, self._answer_index_key = idx, id(self.dataset)
-        qrows = answers.encode_queries(idx, self.queries)
-        return answers.answer_sets(idx, qrows)
+            self._answer_index, self._answer_index_key = answers.build_answer_index(cols, self.device), id(self.dataset)
+        return answers.answer_sets(self._answer_index, answers.encode_queries(self._answer_index, queries))
 
     def answer_sets(self):
         """host copy of answer_sets_device(): (offsets int64 [nq+1], rows int32 [nnz])"""
@@ -200,28 +269,41 @@ class Recommender:
         return query_sim
 
     # ---- new queries: probes of the index of the last compute_querySimilarities run (device) ---------------------------
-    def _new_query_rows(self, queries):
-        """(index, sig, norm2, keys) of new queries given in parse_queries' form (one column per dataset feature,
-        "" = unconstrained): answer sets through the cached AnswerIndex, MinHash under the run's own table"""
-        from qrlsh import answers
+    def _run_index(self, tail, count=None, lists=False):
+        """The QueryIndex of the last run, every live operation's way to it: made from the run's result on first need
+        (with the run's lists, at the run's K) and bound there and then.  ValueError, in this order: no finished run
+        ("... has not run: " + tail); count="queries" / "columns": an index that does not hold the served queries
+        (/ the ratings' columns); lists=True: live lists that a call without update_lists=True dropped."""
         from qrlsh.index import QueryIndex
-        res = getattr(self, "last_result", None)
-        if res is None or getattr(self, "last_table", None) is None:
-            raise ValueError("compute_querySimilarities has not run: there is no index to look new queries up in")
+        if self.last_result is None or self.last_table is None:
+            raise ValueError("compute_querySimilarities has not run: " + tail)
+        if self._query_index is None:
+            self._query_index = QueryIndex.from_result(self.last_result, self.last_table, lists=True)
+        qi = self._query_index
+        if count is not None:
+            self._index_in_step(qi, columns=count == "columns")
+        if lists and qi.lists is None:
+            raise ValueError("the live lists were dropped by a call without update_lists=True; "
+                             "compute_querySimilarities starts afresh")
+        return qi
+
+    def _index_in_step(self, qi, columns=False):
+        if qi.n != self.queriesIDs.size or (columns and self.ratings.shape[1] != qi.n):
+            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+
+    def _new_query_rows(self, queries, lists=False):
+        """(index, sig, norm2, keys) of new queries given in parse_queries' form (one column per dataset feature,
+        "" = unconstrained): answer sets through the cached AnswerIndex, MinHash under the run's own table.  lists=True
+        refuses dropped live lists (_run_index) before the new texts reach the live table's dictionary."""
+        qi = self._run_index("there is no index to look new queries up in", lists=lists)
         q = np.asarray(_as_numpy(queries), dtype=object)
         if q.ndim != 2 or q.shape[1] != len(self.datasetFeatures):
             raise ValueError("queries must have one column per dataset feature (%d)" % len(self.datasetFeatures))
-        if getattr(self, "_query_index", None) is None:
-            self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
-        qi = self._query_index
-        lt = getattr(self, "_live_table", None)
+        lt = self._live_table
         if lt is not None:          # rows have come or gone: the table in slot numbering answers
             offsets, rows = lt.answer_sets(lt.encode(q))
-            sig, norm2, keys = qi.signatures(offsets, rows)
-            return qi, sig, norm2, keys
-        if getattr(self, "_answer_index", None) is None or getattr(self, "_answer_index_key", None) != id(self.dataset):
-            self.answer_sets_device()  # (re)builds the cached AnswerIndex of this dataset
-        offsets, rows = answers.answer_sets(self._answer_index, answers.encode_queries(self._answer_index, q))
+        else:
+            offsets, rows = self._answer_sets_of(q)
         sig, norm2, keys = qi.signatures(offsets, rows)
         return qi, sig, norm2, keys
 
@@ -246,19 +328,11 @@ class Recommender:
                 raise ValueError("ids of dtype %s do not fit %s of dtype %s" % (labels.dtype, name, cur.dtype))
         return labels
 
-    def _refuse_dropped_lists(self, update_lists):
-        """ValueError for update_lists=True after a call without it dropped the live lists -- raised before the call
-        touches anything (an index that does not exist yet is made with the run's lists and has nothing dropped)"""
-        qi = getattr(self, "_query_index", None)
-        if update_lists and qi is not None and qi.lists is None:
-            raise ValueError("the live lists were dropped by a call without update_lists=True; "
-                             "compute_querySimilarities starts afresh")
-
     def _user_index_in_step(self, block=None):
         """self.user_index when it holds self.ratings' shape now (it then follows the column operation under way), else
         None: an index that is already out of step is left alone.  A ratings block the index would refuse is refused
         here, before the query index takes the batch."""
-        ui = getattr(self, "user_index", None)
+        ui = self.user_index
         if ui is None or (ui.nu, ui.nq) != tuple(self.ratings.shape):
             return None
         if block is not None and block.size and (block.min() < 0 or block.max() >= 2**31):
@@ -285,26 +359,18 @@ class Recommender:
         A user index in step with self.ratings (live_user_similarities) follows, whatever update_lists says:
         UserLists.add_columns takes the block (m unrated columns without one), so rate, recommend_users and
         predict_users keep serving from it."""
-        self._refuse_dropped_lists(update_lists)        # before the new texts reach the live table's dictionary
-        qi, sig, norm2, keys = self._new_query_rows(queries)
+        qi, sig, norm2, keys = self._new_query_rows(queries, lists=update_lists)
         q = np.asarray(_as_numpy(queries), dtype=object)
         m = q.shape[0]
         nu = self.usersIDs.size
-        if ratings is None:
-            block = np.zeros((nu, m), dtype=np.int64)
-        else:
-            block = np.asarray(_as_numpy(ratings))
-            if block.ndim != 2 or block.shape != (nu, m) or not np.issubdtype(block.dtype, np.integer):
-                raise ValueError("ratings must be an integer [users, m] = [%d, %d] block" % (nu, m))
-            block = block.astype(np.int64)
-        if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
-            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        block = np.zeros((nu, m), dtype=np.int64) if ratings is None else _ratings_block(ratings, nu, m)
+        self._index_in_step(qi, columns=True)
         pos = np.arange(qi.n, qi.n + m, dtype=np.int64)
         cur = self.queriesIDs
         labels = self._ids_like(cur, ids, pos, "query", "queriesIDs")
         ui = self._user_index_in_step(None if ratings is None else block)
-        first, _ = qi.append(sig, norm2, keys, update_lists=update_lists)
-        if getattr(self, "_live_table", None) is not None:
+        qi.append(sig, norm2, keys, update_lists=update_lists)
+        if self._live_table is not None:
             self._live_table.add_queries(self._live_table.encode(q))
         if ui is not None:
             ui.add_columns(m if ratings is None else block)
@@ -323,24 +389,11 @@ class Recommender:
         the flag the live lists are dropped, and a later update_lists=True raises ValueError.  last_result stays the
         closed-set run's output.  A user index in step with self.ratings follows (UserLists.remove_columns), whatever
         update_lists says."""
-        from qrlsh.index import QueryIndex
-        res = getattr(self, "last_result", None)
-        if res is None or getattr(self, "last_table", None) is None:
-            raise ValueError("compute_querySimilarities has not run: there is no index to take queries out of")
-        if getattr(self, "_query_index", None) is None:
-            self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
-        qi = self._query_index
-        if update_lists and qi.lists is None:
-            raise ValueError("the live lists were dropped by an add_queries or remove_queries without update_lists=True; "
-                             "compute_querySimilarities starts afresh")
-        if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
-            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
-        pos = np.asarray(_as_numpy(positions)).reshape(-1)
-        if pos.size and not np.issubdtype(pos.dtype, np.integer):
-            raise ValueError("positions must be integers")
+        qi = self._run_index("there is no index to take queries out of", count="columns", lists=update_lists)
+        pos = _positions(positions)
         ui = self._user_index_in_step()
         new_pos = ops.to_host(qi.remove(pos, update_lists=update_lists))
-        if getattr(self, "_live_table", None) is not None:
+        if self._live_table is not None:
             self._live_table.remove_queries(new_pos)
         if ui is not None:
             ui.remove_columns(pos)
@@ -361,27 +414,15 @@ class Recommender:
         run's K.  Without the flag the live lists are dropped, and a later update_lists=True raises ValueError
         before anything changes.  last_result stays the closed-set run's output.  With a ratings block, a user index in step with self.ratings
         follows (UserLists.set_columns), whatever update_lists says; without one it is not touched."""
-        self._refuse_dropped_lists(update_lists)        # before the new texts reach the live table's dictionary
-        qi, sig, norm2, keys = self._new_query_rows(queries)
-        if qi.n != self.queriesIDs.size or self.ratings.shape[1] != qi.n:
-            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+        qi, sig, norm2, keys = self._new_query_rows(queries, lists=update_lists)
+        self._index_in_step(qi, columns=True)
         q = np.asarray(_as_numpy(queries), dtype=object)
         m = q.shape[0]
-        pos = np.asarray(_as_numpy(positions)).reshape(-1)
-        if pos.size and not np.issubdtype(pos.dtype, np.integer):
-            raise ValueError("positions must be integers")
-        pos = pos.astype(np.int64)
-        if pos.size != m or np.unique(pos).size != m or (m and (pos.min() < 0 or pos.max() >= qi.n)):
-            raise ValueError("positions must be %d distinct integers in [0, %d)" % (m, qi.n))
-        nu = self.usersIDs.size
-        block = None
-        if ratings is not None:
-            block = np.asarray(_as_numpy(ratings))
-            if block.ndim != 2 or block.shape != (nu, m) or not np.issubdtype(block.dtype, np.integer):
-                raise ValueError("ratings must be an integer [users, m] = [%d, %d] block" % (nu, m))
+        pos = _positions(positions, distinct=(m, qi.n))
+        block = None if ratings is None else _ratings_block(ratings, self.usersIDs.size, m)
         ui = self._user_index_in_step(block) if block is not None else None
         qi.replace(pos, sig, norm2, keys, update_lists=update_lists)
-        if getattr(self, "_live_table", None) is not None:
+        if self._live_table is not None:
             self._live_table.set_queries(pos, self._live_table.encode(q))
         if ui is not None:
             ui.set_columns(pos, block)
@@ -395,20 +436,9 @@ class Recommender:
     def _live_rows(self, update_lists):
         """(LiveTable, QueryIndex) of the last run; the table is built on first use from self.dataset (slot = position),
         self.queries and the run's permutation table (its rows are the capacity)"""
-        from qrlsh.index import QueryIndex
         from qrlsh.table import LiveTable
-        res = getattr(self, "last_result", None)
-        if res is None or getattr(self, "last_table", None) is None:
-            raise ValueError("compute_querySimilarities has not run: there is no index for rows to come and go under")
-        if getattr(self, "_query_index", None) is None:
-            self._query_index = QueryIndex.from_result(res, self.last_table, lists=True)
-        qi = self._query_index
-        if qi.n != self.queriesIDs.size:
-            raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
-        if update_lists and qi.lists is None:
-            raise ValueError("the live lists were dropped by a call without update_lists=True; "
-                             "compute_querySimilarities starts afresh")
-        if getattr(self, "_live_table", None) is None:
+        qi = self._run_index("there is no index for rows to come and go under", count="queries", lists=update_lists)
+        if self._live_table is None:
             if len(self.datasetFeatures) > 63:
                 raise ValueError("rows come and go under at most 63 dataset features, got %d" % len(self.datasetFeatures))
             cols = [self.dataset[f].to_numpy() for f in self.datasetFeatures]
@@ -455,14 +485,10 @@ class Recommender:
         die, the served queries whose minimum sat on one of them get their answer sets taken again
         (qrlsh.LiveTable.remove_rows / QueryIndex.set), and self.dataset keeps the live rows only (index reset).
         -> int64 host array [old rows]: the new position of every old one, -1 for a removed one."""
-        pos = np.asarray(_as_numpy(positions)).reshape(-1)
-        if pos.size and not np.issubdtype(pos.dtype, np.integer):
-            raise ValueError("positions must be integers")
+        pos = _positions(positions)
         lt, qi = self._live_rows(update_lists)
         drows = self.dataset.shape[0]
-        pos = np.unique(pos.astype(np.int64))
-        if pos.size and (pos[0] < 0 or pos[-1] >= drows):
-            raise ValueError("position outside [0, %d)" % drows)
+        pos = _positions(pos, below=drows)
         lt.remove_rows(self.row_slots[pos], qi, update_lists=update_lists)
         keep = np.ones(drows, dtype=bool)
         keep[pos] = False
@@ -473,22 +499,32 @@ class Recommender:
     def _live_lists(self):
         """(src, dst, val) that know every added query, or None: the run's own lists before any append, the index's
         while add_queries(update_lists=True) kept them current"""
-        res = getattr(self, "last_result", None)
+        res, qi = self.last_result, self._query_index
         if res is None:
             return None
-        qi = getattr(self, "_query_index", None)
         if qi is None:
             return (res.src, res.dst, res.val) if res.sig.shape[0] == self.queriesIDs.size else None
         return qi.lists if qi.n == self.queriesIDs.size else None
+
+    def _lists_or_refuse(self, lists=None):
+        """a caller's triple (_lists_or_live) or the live lists; ValueError when there are none"""
+        lists = self._lists_or_live(lists)
+        if lists is None:
+            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        return lists
+
+    def _sum_order(self, sum_order):
+        """the checked summation order of a serving call (None: self.sum_order)"""
+        sum_order = self.sum_order if sum_order is None else sum_order
+        if sum_order not in ("pairwise", "sequential"):
+            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        return sum_order
 
     def current_query_similarities(self):
         """the dict compute_querySimilarities returns, from the live lists: before any add_queries the run's own, after
         add_queries(update_lists=True) those of all queries served now (list length: the run's K).  ValueError when
         there are none (no run yet, or an add_queries without update_lists dropped them)."""
-        lists = self._live_lists()
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
-        return pipeline.sims_to_dict(*lists)
+        return pipeline.sims_to_dict(*self._lists_or_refuse())
 
     def similar_queries(self, queries):
         """{x: {'indexes': int64[<=K], 'values': float64[<=K]}} for new queries x = 0 .. m-1 (rows of `queries`): the
@@ -505,8 +541,7 @@ class Recommender:
         return out
 
     def _new_query_columns(self, queries, sum_order):
-        if sum_order not in ("pairwise", "sequential"):
-            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        sum_order = self._sum_order(sum_order)
         qi, sig, norm2, keys = self._new_query_rows(queries)
         off, idx, milli, _ = qi.neighbours(sig, norm2, keys)
         return qi.predict_columns(self.ratings, off, idx, milli, sum_order, self.query_weight, self.user_weight,
@@ -515,8 +550,7 @@ class Recommender:
     def predict_new_queries(self, queries, sum_order=None):
         """DataFrame usersIDs x new queries (0 .. m-1): the prediction compute_scores would give each user's cell of a
         new query appended as an unrated column (recommender.py:313-331; its user side is 0)."""
-        cols = self._new_query_columns(queries, self.sum_order if sum_order is None else sum_order)
-        final = ops.to_host(cols).T
+        final = ops.to_host(self._new_query_columns(queries, sum_order)).T
         return pd.DataFrame(final, index=self.usersIDs, columns=range(final.shape[1])).astype(int)
 
     def recommend_new_queries(self, queries, k, sum_order=None):
@@ -525,17 +559,9 @@ class Recommender:
         have one."""
         from qrlsh import recommend as rec
         from qrlsh.index import QueryIndex
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= rec.MAX_K:
-            raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
-        cols = self._new_query_columns(queries, self.sum_order if sum_order is None else sum_order)
-        users, vals, avail = QueryIndex.top_users(cols, int(k))
-        users, vals, avail = ops.to_host(users), ops.to_host(vals), ops.to_host(avail)
-        out = {}
-        for x in range(len(avail)):
-            n = min(int(k), int(avail[x]))
-            out[x] = {"users": users[x, :n].astype(np.int64), "values": vals[x, :n].astype(np.int64),
-                      "available": int(avail[x])}
-        return out
+        k = _int_in(k, "k", 1, rec.MAX_K)
+        users, vals, avail = QueryIndex.top_users(self._new_query_columns(queries, sum_order), k)
+        return _served(None, users, vals, avail, k, "users")
 
     # ---- N4: user similarity (clustering = the reference's sklearn call on the host; the rest on the device) ----
     def compute_userSimilarities(self):
@@ -591,11 +617,8 @@ class Recommender:
         go unused); the query side is not touched -- its lists do not depend on ratings.  ValueError for a wrong shape,
         a non-integer block, a value the index refuses or a wrong id count or kind (nothing changed).
         -> int64 [m], the positions assigned."""
-        block = np.asarray(_as_numpy(ratings))
         nu, nq = self.ratings.shape
-        if block.ndim != 2 or block.shape[1] != nq or not np.issubdtype(block.dtype, np.integer):
-            raise ValueError("ratings must be an integer [m, queries] = [m, %d] block" % nq)
-        block = block.astype(np.int64)
+        block = _ratings_block(ratings, None, nq)
         m = block.shape[0]
         pos = np.arange(nu, nu + m, dtype=np.int64)
         new_ids = self._ids_like(self.usersIDs, ids, pos, "user", "usersIDs")
@@ -612,13 +635,8 @@ class Recommender:
         self.usersIDs and self.ratings, and the users left are renumbered by rank.  A user index in step with
         self.ratings follows (UserLists.remove_users: the lists stay exact); one out of step is left alone.
         -> int64 host array [old count]: the new position of every old one, -1 for a removed one."""
-        pos = np.asarray(_as_numpy(positions)).reshape(-1)
-        if pos.size and not np.issubdtype(pos.dtype, np.integer):
-            raise ValueError("positions must be integers")
-        pos = np.unique(pos.astype(np.int64))
         nu = self.usersIDs.size
-        if pos.size and (pos[0] < 0 or pos[-1] >= nu):
-            raise ValueError("position outside [0, %d)" % nu)
+        pos = _positions(positions, below=nu)
         if pos.size >= nu:
             raise ValueError("no user would be left")
         ui = self._user_index_in_step()
@@ -637,7 +655,7 @@ class Recommender:
         an index, for a position outside range or a negative value (nothing changed), and for an index that fell out of
         step with self.ratings (add_queries, remove_queries and replace_queries keep an index in step that was in step
         when they were called).  -> rows of the lists rewritten"""
-        ui = getattr(self, "user_index", None)
+        ui = self.user_index
         if ui is None:
             raise ValueError("there is no user index: call live_user_similarities first")
         if ui.nu != self.ratings.shape[0] or ui.nq != self.ratings.shape[1]:
@@ -654,14 +672,11 @@ class Recommender:
         -> (query_K, user_K) for set_list_lengths, None for a side left alone -- one whose best cut is >= its current
         length (tune never regrows).  ValueError before anything changes: a best cut of 0 (a side switched off is not a
         list length), or a user cut without a user index in step."""
-        from qrlsh.index import QueryIndex
         query_K = user_K = None
         if q_cut is not None:
             if q_cut < 1:
                 raise ValueError("the best setting switches the query side off (cut 0): a list length is >= 1, nothing applied")
-            qi = getattr(self, "_query_index", None)
-            if qi is None:
-                qi = self._query_index = QueryIndex.from_result(self.last_result, self.last_table, lists=True)
+            qi = self._run_index("there are no lists to change")
             if qi.lists is not None and q_cut < qi.lists_K:
                 query_K = int(q_cut)
         if u_cut is not None:
@@ -686,32 +701,20 @@ class Recommender:
         ValueError before anything changes: a length outside range, no finished run, no live lists, an index that does
         not hold the served queries, or user_K without a user index in step.
         -> (query rows probed again, user rows rescored), None for a side left alone."""
-        from qrlsh.index import QueryIndex, MAX_K, _int_arg
+        from qrlsh.index import MAX_K
         from qrlsh.userlists import MAX_K as USER_MAX_K
         qi = ui = None
         if query_K is not None:
-            query_K = _int_arg(query_K, "query_K", 1, MAX_K)
-            res = getattr(self, "last_result", None)
-            if res is None or getattr(self, "last_table", None) is None:
-                raise ValueError("compute_querySimilarities has not run: there are no lists to change")
-            qi = getattr(self, "_query_index", None)
-            made = qi is None
-            if made:
-                qi = QueryIndex.from_result(res, self.last_table, lists=True)
-            if qi.lists is None:
-                raise ValueError("the live lists were dropped by a call without update_lists=True; "
-                                 "compute_querySimilarities starts afresh")
-            if qi.n != self.queriesIDs.size:
-                raise ValueError("the index holds %d queries, the recommender %d" % (qi.n, self.queriesIDs.size))
+            query_K = _int_in(query_K, "query_K", 1, MAX_K)
+            qi = self._run_index("there are no lists to change", count="queries", lists=True)
         if user_K is not None:
-            user_K = _int_arg(user_K, "user_K", 1, USER_MAX_K)
+            user_K = _int_in(user_K, "user_K", 1, USER_MAX_K)
             ui = self._user_index_in_step()
             if ui is None:
                 raise ValueError("user_K needs a user index in step with self.ratings (live_user_similarities)")
         picked_q = picked_u = None
         if qi is not None:
-            picked_q = qi.set_list_length(query_K)      # raises before it binds anything
-            self._query_index = qi
+            picked_q = qi.set_list_length(query_K)      # raises before it changes anything
         if ui is not None:
             picked_u = ui.set_list_length(user_K)
         return picked_q, picked_u
@@ -758,17 +761,9 @@ class Recommender:
         'available' = len(just_scored), the prompt's [Max: N].  Raises ValueError for a bad k, shape or user id."""
         from qrlsh import recommend as rec
         pred = predictions.to_numpy() if hasattr(predictions, "to_numpy") else predictions
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        users = _ids_arg(users)
         idx, val, avail = rec.top_k(self.ratings, pred, k, users=users, device=self.device)
-        idx, val, avail = ops.to_host(idx), ops.to_host(val), ops.to_host(avail)
-        ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
-        out = {}
-        for i, u in enumerate(ids):
-            n = min(int(k), int(avail[i]))
-            out[u] = {"indexes": idx[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
-                      "available": int(avail[i])}
-        return out
+        return _served(users, idx, val, avail, k, "indexes")
 
     # ---- serving chosen users from the live lists: no prediction matrix -------------------------------------------
     def _lists_or_live(self, lists):
@@ -781,13 +776,8 @@ class Recommender:
         return lists
 
     def _serving_inputs(self, sum_order, user_sim, ratings, lists=None):
-        lists = self._lists_or_live(lists)
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
-        sum_order = self.sum_order if sum_order is None else sum_order
-        if sum_order not in ("pairwise", "sequential"):
-            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
-        ui = getattr(self, "user_index", None)
+        lists, sum_order = self._lists_or_refuse(lists), self._sum_order(sum_order)
+        ui = self.user_index
         if ui is not None and user_sim is None and ratings is None and (ui.nu, ui.nq) == tuple(self.ratings.shape):
             return lists, sum_order, ui.as_user_sims(), ui.ratings   # the live user lists and their device matrix
         if user_sim is None:
@@ -804,23 +794,13 @@ class Recommender:
         ratings: the utility matrix where the caller holds it, e.g. its device copy (default: self.ratings).
         -> the dict recommend() returns.  Raises ValueError for a bad k, sum_order or user id."""
         from qrlsh import recommend as rec
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= rec.MAX_K:
-            raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        k, users = _int_in(k, "k", 1, rec.MAX_K), _ids_arg(users)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings, lists)
-        idx, val, avail = rec.for_users(ratings, lists[0], lists[1], lists[2], user_sim, users, int(k),
+        idx, val, avail = rec.for_users(ratings, lists[0], lists[1], lists[2], user_sim, users, k,
                                         sum_order=sum_order, query_weight=self.query_weight,
                                         user_weight=self.user_weight, default_mean=self.default_mean,
                                         device=self.device)
-        idx, val, avail = ops.to_host(idx), ops.to_host(val), ops.to_host(avail)
-        ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
-        out = {}
-        for i, u in enumerate(ids):
-            n = min(int(k), int(avail[i]))
-            out[u] = {"indexes": idx[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
-                      "available": int(avail[i])}
-        return out
+        return _served(users, idx, val, avail, k, "indexes")
 
     def recommend_users_diverse(self, users, k, penalty=None, max_sim=None, pool=None, sum_order=None, user_sim=None,
                                 ratings=None):
@@ -833,49 +813,37 @@ class Recommender:
         -> recommend_users' dict with 'redundancy' added: int64, the r each listed query had when it was picked (the
         lists can be shorter than min(k, available) when max_sim excludes).  Raises ValueError for a bad k, pool,
         penalty, max_sim, sum_order or user id."""
-        import importlib
-        dv = importlib.import_module("qrlsh.diversify")   # qrlsh.diversify itself is the function
+        dv = _diversify()
         penalty = self.diversity_penalty if penalty is None else penalty
         max_sim = self.diversity_max_sim if max_sim is None else max_sim
         k, penalty, max_sim = dv._check_rule(k, penalty, max_sim)
         pool = dv._check_pool(k, pool)
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        users = _ids_arg(users)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
-        out = dv.for_users_diverse(ratings, lists[0], lists[1], lists[2], user_sim, users, k, pool=pool,
-                                   penalty=penalty, max_sim=max_sim, sum_order=sum_order,
-                                   query_weight=self.query_weight, user_weight=self.user_weight,
-                                   default_mean=self.default_mean, device=self.device)
-        idx, val, red, count, avail = (ops.to_host(t) for t in out)
-        ids = range(len(avail)) if users is None else [int(x) for x in ops.to_host(users)]
-        recs = {}
-        for i, u in enumerate(ids):
-            n = int(count[i])
-            recs[u] = {"indexes": idx[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
-                       "available": int(avail[i]), "redundancy": red[i, :n].astype(np.int64)}
-        return recs
+        idx, val, red, count, avail = dv.for_users_diverse(
+            ratings, lists[0], lists[1], lists[2], user_sim, users, k, pool=pool, penalty=penalty, max_sim=max_sim,
+            sum_order=sum_order, query_weight=self.query_weight, user_weight=self.user_weight,
+            default_mean=self.default_mean, device=self.device)
+        return _served(users, idx, val, avail, count, "indexes", redundancy=red)
 
     def list_redundancy(self, recs):
         """How redundant served lists are, by the live neighbour lists: recs is a dict recommend / recommend_users /
         recommend_users_diverse returned.  -> qrlsh.Redundancy: .words[i] = (entries, in-list pairs of stored
         neighbours, the sum of their similarities in milli, the largest) for the i-th user of the dict, .totals,
         .pairs_per_list, .mean_sim."""
-        import importlib
-        dv = importlib.import_module("qrlsh.diversify")
-        lists = self._live_lists()
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        lists = self._lists_or_refuse()
         rows = [np.asarray(r["indexes"], dtype=np.int64) for r in recs.values()]
         idx = np.full((len(rows), max([len(r) for r in rows] + [1])), -1, dtype=np.int64)
         for i, r in enumerate(rows):
             idx[i, :len(r)] = r
-        return dv.list_redundancy(idx, lists[0], lists[1], lists[2], int(self.queriesIDs.size), device=self.device)
+        return _diversify().list_redundancy(idx, lists[0], lists[1], lists[2], int(self.queriesIDs.size),
+                                            device=self.device)
 
     # ---- how good are the lists themselves: the exact answer-set overlap (qrlsh.fidelity) ----------------------------
     def _answer_set_inputs(self):
         """(offsets, rows, D) as served now: the answer sets from the live table in slot numbering once rows have come or
         gone, otherwise through the cached AnswerIndex"""
-        lt = getattr(self, "_live_table", None)
+        lt = self._live_table
         if lt is not None:
             offsets, rows = lt.answer_sets()
             return offsets, rows, int(lt.D)
@@ -884,11 +852,9 @@ class Recommender:
 
     def _fidelity_inputs(self):
         """(offsets, rows, D, lists, K of the lists) as served now"""
-        lists = self._live_lists()
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
+        lists = self._lists_or_refuse()
         offsets, rows, D = self._answer_set_inputs()
-        qi = getattr(self, "_query_index", None)
+        qi = self._query_index
         K = int(qi.lists_K) if qi is not None else int(self.last_result.K)
         return offsets, rows, D, lists, K
 
@@ -912,11 +878,10 @@ class Recommender:
             lists, own_K = self._lists_or_live(lists), K
             offsets, rows, D = self._answer_set_inputs()
         nq = int(self.queriesIDs.size)
-        K = fd._int_in(own_K if K is None else K, 1, fd.MAX_K, "K")
+        K = _int_in(own_K if K is None else K, "K", 1, fd.MAX_K)
         if positions is None:
             positions = fd.sample_positions(nq, sample, seed)
-        positions = self._query_positions(positions)
-        return fd.list_fidelity(offsets, rows, D, lists[0], lists[1], lists[2], nq, K, queries=positions,
+        return fd.list_fidelity(offsets, rows, D, lists[0], lists[1], lists[2], nq, K, queries=_ids_arg(positions),
                                 device=self.device)
 
     def edge_overlaps(self):
@@ -944,19 +909,18 @@ class Recommender:
         from qrlsh import fidelity as fd
         if K is None:
             K = self._fidelity_inputs()[4]
-        K = fd._int_in(K, 1, fd.MAX_K, "K")
+        K = _int_in(K, "K", 1, fd.MAX_K)
         offsets, rows, D = self._answer_set_inputs()
         if int(offsets.numel()) - 1 != int(self.queriesIDs.size):
             raise ValueError("the answer sets cover %d queries, %d are served" % (int(offsets.numel()) - 1,
                                                                                int(self.queriesIDs.size)))
-        return el.exact_neighbours(offsets, rows, D, K, queries=self._query_positions(positions), device=self.device)
+        return el.exact_neighbours(offsets, rows, D, K, queries=_ids_arg(positions), device=self.device)
 
     def predict_users(self, users, sum_order=None, user_sim=None, ratings=None):
         """DataFrame requested users x queriesIDs: their rows of compute_scores(reuse_lists=True)'s finalPredictions,
         from the live lists (arguments as recommend_users takes them)."""
         from qrlsh import predict
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        users = _ids_arg(users)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
         rows = predict.predict_users(ratings, lists[0], lists[1], lists[2], user_sim, users, self.query_weight,
                                      self.user_weight, self.default_mean, self.device, sum_order=sum_order)
@@ -964,11 +928,6 @@ class Recommender:
         return pd.DataFrame(ops.to_host(rows), index=self.usersIDs[ids], columns=self.queriesIDs).astype(int)
 
     # ---- serving chosen queries from the live lists: their audience, their columns, their utility --------------------
-    def _query_positions(self, positions):
-        if positions is not None and not isinstance(positions, torch.Tensor):
-            positions = np.asarray(positions)
-        return positions
-
     def recommend_queries(self, positions, k, sum_order=None, user_sim=None, ratings=None):
         """"Whom do I show query j?" for queries that are columns of the matrix (recommend_new_queries covers new ones):
         per requested position the k users with the largest non-zero predictions among those who have not rated it,
@@ -980,30 +939,21 @@ class Recommender:
         Raises ValueError for a bad k, sum_order or position."""
         from qrlsh import recommend as rec
         from qrlsh import servequeries as sq
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= rec.MAX_K:
-            raise ValueError("k must be an integer in 1..%d, got %r" % (rec.MAX_K, k))
-        positions = self._query_positions(positions)
+        k, positions = _int_in(k, "k", 1, rec.MAX_K), _ids_arg(positions)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
-        users, val, avail = sq.for_queries(ratings, lists[0], lists[1], lists[2], user_sim, positions, int(k),
+        users, val, avail = sq.for_queries(ratings, lists[0], lists[1], lists[2], user_sim, positions, k,
                                            sum_order=sum_order, query_weight=self.query_weight,
                                            user_weight=self.user_weight, default_mean=self.default_mean,
                                            device=self.device)
-        users, val, avail = ops.to_host(users), ops.to_host(val), ops.to_host(avail)
-        ids = range(len(avail)) if positions is None else [int(x) for x in ops.to_host(positions)]
-        out = {}
-        for i, j in enumerate(ids):
-            n = min(int(k), int(avail[i]))
-            out[j] = {"users": users[i, :n].astype(np.int64), "values": val[i, :n].astype(np.int64),
-                      "available": int(avail[i])}
-        return out
+        return _served(positions, users, val, avail, k, "users")
 
     def predict_queries(self, positions, sum_order=None, user_sim=None, ratings=None):
         """DataFrame usersIDs x queriesIDs[positions]: those columns of compute_scores(reuse_lists=True)'s
         finalPredictions, from the live lists (arguments as recommend_queries takes them)."""
         from qrlsh import servequeries as sq
-        positions = self._query_positions(positions)
+        positions = _ids_arg(positions)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
-        cols = sq.predict_queries(ratings, lists[0], lists[1], lists[2], user_sim, positions, self.query_weight,
+        cols =sq.predict_queries(ratings, lists[0], lists[1], lists[2], user_sim, positions, self.query_weight,
                                   self.user_weight, self.default_mean, self.device, sum_order=sum_order)
         ids = np.arange(self.queriesIDs.size) if positions is None else np.asarray(ops.to_host(positions), dtype=np.int64)
         return pd.DataFrame(ops.to_host(cols).T, index=self.usersIDs, columns=self.queriesIDs[ids]).astype(int)
@@ -1013,7 +963,7 @@ class Recommender:
         every column): per query the users who rated it, predicted and missed users, the sums, the blend's branches,
         and .utility / .mean_rating / .mean_prediction / .coverage (arguments as recommend_queries takes them)."""
         from qrlsh import servequeries as sq
-        positions = self._query_positions(positions)
+        positions = _ids_arg(positions)
         lists, sum_order, user_sim, ratings = self._serving_inputs(sum_order, user_sim, ratings)
         return sq.query_utility(ratings, lists[0], lists[1], lists[2], user_sim, positions, self.query_weight,
                                 self.user_weight, self.default_mean, self.device, sum_order=sum_order)
@@ -1063,12 +1013,7 @@ class Recommender:
         modified.  -> (lists, sum_order, train, truth, user_sim)"""
         from qrlsh.evaluate import holdout as train_copy
         from qrlsh.userlists import UserLists
-        lists = self._lists_or_live(lists)
-        if lists is None:
-            raise ValueError("there are no live lists: run compute_querySimilarities, and add queries with update_lists=True")
-        sum_order = self.sum_order if sum_order is None else sum_order
-        if sum_order not in ("pairwise", "sequential"):
-            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        lists, sum_order = self._lists_or_refuse(lists), self._sum_order(sum_order)
         ui = self._user_index_in_step() if user_sim is None else None
         truth = ui.ratings if ui is not None else torch.from_numpy(
             np.ascontiguousarray(self.ratings, dtype=np.int32)).to(self.device)
@@ -1108,8 +1053,14 @@ class Recommender:
             truth = None
         grid = evaluate_grid(ratings, lists[0], lists[1], lists[2], user_sim, weights, q_cuts=q_cuts, u_cuts=u_cuts,
                              truth=truth, fraction=fraction, seed=seed, sum_order=sum_order, device=self.device)
+        return self._apply_best(grid, metric, min_coverage, q_cuts, u_cuts, apply, apply_cuts)
+
+    def _apply_best(self, grid, metric, floor, q_cuts, u_cuts, apply, apply_cuts):
+        """tune's and tune_ranking's tail: with apply / apply_cuts, grid.best(metric, floor) goes to the live lists (the
+        cuts of the sides whose cuts were given: _cut_plan decides, set_list_lengths applies) and then to the weights, so
+        a refused cut leaves the recommender as it was.  -> grid"""
         if apply or apply_cuts:
-            qc, uc, (qw, uw, dm), _ = grid.best(metric, min_coverage)
+            qc, uc, (qw, uw, dm), _ = grid.best(metric, floor)
             if apply_cuts:
                 self.set_list_lengths(*self._cut_plan(qc if q_cuts is not None else None, uc if u_cuts is not None else None))
             if apply:
@@ -1134,8 +1085,7 @@ class Recommender:
         from qrlsh.ranking import check_arguments, evaluate_ranking as score
         keep_word(fraction)
         check_arguments(k, relevant, candidates)
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        users = _ids_arg(users)
         lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim, lists)
         return score(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, users=users,
                      candidates=candidates, sum_order=sum_order, query_weight=self.query_weight,
@@ -1163,19 +1113,12 @@ class Recommender:
         check_arguments(k, relevant, "heldout")
         if metric not in METRICS:
             raise ValueError("metric must be one of %s" % (METRICS,))
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        users = _ids_arg(users)
         lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
         grid = evaluate_ranking_grid(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, weights,
                                      q_cuts=q_cuts, u_cuts=u_cuts, users=users, sum_order=sum_order,
                                      device=self.device)
-        if apply or apply_cuts:
-            qc, uc, (qw, uw, dm), _ = grid.best(metric, min_recall)
-            if apply_cuts:
-                self.set_list_lengths(*self._cut_plan(qc if q_cuts is not None else None, uc if u_cuts is not None else None))
-            if apply:
-                self.query_weight, self.user_weight, self.default_mean = qw, uw, dm
-        return grid
+        return self._apply_best(grid, metric, min_recall, q_cuts, u_cuts, apply, apply_cuts)
 
     # ---- and which rerank: accuracy and redundancy of the diversified lists per (penalty, max_sim) (qrlsh.diversify) ---
     def tune_diversity(self, k, relevant, settings, pool=None, fraction=0.1, seed=0, users=None, sum_order=None,
@@ -1192,17 +1135,15 @@ class Recommender:
         pairs_per_list <= max_pairs_per_list (DiversityGrid.best), so recommend_users_diverse called without a penalty
         uses it from then on.  Nothing else of self is modified.  ValueError as qrlsh.evaluate_diversity raises it, and
         from best() when apply is set."""
-        import importlib
         from qrlsh.evaluate import keep_word
-        dv = importlib.import_module("qrlsh.diversify")
+        dv = _diversify()
         keep_word(fraction)
         k = dv._check_rule(k, 0, 1001)[0]
         pool = dv._check_pool(k, pool)
         settings = dv._check_settings(settings)
         if metric not in dv.GRID_METRICS:
             raise ValueError("metric must be one of %s" % (dv.GRID_METRICS,))
-        if users is not None and not isinstance(users, torch.Tensor):
-            users = np.asarray(users)
+        users = _ids_arg(users)
         lists, sum_order, train, truth, user_sim = self._holdout_inputs(fraction, seed, sum_order, user_sim)
         grid = dv.evaluate_diversity(train, truth, lists[0], lists[1], lists[2], user_sim, k, relevant, settings,
                                      pool=pool, users=users, sum_order=sum_order, query_weight=self.query_weight,

@@ -428,3 +428,41 @@ def test_argument_errors():
     assert rc == _lib.QRLSH_OK
     fresh = _index(sig[:110], b)
     assert torch.equal(ko, fresh.keys) and torch.equal(io, fresh.ids) and torch.equal(do, fresh.dir)
+
+
+# ------------------------------------------------------------------------- 9. the run's index is bound where it is made
+@pytest.fixture(scope="module")
+def cfg2_run():
+    """a Recommender on golden cfg2 (700 dataset rows) after one compute_querySimilarities, and the dict the run returned"""
+    from test_gpu_recommend import _recommender_on
+    rec, _ = _recommender_on("cfg2")
+    return rec, rec.compute_querySimilarities()
+
+
+FIRST_LIVE_CALLS = {
+    "similar_queries": lambda rec, K: rec.similar_queries(np.asarray(rec.queries, dtype=object)[:1]),
+    "remove_queries": lambda rec, K: rec.remove_queries([]),
+    "remove_rows": lambda rec, K: rec.remove_rows([]),
+    "set_list_lengths": lambda rec, K: rec.set_list_lengths(query_K=K),
+    "tune": lambda rec, K: rec.tune([(0.6, 0.4, 60.0)], q_cuts=[K], fraction=0.5, seed=3, apply_cuts=True),
+}
+
+
+@pytest.mark.parametrize("route", sorted(FIRST_LIVE_CALLS))
+def test_first_live_call_binds_the_runs_index_and_keeps_its_lists(cfg2_run, route):
+    """Each of the five routes to the index of the last run, as the first live call after the run (on a copy of the
+    run's state: no route writes what the copies share), leaves the index bound, over the served queries, and
+    current_query_similarities() what the run itself returned."""
+    import copy
+    ran, run = cfg2_run
+    rec = copy.copy(ran)
+    assert rec._query_index is None and rec.last_result is ran.last_result
+    FIRST_LIVE_CALLS[route](rec, int(rec.last_result.K))
+    assert rec._query_index is not None and rec._query_index.n == rec.queriesIDs.size
+    now = rec.current_query_similarities()
+    assert list(now) == list(run) and len(run) > 0
+    for q, want in run.items():
+        assert sorted(now[q]) == ["indexes", "values"]
+        for key in ("indexes", "values"):
+            assert now[q][key].dtype == want[key].dtype and np.array_equal(now[q][key], want[key]), (q, key)
+    assert ran._query_index is None

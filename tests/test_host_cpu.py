@@ -266,3 +266,81 @@ def test_init_accepts_what_main_py_passes(sub):
     rec2.init(users.to_pandas(), queries, qids, dataset.to_pandas(), ratings.to_pandas())
     assert np.array_equal(rec2.ratings, rec.ratings) and rec2.dataset.equals(rec.dataset)
     assert np.array_equal(rec2.usersIDs, rec.usersIDs) and np.array_equal(rec2.queries, rec.queries)
+
+
+# ------------------------------------------------------------- Recommender: declared run state, one copy of each refusal
+@pytest.fixture()
+def no_library(monkeypatch):
+    from qrlsh import _lib
+
+    def touched(*a, **kw):
+        raise AssertionError("touched the library")
+    monkeypatch.setattr(_lib, "load", touched)
+
+
+RUN_STATE = ("last_result", "last_table", "_query_index", "_live_table", "row_slots", "_answer_index",
+             "_answer_index_key", "user_index")
+
+
+def test_recommender_declares_its_run_state_and_refuses_before_the_library(no_library):
+    """A fresh Recommender reads None from every state attribute, and with the served sets in place but no run every
+    live operation refuses with 'has not run' and every call that serves from the live lists with 'no live lists' --
+    before the library is loaded and before any user similarity is computed."""
+    import recommender as R
+    from helpers import GOLDEN, main_py_inputs
+    fresh = R.Recommender()
+    assert all(getattr(fresh, name, "absent") is None for name in RUN_STATE)
+    rec = R.Recommender()
+    rec.verbose = False
+    rec.init(*main_py_inputs(rec, os.path.join(GOLDEN, "cfg2")))
+
+    def no_similarities():
+        raise AssertionError("computed user similarities")
+    rec.compute_userSimilarities = no_similarities
+    q, row = rec.queries[:2], [["x"] * len(rec.datasetFeatures)]
+    w = [[0.6, 0.4, 60]]
+    not_run = [lambda: rec.add_queries(q), lambda: rec.remove_queries([0]), lambda: rec.replace_queries([0, 1], q),
+               lambda: rec.add_rows(row), lambda: rec.remove_rows([0]), lambda: rec.set_list_lengths(query_K=2),
+               lambda: rec.similar_queries(q),
+               lambda: rec.add_queries(q, update_lists=True), lambda: rec.remove_queries([0], update_lists=True)]
+    for call in not_run:
+        with pytest.raises(ValueError, match="has not run"):
+            call()
+    no_lists = [lambda: rec.recommend_users([0], 5), lambda: rec.recommend_users_diverse([0], 5, 1000),
+                lambda: rec.predict_users([0]), lambda: rec.recommend_queries([0], 5), lambda: rec.predict_queries([0]),
+                lambda: rec.query_utility(), lambda: rec.list_redundancy({0: {"indexes": np.array([1, 2])}}),
+                lambda: rec.list_fidelity(), lambda: rec.edge_overlaps(), lambda: rec.evaluate(),
+                lambda: rec.evaluate(holdout=True), lambda: rec.evaluate_ranking(5, 50), lambda: rec.tune(w),
+                lambda: rec.tune(w, holdout=False), lambda: rec.tune_ranking(5, 50, w),
+                lambda: rec.tune_diversity(5, 50, [(0, 1001)]), lambda: rec.current_query_similarities()]
+    for call in no_lists:
+        with pytest.raises(ValueError, match="no live lists"):
+            call()
+    assert all(getattr(rec, name) is None for name in RUN_STATE if name != "_answer_index_key")
+    assert rec._answer_index_key is None
+
+
+def test_one_integer_check_behind_every_k(no_library):
+    """k = 0, True and 2.5 get the same message, the one format string's, from every door (a sample of 0 is valid: -1
+    stands in for it there)"""
+    import importlib
+    import torch
+    import qrlsh
+    from qrlsh import _args, fidelity, ranking, recommend as rc
+    from qrlsh.index import QueryIndex, MAX_K as INDEX_MAX_K
+    dv = importlib.import_module("qrlsh.diversify")
+    r = np.zeros((2, 3), dtype=np.int32)
+    e = np.zeros(0, dtype=np.int32)
+    qi = QueryIndex.__new__(QueryIndex)       # built without touching a device
+    qi.sig, qi.n, qi.P, qi.b, qi.r, qi.K, qi.table = torch.zeros((5, 12), dtype=torch.int32), 5, 12, 3, 4, 3, None
+    doors = [("k", 1, rc.MAX_K, lambda k: qrlsh.top_k(r, r, k)),
+             ("k", 1, rc.MAX_K, lambda k: qrlsh.for_users(r, e, e, e, {}, [0], k)),
+             ("k", 1, rc.MAX_K, lambda k: ranking.check_arguments(k, 1)),
+             ("k", 1, dv.MAX_POOL, lambda k: dv._check_rule(k, 0, 1001)),
+             ("sample", 0, 2**31 - 1, lambda k: fidelity.sample_positions(10, k)),
+             ("K", 1, INDEX_MAX_K, lambda k: qi.neighbours(torch.zeros((2, 12), dtype=torch.int32), K=k))]
+    for name, lo, hi, door in doors:
+        for bad in (0, True, 2.5) if lo else (-1, True, 2.5):
+            with pytest.raises(ValueError) as err:
+                door(bad)
+            assert str(err.value) == _args.INT_IN_TEXT % (name, lo, hi, bad), (name, bad)
