@@ -16,12 +16,14 @@ import torch
 
 from . import _lib
 from . import ops
+from . import predict, ranking, recommend
 from ._args import _int_in
+from ._inputs import WORKSPACE_BUDGET, blocks, coo_triple, ids32, int_array, like_matrix, lists_csr, on_device
+from ._inputs import or_flags, raise_flags, request_blocks, select_ids
 from .ops import _ptr, _stream
 
 MAX_POOL = _lib.DIVERSIFY_MAX_POOL
 MAX_PENALTY = _lib.DIVERSIFY_MAX_PENALTY
-WORKSPACE_BUDGET = 1 << 30   # bytes of workspace per library call; more requests are served in row blocks
 
 _FLAG_TEXT = ((1, "a query's neighbour index is outside [0, %(nq)d)"),
               (2, "a candidate column is outside [0, %(nq)d)"),
@@ -40,21 +42,6 @@ def _check_rule(k, penalty, max_sim):
             _int_in(max_sim, "max_sim", 0, 1001))
 
 
-def _int_array(x, ndim, name):
-    """an integer tensor / array of `ndim` dimensions (nothing is uploaded)"""
-    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-    if t.dim() != ndim or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise ValueError("%s must be a %d-D integer array, got shape %s %s" % (name, ndim, tuple(t.shape), t.dtype))
-    return t
-
-
-def _coo(q_src, q_dst, q_milli):
-    coo = [_int_array(x, 1, n) for n, x in (("q_src", q_src), ("q_dst", q_dst), ("q_milli", q_milli))]
-    if not coo[0].numel() == coo[1].numel() == coo[2].numel():
-        raise ValueError("q_src, q_dst and q_milli differ in length")
-    return coo
-
-
 def _i32(t, device):
     return t.to(device=device, dtype=torch.int32).contiguous()
 
@@ -64,18 +51,12 @@ def _max_row(q_off):
     return int((q_off[1:] - q_off[:-1]).max().item()) if q_off.numel() > 1 else 0
 
 
-def _block(lib, m, n, max_row, device):
-    """requests per library call under WORKSPACE_BUDGET, and the workspace for them"""
-    blk = m
-    while blk > 1 and int(lib.qrlsh_diversify_workspace_bytes(blk, n, max_row)) > WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    return blk, ops._ws(lib.qrlsh_diversify_workspace_bytes(blk, n, max_row), device)
-
-
-def _raise_flags(word, nq):
-    for bit, text in _FLAG_TEXT:
-        if word & bit:
-            raise ValueError(text % {"nq": nq})
+def _block(lib, m, n, max_row, device, ids=None, full=None):
+    """requests per library call under WORKSPACE_BUDGET, the workspace for them, and request_blocks' ids"""
+    def need(blk):
+        return int(lib.qrlsh_diversify_workspace_bytes(blk, n, max_row))
+    blk, ids = request_blocks(m, need, WORKSPACE_BUDGET, ids=ids, full=full, device=device)
+    return blk, ops._ws(need(blk), device), ids
 
 
 def _rerank(ci, cv, av, csr, nq, k, penalty, max_sim, max_row, device):
@@ -88,20 +69,16 @@ def _rerank(ci, cv, av, csr, nq, k, penalty, max_sim, max_row, device):
     count = torch.empty((m,), dtype=torch.int32, device=device)
     if m == 0:
         return idx, val, red, count
-    blk, ws = _block(lib, m, n, max_row, device)
-    starts = range(0, m, blk)
-    flags = torch.zeros((len(starts),), dtype=torch.int32, device=device)
+    blk, ws, _ = _block(lib, m, n, max_row, device)
+    parts = blocks(m, blk)
+    flags = torch.zeros((len(parts),), dtype=torch.int32, device=device)
     st = _stream()
-    for b, i0 in enumerate(starts):
-        i1 = min(m, i0 + blk)
+    for b, i0, i1 in parts:
         _lib.check(lib.qrlsh_diversify(_ptr(ci[i0:i1]), _ptr(cv[i0:i1]), _ptr(av[i0:i1]), i1 - i0, n, nq, _ptr(csr[0]),
                                        _ptr(csr[1]), _ptr(csr[2]), k, penalty, max_sim, _ptr(idx[i0:i1]),
                                        _ptr(val[i0:i1]), _ptr(red[i0:i1]), _ptr(count[i0:i1]), _ptr(flags[b:b + 1]),
                                        _ptr(ws), ws.numel(), st))
-    word = 0
-    for w in flags.cpu().tolist():   # the one read-back of the call
-        word |= int(w)
-    _raise_flags(word, nq)
+    raise_flags(or_flags(flags.cpu()), _FLAG_TEXT, nq=nq)   # the one read-back of the call
     return idx, val, red, count
 
 
@@ -119,17 +96,16 @@ def diversify(cand_idx, cand_val, avail, q_src, q_dst, q_milli, nq, k, penalty=0
     library's flags, read back once; nothing is returned then)."""
     k, penalty, max_sim = _check_rule(k, penalty, max_sim)
     nq = _int_in(nq, "nq", 0, 2**31 - 1)
-    ci, cv, av = _int_array(cand_idx, 2, "cand_idx"), _int_array(cand_val, 2, "cand_val"), _int_array(avail, 1, "avail")
+    ci, cv, av = int_array(cand_idx, 2, "cand_idx"), int_array(cand_val, 2, "cand_val"), int_array(avail, 1, "avail")
     if tuple(ci.shape) != tuple(cv.shape) or av.shape[0] != ci.shape[0]:
         raise ValueError("cand_idx %s, cand_val %s and avail %s do not belong together"
                          % (tuple(ci.shape), tuple(cv.shape), tuple(av.shape)))
     n = int(ci.shape[1])
     if not k <= n <= MAX_POOL:
         raise ValueError("k <= N <= %d is required, got k=%d N=%d" % (MAX_POOL, k, n))
-    coo = _coo(q_src, q_dst, q_milli)
-    from . import predict
+    coo = coo_triple(q_src, q_dst, q_milli)
     _lib.load()
-    csr = predict.lists_csr(coo, nq, device)
+    csr = lists_csr(coo, nq, device)
     return _rerank(_i32(ci, device), _i32(cv, device), _i32(av, device), csr, nq, k, penalty, max_sim,
                    _max_row(csr[0]), device)
 
@@ -153,7 +129,6 @@ def for_users_diverse(ratings, q_src, q_dst, q_milli, user_sims, users, k, pool=
     and diversify take them.
     -> (idx, val, red, count, avail) device tensors: diversify's four, and for_users' avail (the eligible cells).
     Raises what for_users and diversify raise; every check that needs no device precedes any upload."""
-    from . import predict, recommend
     k, penalty, max_sim = _check_rule(k, penalty, max_sim)
     pool = _check_pool(k, pool)
     recommend._check_select_args(pool, lo, slices)
@@ -188,26 +163,24 @@ def list_redundancy(idx, q_src, q_dst, q_milli, nq, device="cuda"):
     Raises ValueError for a bad shape or nq (before anything is uploaded), and for a neighbour index or a column
     outside [0, nq) and a column twice in one list (through the library's flags)."""
     nq = _int_in(nq, "nq", 0, 2**31 - 1)
-    li = _int_array(idx, 2, "idx")
+    li = int_array(idx, 2, "idx")
     m, k = (int(d) for d in li.shape)
     if not 1 <= k <= MAX_POOL:
         raise ValueError("lists of 1..%d entries are served, got k=%d" % (MAX_POOL, k))
-    coo = _coo(q_src, q_dst, q_milli)
-    from . import predict
+    coo = coo_triple(q_src, q_dst, q_milli)
     lib = _lib.load()
-    csr = predict.lists_csr(coo, nq, device)
+    csr = lists_csr(coo, nq, device)
     li = _i32(li, device)
     out = torch.zeros((4 * m + 5,), dtype=torch.int64, device=device)   # [words m x 4][totals 4][flag]
     if m:
-        blk, ws = _block(lib, m, k, _max_row(csr[0]), device)
+        blk, ws, _ = _block(lib, m, k, _max_row(csr[0]), device)
         st = _stream()
-        for i0 in range(0, m, blk):
-            i1 = min(m, i0 + blk)
+        for _, i0, i1 in blocks(m, blk):
             _lib.check(lib.qrlsh_list_redundancy(_ptr(li[i0:i1]), i1 - i0, k, nq, _ptr(csr[0]), _ptr(csr[1]),
                                                  _ptr(csr[2]), _ptr(out[4 * i0:]), _ptr(out[4 * m:]),
                                                  _ptr(out[4 * m + 4:]), _ptr(ws), ws.numel(), st))
     host = out.cpu().numpy()
-    _raise_flags(int(host[4 * m + 4]), nq)
+    raise_flags(int(host[4 * m + 4]), _FLAG_TEXT, nq=nq)
     return Redundancy(host[:4 * m].reshape(m, 4).copy(), host[4 * m:4 * m + 4].copy())
 
 
@@ -309,7 +282,13 @@ def _grid(ci, cv, av, csr, nq, k, settings, max_row, device, scoring=None, want_
         lists.append(torch.empty((S, m), dtype=torch.int32, device=device))
     back = torch.zeros((S * GRID_TOTALS + 1,), dtype=torch.int64, device=device)   # [totals S x 24][flag: low half]
     if m:
-        blk, ws = _block(lib, m, n, max_row, device)
+        if scoring is None:
+            truth, users, relevant, gain, prefix, counts, nu = None, None, 1, None, None, None, 0
+        else:
+            truth, users, relevant, gain, prefix, counts = scoring
+            nu = int(truth.shape[0])
+        # without users request x is row x: of a later block still row i0 + x
+        blk, ws, users = _block(lib, m, n, max_row, device, users, None if scoring is None else m)
         widest = min(S, MAX_SETTINGS)
         whole = blk >= m
         tmp = None
@@ -318,18 +297,10 @@ def _grid(ci, cv, av, csr, nq, k, settings, max_row, device, scoring=None, want_
                    for w, dt, on in ((k, torch.int32, want_lists), (k, torch.int32, want_lists),
                                      (k, torch.int32, want_lists), (1, torch.int32, want_lists),
                                      (GRID_LINE, torch.int64, want_per_request))]
-        if scoring is None:
-            truth, users, relevant, gain, prefix, counts, nu = None, None, 1, None, None, None, 0
-        else:
-            truth, users, relevant, gain, prefix, counts = scoring
-            nu = int(truth.shape[0])
-            if users is None and not whole:   # request x of a later block is still row i0 + x
-                users = torch.arange(m, dtype=torch.int32, device=device)
         st = _stream()
         for c0 in range(0, S, MAX_SETTINGS):
             c1 = min(S, c0 + MAX_SETTINGS)
-            for i0 in range(0, m, blk):
-                i1 = min(m, i0 + blk)
+            for _, i0, i1 in blocks(m, blk):
                 if whole:
                     outs = [t[c0:c1] for t in lists] if want_lists else [None] * 4
                     outs.append(per[c0:c1] if want_per_request else None)
@@ -349,13 +320,12 @@ def _grid(ci, cv, av, csr, nq, k, settings, max_row, device, scoring=None, want_
                             shape = (c1 - c0, i1 - i0) + tuple(dst.shape[2:])
                             dst[c0:c1, i0:i1] = src[:int(np.prod(shape))].view(shape)
     host = back.cpu().numpy()   # the flags together with the totals
-    _raise_flags(int(host[S * GRID_TOTALS]), nq)
+    raise_flags(int(host[S * GRID_TOTALS]), _FLAG_TEXT, nq=nq)
     return DiversityGrid(settings, host[:S * GRID_TOTALS].copy(), per, *(lists or [None] * 4))
 
 
 def _scoring_checks(k, m, relevant, gains):
     """the scoring arguments that need no device -> (relevant, gain, gain_prefix) host values"""
-    from . import ranking
     if isinstance(relevant, bool) or not isinstance(relevant, (int, np.integer)) or not 1 <= int(relevant) < 2**31:
         raise ValueError("relevant must be an int32 >= 1, got %r" % (relevant,))
     gain, prefix = ranking._gain_tables(gains, k, m)
@@ -382,20 +352,20 @@ def diversify_grid(cand_idx, cand_val, avail, q_src, q_dst, q_milli, nq, k, sett
     k = _check_rule(k, 0, 1001)[0]
     settings = _check_settings(settings)
     nq = _int_in(nq, "nq", 0, 2**31 - 1)
-    ci, cv, av = _int_array(cand_idx, 2, "cand_idx"), _int_array(cand_val, 2, "cand_val"), _int_array(avail, 1, "avail")
+    ci, cv, av = int_array(cand_idx, 2, "cand_idx"), int_array(cand_val, 2, "cand_val"), int_array(avail, 1, "avail")
     if tuple(ci.shape) != tuple(cv.shape) or av.shape[0] != ci.shape[0]:
         raise ValueError("cand_idx %s, cand_val %s and avail %s do not belong together"
                          % (tuple(ci.shape), tuple(cv.shape), tuple(av.shape)))
     m, n = (int(d) for d in ci.shape)
     if not k <= n <= MAX_POOL:
         raise ValueError("k <= N <= %d is required, got k=%d N=%d" % (MAX_POOL, k, n))
-    coo = _coo(q_src, q_dst, q_milli)
+    coo = coo_triple(q_src, q_dst, q_milli)
     scoring = None
     if truth is None:
         if users is not None or request_counts is not None or gains is not None or relevant is not None:
             raise ValueError("users, relevant, gains and request_counts need a truth")
     else:
-        tt = _int_array(truth, 2, "truth")
+        tt = int_array(truth, 2, "truth")
         nu = int(tt.shape[0])
         if int(tt.shape[1]) != nq:
             raise ValueError("truth has %d columns, nq = %d" % (int(tt.shape[1]), nq))
@@ -405,25 +375,21 @@ def diversify_grid(cand_idx, cand_val, avail, q_src, q_dst, q_milli, nq, k, sett
                 raise ValueError("%d requests but %d rows of truth: pass users" % (m, nu))
             ut = None
         else:
-            ut = _int_array(users, 1, "users")
-            if ut.numel() != m:
-                raise ValueError("users must name one row per request (%d), got %d" % (m, ut.numel()))
-            if not ut.is_cuda and m and (int(ut.min()) < 0 or int(ut.max()) >= nu):
-                raise ValueError("user id outside [0, %d)" % nu)
+            named, ut, _ = select_ids(users, nu, "user", "users", host_tensors=True)
+            if named != m:
+                raise ValueError("users must name one row per request (%d), got %d" % (m, named))
         rc = None
         if request_counts is not None:
-            rc = _int_array(request_counts, 2, "request_counts")
+            rc = int_array(request_counts, 2, "request_counts")
             if tuple(rc.shape) != (m, 2):
                 raise ValueError("request_counts must have shape (%d, 2), got %s" % (m, tuple(rc.shape)))
         scoring = (tt, ut, relevant, gain, prefix, rc)
-    from . import predict
     _lib.load()
-    csr = predict.lists_csr(coo, nq, device)
+    csr = lists_csr(coo, nq, device)
     if scoring is not None:
         tt, ut, relevant, gain, prefix, rc = scoring
-        if ut is not None:   # ids past int32 must stay out of range, not wrap into it
-            ut = ut.to(device=device, dtype=torch.int64).clamp(-1, nu).to(torch.int32).contiguous()
-        scoring = (_i32(tt, device), ut, relevant, torch.from_numpy(gain).to(device), torch.from_numpy(prefix).to(device),
+        scoring = (_i32(tt, device), None if ut is None else ids32(ut, nu, device), relevant,
+                   torch.from_numpy(gain).to(device), torch.from_numpy(prefix).to(device),
                    None if rc is None else rc.to(device=device, dtype=torch.int64).contiguous())
     return _grid(_i32(ci, device), _i32(cv, device), _i32(av, device), csr, nq, k, settings, _max_row(csr[0]), device,
                  scoring, want_per_request, want_lists)
@@ -440,24 +406,18 @@ def evaluate_diversity(train, truth, q_src, q_dst, q_milli, user_sims, k, releva
     settings, want_per_request, want_lists: as diversify_grid takes them.  Setting (0, 1001) gives evaluate_ranking(...,
     k)'s figures.  -> DiversityGrid.  Raises what evaluate_ranking and diversify_grid raise; every check that needs no
     device precedes any upload."""
-    from . import predict, ranking
-    from .recommend import _matrix, _on_device
     k = _check_rule(k, 0, 1001)[0]
     pool = _check_pool(k, pool)
     settings = _check_settings(settings)
     ranking.check_arguments(pool, relevant, "all", lo, slices)
     a = predict.ServeInputs(train, q_src, q_dst, q_milli, user_sims, users, sum_order)
-    truth = _matrix(truth, "truth")
-    if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
-        raise ValueError("truth has shape %s, train %s" % (tuple(truth.shape), (a.nu, a.nq)))
+    truth = like_matrix(truth, "truth", (a.nu, a.nq), "train")
     relevant, gain, prefix = _scoring_checks(k, a.m, relevant, gains)
     pool_gains = ranking._gain_tables(None, pool, a.m)
-    weights = tuple(d if w is None else w for w, d in ((query_weight, predict.QUERY_WEIGHT),
-                                                       (user_weight, predict.USER_WEIGHT),
-                                                       (default_mean, predict.DEFAULT_MEAN)))
+    weights = predict.weights(query_weight, user_weight, default_mean)
     _lib.load()
     a.upload(device)
-    t = _on_device(truth, device)
+    t = on_device(truth, device)
     ev = ranking._score(a, t, pool, relevant, "all", pool_gains[0], pool_gains[1], lo, slices, weights)
     dev = a.r.device
     scoring = (t, a.ut, relevant, torch.from_numpy(gain).to(dev), torch.from_numpy(prefix).to(dev),

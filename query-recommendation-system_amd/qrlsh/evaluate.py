@@ -17,8 +17,9 @@ import torch
 
 from . import _lib
 from . import ops
+from ._inputs import ServeInputs, ids32, int_array, like_matrix, matrix, on_device
 from .ops import _ptr, _stream
-from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT, ServeInputs
+from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT
 
 BRANCHES = (("query", 0), ("user", 4), ("both", 8))   # the three non-zero branches of the blend -> first word
 
@@ -92,14 +93,13 @@ def holdout(ratings, fraction, seed=0, device="cuda"):
     cells set to 0 -- about `fraction` of them, chosen by the sample rule (is_kept) under `seed`.  Out of place: the
     input is not modified.  -> (int32 device tensor (nu, nq), the number of cells held out).
     ValueError for a fraction outside [0, 1]."""
-    from .recommend import _matrix, _on_device
     keep, seed = keep_word(fraction), _seed_word(seed)
-    a = _matrix(ratings, "ratings")
+    a = matrix(ratings, "ratings")
     nu, nq = (int(d) for d in a.shape)
     if nu >= 2**31 or nq >= 2**31:
         raise ValueError("at most 2^31 - 1 rows and columns")
     lib = _lib.load()
-    r = _on_device(a, device)
+    r = on_device(a, device)
     out = torch.empty_like(r)
     count = torch.zeros((1,), dtype=torch.int64, device=r.device)
     _lib.check(lib.qrlsh_ratings_holdout(_ptr(r), nu, nq, seed, keep, _ptr(out), _ptr(count), _stream()))
@@ -118,18 +118,15 @@ def evaluate(ratings, q_src, q_dst, q_milli, user_sims, truth=None, fraction=1.0
     -> Evaluation (per_user on the device; one read-back: the totals and the flags).
     ValueError for a fraction outside [0, 1], a truth of another shape, a bad sum_order, a list longer than 64 and a
     neighbour index outside [0, nq)."""
-    from .recommend import _matrix, _on_device
     keep, seed = keep_word(fraction), _seed_word(seed)
     a = ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, None, sum_order)
     if truth is not None:
-        truth = _matrix(truth, "truth")
-        if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
-            raise ValueError("truth has shape %s, ratings %s" % (tuple(truth.shape), (a.nu, a.nq)))
+        truth = like_matrix(truth, "truth", (a.nu, a.nq), "ratings")
     if a.nu >= 2**31:
         raise ValueError("at most 2^31 - 1 users")
     lib = _lib.load()
     a.upload(device)
-    t = a.r if truth is None else _on_device(truth, device)
+    t = a.r if truth is None else on_device(truth, device)
     dev = a.r.device
     per_user = torch.empty((a.nu, 16), dtype=torch.int64, device=dev)
     back = torch.zeros((17,), dtype=torch.int64, device=dev)    # [totals: 16][flags: the low half of word 16]
@@ -140,7 +137,7 @@ def evaluate(ratings, q_src, q_dst, q_milli, user_sims, truth=None, fraction=1.0
                                   float(default_mean), a.sum_order, seed, keep, _ptr(per_user), _ptr(back), _ptr(pred),
                                   _ptr(back[16:]), _ptr(ws), ws.numel(), _stream()))
     host = back.cpu().numpy()
-    a.raise_flags(torch.from_numpy(host[16:]))
+    a.raise_flags(host[16:])
     return Evaluation(host[:16], per_user=per_user, predictions=pred)
 
 
@@ -154,14 +151,9 @@ def evaluate_cells(ratings, q_src, q_dst, q_milli, user_sims, users, queries, va
     ValueError as evaluate raises it, and for a user or query id outside the matrix (host ids before anything is
     uploaded; device ids through the library's flag)."""
     a = ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, users if users is not None else [], sum_order)
-    cols = []
-    for name, x in (("queries", queries), ("values", values)):
-        c = x if isinstance(x, torch.Tensor) else torch.as_tensor(np.asarray(x))
-        if c.dim() != 1 or (c.numel() and (c.dtype.is_floating_point or c.dtype.is_complex or c.dtype == torch.bool)):
-            raise ValueError("%s must be a 1-D integer sequence" % name)
-        if c.numel() != a.m:
-            raise ValueError("users, queries and values differ in length")
-        cols.append(c)
+    cols = [int_array(queries, 1, "queries"), int_array(values, 1, "values")]
+    if not cols[0].numel() == cols[1].numel() == a.m:
+        raise ValueError("users, queries and values differ in length")
     if not cols[0].is_cuda and cols[0].numel() and (int(cols[0].min()) < 0 or int(cols[0].max()) >= a.nq):
         raise ValueError("query id outside [0, %d)" % a.nq)
     if a.nu >= 2**31:
@@ -169,7 +161,7 @@ def evaluate_cells(ratings, q_src, q_dst, q_milli, user_sims, users, queries, va
     lib = _lib.load()
     a.upload(device)
     dev = a.r.device
-    cq = cols[0].to(device=dev, dtype=torch.int64).clamp(-1, a.nq).to(torch.int32).contiguous()
+    cq = ids32(cols[0], a.nq, dev)
     cv = cols[1].to(device=dev, dtype=torch.int32).contiguous()
     back = torch.zeros((17,), dtype=torch.int64, device=dev)
     pred = torch.empty((a.m,), dtype=torch.int32, device=dev) if want_predictions else None
@@ -180,5 +172,5 @@ def evaluate_cells(ratings, q_src, q_dst, q_milli, user_sims, users, queries, va
     host = back.cpu().numpy()
     if int(host[16]) & 4 and a.m and bool(((cq < 0) | (cq >= a.nq)).any().item()):
         raise ValueError("query id outside [0, %d)" % a.nq)
-    a.raise_flags(torch.from_numpy(host[16:]))
+    a.raise_flags(host[16:])
     return Evaluation(host[:16], predictions=pred)

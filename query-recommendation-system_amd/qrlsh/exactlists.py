@@ -11,11 +11,11 @@ import torch
 from . import _lib
 from . import ops
 from ._args import _int_in
-from .fidelity import MAX_D, MAX_K, _csr, _ids32, _int_array
+from ._inputs import MAX_REQUESTS, WORKSPACE_BUDGET, answer_csr, blocks, ids32, or_flags, raise_flags
+from ._inputs import request_blocks, select_ids
 from .ops import _ptr, _stream
-
-WORKSPACE_BUDGET = 1 << 30   # bytes of partial lists per library call; more requests run as successive calls
-MAX_REQUESTS = 1 << 24       # requests per library call
+MAX_K = _lib.FIDELITY_MAX_K
+MAX_D = _lib.FIDELITY_MAX_D
 
 _FLAG_TEXT = ((4, "a chosen query is outside [0, %(nq)d)"),
               (8, "an answer-set row id is outside [0, %(D)d)"))
@@ -84,46 +84,32 @@ def exact_neighbours(offsets, rows, D, K, queries=None, slices=0, device="cuda")
     K = _int_in(K, "K", 1, MAX_K)
     D = _int_in(D, "D", 0, MAX_D)
     slices = _int_in(slices, "slices", 0, 256)
-    off, r = _csr(offsets, rows)
+    off, r = answer_csr(offsets, rows)
     nq = int(off.numel()) - 1
-    ids = None
-    if queries is not None:
-        ids = _int_array(queries, "queries")
-        if not ids.is_cuda and ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= nq):
-            raise ValueError("query id outside [0, %d)" % nq)
-    m = nq if ids is None else int(ids.numel())
+    m, ids, _ = select_ids(queries, nq, "query", "queries", host_tensors=True)
     if m and not nq:
         raise ValueError("query id outside [0, 0)")
     lib = _lib.load()
     off = off.to(device=device, dtype=torch.int64).contiguous()
     r = r.to(device=device, dtype=torch.int32).contiguous()
-    ids = torch.arange(nq, dtype=torch.int32, device=device) if ids is None else _ids32(ids, nq, device)
+    ids = torch.arange(nq, dtype=torch.int32, device=device) if ids is None else ids32(ids, nq, device)
     dst = torch.full((m, K), -1, dtype=torch.int32, device=device)       # the library writes nothing when nq is 0
     inter = torch.zeros((2, m, K), dtype=torch.int32, device=device)
     counts = torch.zeros((m, 2), dtype=torch.int32, device=device)
     G = max(1, int(lib.qrlsh_list_fidelity_group(D)))
-    blk = min(max(m, 1), MAX_REQUESTS)
 
     def scratch_bytes(n):
         return n * int(lib.qrlsh_exact_neighbours_slices(nq, n, D, slices)) * K * 3 * 4
-    while blk > G and scratch_bytes(blk) > WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    blk = (blk + G - 1) // G * G          # whole groups per call
-    starts = range(0, m, blk)
-    flags = torch.zeros((max(len(starts), 1),), dtype=torch.int32, device=device)
+    blk, _ = request_blocks(m, scratch_bytes, WORKSPACE_BUDGET, group=G, cap=MAX_REQUESTS)
+    parts = blocks(m, blk)
+    flags = torch.zeros((max(len(parts), 1),), dtype=torch.int32, device=device)
     # a shorter last block can run more slices than the full ones
-    scratch = ops._ws(max(scratch_bytes(min(m, i0 + blk) - i0) for i0 in starts), device) if m else None
+    scratch = ops._ws(max(scratch_bytes(i1 - i0) for _, i0, i1 in parts), device) if m else None
     st = _stream()
-    for b, i0 in enumerate(starts):
-        i1 = min(m, i0 + blk)
+    for b, i0, i1 in parts:
         _lib.check(lib.qrlsh_exact_neighbours(_ptr(off), _ptr(r), nq, D, _ptr(ids[i0:i1]), i1 - i0, K, slices,
                                               _ptr(dst[i0:i1]), _ptr(inter[0, i0:i1]), _ptr(inter[1, i0:i1]),
                                               _ptr(counts[i0:i1]), _ptr(flags[b:]), _ptr(scratch),
                                               scratch_bytes(i1 - i0), st))
-    word = 0
-    for w in flags.cpu().tolist():
-        word |= int(w)
-    for bit, text in _FLAG_TEXT:
-        if word & bit:
-            raise ValueError(text % {"nq": nq, "D": D})
+    raise_flags(or_flags(flags.cpu()), _FLAG_TEXT, nq=nq, D=D)
     return ExactLists(K, ids, dst, inter[0], inter[1], counts[:, 0].contiguous(), counts[:, 1].contiguous())

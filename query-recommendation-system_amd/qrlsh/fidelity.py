@@ -11,44 +11,18 @@ import torch
 
 from . import _lib
 from ._args import _int_in
+from ._inputs import MAX_REQUESTS, WORKSPACE_BUDGET, answer_csr, blocks, coo_triple, ids32, int_array, lists_csr
+from ._inputs import or_flags, raise_flags, request_blocks, select_ids
 from .ops import _ptr, _stream
 
 MAX_K = _lib.FIDELITY_MAX_K
 MAX_D = _lib.FIDELITY_MAX_D
-WORKSPACE_BUDGET = 1 << 30   # bytes of per-request output per library call; more requests run as successive calls
-MAX_REQUESTS = 1 << 24       # requests per library call
 _REQUEST_BYTES = 4 * MAX_K * 4 + 8 * 8
 
 _FLAG_TEXT = ((1, "a chosen query's list row is longer than %d entries" % MAX_K),
               (2, "a query's neighbour index is outside [0, %(nq)d)"),
               (4, "a chosen query is outside [0, %(nq)d)"),
               (8, "an answer-set row id is outside [0, %(D)d)"))
-
-
-def _int_array(x, name):
-    """a 1-D integer tensor / array (nothing is uploaded)"""
-    if not isinstance(x, torch.Tensor):
-        x = np.asarray(x)
-        if x.ndim == 1 and x.size == 0:      # an empty sequence has no dtype of its own
-            x = x.astype(np.int64)
-    t = x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
-    if t.dim() != 1 or t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
-        raise ValueError("%s must be a 1-D integer array, got shape %s %s" % (name, tuple(t.shape), t.dtype))
-    return t
-
-
-def _csr(offsets, rows):
-    off, r = _int_array(offsets, "offsets"), _int_array(rows, "rows")
-    if off.numel() < 1:
-        raise ValueError("offsets must hold nq + 1 entries")
-    if off.numel() - 1 >= 2**31:
-        raise ValueError("at most 2^31 - 1 queries")
-    return off, r
-
-
-def _ids32(t, bound, device):
-    """ids as int32 on the device; ids past int32 stay out of range instead of wrapping into it"""
-    return t.to(device=device, dtype=torch.int64).clamp(-1, bound).to(torch.int32).contiguous()
 
 
 def group_size(D):
@@ -119,15 +93,15 @@ def edge_overlaps(offsets, rows, src, dst, device="cuda"):
     inter / (|A| + |B| - inter).  src == dst gives |A|; two empty sets give 0.  Tensors are used where they are.
     Raises ValueError for a bad shape (before anything is uploaded) and for an edge end outside [0, nq) (through the
     library's flag, read back once; nothing is returned then)."""
-    off, r = _csr(offsets, rows)
-    s, d = _int_array(src, "src"), _int_array(dst, "dst")
+    off, r = answer_csr(offsets, rows)
+    s, d = int_array(src, 1, "src"), int_array(dst, 1, "dst")
     if s.numel() != d.numel():
         raise ValueError("src and dst differ in length")
     nq, n = int(off.numel()) - 1, int(s.numel())
     lib = _lib.load()
     off = off.to(device=device, dtype=torch.int64).contiguous()
     r = r.to(device=device, dtype=torch.int32).contiguous()
-    s, d = _ids32(s, nq, device), _ids32(d, nq, device)
+    s, d = ids32(s, nq, device), ids32(d, nq, device)
     out = torch.empty((n,), dtype=torch.int32, device=device)
     flag = torch.zeros((1,), dtype=torch.int32, device=device)
     _lib.check(lib.qrlsh_edge_overlaps(_ptr(off), _ptr(r), nq, _ptr(s), _ptr(d), n, _ptr(out), _ptr(flag), _stream()))
@@ -151,56 +125,37 @@ def list_fidelity(offsets, rows, D, q_src, q_dst, q_milli, nq, K, queries=None, 
     nq = _int_in(nq, "nq", 0, 2**31 - 1)
     D = _int_in(D, "D", 0, MAX_D)
     slices = _int_in(slices, "slices", 0, 256)
-    off, r = _csr(offsets, rows)
+    off, r = answer_csr(offsets, rows)
     if off.numel() != nq + 1:
         raise ValueError("offsets holds %d entries, nq + 1 = %d" % (off.numel(), nq + 1))
-    coo = [_int_array(x, n) for n, x in (("q_src", q_src), ("q_dst", q_dst), ("q_milli", q_milli))]
-    if not coo[0].numel() == coo[1].numel() == coo[2].numel():
-        raise ValueError("q_src, q_dst and q_milli differ in length")
-    ids = chosen = None
-    if queries is not None:
-        ids = _int_array(queries, "queries")
-        if not ids.is_cuda:
-            if ids.numel() and (int(ids.min()) < 0 or int(ids.max()) >= nq):
-                raise ValueError("query id outside [0, %d)" % nq)
-            chosen = ids.numpy().astype(np.int64)
-    m = nq if ids is None else int(ids.numel())
-    from . import predict
+    coo = coo_triple(q_src, q_dst, q_milli)
+    m, chosen, vouched = select_ids(queries, nq, "query", "queries", host_tensors=True)
     lib = _lib.load()
     off = off.to(device=device, dtype=torch.int64).contiguous()
     r = r.to(device=device, dtype=torch.int32).contiguous()
-    q_off, q_idx, _ = predict.lists_csr(coo, nq, device)
-    if ids is not None:
-        ids = _ids32(ids, nq, device)
+    q_off, q_idx, _ = lists_csr(coo, nq, device)
     G = max(1, int(lib.qrlsh_list_fidelity_group(D)))
-    blk = min(max(m, 1), MAX_REQUESTS)
-    while blk > G and blk * _REQUEST_BYTES > WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    blk = (blk + G - 1) // G * G          # whole groups per call
-    if blk < m and ids is None:
-        ids = torch.arange(nq, dtype=torch.int32, device=device)
-    starts = range(0, m, blk)
+    blk, ids = request_blocks(m, lambda blk: blk * _REQUEST_BYTES, WORKSPACE_BUDGET,
+                              ids=None if chosen is None else ids32(chosen, nq, device), full=nq, device=device,
+                              group=G, cap=MAX_REQUESTS)
+    parts = blocks(m, blk)
     # one buffer, one read-back: [words m x 8][totals 8][one flag slot per call] int64, then the four entry arrays int32
-    head = m * 8 + 8 + len(starts)
+    head = m * 8 + 8 + len(parts)
     back = torch.zeros((head + 4 * m * (MAX_K // 2),), dtype=torch.int64, device=device)
     ent = back[head:].view(torch.int32).view(4, m, MAX_K)
     st = _stream()
-    for b, i0 in enumerate(starts):
-        i1 = min(m, i0 + blk)
+    for b, i0, i1 in parts:
         _lib.check(lib.qrlsh_list_fidelity(_ptr(off), _ptr(r), nq, D, _ptr(q_off), _ptr(q_idx),
                                            None if ids is None else _ptr(ids[i0:i1]), i1 - i0, K, slices,
                                            _ptr(ent[0, i0:i1]), _ptr(ent[1, i0:i1]), _ptr(ent[2, i0:i1]),
                                            _ptr(ent[3, i0:i1]), _ptr(back[i0 * 8:i1 * 8]), _ptr(back[m * 8:]),
                                            _ptr(back[m * 8 + 8 + b:]), st))
     host = back.cpu().numpy()
-    word = 0
-    for w in host[m * 8 + 8:head].tolist():
-        word |= int(w)
-    for bit, text in _FLAG_TEXT:
-        if word & bit:
-            raise ValueError(text % {"nq": nq, "D": D})
+    raise_flags(or_flags(host[m * 8 + 8:head]), _FLAG_TEXT, nq=nq, D=D)
     e = host[head:].view(np.int32).reshape(4, m, MAX_K)
-    if chosen is None:   # device ids: the flags have vouched for them
-        chosen = np.arange(m, dtype=np.int64) if queries is None else ids.cpu().numpy().astype(np.int64)
+    if chosen is None:
+        chosen = np.arange(m, dtype=np.int64)
+    elif vouched:   # device ids: the flags have vouched for them
+        chosen = ids.cpu().numpy().astype(np.int64)
     return ListFidelity(K, chosen, host[:m * 8].reshape(m, 8).copy(), host[m * 8:m * 8 + 8].copy(),
                         {"inter": e[0].copy(), "union": e[1].copy(), "better": e[2].copy(), "equal": e[3].copy()})

@@ -21,29 +21,22 @@ Queries change with replace / set (csrc/replace.hip): chosen ids take new rows a
 their old records and gain the new ones where (mix bits, id) puts them, and held lists are kept exact on the way.
 
 Everything runs on the device; the indexed data never leaves it."""
-import numpy as np
 import torch
 
 from . import _lib, ops
 from ._args import _int_in
+from ._inputs import int_array, matrix, on_device, sum_order_code
 from .pipeline import max_candidates
 from .predict import QUERY_WEIGHT, USER_WEIGHT, DEFAULT_MEAN
+from .recommend import top_k
 
 MAX_K = _lib.INDEX_MAX_K
-SUM_ORDERS = {"pairwise": _lib.SUM_PAIRWISE, "sequential": _lib.SUM_SEQUENTIAL}
 
 
 def _ids_arg(ids, dev):
     """the ids of remove() / replace(): a tensor or array of integers (floats and bools: ValueError) -> flat int64
     tensor on dev"""
-    if isinstance(ids, torch.Tensor):
-        if ids.dtype.is_floating_point or ids.dtype == torch.bool:
-            raise ValueError("ids must be integers")
-        return ids.reshape(-1).to(dev, torch.int64)
-    a = np.asarray(ids).reshape(-1)
-    if a.size and not np.issubdtype(a.dtype, np.integer):
-        raise ValueError("ids must be integers")
-    return torch.from_numpy(a.astype(np.int64)).to(dev)
+    return int_array(ids, None, "ids").reshape(-1).to(dev, torch.int64)
 
 
 def _u32_bits(t):
@@ -118,6 +111,17 @@ class QueryIndex:
             if not ok:
                 raise ValueError("the lists must be ordered by src and name queries in [0, %d)" % self.n)
         return tuple(lists)
+
+    @property
+    def _probe_step(self):
+        """the queries of one probe call: the library takes m * b < 2^32 words per call"""
+        return max(1, (2**32 - 1) // self.b)
+
+    def _empty_lists(self, parts=3):
+        """the CSR lists of no probe row: zeros [1] int64 and `parts` empty int32 tensors"""
+        dev = self.sig.device
+        return (torch.zeros((1,), dtype=torch.int64, device=dev),) + tuple(
+            torch.empty((0,), dtype=torch.int32, device=dev) for _ in range(parts))
 
     @staticmethod
     def _K_rule(n):
@@ -200,7 +204,7 @@ class QueryIndex:
             raise ValueError("lists are kept for fewer than 2^31 queries")
         if m == 0:
             return n, 0
-        step = max(1, (2**32 - 1) // self.b)      # the probe of an update takes m * b < 2^32 words per call
+        step = self._probe_step
         if update_lists and m > step:
             for q0 in range(0, m, step):
                 q1 = min(m, q0 + step)
@@ -306,7 +310,7 @@ class QueryIndex:
         if bool(((t[0] < 0) | (t[-1] >= n) | (t[1:] == t[:-1]).any()).item()):
             raise ValueError("ids must be distinct and lie in [0, %d)" % n)
         sig, norm2, keys = sig[order].contiguous(), norm2[order].contiguous(), keys[:, order].contiguous()
-        step = max(1, (2**32 - 1) // self.b)      # the probe of an update takes m * b < 2^32 words per call
+        step = self._probe_step
         if update_lists and m > step:             # successive replacements give the same lists
             self._replace_check_lists(t)
             picked = 0
@@ -351,15 +355,13 @@ class QueryIndex:
         """probe(q0, q1) -> (off, idx, milli, ...) of probe rows q0 .. q1-1, called for chunks of m * b < 2^32 words (what
         the library takes per call; the results do not depend on the split) -> the same for all m rows, offsets stitched.
         m = 0 gives the empty (off, idx, milli) of _probe_indexed; neighbours() answers m = 0 itself"""
-        step = max(1, (2**32 - 1) // self.b)
+        step = self._probe_step
         parts = [probe(q0, min(m, q0 + step)) for q0 in range(0, m, step)]
         if len(parts) == 1:
             return parts[0]
-        dev = self.sig.device
         if not parts:
-            e = torch.empty((0,), dtype=torch.int32, device=dev)
-            return torch.zeros((1,), dtype=torch.int64, device=dev), e, e
-        offs, base = [torch.zeros((1,), dtype=torch.int64, device=dev)], 0
+            return self._empty_lists(2)
+        offs, base = [torch.zeros((1,), dtype=torch.int64, device=self.sig.device)], 0
         for p in parts:
             offs.append(p[0][1:] + base)
             base += p[1].numel()
@@ -431,11 +433,8 @@ class QueryIndex:
         K = self.K if K is None else _int_in(K, "K", 1, MAX_K)
         first_id = _int_in(first_id, "first_id", 0, max(self.n, 0))
         m = _int_in(m, "m", 0, self.n - first_id)
-        dev = self.sig.device
         if m == 0:
-            z = torch.zeros((1,), dtype=torch.int64, device=dev)
-            e = torch.empty((0,), dtype=torch.int32, device=dev)
-            return z, e, e.clone(), e.clone()
+            return self._empty_lists()
         if m * self.b >= 2**32:
             raise ValueError("at most %d queries per call" % ((2**32 - 1) // self.b))
         sig, norm2, keys = self._probe_rows(self.sig[first_id:first_id + m], self.norm2[first_id:first_id + m].contiguous(),
@@ -457,11 +456,8 @@ class QueryIndex:
         K = self.K if K is None else _int_in(K, "K", 1, MAX_K)
         sig, norm2, keys = self._probe_rows(sig, norm2, keys)
         m = sig.shape[0]
-        dev = self.sig.device
         if m == 0:
-            z = torch.zeros((1,), dtype=torch.int64, device=dev)
-            e = torch.empty((0,), dtype=torch.int32, device=dev)
-            return z, e, e.clone(), e.clone()
+            return self._empty_lists()
         return self._chunked(m, lambda q0, q1: self._run(sig[q0:q1], norm2[q0:q1], keys[:, q0:q1].contiguous(), K)[0][:4])
 
     def candidates(self, sig, norm2=None, keys=None):
@@ -484,19 +480,8 @@ class QueryIndex:
                         user_weight=USER_WEIGHT, default_mean=DEFAULT_MEAN):
         """ratings: (nu, n) utility matrix of the indexed queries (0 = missing; array or tensor); (off, idx, milli):
         neighbours()' lists.  -> int32 device tensor [m, nu]: every user's predicted cell of each new query."""
-        if sum_order not in SUM_ORDERS:
-            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
-        if isinstance(ratings, torch.Tensor):
-            if ratings.dim() != 2 or ratings.dtype.is_floating_point or ratings.dtype == torch.bool:
-                raise ValueError("ratings must be a 2-D integer matrix")
-            r = ratings
-        else:
-            a = np.asarray(ratings.to_numpy() if hasattr(ratings, "to_numpy") else ratings)
-            if a.ndim != 2 or not np.issubdtype(a.dtype, np.integer):
-                raise ValueError("ratings must be a 2-D integer matrix")
-            if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
-                raise ValueError("ratings hold values outside int32")
-            r = a
+        sum_order = sum_order_code(sum_order)
+        r = matrix(ratings, "ratings")
         if r.shape[1] != self.n:
             raise ValueError("ratings have %d columns, the index %d queries" % (r.shape[1], self.n))
         if r.shape[0] > 65535 * 256:
@@ -505,19 +490,15 @@ class QueryIndex:
             if not isinstance(t, torch.Tensor) or t.dim() != 1:
                 raise ValueError("%s must be a 1-D device tensor (neighbours()' output)" % name)
         dev = self.sig.device
-        if not isinstance(r, torch.Tensor):
-            r = torch.from_numpy(np.ascontiguousarray(r, dtype=np.int32))
-        r = r.to(device=dev, dtype=torch.int32).contiguous()
-        return ops.predict_columns(r, off.to(dev, torch.int64).contiguous(), idx.to(dev, torch.int32).contiguous(),
-                                   milli.to(dev, torch.int32).contiguous(), query_weight, user_weight, default_mean,
-                                   SUM_ORDERS[sum_order])
+        return ops.predict_columns(on_device(r, dev), off.to(dev, torch.int64).contiguous(),
+                                   idx.to(dev, torch.int32).contiguous(), milli.to(dev, torch.int32).contiguous(),
+                                   query_weight, user_weight, default_mean, sum_order)
 
     @staticmethod
     def top_users(columns, k):
         """columns: predict_columns' [m, nu] output.  -> (users int32 [m, k], values int32 [m, k], avail int32 [m]): per
         new query the users with the largest non-zero predictions, value descending then user ascending (-1 / 0
         padding), and how many users have one (qrlsh_recommend_topk over the rows, nothing rated)."""
-        from .recommend import top_k
         if not isinstance(columns, torch.Tensor) or columns.dim() != 2:
             raise ValueError("columns must be predict_columns' 2-D device tensor")
         zeros = torch.zeros_like(columns, dtype=torch.int32)

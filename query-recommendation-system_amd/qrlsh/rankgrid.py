@@ -15,10 +15,11 @@ import torch
 
 from . import _lib
 from . import ops
-from .ops import _ptr, _stream
-from .predict import ServeInputs
-from .ranking import check_arguments, _gain_tables
+from . import recommend
 from . import tune
+from ._inputs import ServeInputs, blocks, like_matrix, on_device, or_flags, request_blocks
+from .ops import _ptr, _stream
+from .ranking import check_arguments, _gain_tables
 
 METRICS = ("ndcg", "precision", "recall", "hit_rate")   # best(): the highest
 
@@ -123,14 +124,10 @@ def evaluate_ranking_grid(train, truth, q_src, q_dst, q_milli, user_sims, k, rel
     ValueError, before anything is uploaded, for a bad k, relevant, gains, sum_order, cuts or weights, a truth of another
     shape and a host user id outside the matrix; through the library's flags for a list longer than 64, a neighbour index
     outside [0, nq) and a device user id outside [0, nu)."""
-    from . import recommend
-    from .recommend import _matrix, _on_device
     k = check_arguments(k, relevant, "heldout")
     qc, uc, w = tune._cuts(q_cuts, "q_cuts"), tune._cuts(u_cuts, "u_cuts"), tune._weights(weights)
     a = ServeInputs(train, q_src, q_dst, q_milli, user_sims, users, sum_order)
-    truth = _matrix(truth, "truth")
-    if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
-        raise ValueError("truth has shape %s, train %s" % (tuple(truth.shape), (a.nu, a.nq)))
+    truth = like_matrix(truth, "truth", (a.nu, a.nq), "train")
     m, nq = a.m, a.nq
     gain, prefix = _gain_tables(gains, k, m)
     ncq, ncu = len(qc), len(uc)
@@ -139,7 +136,7 @@ def evaluate_ranking_grid(train, truth, q_src, q_dst, q_milli, user_sims, k, rel
     lib = _lib.load()
     a.upload(device)
     dev = a.r.device
-    t = _on_device(truth, device)
+    t = on_device(truth, device)
     if m == 0:
         per = torch.empty((0, ncq, ncu, len(w), 8), dtype=torch.int64, device=dev) if want_per_request else None
         return RankingGridEvaluation(qc, uc, w, np.zeros((ncq, ncu, len(w), 16), dtype=np.int64), per)
@@ -151,18 +148,10 @@ def evaluate_ranking_grid(train, truth, q_src, q_dst, q_milli, user_sims, k, rel
     size = lib.qrlsh_evaluate_ranking_grid_workspace_bytes
     widest = min(tune.MAX_SETTINGS // (ncq * ncu), len(w)) * ncq * ncu   # the settings of the largest call
 
-    def blocks(blk):
-        return [(i0, min(m, i0 + blk)) for i0 in range(0, m, blk)]
-
     def need(blk):
-        return max(int(size(i1 - i0, nq, ncq, ncu, widest, int(cells[i0:i1].sum()))) for i0, i1 in blocks(blk))
+        return max(int(size(i1 - i0, nq, ncq, ncu, widest, int(cells[i0:i1].sum()))) for _, i0, i1 in blocks(m, blk))
 
-    blk = m
-    while blk > 1 and need(blk) > recommend.WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    ut = a.ut
-    if ut is None and blk < m:
-        ut = torch.arange(a.nu, dtype=torch.int32, device=dev)
+    blk, ut = request_blocks(m, need, recommend.WORKSPACE_BUDGET, ids=a.ut, full=a.nu, device=dev)
     ws = ops._ws(need(blk), dev)
     st = _stream()
 
@@ -170,26 +159,24 @@ def evaluate_ranking_grid(train, truth, q_src, q_dst, q_milli, user_sims, k, rel
         nw = hi - lo
         s = ncq * ncu * nw
         per = torch.empty((m, ncq, ncu, nw, 8), dtype=torch.int64, device=dev) if want_per_request else None
-        parts = blocks(blk)
+        parts = blocks(m, blk)
         back = torch.zeros((len(parts), s * 16 + 1), dtype=torch.int64, device=dev)   # per block [totals][flags]
-        for b, (i0, i1) in enumerate(parts):
+        for b, i0, i1 in parts:
             _lib.check(lib.qrlsh_evaluate_ranking_grid(
                 _ptr(a.r), _ptr(t), a.nu, nq, _ptr(a.q_off), _ptr(a.q_idx), _ptr(a.q_milli), _ptr(a.u_idx),
                 _ptr(a.u_val), a.ku, _ptr(d_qc), ncq, _ptr(d_uc), ncu, _ptr(d_w[lo:hi]), nw, a.sum_order,
                 None if ut is None else _ptr(ut[i0:i1]), i1 - i0, k, int(relevant), _ptr(gain_d), _ptr(prefix_d),
                 int(cells[i0:i1].sum()), None if per is None else _ptr(per[i0:i1]), _ptr(back[b]), None,
                 _ptr(back[b, s * 16:]), _ptr(ws), ws.numel(), st))
-        bits = torch.tensor([1, 2, 4, 8, 16], dtype=torch.int64, device=dev)
-        flag = (back[:, s * 16:] & bits).amax(dim=0).sum().reshape(1)      # the blocks' flag words, or-ed
-        return back[:, :s * 16].sum(dim=0).view(ncq, ncu, nw, 16), per, flag
+        return back[:, :s * 16].sum(dim=0).view(ncq, ncu, nw, 16), per, or_flags(back[:, s * 16:], device_bits=5)
 
     totals, per, flags = tune.sweep(len(w), ncq, ncu, launch)
     host = torch.cat([totals.reshape(-1), flags]).cpu().numpy()     # the one read-back
     n = totals.numel()
-    f = int(np.bitwise_or.reduce(host[n:]))
+    f = or_flags(host[n:])
     if f & 16:
         raise RuntimeError("the matrices changed while they were evaluated: more test cells than were counted")
     if f & 8:
         raise ValueError("gains and cuts must not be negative")
-    a.raise_flags(torch.from_numpy(host[n:] & 7))
+    a.raise_flags(host[n:] & 7)
     return RankingGridEvaluation(qc, uc, w, host[:n], per_request=per)

@@ -13,9 +13,11 @@ import torch
 
 from . import _lib
 from . import ops
+from . import recommend
 from ._args import _int_in
+from ._inputs import ServeInputs, blocks, like_matrix, on_device, or_flags, request_blocks
 from .ops import _ptr, _stream
-from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT, ServeInputs
+from .predict import DEFAULT_MEAN, QUERY_WEIGHT, USER_WEIGHT
 
 CANDIDATES = {"all": _lib.RANK_ALL, "heldout": _lib.RANK_HELDOUT}
 WORDS = ("listed", "hits", "known", "first_hit", "dcg", "relevant", "test", "avail")   # a line of per_user
@@ -85,7 +87,6 @@ class RankingEvaluation:
 
 def check_arguments(k, relevant, candidates="all", lo=0, slices=0):
     """ValueError for a bad k, relevant, candidates, lo or slices (no device, no library) -> int(k)"""
-    from . import recommend
     k = _int_in(k, "k", 1, recommend.MAX_K)
     if isinstance(relevant, bool) or not isinstance(relevant, (int, np.integer)) or not 1 <= int(relevant) < 2**31:
         raise ValueError("relevant must be an int32 >= 1, got %r" % (relevant,))
@@ -132,23 +133,19 @@ def evaluate_ranking(train, truth, q_src, q_dst, q_milli, user_sims, k, relevant
     negative, or m x their sum >= 2^63), lo, slices or sum_order, a truth of another shape and a user id outside the
     matrix; through the library's flags for a list longer than 64, a neighbour index outside [0, nq) and a device user
     id outside [0, nu)."""
-    from .recommend import _matrix, _on_device
     k = check_arguments(k, relevant, candidates, lo, slices)
     a = ServeInputs(train, q_src, q_dst, q_milli, user_sims, users, sum_order)
-    truth = _matrix(truth, "truth")
-    if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
-        raise ValueError("truth has shape %s, train %s" % (tuple(truth.shape), (a.nu, a.nq)))
+    truth = like_matrix(truth, "truth", (a.nu, a.nq), "train")
     gain, prefix = _gain_tables(gains, k, a.m)
     _lib.load()
     a.upload(device)
-    return _score(a, _on_device(truth, device), k, relevant, candidates, gain, prefix, lo, slices,
+    return _score(a, on_device(truth, device), k, relevant, candidates, gain, prefix, lo, slices,
                   (query_weight, user_weight, default_mean))
 
 
 def _score(a, t, k, relevant, candidates, gain, prefix, lo, slices, weights):
     """evaluate_ranking over uploaded ServeInputs `a`, the device truth `t` and checked gain tables (host arrays);
     weights = (query_weight, user_weight, default_mean)"""
-    from . import recommend
     lib = _lib.load()
     m, nq = a.m, a.nq
     dev = a.r.device
@@ -159,29 +156,23 @@ def _score(a, t, k, relevant, candidates, gain, prefix, lo, slices, weights):
     per_user = torch.empty((m, 8), dtype=torch.int64, device=dev)
     if m == 0:
         return RankingEvaluation(np.zeros(16, dtype=np.int64), idx, val, avail, per_user, prefix_d)
-    size = lib.qrlsh_evaluate_ranking_workspace_bytes
-    blk = m
-    while blk > 1 and int(size(blk, nq, k, int(slices))) > recommend.WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    ut = a.ut
-    if ut is None and blk < m:
-        ut = torch.arange(a.nu, dtype=torch.int32, device=dev)
-    ws = ops._ws(size(blk, nq, k, int(slices)), dev)
-    starts = range(0, m, blk)
-    back = torch.zeros((len(starts), 17), dtype=torch.int64, device=dev)   # per block [totals: 16][flags: low half]
+    def need(blk):
+        return int(lib.qrlsh_evaluate_ranking_workspace_bytes(blk, nq, k, int(slices)))
+    blk, ut = request_blocks(m, need, recommend.WORKSPACE_BUDGET, ids=a.ut, full=a.nu, device=dev)
+    ws = ops._ws(need(blk), dev)
+    parts = blocks(m, blk)
+    back = torch.zeros((len(parts), 17), dtype=torch.int64, device=dev)   # per block [totals: 16][flags: low half]
     args = a.lists_args(*weights)
     st = _stream()
-    for b, i0 in enumerate(starts):
-        i1 = min(m, i0 + blk)
+    for b, i0, i1 in parts:
         _lib.check(lib.qrlsh_evaluate_ranking(args[0], _ptr(t), *args[1:], None if ut is None else _ptr(ut[i0:i1]),
                                               i1 - i0, k, int(relevant), CANDIDATES[candidates], int(lo), int(slices),
                                               _ptr(gain_d), _ptr(prefix_d), _ptr(idx[i0:i1]), _ptr(val[i0:i1]),
                                               _ptr(avail[i0:i1]), _ptr(per_user[i0:i1]), _ptr(back[b]),
                                               _ptr(back[b, 16:]), _ptr(ws), ws.numel(), st))
-    bits = torch.tensor([1, 2, 4, 8], dtype=torch.int64, device=dev)
-    flag = (back[:, 16:] & bits).amax(dim=0).sum().reshape(1)          # the blocks' flag words, or-ed
+    flag = or_flags(back[:, 16:], device_bits=4)
     host = torch.cat([back[:, :16].sum(dim=0), flag]).cpu().numpy()     # the one read-back
     if int(host[16]) & 8:
         raise ValueError("gains must not be negative")
-    a.raise_flags(torch.from_numpy(host[16:] & 7))
+    a.raise_flags(host[16:] & 7)
     return RankingEvaluation(host[:16], idx, val, avail, per_user, prefix_d)

@@ -9,39 +9,14 @@ import torch
 
 from . import _lib
 from . import ops
+from . import predict
 from ._args import _int_in
+from ._inputs import WORKSPACE_BUDGET, blocks, ids32, request_blocks, select_ids
+from ._inputs import matrix as _matrix, on_device as _on_device
 from .ops import _ptr, _stream
 
 MAX_K = _lib.RECOMMEND_MAX_K
 MAX_SLICES = 256
-WORKSPACE_BUDGET = 1 << 30   # bytes of workspace per library call; larger user sets are served in row blocks
-
-
-def _matrix(x, name):
-    """2-D int32 view of a tensor / array / DataFrame; host data is checked to fit int32 (nothing is uploaded)"""
-    if isinstance(x, torch.Tensor):
-        if x.dim() != 2:
-            raise ValueError("%s must be 2-D, got shape %s" % (name, tuple(x.shape)))
-        if x.dtype.is_floating_point or x.dtype.is_complex or x.dtype == torch.bool:
-            raise ValueError("%s must hold integers, got %s" % (name, x.dtype))
-        return x
-    a = np.asarray(x.to_numpy() if hasattr(x, "to_numpy") else x)
-    if a.ndim != 2:
-        raise ValueError("%s must be 2-D, got shape %s" % (name, a.shape))
-    if a.dtype != np.int32:
-        if not np.issubdtype(a.dtype, np.integer):
-            raise ValueError("%s must hold integers, got %s" % (name, a.dtype))
-        if a.size and (a.min() < np.iinfo(np.int32).min or a.max() > np.iinfo(np.int32).max):
-            raise ValueError("%s holds values outside int32" % name)
-    return a
-
-
-def _on_device(x, device):
-    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.int32))
-    t = t.to(device=device, dtype=torch.int32).contiguous()
-    if t.data_ptr() % 16:
-        t = t.clone()   # the kernels read rows as 16-byte vectors from a 16-byte-aligned base
-    return t
 
 
 def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
@@ -63,24 +38,7 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
     nu, nq = (int(d) for d in r.shape)
     if nq >= 2**31:
         raise ValueError("at most 2^31 - 1 queries per row")
-    check_flag = False
-    if users is None:
-        u = None
-        m = nu
-    elif isinstance(users, torch.Tensor):
-        if users.dim() != 1 or users.dtype.is_floating_point or users.dtype == torch.bool:
-            raise ValueError("users must be a 1-D integer tensor")
-        u = users
-        m = int(u.numel())
-        check_flag = True
-    else:
-        ua = np.asarray(users)
-        if ua.ndim != 1 or not (ua.size == 0 or np.issubdtype(ua.dtype, np.integer)):
-            raise ValueError("users must be a 1-D sequence of integer row ids")
-        if ua.size and (ua.min() < 0 or ua.max() >= nu):
-            raise ValueError("user id outside [0, %d)" % nu)
-        u = ua
-        m = int(ua.size)
+    m, u, check_flag = select_ids(users, nu, "user", "users")
 
     lib = _lib.load()
     rt, pt = _on_device(r, device), _on_device(p, device)
@@ -89,18 +47,14 @@ def top_k(ratings, predictions, k, users=None, lo=0, slices=0, device="cuda"):
     avail = torch.empty((m,), dtype=torch.int32, device=device)
     if m == 0:
         return idx, val, avail
-    blk = m
-    while blk > 1 and int(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices))) > WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    if u is None and blk < m:
-        u = torch.arange(nu, dtype=torch.int32, device=device)
-    ut = None if u is None else (u if isinstance(u, torch.Tensor) else torch.from_numpy(u.astype(np.int64)))
-    if ut is not None:   # ids past int32 must stay out of range, not wrap into it
-        ut = ut.to(device=device, dtype=torch.int64).clamp(-1, nu).to(torch.int32).contiguous()
-    ws = ops._ws(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices)), device)
+
+    def need(blk):
+        return int(lib.qrlsh_recommend_workspace_bytes(blk, nq, k, int(slices)))
+    blk, ut = request_blocks(m, need, WORKSPACE_BUDGET, ids=None if u is None else ids32(u, nu, device), full=nu,
+                             device=device)
+    ws = ops._ws(need(blk), device)
     st = _stream()
-    for i0 in range(0, m, blk):
-        i1 = min(m, i0 + blk)
+    for _, i0, i1 in blocks(m, blk):
         _lib.check(lib.qrlsh_recommend_topk(_ptr(rt), _ptr(pt), nu, nq, None if ut is None else _ptr(ut[i0:i1]),
                                             i1 - i0, k, int(lo), int(slices), _ptr(idx[i0:i1]), _ptr(val[i0:i1]),
                                             _ptr(avail[i0:i1]), _ptr(ws), ws.numel(), st))
@@ -129,7 +83,6 @@ def for_users(ratings, q_src, q_dst, q_milli, user_sims, users, k, lo=0, slices=
     Raises ValueError for a bad k, slices, lo, shape or sum_order, a list longer than 64, a neighbour index outside
     [0, nq) and a user id outside [0, nu) (host ids before anything is uploaded; device ids and the lists through
     the library's flags)."""
-    from . import predict
     k = _check_select_args(k, lo, slices)
     a = predict.ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, users, sum_order)
     _lib.load()
@@ -139,7 +92,6 @@ def for_users(ratings, q_src, q_dst, q_milli, user_sims, users, k, lo=0, slices=
 
 def _serve(a, k, lo, slices, query_weight, user_weight, default_mean, device):
     """for_users over checked and uploaded ServeInputs (for_users_diverse shares them with its rerank)"""
-    from . import predict
     m, nq = a.m, a.nq
     lib = _lib.load()
     idx = torch.empty((m, k), dtype=torch.int32, device=device)
@@ -147,21 +99,16 @@ def _serve(a, k, lo, slices, query_weight, user_weight, default_mean, device):
     avail = torch.empty((m,), dtype=torch.int32, device=device)
     if m == 0:
         return idx, val, avail
-    blk = m
-    while blk > 1 and int(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices))) > WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    ut = a.ut
-    if ut is None and blk < m:
-        ut = torch.arange(a.nu, dtype=torch.int32, device=device)
-    ws = ops._ws(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices)), device)
-    starts = range(0, m, blk)
-    flags = torch.zeros((len(starts),), dtype=torch.int32, device=device)
-    args = a.lists_args(predict.QUERY_WEIGHT if query_weight is None else query_weight,
-                        predict.USER_WEIGHT if user_weight is None else user_weight,
-                        predict.DEFAULT_MEAN if default_mean is None else default_mean)
+
+    def need(blk):
+        return int(lib.qrlsh_recommend_users_workspace_bytes(blk, nq, k, int(slices)))
+    blk, ut = request_blocks(m, need, WORKSPACE_BUDGET, ids=a.ut, full=a.nu, device=device)
+    ws = ops._ws(need(blk), device)
+    parts = blocks(m, blk)
+    flags = torch.zeros((len(parts),), dtype=torch.int32, device=device)
+    args = a.lists_args(*predict.weights(query_weight, user_weight, default_mean))
     st = _stream()
-    for b, i0 in enumerate(starts):
-        i1 = min(m, i0 + blk)
+    for b, i0, i1 in parts:
         _lib.check(lib.qrlsh_recommend_users(*args, None if ut is None else _ptr(ut[i0:i1]), i1 - i0, k, int(lo),
                                              int(slices), _ptr(idx[i0:i1]), _ptr(val[i0:i1]), _ptr(avail[i0:i1]),
                                              _ptr(flags[b:b + 1]), _ptr(ws), ws.numel(), st))

@@ -8,6 +8,7 @@ import torch
 from . import _lib
 from . import ops
 from . import predict
+from ._inputs import blocks, request_blocks
 from .ops import _ptr, _stream
 from .recommend import WORKSPACE_BUDGET, _check_select_args
 
@@ -41,12 +42,6 @@ def _ratio(num, den):
     return out
 
 
-def _weights(query_weight, user_weight, default_mean):
-    return (predict.QUERY_WEIGHT if query_weight is None else query_weight,
-            predict.USER_WEIGHT if user_weight is None else user_weight,
-            predict.DEFAULT_MEAN if default_mean is None else default_mean)
-
-
 def _run(a, weights, device, k=None, lo=0, slices=0, want_columns=False, want_words=False):
     """The requests of checked and uploaded ServeInputs(ids="queries") in blocks under WORKSPACE_BUDGET, counting the
     raw columns (cols_tmp) plus the workspace.  k = None: qrlsh_predict_queries (columns when asked for, else the words
@@ -65,21 +60,16 @@ def _run(a, weights, device, k=None, lo=0, slices=0, want_columns=False, want_wo
     def ws_bytes(blk):
         return int(lib.qrlsh_recommend_users_workspace_bytes(blk, nu, k, slices)) if k is not None else 0
 
-    blk = m
-    while blk > 1 and blk * nu * 4 + ws_bytes(blk) > WORKSPACE_BUDGET:
-        blk = (blk + 1) // 2
-    ids = a.ut
-    if ids is None and blk < m:
-        ids = torch.arange(a.nq, dtype=torch.int32, device=device)
+    blk, ids = request_blocks(m, lambda blk: blk * nu * 4 + ws_bytes(blk), WORKSPACE_BUDGET, ids=a.ut, full=a.nq,
+                              device=device)
     cols = ops._ws(blk * nu * 4, device)
     ws = ops._ws(ws_bytes(blk), device)
-    starts = range(0, m, blk)
+    parts = blocks(m, blk)
     # the words and, behind them, one 8-byte slot per block whose low half is that block's flag word
-    back = torch.zeros((m * 8 + len(starts),), dtype=torch.int64, device=device)
+    back = torch.zeros((m * 8 + len(parts),), dtype=torch.int64, device=device)
     args = a.lists_args(*weights)
     st = _stream()
-    for b, i0 in enumerate(starts):
-        i1 = min(m, i0 + blk)
+    for b, i0, i1 in parts:
         q = None if ids is None else _ptr(ids[i0:i1])
         words = _ptr(back[i0 * 8:i1 * 8]) if want_words else None
         flags = _ptr(back[m * 8 + b:m * 8 + b + 1])
@@ -107,7 +97,7 @@ def predict_queries(ratings, q_src, q_dst, q_milli, user_sims, queries, query_we
     a = predict.ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, queries, sum_order, ids="queries")
     _lib.load()
     a.upload(device)
-    out, _, words = _run(a, _weights(query_weight, user_weight, default_mean), device, want_columns=True,
+    out, _, words = _run(a, predict.weights(query_weight, user_weight, default_mean), device, want_columns=True,
                          want_words=bool(utility))
     return (out, words) if utility else out
 
@@ -124,7 +114,7 @@ def for_queries(ratings, q_src, q_dst, q_milli, user_sims, queries, k, lo=0, sli
     a = predict.ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, queries, sum_order, ids="queries")
     _lib.load()
     a.upload(device)
-    _, sel, words = _run(a, _weights(query_weight, user_weight, default_mean), device, k=k, lo=int(lo),
+    _, sel, words = _run(a, predict.weights(query_weight, user_weight, default_mean), device, k=k, lo=int(lo),
                          slices=int(slices), want_words=bool(utility))
     return sel + (words,) if utility else sel
 
@@ -137,4 +127,4 @@ def query_utility(ratings, q_src, q_dst, q_milli, user_sims, queries=None, query
     a = predict.ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, queries, sum_order, ids="queries")
     _lib.load()
     a.upload(device)
-    return _run(a, _weights(query_weight, user_weight, default_mean), device, want_words=True)[2]
+    return _run(a, predict.weights(query_weight, user_weight, default_mean), device, want_words=True)[2]

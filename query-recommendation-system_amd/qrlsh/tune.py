@@ -12,10 +12,10 @@ import numpy as np
 import torch
 
 from . import _lib
-from .evaluate import keep_word, _seed_word
 from . import ops
+from ._inputs import ServeInputs, like_matrix, on_device, or_flags
+from .evaluate import keep_word, _seed_word
 from .ops import _ptr, _stream
-from .predict import ServeInputs
 
 MAX_CUTS = 4          # QRLSH_GRID_MAX_CUTS
 MAX_SETTINGS = 128    # QRLSH_GRID_MAX_SETTINGS
@@ -126,19 +126,16 @@ def evaluate_grid(ratings, q_src, q_dst, q_milli, user_sims, weights, q_cuts=Non
     -> GridEvaluation (one read-back: the totals and the flags).
     ValueError for empty or negative cuts or more than 4 per side, weights of another shape, a fraction outside [0, 1],
     a bad sum_order, a truth of another shape, and the lists' flags as evaluate() raises them."""
-    from .recommend import _matrix, _on_device
     qc, uc, w = _cuts(q_cuts, "q_cuts"), _cuts(u_cuts, "u_cuts"), _weights(weights)
     keep, seed = keep_word(fraction), _seed_word(seed)
     a = ServeInputs(ratings, q_src, q_dst, q_milli, user_sims, None, sum_order)
     if truth is not None:
-        truth = _matrix(truth, "truth")
-        if tuple(int(d) for d in truth.shape) != (a.nu, a.nq):
-            raise ValueError("truth has shape %s, ratings %s" % (tuple(truth.shape), (a.nu, a.nq)))
+        truth = like_matrix(truth, "truth", (a.nu, a.nq), "ratings")
     if a.nu >= 2**31:
         raise ValueError("at most 2^31 - 1 users")
     lib = _lib.load()
     a.upload(device)
-    t = a.r if truth is None else _on_device(truth, device)
+    t = a.r if truth is None else on_device(truth, device)
     dev = a.r.device
     ncq, ncu = len(qc), len(uc)
     d_qc = torch.tensor(qc, dtype=torch.int32, device=dev)
@@ -161,7 +158,7 @@ def evaluate_grid(ratings, q_src, q_dst, q_milli, user_sims, weights, q_cuts=Non
     totals, per_user, flags = sweep(len(w), ncq, ncu, launch)
     host = torch.cat([totals.reshape(-1), flags]).cpu().numpy()
     n = totals.numel()
-    if int(np.bitwise_or.reduce(host[n:])) & 8:
+    if or_flags(host[n:]) & 8:
         raise ValueError("a cut is negative")   # (checked above: the library's own check)
-    a.raise_flags(torch.from_numpy(host[n:] & 7))
+    a.raise_flags(host[n:] & 7)
     return GridEvaluation(qc, uc, w, host[:n], per_user=per_user)

@@ -27,6 +27,7 @@ import torch
 import qrlsh
 from qrlsh import ops, pipeline
 from qrlsh._args import _int_in
+from qrlsh._inputs import sum_order_code
 from lsh import LSH  # noqa: F401  (same import the reference has)
 
 # constants (recommender.py:30-34)
@@ -516,8 +517,7 @@ class Recommender:
     def _sum_order(self, sum_order):
         """the checked summation order of a serving call (None: self.sum_order)"""
         sum_order = self.sum_order if sum_order is None else sum_order
-        if sum_order not in ("pairwise", "sequential"):
-            raise ValueError("sum_order must be 'pairwise' or 'sequential'")
+        sum_order_code(sum_order)
         return sum_order
 
     def current_query_similarities(self):

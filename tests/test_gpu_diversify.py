@@ -142,6 +142,25 @@ def test_row_blocked_calls_equal_one_call(monkeypatch):
     assert calls.count("qrlsh_list_redundancy") == 8
 
 
+def test_list_redundancy_in_row_blocks_equals_its_single_call(monkeypatch):
+    dv = importlib.import_module("qrlsh.diversify")
+    lib = qrlsh._lib.load()
+    c = case("main")
+    pools = c.arrays()[0]                                # the padded pools as lists of N entries
+    whole = qrlsh.list_redundancy(pools, *c.coo(), c.nq, device=DEV)
+    calls = []
+    real = lib.qrlsh_list_redundancy
+
+    def counted(*args):
+        calls.append(args[1])
+        return real(*args)
+    monkeypatch.setattr(lib, "qrlsh_list_redundancy", counted)
+    monkeypatch.setattr(dv, "WORKSPACE_BUDGET", int(lib.qrlsh_diversify_workspace_bytes(40, c.N, DC.K_LISTS)))
+    split = qrlsh.list_redundancy(pools, *c.coo(), c.nq, device=DEV)
+    assert calls == [38] * 7 + [34]                      # 300 -> 150 -> 75 -> 38 per call, a short last block
+    assert_same((split.words, split.totals), (whole.words, whole.totals), "blocked", ("words", "totals"))
+
+
 # ------------------------------------------------------------------------------------------------------- 3. serving
 ORDERS = {"pairwise": O.np_sum_order, "sequential": PC.sequential_sum}
 USERS = [0, 3, 9, 200, 332, 3]

@@ -218,6 +218,30 @@ def test_host_layer_runs_request_blocks(planted, monkeypatch):
     FC.same_result(_run(case, chosen), case.ref(chosen))
 
 
+def test_host_layer_splits_under_its_budget_into_whole_groups(monkeypatch):
+    from qrlsh import _lib, fidelity
+    case = FC.planted_case(33, nq=70)
+    G = _group(33)
+    assert case.nq > 2 * G
+    whole = _run(case)
+    FC.same_result(whole, case.ref())
+    lib = _lib.load()
+    calls = []
+    real = lib.qrlsh_list_fidelity
+
+    def counted(*args):
+        calls.append(args[7])
+        return real(*args)
+    monkeypatch.setattr(lib, "qrlsh_list_fidelity", counted)
+    monkeypatch.setattr(fidelity, "WORKSPACE_BUDGET", G * fidelity._REQUEST_BYTES)     # one group per call
+    split = _run(case)                                   # every query, unnamed: the blocks are served by made-up ids
+    assert calls == [G, G, case.nq - 2 * G]
+    FC.same_result(split, case.ref())
+    assert np.array_equal(split.queries, whole.queries) and np.array_equal(split.per_request, whole.per_request)
+    assert np.array_equal(split.totals, whole.totals)
+    assert all(np.array_equal(split.entries[name], whole.entries[name]) for name in whole.entries)
+
+
 def _with(case, **kw):
     a = dict(offsets=case.offsets, rows=case.rows, D=case.D, src=case.src, dst=case.dst, val=case.val, K=case.K, name="bad")
     a.update(kw)

@@ -269,3 +269,24 @@ def test_out_of_range_user_raises_from_flag_and_leaves_no_fault():
         qrlsh.top_k(*short, 4, users=torch.tensor([0, 31], device=DEV))
     torch.cuda.synchronize()
     assert_exact(dev_topk(r, p, 4), restate_all(r, p, 4), "after the flagged calls")
+
+
+# ---------------------------------------------------------------------------------------------------- 6. row blocks
+def test_all_users_split_into_row_blocks_match_the_single_call(monkeypatch):
+    """37 rows under a budget that admits 10 per call (slices=1: the rows form has no workspace, so nothing would
+    split): 37 -> 19 -> 10, four library calls, the last of 7 rows, served by the ids the split had to make"""
+    from qrlsh import _lib, recommend
+    lib = _lib.load()
+    r, p = _heavy_ties(37, 40, 23)
+    want = dev_topk(r, p, 5, slices=1)
+    assert_exact(want, restate_all(r, p, 5), "one call")
+    calls = []
+    real = lib.qrlsh_recommend_topk
+
+    def counted(*args):
+        calls.append(args[5])
+        return real(*args)
+    monkeypatch.setattr(lib, "qrlsh_recommend_topk", counted)
+    monkeypatch.setattr(recommend, "WORKSPACE_BUDGET", int(lib.qrlsh_recommend_workspace_bytes(10, 40, 5, 1)))
+    assert_exact(dev_topk(r, p, 5, slices=1), want, "row blocks")
+    assert calls == [10, 10, 10, 7]

@@ -292,3 +292,31 @@ def test_recommender_serves_chosen_users_in_every_state(sub):
     del rec.compute_userSimilarities
     final = rec.compute_scores(reuse_lists=True)[1]
     _same_answers(rec.recommend_users(users, 7), rec.recommend(final, 7, users))
+
+
+# ----------------------------------------------------------------------------------------------------- 7. row blocks
+def test_row_blocks_match_the_single_call_and_name_a_bad_id_of_the_last_block(monkeypatch):
+    """37 rows under a budget that admits 10 per call: 37 -> 19 -> 10, four library calls, the last of 7 rows"""
+    from qrlsh import _lib, recommend
+    lib = _lib.load()
+    ratings, coo, us = _random_case(41, 37, 40, 12, 5)
+    want = host(*qrlsh.for_users(ratings, *coo, us, None, 5, device=DEV))
+    full = predict.fill_predictions(ratings, *coo, us, device=DEV)
+    assert_same(want, restate(ratings, host(full), 5), "one call")
+    calls = []
+    real = lib.qrlsh_recommend_users
+
+    def counted(*args):
+        calls.append(args[14])
+        return real(*args)
+    monkeypatch.setattr(lib, "qrlsh_recommend_users", counted)
+    monkeypatch.setattr(recommend, "WORKSPACE_BUDGET", int(lib.qrlsh_recommend_users_workspace_bytes(10, 40, 5, 0)))
+    assert_same(host(*qrlsh.for_users(ratings, *coo, us, None, 5, device=DEV)), want, "row blocks")
+    assert calls == [10, 10, 10, 7]
+    users = list(range(36, -1, -1))
+    got = host(*qrlsh.for_users(ratings, *coo, us, torch.tensor(users, device=DEV), 5, device=DEV))
+    assert_same(got, tuple(w[users] for w in want), "row blocks, device ids")
+    users[33] = 37                                        # the only bad id, in the block of the last 7
+    with pytest.raises(ValueError, match=r"user id 37 \(position 33\) outside \[0, 37\)"):
+        qrlsh.for_users(ratings, *coo, us, torch.tensor(users, device=DEV), 5, device=DEV)
+    torch.cuda.synchronize()
