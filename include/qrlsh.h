@@ -994,6 +994,58 @@ int qrlsh_exact_neighbours(const int64_t *offsets, const int32_t *rows, int64_t 
                            int64_t m, int32_t K, int32_t slices, int32_t *dst_out, int32_t *inter_out, int32_t *union_out,
                            int32_t *counts_out, uint32_t *flags_out, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- exact lists from postings: the same lists from a row -> queries index of the answer sets ---------------------------
+ * qrlsh_answer_postings: the transpose of the CSR answer sets (offsets int64 [nq + 1], rows int32 [nnz], over D table
+ *   rows).  p_off_out int64 [D + 1], p_qry_out int32 [nnz]: the queries whose answer set holds row d are
+ *   p_qry[p_off[d] .. p_off[d + 1]), ascending.  The transpose is unique; every word of both outputs is written by every
+ *   call (nnz = 0 or D = 0 still writes p_off).
+ *   Four steps on one stream: a check of the offsets; one word row << 32 | query per CSR entry, in CSR order;
+ *   qrlsh_sort_u64 over bits [32, 32 + bits(D)) -- stable, so the queries of a row stay ascending; p_qry from the low
+ *   words and p_off[d] = the first sorted position whose row is >= d, a binary search per d.
+ *   *flags_out (device uint32, zeroed by the caller, required): bit 3 a row id outside [0, D) (qrlsh_list_fidelity's bit;
+ *   the entry is never used as an index: it is filed under row 0), bit 5 offsets is not a CSR over nnz entries (first != 0,
+ *   last != nnz, or decreasing; every index stays inside the arrays all the same).  A flagged result is not to be used.
+ *   scratch: qrlsh_answer_postings_scratch_bytes(nnz, D) bytes, 16-byte aligned -- two arrays of nnz 64-bit words and a
+ *   qrlsh_sort_workspace_bytes(nnz, 1) behind them; 0 for nnz = 0 and for arguments the call would refuse.  It need not be
+ *   initialised and holds nothing afterwards.  QRLSH_EWORKSPACE when scratch_bytes is smaller.
+ *   Limits: nq < 2^31, 0 <= D <= 2^20, nnz >= 0 (QRLSH_EINVAL otherwise); nnz <= 2^32 - 1, what qrlsh_sort_u64 serves
+ *   (QRLSH_EUNSUPPORTED above).  Every check precedes any device work.
+ * qrlsh_exact_neighbours_postings: qrlsh_exact_neighbours' result, word for word, served from the postings.  offsets, rows,
+ *   nq, D, queries, m, K, the four outputs and their padding, counts_out, the order (J descending by cross-multiplication in
+ *   int64, ties by id ascending, cut at K), the limits and the return codes are qrlsh_exact_neighbours' above; there are
+ *   no slices.  p_off int64 [D + 1] / p_qry int32 [offsets[nq]]: qrlsh_answer_postings of the same answer sets.
+ *   One 1024-thread workgroup per request s with a = |A(s)| rows.  inter(s, j) is the number of the a posting lists that
+ *   hold j and |A(j)| = offsets[j + 1] - offsets[j], so A(j) is never read: the work follows the request's matches.
+ *   The ids are served in passes over disjoint windows that tile [0, nq) in ascending order.  A window is a pass when it
+ *   holds at most C = qrlsh_exact_postings_pass_entries() list entries (counted exactly beforehand, by binary searches of
+ *   its bounds in the a lists) or is a single id; the first cut is ceil(entries / C) windows of equal width, and a window
+ *   that is no pass is halved from the same start until it is one.  A pass counts multiplicities in an LDS hash table of
+ *   2 C slots (at most half full: at most C distinct ids, or one), then walks the slots: a candidate whose bound
+ *   inter / a (union >= a) is below the K-th entry kept so far is dropped before anything is gathered; a survivor goes to
+ *   an LDS queue by an atomic cursor, and between two workgroup barriers the queue is drained -- the exact union from two
+ *   offsets, the comparison repeated, the kept list updated by one wave -- with the walk repeated for what the queue did
+ *   not hold.  No lock and no wait of one thread on another; rows of s beyond the 512 whose list cursors stay in LDS are
+ *   read from memory at every window.
+ *   *flags_out (device uint32, zeroed by the caller, required): bit 2 a chosen query outside [0, nq) (its row is all
+ *   padding, its counts 0), bit 3 a row id of a chosen query outside [0, D) (checked before it indexes p_off; that row is
+ *   skipped), bit 4 the postings do not belong to these answer sets: p_off[0] != 0 or p_off[D] != offsets[nq], bounds of a
+ *   list a request reads outside [0, offsets[nq]] or decreasing, or an entry of such a list outside [0, nq) (checked
+ *   before it indexes offsets; never a candidate).  A flagged result is not to be used.
+ *   scratch: qrlsh_exact_postings_scratch_bytes(nq, m, K) bytes = 0: everything stays in LDS; the arguments are there for a
+ *   form that needs some.  m = 0 or nq = 0 returns at once with nothing written; nothing of size m x nq is written or
+ *   allocated.  Integer arithmetic only.
+ * No allocation, one stream, no read-back. */
+size_t qrlsh_answer_postings_scratch_bytes(int64_t nnz, int64_t D);
+int qrlsh_answer_postings(const int64_t *offsets, const int32_t *rows, int64_t nq, int64_t nnz, int64_t D,
+                          int64_t *p_off_out, int32_t *p_qry_out, uint32_t *flags_out, void *scratch, size_t scratch_bytes,
+                          void *stream);
+int32_t qrlsh_exact_postings_pass_entries(void);
+size_t qrlsh_exact_postings_scratch_bytes(int64_t nq, int64_t m, int32_t K);
+int qrlsh_exact_neighbours_postings(const int64_t *offsets, const int32_t *rows, int64_t nq, int64_t D, const int64_t *p_off,
+                                    const int32_t *p_qry, const int32_t *queries, int64_t m, int32_t K, int32_t *dst_out,
+                                    int32_t *inter_out, int32_t *union_out, int32_t *counts_out, uint32_t *flags_out,
+                                    void *scratch, size_t scratch_bytes, void *stream);
+
 /* ---- evaluation: the prediction error on rated cells, hold-out and leave-one-out -----------------------------------
  * The blend of cell (i, j) never reads ratings[i][j]: a rated cell can be predicted as if it were unrated and compared
  * with its rating.  Predictions and ratings are integers, so every statistic is an exact integer sum, independent of the

@@ -43,6 +43,7 @@ from .diversify import diversify, for_users_diverse, list_redundancy, Redundancy
 from .diversify import diversify_grid, evaluate_diversity, DiversityGrid  # noqa: F401
 from .fidelity import edge_overlaps, list_fidelity, ListFidelity  # noqa: F401
 from .exactlists import exact_neighbours, ExactLists  # noqa: F401
+from .postings import answer_postings, AnswerPostings  # noqa: F401
 from .evaluate import holdout, evaluate, evaluate_cells, Evaluation  # noqa: F401
 from .ranking import dcg_gains, evaluate_ranking, RankingEvaluation  # noqa: F401
 from .tune import evaluate_grid, GridEvaluation  # noqa: F401

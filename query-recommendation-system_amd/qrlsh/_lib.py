@@ -188,6 +188,12 @@ SIGNATURES = {
     "qrlsh_exact_neighbours_slices": (_i32, [_i64, _i64, _i64, _i32]),
     "qrlsh_exact_neighbours": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                               _vp]),
+    "qrlsh_answer_postings_scratch_bytes": (_sz, [_i64, _i64]),
+    "qrlsh_answer_postings": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "qrlsh_exact_postings_pass_entries": (_i32, []),
+    "qrlsh_exact_postings_scratch_bytes": (_sz, [_i64, _i64, _i32]),
+    "qrlsh_exact_neighbours_postings": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
+                                                       _vp, _vp, _sz, _vp]),
     "qrlsh_ratings_holdout": (ctypes.c_int, [_vp, _i64, _i64, _u64, _u64, _vp, _vp, _vp]),
     "qrlsh_evaluate_workspace_bytes": (_sz, [_i64, _i64]),
     "qrlsh_evaluate": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i32, ctypes.c_double,

@@ -10,6 +10,7 @@ import torch
 
 from . import _lib
 from . import ops
+from . import postings as _postings
 from ._args import _int_in
 from ._inputs import MAX_REQUESTS, WORKSPACE_BUDGET, answer_csr, blocks, ids32, or_flags, raise_flags
 from ._inputs import request_blocks, select_ids
@@ -71,13 +72,18 @@ def slice_count(nq, m, D, slices=0):
     return int(_lib.load().qrlsh_exact_neighbours_slices(int(nq), int(m), int(D), int(slices)))
 
 
-def exact_neighbours(offsets, rows, D, K, queries=None, slices=0, device="cuda"):
+def exact_neighbours(offsets, rows, D, K, queries=None, slices=0, device="cuda", postings=None):
     """The exact top K by Jaccard of chosen queries over all nq queries -> ExactLists (one read-back, for the flags).
     offsets (nq + 1,) / rows: the CSR answer sets over D table rows (row ids in [0, D), ascending per query, as
     answer_sets gives them); K in 1..64; queries: ids of the chosen queries (any order, repeats allowed; a host sequence
     or a device tensor), None = all; slices: 0 = automatic, else 1..256 slices of the ids (the result depends on
     neither).  Tensors are used where they are, host data is uploaded.  Requests run in blocks of whole workgroups whose
     partial lists stay within WORKSPACE_BUDGET.
+    postings: None = the sweep over all queries; an AnswerPostings (answer_postings() of the same answer sets) = the same
+    lists, word for word, from the posting lists of each request's own rows: the cost follows the request's matches, not
+    nq ("Exact lists from postings").  slices must stay 0 with it; postings built from another
+    shape (nq, entries, D) are refused before any device work, postings of another CSR of the same shape by the library's
+    flag where a request meets the difference.
     Raises ValueError before anything is uploaded for a bad K, D (at most 2^20), slices or shape and a host query id
     outside [0, nq); through the library's flags for a device query id outside [0, nq) and an answer-set row id outside
     [0, D) (nothing is returned then)."""
@@ -89,10 +95,15 @@ def exact_neighbours(offsets, rows, D, K, queries=None, slices=0, device="cuda")
     m, ids, _ = select_ids(queries, nq, "query", "queries", host_tensors=True)
     if m and not nq:
         raise ValueError("query id outside [0, 0)")
+    if postings is not None:
+        _postings.check_postings(postings, nq, int(r.numel()), D, slices)
     lib = _lib.load()
     off = off.to(device=device, dtype=torch.int64).contiguous()
     r = r.to(device=device, dtype=torch.int32).contiguous()
     ids = torch.arange(nq, dtype=torch.int32, device=device) if ids is None else ids32(ids, nq, device)
+    if postings is not None:
+        dst, inter, union, counts = _postings.exact_lists(off, r, nq, D, K, ids, m, postings, device)
+        return ExactLists(K, ids, dst, inter, union, counts[:, 0].contiguous(), counts[:, 1].contiguous())
     dst = torch.full((m, K), -1, dtype=torch.int32, device=device)       # the library writes nothing when nq is 0
     inter = torch.zeros((2, m, K), dtype=torch.int32, device=device)
     counts = torch.zeros((m, 2), dtype=torch.int32, device=device)

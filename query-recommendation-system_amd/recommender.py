@@ -894,7 +894,16 @@ class Recommender:
         inter = fd.edge_overlaps(offsets, rows, lists[0], lists[1], device=self.device)
         return lists[0], lists[1], lists[2], inter, offsets[1:] - offsets[:-1]
 
-    def exact_query_lists(self, K=None, positions=None):
+    def answer_postings(self):
+        """The row -> queries index of the answer sets as served now -> qrlsh.AnswerPostings, built on the device from the
+        CSR every other call here reads (current after every live operation).  Nothing is kept on the instance: postings
+        held across add_queries / remove_queries / replace_queries, add_rows or remove_rows are the caller's, and
+        exact_query_lists refuses them once the shape of the answer sets has moved."""
+        from qrlsh import postings as po
+        offsets, rows, D = self._answer_set_inputs()
+        return po.answer_postings(offsets, rows, D, device=self.device)
+
+    def exact_query_lists(self, K=None, positions=None, postings=None):
         """The exact neighbour lists of the queries as served now -> qrlsh.ExactLists (.dst, .inter, .union, .listed,
         .positives, .coo()): per requested position the top K queries by Jaccard over the answer sets, J descending,
         ties by position ascending -- what list_fidelity holds the served lists to.  Read from the answer sets as they
@@ -903,7 +912,11 @@ class Recommender:
         LSH from the next operation on).  .coo() is the `lists` argument of evaluate, evaluate_ranking, recommend_users
         and list_fidelity when positions is None.  K: 1..64, None = the live lists' own (ValueError when there are none);
         positions: 0-based queries (any order; a host sequence or a device tensor), None = all -- every query against
-        every query: minutes at 10 M queries.
+        every query: by the sweep (postings=None) minutes at 10 M queries.
+        postings: None = the sweep over all queries; True = build the row -> queries index for this call
+        (answer_postings()) and serve every request from the posting lists of its own rows, the same lists word for
+        word at a cost that follows the matches; a qrlsh.AnswerPostings = used as given (ValueError when its shape is no
+        longer that of the answer sets).
         ValueError for a bad K or position and for more than 2^20 table rows."""
         from qrlsh import exactlists as el
         from qrlsh import fidelity as fd
@@ -914,7 +927,13 @@ class Recommender:
         if int(offsets.numel()) - 1 != int(self.queriesIDs.size):
             raise ValueError("the answer sets cover %d queries, %d are served" % (int(offsets.numel()) - 1,
                                                                                int(self.queriesIDs.size)))
-        return el.exact_neighbours(offsets, rows, D, K, queries=_ids_arg(positions), device=self.device)
+        if postings is True:
+            from qrlsh import postings as po
+            postings = po.answer_postings(offsets, rows, D, device=self.device)
+        elif postings is False:
+            postings = None
+        return el.exact_neighbours(offsets, rows, D, K, queries=_ids_arg(positions), device=self.device,
+                                   postings=postings)
 
     def predict_users(self, users, sum_order=None, user_sim=None, ratings=None):
         """DataFrame requested users x queriesIDs: their rows of compute_scores(reuse_lists=True)'s finalPredictions,
