@@ -1031,6 +1031,20 @@ int qrlsh_exact_neighbours(const int64_t *offsets, const int32_t *rows, int64_t 
  *   skipped), bit 4 the postings do not belong to these answer sets: p_off[0] != 0 or p_off[D] != offsets[nq], bounds of a
  *   list a request reads outside [0, offsets[nq]] or decreasing, or an entry of such a list outside [0, nq) (checked
  *   before it indexes offsets; never a candidate).  A flagged result is not to be used.
+ *   WHAT BIT 4 DOES NOT SEE: postings built from OTHER answer sets of the same nq, nnz and D (a stale index: two
+ *   queries of equal size swapped, sets replaced at the same total size) whose bounds and ids are all in range.  The
+ *   intersections then come from the old lists and the unions from the new offsets: plausible numbers under no flag,
+ *   for a request whose own set changed as for one whose neighbours changed.  Postings held across any change of the
+ *   answer sets are the caller's responsibility.  (Every list a request s reads must hold s exactly once, and a count
+ *   of those entries in the fill refuses a request whose own set changed; measured at 0.6 % of the kernel at 16 384
+ *   requests, outside the parent's run-to-run spread, it is not built:
+ *   profiles/exact_postings_self_check_parent_vs_branch.json.)
+ *   Rows twice in one answer set are outside this route as they are outside qrlsh_exact_neighbours' contract (rows
+ *   distinct per query); they are not detected: the list of such a row is read twice and its holders count double.
+ *   qrlsh_exact_postings_list_cursors() = 512, the lists whose cursors stay in LDS, and qrlsh_exact_postings_queue() =
+ *   1024, the survivors the queue holds between two drains, qrlsh_exact_postings_threads() = 1024, the threads of a
+ *   request's workgroup (the lanes per list of the fill follow from it): exported, like C, for tests that build shapes
+ *   around them.
  *   scratch: qrlsh_exact_postings_scratch_bytes(nq, m, K) bytes = 0: everything stays in LDS; the arguments are there for a
  *   form that needs some.  m = 0 or nq = 0 returns at once with nothing written; nothing of size m x nq is written or
  *   allocated.  Integer arithmetic only.
@@ -1040,6 +1054,9 @@ int qrlsh_answer_postings(const int64_t *offsets, const int32_t *rows, int64_t n
                           int64_t *p_off_out, int32_t *p_qry_out, uint32_t *flags_out, void *scratch, size_t scratch_bytes,
                           void *stream);
 int32_t qrlsh_exact_postings_pass_entries(void);
+int32_t qrlsh_exact_postings_list_cursors(void);
+int32_t qrlsh_exact_postings_queue(void);
+int32_t qrlsh_exact_postings_threads(void);
 size_t qrlsh_exact_postings_scratch_bytes(int64_t nq, int64_t m, int32_t K);
 int qrlsh_exact_neighbours_postings(const int64_t *offsets, const int32_t *rows, int64_t nq, int64_t D, const int64_t *p_off,
                                     const int32_t *p_qry, const int32_t *queries, int64_t m, int32_t K, int32_t *dst_out,

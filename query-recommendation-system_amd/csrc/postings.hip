@@ -416,6 +416,9 @@ QRLSH_EXPORT int qrlsh_answer_postings(const int64_t *offsets, const int32_t *ro
 }
 
 QRLSH_EXPORT int32_t qrlsh_exact_postings_pass_entries(void) { return PP_PASS_ENTRIES; }
+QRLSH_EXPORT int32_t qrlsh_exact_postings_list_cursors(void) { return PX_LISTS; }
+QRLSH_EXPORT int32_t qrlsh_exact_postings_queue(void) { return PX_QUEUE; }
+QRLSH_EXPORT int32_t qrlsh_exact_postings_threads(void) { return PX_THREADS; }
 
 QRLSH_EXPORT size_t qrlsh_exact_postings_scratch_bytes(int64_t nq, int64_t m, int32_t K) {
   (void)nq, (void)m, (void)K;

@@ -191,6 +191,9 @@ SIGNATURES = {
     "qrlsh_answer_postings_scratch_bytes": (_sz, [_i64, _i64]),
     "qrlsh_answer_postings": (ctypes.c_int, [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
     "qrlsh_exact_postings_pass_entries": (_i32, []),
+    "qrlsh_exact_postings_list_cursors": (_i32, []),
+    "qrlsh_exact_postings_queue": (_i32, []),
+    "qrlsh_exact_postings_threads": (_i32, []),
     "qrlsh_exact_postings_scratch_bytes": (_sz, [_i64, _i64, _i32]),
     "qrlsh_exact_neighbours_postings": (ctypes.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
                                                        _vp, _vp, _sz, _vp]),

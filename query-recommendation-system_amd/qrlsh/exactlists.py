@@ -82,8 +82,9 @@ def exact_neighbours(offsets, rows, D, K, queries=None, slices=0, device="cuda",
     postings: None = the sweep over all queries; an AnswerPostings (answer_postings() of the same answer sets) = the same
     lists, word for word, from the posting lists of each request's own rows: the cost follows the request's matches, not
     nq ("Exact lists from postings").  slices must stay 0 with it; postings built from another
-    shape (nq, entries, D) are refused before any device work, postings of another CSR of the same shape by the library's
-    flag where a request meets the difference.
+    shape (nq, entries, D) are refused before any device work.  Postings of another CSR of the same shape are refused by
+    the library's flag only where a request meets a bound or an id out of range; otherwise they are NOT refused and the
+    numbers are wrong (qrlsh/postings.py).
     Raises ValueError before anything is uploaded for a bad K, D (at most 2^20), slices or shape and a host query id
     outside [0, nq); through the library's flags for a device query id outside [0, nq) and an answer-set row id outside
     [0, D) (nothing is returned then)."""

@@ -4,7 +4,13 @@
 The postings are the transpose of the CSR answer sets: row d of the table -> the queries whose answer set holds d,
 ascending.  A request reads the posting lists of its own rows, so its cost follows its matches instead of a sweep over all
 queries; the result is word for word that of the sweep route.  Built on the device on demand and never kept current:
-an AnswerPostings carries the shape it was built from, and a call refuses one whose shape is not the CSR's."""
+an AnswerPostings carries the shape it was built from, and a call refuses one whose shape is not the CSR's.
+
+A stale index of the SAME shape (nq, entries and D unchanged: two queries of equal size swapped, a replace_queries whose new
+sets have the same total size) passes that check, and the library's flag bit 4 ("do not belong") sees only bounds and
+ids out of range: such postings are NOT refused, neither for a request whose own answer set changed nor for one whose
+neighbours' sets changed.  The result then has intersections from the old lists and unions from the new offsets, and no
+flag.  Postings held across any change of the answer sets are the caller's responsibility."""
 import torch
 
 from . import _lib

@@ -898,7 +898,10 @@ class Recommender:
         """The row -> queries index of the answer sets as served now -> qrlsh.AnswerPostings, built on the device from the
         CSR every other call here reads (current after every live operation).  Nothing is kept on the instance: postings
         held across add_queries / remove_queries / replace_queries, add_rows or remove_rows are the caller's, and
-        exact_query_lists refuses them once the shape of the answer sets has moved."""
+        exact_query_lists refuses them once the shape of the answer sets has moved (queries, entries or table rows).
+        Held postings whose shape still fits -- a replace_queries whose new answer sets have the same total size --
+        are NOT refused: every position is then served from the old lists with wrong numbers and no error.  Rebuild
+        after every live operation, or pass postings=True."""
         from qrlsh import postings as po
         offsets, rows, D = self._answer_set_inputs()
         return po.answer_postings(offsets, rows, D, device=self.device)
@@ -916,7 +919,8 @@ class Recommender:
         postings: None = the sweep over all queries; True = build the row -> queries index for this call
         (answer_postings()) and serve every request from the posting lists of its own rows, the same lists word for
         word at a cost that follows the matches; a qrlsh.AnswerPostings = used as given (ValueError when its shape is no
-        longer that of the answer sets).
+        longer that of the answer sets; held postings of the same shape are NOT refused, whatever changed -- see
+        answer_postings()).
         ValueError for a bad K or position and for more than 2^20 table rows."""
         from qrlsh import exactlists as el
         from qrlsh import fidelity as fd

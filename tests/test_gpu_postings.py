@@ -2,7 +2,9 @@
 qrlsh_exact_neighbours_postings, qrlsh.answer_postings, exact_neighbours(postings=...), Recommender.answer_postings /
 exact_query_lists(postings=...)).  The postings are compared byte for byte with the numpy transpose of
 tests/postings_cases.py, every output word of the lists with the restatements there and in tests/exactlists_cases.py, and
-the sweep route (postings=None) is run beside the new one as a second oracle.  No tolerances."""
+the sweep route (postings=None) is run beside the new one as a second oracle.  No tolerances.  The cases beyond one pass
+(several halved windows beside more than 512 lists, single-id passes, probe chains, lane counts, late windows, a mixed
+launch) prove on the CPU, in their builders, that they reach their path."""
 import numpy as np
 import pytest
 import torch
@@ -159,8 +161,13 @@ def test_a_row_held_by_every_query_and_a_request_of_more_lists_than_stay_in_lds(
 @pytest.fixture(scope="module")
 def pass_entries():
     from qrlsh import _lib
-    C = int(_lib.load().qrlsh_exact_postings_pass_entries())
+    lib = _lib.load()
+    C = int(lib.qrlsh_exact_postings_pass_entries())
     assert C == PC.PASS_ENTRIES
+    # the cases are built around these two as well: a changed constant fails here instead of hollowing the cases out
+    assert int(lib.qrlsh_exact_postings_queue()) == PC.QUEUE
+    assert int(lib.qrlsh_exact_postings_list_cursors()) == PC.LIST_CURSORS
+    assert int(lib.qrlsh_exact_postings_threads()) == PC.THREADS
     return C
 
 
@@ -186,6 +193,107 @@ def test_nothing_pruned_and_more_survivors_than_the_queue(pass_entries):
     got = _check(many, 10, many.requests)
     assert got.dst[0].min().item() > PC.QUEUE            # the kept entries all came in a late round of the walk
     _check(many, 64, many.requests, sweep=False)
+
+
+# ---- more than one window beside more than 512 lists, single-id passes, probe chains, lanes, late windows ---------------
+def test_long_requests_over_several_halved_windows(pass_entries):
+    """a = 511 / 512 / 513 / 600 side by side, 3 - 4 non-empty passes each, every one with lo > 0 and found by halving
+    (PC.long_windows_case asserts it): the per-window bounds of the requests whose cursors do not stay in LDS"""
+    case = PC.long_windows_case(C=pass_entries)
+    got = _check(case, 64, case.requests)
+    assert got.positives.tolist()[:4] == [63] * 4 and got.positives[5].item() == 0
+    _check(case, 1, case.requests)
+    _check(case, 9)                                       # every query, the 4032 empty ones among them
+
+
+def test_passes_of_a_single_id_with_more_than_C_entries(pass_entries):
+    """request 0 reads C + 8 lists; ids 0 (itself: the table stays empty), 17, 18 and 19 are passes of one id holding
+    C + 8, C + 8, C + 8 and C + 1 entries (PC.hot_id_case asserts it): the hi - lo <= 1 arm of the pass rule"""
+    case = PC.hot_id_case(C=pass_entries)
+    got = _check(case, 64, case.requests)
+    assert got.inter[0, :3].tolist() == [case.D, case.D, pass_entries + 1] and got.dst[0, :3].tolist() == [17, 18, 19]
+    _check(case, 1, case.requests)
+    _check(case, 3)
+
+
+def test_probe_chains_that_wrap_with_different_multiplicities(pass_entries):
+    """767 keys whose home slots are the last 32 and the first 64 of the table: chains run past slot 16383 into a crowded
+    slot 0 .. 63; colliding keys count 1, 2 or 3 (PC.probe_chain_case asserts it)"""
+    case = PC.probe_chain_case(C=pass_entries)
+    got = _check(case, 64, case.requests)
+    assert got.positives[0].item() == 767 and got.positives[3].item() == 0
+    _check(case, 1, case.requests)
+    _check(case, 7, case.requests)
+
+
+def test_every_lane_count_of_the_fill():
+    """a = 1 .. 512: L = 1024 .. 2 lanes per list, each request with lists both longer and shorter than its L
+    (PC.lanes_case asserts it)"""
+    case = PC.lanes_case()
+    _check(case, 10, case.requests)
+    _check(case, 64, case.requests[::-1])
+
+
+def test_a_threshold_of_the_first_window_prunes_the_later_ones(pass_entries):
+    """later windows hold candidates whose bound is below the K-th entry, whose bound EQUALS it and whose J equals it
+    exactly (higher ids: they lose the tie); in request nq - 2 the equal class lies below the kept ids and wins
+    (PC.late_windows_case asserts all of it with fractions)"""
+    case = PC.late_windows_case(C=pass_entries)
+    got = _check(case, 8, case.requests)
+    assert got.dst[0].tolist() == list(range(1, 9)) and got.positives[0].item() > 2 * pass_entries
+    _check(case, 9, case.requests)                        # one place more: the lowest id of the tied class takes it
+    _check(case, 1, case.requests)
+
+
+@pytest.fixture(scope="module")
+def random_grid():
+    return {(c.nq, c.D): c for c in PC.random_cases(0)}
+
+
+@pytest.mark.parametrize("nq,D", PC.RANDOM_GRID)
+def test_seeded_random_sets(random_grid, nq, D):
+    case = random_grid[nq, D]
+    for K in PC.RANDOM_KS:
+        _check(case, K, case.requests)
+
+
+def test_every_path_in_one_launch(pass_entries):
+    """a = 0, a = 1, a = 513 over halved windows, the hot-id request with its single-id passes, short requests and
+    repeats, unsorted, in one call (PC.mixed_case asserts the plans of the concatenated case)"""
+    case = PC.mixed_case(C=pass_entries)
+    for K in (5, 64):
+        want = case.ref(K, case.requests)
+        got = _check(case, K, case.requests)
+        assert got.queries.tolist() == case.requests
+        dev = _run(case, K, torch.tensor(case.requests, dtype=torch.int32, device=DEV))
+        XC.same_lists(dev, want)
+
+
+def test_flags_raised_from_a_long_request():
+    import qrlsh
+    case = PC.long_windows_case()
+    postings = _build(case)
+    s = case.requests[0]                                  # holds all 600 rows
+    at = PC.LIST_CURSORS + 38
+    assert case.offsets[s + 1] - case.offsets[s] > at >= PC.LIST_CURSORS
+    # bit 3: a row id outside [0, D) at a position past the lists whose cursors stay in LDS, postings of the unbroken sets
+    for bad in (case.D, -1):
+        rows = case.rows.copy()
+        rows[case.offsets[s] + at] = bad
+        with pytest.raises(ValueError, match="row id"):
+            _run(_broken(case, rows=rows), 5, [0, s], postings)
+    # bit 4: an entry = nq at the end of a list that only the long request reads
+    others = set(np.concatenate([case.rows[case.offsets[q]:case.offsets[q + 1]] for q in case.requests[1:]]).tolist())
+    row = max(r for r in range(PC.LIST_CURSORS, case.D) if r not in others)
+    p_off = postings.p_off.cpu().numpy()
+    end = int(p_off[row + 1]) - 1
+    assert end > int(p_off[row]) and int(postings.p_qry[end].item()) > s     # not the request's own entry
+    planted = qrlsh.AnswerPostings(postings.p_off, postings.p_qry.clone(), postings.D, postings.nq, postings.nnz)
+    planted.p_qry[end] = case.nq
+    with pytest.raises(ValueError, match="do not belong"):
+        _run(case, 5, [s], planted)
+    XC.same_lists(_run(case, 5, case.requests[1:], planted), case.ref(5, case.requests[1:]))   # nobody else reads it
+    XC.same_lists(_run(case, 5, [s], postings), case.ref(5, [s]))
 
 
 # ---- requests ----------------------------------------------------------------------------------------------------------
@@ -326,4 +434,17 @@ def test_recommender_postings_follow_the_live_operations():
         rec.exact_query_lists(K=3, postings=held)          # stale: three queries more
     _same_as_the_sweep(rec, 3, "queries added")
     rec.remove_rows([0, 5, 17, rec.dataset.shape[0] - 1], update_lists=True)
-    _same_as_the_sweep(rec, 3, "rows removed")
+    held = _same_as_the_sweep(rec, 3, "rows removed")
+    rec.remove_queries([1, rec.queriesIDs.size - 1], update_lists=True)
+    with pytest.raises(ValueError, match="built from"):
+        rec.exact_query_lists(K=3, postings=held)          # stale: two queries fewer
+    held = _same_as_the_sweep(rec, 3, "queries removed")
+    from qrlsh import ops
+    off, _, _ = rec._answer_set_inputs()
+    sizes = np.diff(ops.to_host(off))
+    p, t = next((p, t) for p in range(sizes.size) for t in range(sizes.size) if sizes[p] != sizes[t] and sizes[t] > 0)
+    rec.replace_queries([p], np.asarray(rec.queries, dtype=object)[t:t + 1], update_lists=True)
+    assert int(ops.to_host(rec._answer_set_inputs()[0])[-1]) != held.nnz and held.nq == rec.queriesIDs.size
+    with pytest.raises(ValueError, match="built from"):
+        rec.exact_query_lists(K=3, postings=held)          # stale: as many queries, another entry count
+    _same_as_the_sweep(rec, 3, "a query replaced by one of another size")

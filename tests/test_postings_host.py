@@ -52,6 +52,90 @@ def test_case_builders_assert_their_point():
     PC.every_query_case(), PC.empty_rows_case()
 
 
+SMALL = dict(D=40, nq=256, base=100, span=16, per=20)     # long_windows_case under C = 64 and 32 cursors
+
+
+def _small_cases():
+    """the new shapes shrunk (a small C passed in), each with a K that cuts its lists and one that does not"""
+    return ((PC.long_windows_case(C=64, cursors=32, **SMALL), 5), (PC.hot_id_case(C=64), 3),
+            (PC.probe_chain_case(nq=1 << 15), 64), (PC.late_windows_case(C=128), 8),
+            (PC.lanes_case(nq=400, sizes=(1, 2, 3, 5, 8, 9, 16, 17), shared=60, threads=64, cursors=32), 7),
+            (PC.mixed_case(C=64, cursors=32, **SMALL), 4))
+
+
+def test_new_case_builders_assert_their_point():
+    """every new builder at the size the GPU tests run: the path assertions through plan_ref / slot_ref hold for the C,
+    the queue and the cursor count the library exports"""
+    from qrlsh import _lib
+    lib = _lib.load()
+    assert lib.qrlsh_exact_postings_pass_entries() == PC.PASS_ENTRIES == PC.TABLE_SLOTS // 2
+    assert lib.qrlsh_exact_postings_queue() == PC.QUEUE and lib.qrlsh_exact_postings_list_cursors() == PC.LIST_CURSORS
+    assert lib.qrlsh_exact_postings_threads() == PC.THREADS
+    long = PC.long_windows_case()
+    assert long.nq == 4096 and long.D == 600 and 19_000 < len(long.rows) < 21_000
+    hot = PC.hot_id_case()
+    assert hot.D == PC.PASS_ENTRIES + 8 and hot.requests == [0, 19, 30, 5]
+    chain = PC.probe_chain_case()
+    assert chain.nq == 1 << 17
+    slots = np.array([PC.slot_ref(j) for j in range(chain.nq)])
+    assert int((slots >= PC.TABLE_SLOTS - 32).sum()) == 255 and slots.max() == PC.TABLE_SLOTS - 1 and slots.min() == 0
+    lanes = PC.lanes_case()
+    assert sorted({PC.lanes_ref(a) for a in PC.LANE_SIZES + (513,)}) == [1, 2, 4, 8, 16, 32, 64, 128, 256, 512, 1024]
+    assert len(lanes.requests) == len(PC.LANE_SIZES) + 1
+    PC.late_windows_case(), PC.mixed_case()
+    grid = PC.random_cases(0)
+    assert [(c.nq, c.D) for c in grid] == [(nq, D) for nq in (257, 5000) for D in (8, 64, 700)]
+    assert all(len(c.requests) == 16 for c in grid) and PC.RANDOM_KS == (1, 7, 63, 64)
+    for case in (long, hot, chain, lanes, grid[-1]):
+        assert len(case.rows) <= 250_000, case.name
+
+
+def test_plan_restatement_against_brute_force_counts():
+    """plan_ref's windows tile [0, nq) in order, each count is the number of list entries with an id inside it (counted
+    entry by entry from the dict-of-lists postings), a pass holds at most C entries or one id, and a window was halved
+    only because it was no pass: the window before its last halving holds more than C"""
+    for case, C in ((PC.long_windows_case(C=64, cursors=32, **SMALL), 64), (PC.hot_id_case(C=16), 16),
+                    (PC.late_windows_case(C=128), 128)):
+        held = PC.postings_lists(case.offsets, case.rows, case.D)
+        halved = single = 0
+        for s in case.requests:
+            mine = case.rows[case.offsets[s]:case.offsets[s + 1]].tolist()
+            entries = [j for d in mine for j in held[d]]
+
+            def count(lo, hi):
+                return sum(1 for j in entries if lo <= j < hi)
+            plan = PC.plan_ref(case, s, C)
+            if not entries:
+                assert plan == []
+                continue
+            windows = -(-len(entries) // C)
+            width = case.nq if windows == 1 else -(-case.nq // windows)
+            assert [p[0] for p in plan] == [0] + [p[1] for p in plan[:-1]] and plan[-1][1] == case.nq
+            assert sum(p[2] for p in plan) == len(entries)
+            for lo, hi, n, h in plan:
+                assert n == count(lo, hi) and (n <= C or hi - lo == 1) and hi > lo
+                top = min(lo + width, case.nq)
+                for _ in range(h):
+                    before, top = top, lo + (top - lo) // 2
+                assert top == hi
+                if h:
+                    assert count(lo, before) > C and before - lo >= 2
+                halved += h
+                single += n > C
+        assert halved > 0, case.name
+        assert single > 0 or "hot" not in case.name
+
+
+def test_fast_reference_on_the_new_shapes_shrunk():
+    for case, K in _small_cases():
+        for k in sorted({1, K}):
+            XC.same_lists(case.ref(k, case.requests), XC.exact_ref(case.offsets, case.rows, k, case.requests),
+                          "%s K=%d" % (case.name, k))
+    for case in PC.random_cases(1, grid=((257, 8), (257, 64), (257, 700))):
+        for K in (1, 63):
+            XC.same_lists(case.ref(K, case.requests), XC.exact_ref(case.offsets, case.rows, K, case.requests), case.name)
+
+
 # ---- Python's checks come before the library is loaded -----------------------------------------------------------------
 @pytest.fixture
 def no_library(monkeypatch):
@@ -119,6 +203,8 @@ def test_scratch_sizes_on_both_sides_of_their_constants():
     for bad in ((-1, 5), (1 << 32, 5), (5, -1), (5, (1 << 20) + 1)):
         assert size(*bad) == 0, bad
     assert lib.qrlsh_exact_postings_pass_entries() == PC.PASS_ENTRIES
+    assert lib.qrlsh_exact_postings_queue() == PC.QUEUE and lib.qrlsh_exact_postings_list_cursors() == PC.LIST_CURSORS
+    assert lib.qrlsh_exact_postings_threads() == PC.THREADS
     for args in ((0, 0, 1), (1, 1, 1), (10_000_000, 1 << 24, 64), (-1, -1, 0), (5, 5, 65)):
         assert lib.qrlsh_exact_postings_scratch_bytes(*args) == 0, args            # everything stays in LDS
 
@@ -134,6 +220,8 @@ def test_c_surface():
         assert len(decl.group(1).split(",")) == nargs == len(_lib.SIGNATURES[name][1]), name
     assert re.search(r"^int32_t qrlsh_exact_postings_pass_entries\(void\);", hdr, re.M)
     assert _lib.SIGNATURES["qrlsh_exact_postings_pass_entries"][1] == []
+    for name in ("qrlsh_exact_postings_list_cursors", "qrlsh_exact_postings_queue", "qrlsh_exact_postings_threads"):
+        assert re.search(r"^int32_t %s\(void\);" % name, hdr, re.M) and _lib.SIGNATURES[name][1] == [], name
     assert {"answer_postings", "AnswerPostings", "exact_neighbours"} <= set(qrlsh.__all__)
     # no export of the new file matches the pattern of the recorded workspace sizes
     import importlib.util
